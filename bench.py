@@ -7,10 +7,11 @@ resident in HBM before the timed region; the output stays in HBM.  With N GPUs t
 ranks (rank r renders [r*512/N, (r+1)*512/N) of every pixel), the per-pixel sums are added on rank 0 by ONE RCCL
 reduce issued inside the library (cr_group_render) and divided by 512 there -- a fixed job, so scaling is "strong".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes the frame of the last timed step (rank 0's) to DIR as .npy
+(see dump_outputs); scenes and seeds are fixed, so two builds run with the same arguments can be compared frame for frame.
 
 Summation order: the library default (CR_SUM_RELAXED: the same paths, attenuations multiplied in path order, samples added
 as 64-bit fixed point -- within 1e-12 of the reference order, equal work counters; include/crucible_hip.h).  The line
@@ -41,7 +42,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md (6.29 TB/s measured copy)
+HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (6.29 TB/s measured copy)
 VALU_PEAK_TFLOPS = {"f32": 157.3, "f64": 78.65}   # guide: 157.3 TFLOP/s f32 vector (FMA = 2); f64 vector is half rate
 # What the chip SUSTAINS on this pool (scripts/calib/valu_peak.hip, profiles/r03_valu_calib.txt): whatever the occupancy, a SIMD
 # retires one wave64 f64 add / mul / max per ~2.1 ns and one f32 add per ~1.2 ns (the clock drops as more waves issue), i.e.
@@ -120,6 +121,30 @@ def host_cores():
     return max(1, n)
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6    # --dump-outputs: frames up to this size are written whole
+DUMP_SAMPLE_PIXELS = 1 << 20     # larger frames: this many pixels (24 MB of f64 + 8 MB of indices)
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: `frame` (the H x W x 3 device tensor the render path hands its caller, f32 or f64 as rendered) as
+    path/image.npy.  A frame over DUMP_LIMIT_BYTES is written as a sample instead: DUMP_SAMPLE_PIXELS pixels drawn without
+    replacement by a fixed-seed generator (so the same pixels for the same frame size), their values as
+    path/image_sample.npy (N x 3) and their flat indices y*W + x as path/image_sample_pixel.npy (float64, exact)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    H, W, _ = frame.shape
+    if frame.numel() * frame.element_size() <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(path, "image.npy"), frame.cpu().numpy())
+        return ["image.npy"]
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, size=DUMP_SAMPLE_PIXELS, replace=False))
+    pix = frame.reshape(H * W, 3)[torch.from_numpy(idx).to(frame.device)]
+    np.save(os.path.join(path, "image_sample.npy"), pix.cpu().numpy())
+    np.save(os.path.join(path, "image_sample_pixel.npy"), idx.astype(np.float64))
+    return ["image_sample.npy", "image_sample_pixel.npy"]
+
+
 def cpu_baseline(scene, seed, target_s, faithful):
     """Time the f64 oracle on sample indices [0, k) of the same workload (all pixels), on the host cores this process
     may use.  A GPU box can report far more logical CPUs than its share (256 vs 16): the thread count is the one of
@@ -195,7 +220,14 @@ def main():
     ap.add_argument("--reduce", choices=["library", "torch", "gloo"], default="library",
                     help="N>1: library = cr_group_render (RCCL reduce inside the C ABI); torch = torch.distributed (nccl) reduce of the "
                          "sums; gloo = reduce host copies (rehearsal of the multi-rank flow with ranks sharing one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step (rank 0's) to DIR/image.npy; frames over "
+                         "64 MB as a fixed, seeded sample of pixels (DIR/image_sample.npy, DIR/image_sample_pixel.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     import torch
     import torch.distributed as dist
@@ -343,6 +375,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=ctl)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # what the timed path computed in its last step, taken before the extra lines below render anything
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, out)
+        print(f"bench: wrote {', '.join(names)} to {args.dump_outputs}", file=sys.stderr)
 
     # the opt-in f32 mode, carried as an extra key (it is NOT the reference's arithmetic)
     f32_line = None

@@ -1,6 +1,6 @@
 """The reference's own known-answer tests, replayed against the oracle.
 
-Each test names the Rust test it restates (file:line in /root/reference).  These are the
+Each test names the Rust test it restates (file:line in the reference's sources).  These are the
 only results the reference pins for this path; they cover the arithmetic helpers, the
 PPM byte mapping, average_samples and the keyframe evaluation.
 """
