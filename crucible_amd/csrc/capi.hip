@@ -67,13 +67,15 @@ template <typename real> struct DevScene {
                                              // (empty, or grown over hidden objects too) is not what refit derives
     DevBuf entries_refit;                    // working copy whose boxes refit_level_kernel rewrites per frame
     DevBuf screen, screen_refit;             // f64, unordered trees: the f32 screening records of entries / entries_refit
+    DevBuf screen_overflow;                  // f64: one int, set by the record kernels when a box plane lies beyond the f32 range
+    bool screen_usable = true;               // f64: `screen` may be walked on (no box plane beyond the f32 range)
     bool ordered = false;                    // CR_BVH_SAH_ORDERED: `entries` holds EntryO records
     size_t entry_bytes = sizeof(Entry<real>);
     std::vector<int8_t> host_axis;           // ordered: split axis per wrapper (-1 leaf), same order as host_entries
     std::vector<int32_t> level_begin;        // entries of tree level l are [level_begin[l], level_begin[l+1])
     std::vector<Entry<real>> host_entries;   // the tree over the scene's objects (for cr_export_bvh); the device copy names primitive runs
     std::vector<int32_t> leaf_desc;          // leaf-order position -> index in the caller's primitive list
-    void release() { entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
+    void release() { entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
 };
 
 }   // namespace
@@ -530,20 +532,30 @@ int32_t build_lbvh(CrHandle* h, const std::vector<Prim<real>>& src, const std::v
 }
 
 // The f32 screening records of a (possibly refitted) f64 wrapper array, in the layout of the tree (ScreenEntry / ScreenEntryO).
-int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevBuf& out) {
+// *usable = false when a finite f64 plane lies beyond the f32 range (screen_from_entries_kernel): the walk must not screen
+// on these records.  Synchronises the stream.
+int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevBuf& out, bool* usable) {
     const size_t rec = ds.ordered ? sizeof(ScreenEntryO) : sizeof(ScreenEntry);
     HIP_TRY(h, out.ensure((size_t)ds.n_entries * rec, ds.ordered ? entry_pad<ScreenEntryO>() : entry_pad<ScreenEntry>()));
+    HIP_TRY(h, ds.screen_overflow.ensure(sizeof(int32_t)));
+    HIP_TRY(h, hipMemsetAsync(ds.screen_overflow.p, 0, sizeof(int32_t), h->stream));
     const dim3 grid((unsigned)((ds.n_entries + 255) / 256));
-    if (ds.ordered) hipLaunchKernelGGL(screen_from_ordered_entries_kernel, grid, dim3(256), 0, h->stream, (const EntryO<double>*)entries, (ScreenEntryO*)out.p, ds.n_entries);
-    else hipLaunchKernelGGL(screen_from_entries_kernel<double>, grid, dim3(256), 0, h->stream, (const Entry<double>*)entries, (ScreenEntry*)out.p, ds.n_entries);
+    int32_t* flag = (int32_t*)ds.screen_overflow.p;
+    if (ds.ordered) hipLaunchKernelGGL(screen_from_ordered_entries_kernel, grid, dim3(256), 0, h->stream, (const EntryO<double>*)entries, (ScreenEntryO*)out.p, ds.n_entries, flag);
+    else hipLaunchKernelGGL(screen_from_entries_kernel<double>, grid, dim3(256), 0, h->stream, (const Entry<double>*)entries, (ScreenEntry*)out.p, ds.n_entries, flag);
     HIP_TRY(h, hipGetLastError());
+    int32_t overflow = 0;
+    HIP_TRY(h, hipMemcpyAsync(&overflow, flag, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *usable = overflow == 0;
     return CR_OK;
 }
 // f32 scenes: the same boxes in ScreenEntry's link layout (the walk's inner loop reads that one), unordered trees only
-int32_t make_screen(CrHandle* h, DevScene<float>& ds, const void* entries, DevBuf& out) {
+int32_t make_screen(CrHandle* h, DevScene<float>& ds, const void* entries, DevBuf& out, bool* usable) {
+    *usable = true;
     if (ds.ordered) { out.release(); return CR_OK; }
     HIP_TRY(h, out.ensure((size_t)ds.n_entries * sizeof(ScreenEntry), entry_pad<ScreenEntry>()));
-    hipLaunchKernelGGL(screen_from_entries_kernel<float>, dim3((unsigned)((ds.n_entries + 255) / 256)), dim3(256), 0, h->stream, (const Entry<float>*)entries, (ScreenEntry*)out.p, ds.n_entries);
+    hipLaunchKernelGGL(screen_from_entries_kernel<float>, dim3((unsigned)((ds.n_entries + 255) / 256)), dim3(256), 0, h->stream, (const Entry<float>*)entries, (ScreenEntry*)out.p, ds.n_entries, (int32_t*)nullptr);
     HIP_TRY(h, hipGetLastError());
     return CR_OK;
 }
@@ -882,7 +894,7 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     if (ds.n_entries > 0) {   // the f32 screening records of an f64 scene / the link-layout records of an f32 scene (pathtrace.hpp walk_round)
-        int32_t rc = make_screen(h, ds, ds.entries.p, ds.screen);
+        int32_t rc = make_screen(h, ds, ds.entries.p, ds.screen, &ds.screen_usable);
         if (rc != CR_OK) return rc;
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     } else ds.screen.release();
@@ -1365,14 +1377,17 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     }
     // f64 megakernel on an unordered tree: the walk decides its box tests on the f32 screening records (half the bytes
     // per step), see walk_round (A/B in profiles/experiments/r03_screen_ab.txt).
+    // (not on a tree with a box plane beyond the f32 range: make_screen)
     bool screen = h->pipeline == 0 && ds.screen.p != nullptr && ds.n_entries > 0 && h->screen_boxes && ds.n_entries < (ds.ordered ? kScreenMaxEntriesO : kScreenMaxEntries);
     if (screen) {
         a.screen = ds.screen.p;
+        bool usable = ds.screen_usable;
         if (refit) {
-            int32_t rc = make_screen(h, ds, ds.entries_refit.p, ds.screen_refit);
+            int32_t rc = make_screen(h, ds, ds.entries_refit.p, ds.screen_refit, &usable);
             if (rc != CR_OK) return rc;
             a.screen = ds.screen_refit.p;
         }
+        if (!usable) { screen = false; a.screen = nullptr; }
     }
     // a SCREEN kernel stages screening records where the others stage wrappers
     const size_t screen_rec = ds.ordered ? sizeof(ScreenEntryO) : sizeof(ScreenEntry);

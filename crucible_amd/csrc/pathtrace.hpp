@@ -1085,10 +1085,62 @@ template <typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd) {
 // a box plane or origin component below the normal f32 range and a product that underflows).  Hence hi32 - lo32 < -TH proves Aabb::hit's
 // `max <= min` (a miss), hi32 - lo32 > TH proves a hit, and only a lane with |hi32 - lo32| <= TH evaluates Aabb::hit in f64
 // on the f64 box.  Overflow and NaN land there too (every comparison with them is false), and the round uses the screen only
-// when |if| lies in [2^-100, 2^100] and |of| <= 2^100 on every axis.  The decisions -- hence the walk, the counters and the image -- are those of the f64 test.
+// when |if| lies in [2^-100, 2^100] and |of| <= 2^100 on every axis, on trees whose f64 planes all lie in the f32 range
+// (screen_from_entries_kernel reports any other; capi.hip then walks without the screen).  The decisions -- hence the walk, the counters and the image -- are those of the f64 test.
 // SCREEN is a kernel variant of its own: a kernel that carried both the f32 loop and the f64 min/max loop lost 5 % on the
 // teapot frames to register pressure.  In a SCREEN kernel a ray whose
 // 1/direction is infinite, or outside the f32 range above, walks with Aabb::hit's compare/select form (valid for every ray).
+// The screen's pieces, one record at a time (tests/walk_check.hip runs them on the device).  of*, if*: the f32 roundings of
+// the origin and of 1/direction; mo = max |of|, pmax / pmin = max / min |if|.  screen_in_range: a ray the f64 screen may decide
+// (finite 1/direction, and the range above); screen_th0: from Q's three terms screen_q, the part of TH
+// that does not depend on the box -- 2^-21 Q, plus what rounding a box plane or an origin component BELOW the normal f32
+// range can add (2^-149 each, times |if| <= 2^100), plus a product that underflows.
+CR_D void screen_extents(float ofx, float ofy, float ofz, float ifx, float ify, float ifz, float& mo, float& pmax, float& pmin) {
+    mo = r_max(r_max(__builtin_fabsf(ofx), __builtin_fabsf(ofy)), __builtin_fabsf(ofz));
+    pmax = r_max(r_max(__builtin_fabsf(ifx), __builtin_fabsf(ify)), __builtin_fabsf(ifz));
+    pmin = r_min(r_min(__builtin_fabsf(ifx), __builtin_fabsf(ify)), __builtin_fabsf(ifz));
+}
+CR_D bool screen_in_range(bool exact_box, float mo, float pmax, float pmin) {
+    return !exact_box && pmin >= 0x1.0p-100f && pmax <= 0x1.0p100f && mo <= 0x1.0p100f;
+}
+CR_D float screen_q(float of, float inv_f) { return __builtin_fabsf(of * inv_f); }   // |of if| on one axis
+CR_D float screen_th0(float qx, float qy, float qz, float pmax) {
+    return __builtin_fmaf(0x1.0p-21f, r_max(r_max(qx, qy), qz), __builtin_fmaf(pmax * 0x1.0p-100f, 0x1.0p-47f, 1e-35f));
+}
+// f64 kernels: hi32 - lo32 on the screening box b, and its TH in `th`.  The decision is d < -th (miss) or d > th (hit);
+// anything else (NaN included) is left to Aabb::hit in f64.
+// hi = r_min(r_min(fx, fy), r_min(fz, tmaxf)) and m = r_max(|lo|, |hi|), written out: the compiler re-quiets the
+// loop-invariant tmaxf with a v_max_f32 x, x at every step (instruction selection works block by block and
+// cannot see that it is a number), and one VALU instruction in the walk loop is about 1.5 % of the frame
+CR_D float screen_box_d(const float* b, Pair<float> fox, Pair<float> foy, Pair<float> foz, Pair<float> fix, Pair<float> fiy, Pair<float> fiz,
+                        float tminf, float tmaxf, float th0, float& th) {
+    const Pair<float> tx = (Pair<float>{b[0], b[1]} - fox) * fix;
+    const Pair<float> ty = (Pair<float>{b[2], b[3]} - foy) * fiy;
+    const Pair<float> tz = (Pair<float>{b[4], b[5]} - foz) * fiz;
+    const float nx = r_min(tx.x, tx.y), ny = r_min(ty.x, ty.y), nz = r_min(tz.x, tz.y);
+    const float fx = r_max(tx.x, tx.y), fy = r_max(ty.x, ty.y), fz = r_max(tz.x, tz.y);
+    const float lo = r_max(r_max(nx, ny), r_max(nz, tminf));
+    float hi, m;
+    asm("v_min_f32_e32 %0, %2, %3\n\tv_min3_f32 %0, %4, %5, %0\n\tv_max_f32_e64 %1, |%6|, |%0|"
+        : "=&v"(hi), "=v"(m) : "v"(fz), "v"(tmaxf), "v"(fx), "v"(fy), "v"(lo));
+    th = __builtin_fmaf(0x1.0p-20f, m, th0);
+    return hi - lo;
+}
+// f32 kernels (EXACT): Aabb::hit's `max <= min -> miss` on the record, with the same operations as box_miss_fast (min(h, tmax)
+// <= lo there is h <= lo || tmax <= lo)
+CR_D bool screen_box_miss_exact(const float* b, Pair<float> fox, Pair<float> foy, Pair<float> foz, Pair<float> fix, Pair<float> fiy,
+                                Pair<float> fiz, float tminf, float tmaxf) {
+    const Pair<float> tx = (Pair<float>{b[0], b[1]} - fox) * fix;
+    const Pair<float> ty = (Pair<float>{b[2], b[3]} - foy) * fiy;
+    const Pair<float> tz = (Pair<float>{b[4], b[5]} - foz) * fiz;
+    const float nx = r_min(tx.x, tx.y), ny = r_min(ty.x, ty.y), nz = r_min(tz.x, tz.y);
+    const float fx = r_max(tx.x, tx.y), fy = r_max(ty.x, ty.y), fz = r_max(tz.x, tz.y);
+    const float lo = r_max(r_max(nx, ny), r_max(nz, tminf));
+    float hi;
+    asm("v_min_f32_e32 %0, %1, %2\n\tv_min3_f32 %0, %3, %4, %0" : "=&v"(hi) : "v"(fz), "v"(tmaxf), "v"(fx), "v"(fy));
+    return hi <= lo;
+}
+
 template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false>
 CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, const Prim<real>* prims, V3<real> ro, V3<real> rd, real rtime,
                      WalkState<real>& w, bool walking, uint32_t budget, unsigned long long& c_node, uint32_t& c_prim, Diag* dg = nullptr,
@@ -1110,49 +1162,32 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
         if constexpr (SCREEN) {
             const float ofx = (float)ro.x, ofy = (float)ro.y, ofz = (float)ro.z;
             const float ifx = (float)w.inv.x, ify = (float)w.inv.y, ifz = (float)w.inv.z;
-            const float mo = r_max(r_max(__builtin_fabsf(ofx), __builtin_fabsf(ofy)), __builtin_fabsf(ofz));
-            const float pmax = r_max(r_max(__builtin_fabsf(ifx), __builtin_fabsf(ify)), __builtin_fabsf(ifz));
-            const float pmin = r_min(r_min(__builtin_fabsf(ifx), __builtin_fabsf(ify)), __builtin_fabsf(ifz));
+            float mo, pmax, pmin;
+            screen_extents(ofx, ofy, ofz, ifx, ify, ifz, mo, pmax, pmin);
             // (an f32 kernel's test on the record is Aabb::hit itself for every ray with finite 1/direction: no range to respect)
             bool screened;
             if constexpr (EXACT) screened = !w.exact_box;
-            else screened = !w.exact_box && pmin >= 0x1.0p-100f && pmax <= 0x1.0p100f && mo <= 0x1.0p100f;
+            else screened = screen_in_range(w.exact_box, mo, pmax, pmin);
             if (!screened) exact_steps = 0xffffffffu;
             else {
-                const float qx = __builtin_fabsf(ofx * ifx), qy = __builtin_fabsf(ofy * ify), qz = __builtin_fabsf(ofz * ifz);
+                const float qx = screen_q(ofx, ifx), qy = screen_q(ofy, ify), qz = screen_q(ofz, ifz);
                 const Pair<float> fox = {ofx, ofx}, foy = {ofy, ofy}, foz = {ofz, ofz};
                 const Pair<float> fix = {ifx, ifx}, fiy = {ify, ify}, fiz = {ifz, ifz};
                 const float tminf = 0.001f;
                 float tmaxf = (float)w.best_t;   // tmax cannot change inside the loop
-                // the part of TH that does not depend on the box: 2^-21 Q, plus what rounding a box plane or an origin component
-                // BELOW the normal f32 range can add (2^-149 each, times |if| <= 2^100), plus a product that underflows
-                const float th0 = __builtin_fmaf(0x1.0p-21f, r_max(r_max(qx, qy), qz), __builtin_fmaf(pmax * 0x1.0p-100f, 0x1.0p-47f, 1e-35f));
+                const float th0 = screen_th0(qx, qy, qz, pmax);
                 asm volatile("" : "+v"(tmaxf));   // keep it in a register: the allocator would re-convert tmax at every step
                 uint32_t nodes = 0;
                 // Aabb::hit of the wrapper at index `idx` decided on its screening box `b`: true = miss
                 auto box_miss = [&](const float* b, int32_t idx) -> bool {
-                    const Pair<float> tx = (Pair<float>{b[0], b[1]} - fox) * fix;
-                    const Pair<float> ty = (Pair<float>{b[2], b[3]} - foy) * fiy;
-                    const Pair<float> tz = (Pair<float>{b[4], b[5]} - foz) * fiz;
-                    const float nx = r_min(tx.x, tx.y), ny = r_min(ty.x, ty.y), nz = r_min(tz.x, tz.y);
-                    const float fx = r_max(tx.x, tx.y), fy = r_max(ty.x, ty.y), fz = r_max(tz.x, tz.y);
-                    const float lo = r_max(r_max(nx, ny), r_max(nz, tminf));
-                    // hi = r_min(r_min(fx, fy), r_min(fz, tmaxf)) and m = r_max(|lo|, |hi|), written out: the compiler re-quiets the
-                    // loop-invariant tmaxf with a v_max_f32 x, x at every step (instruction selection works block by block and
-                    // cannot see that it is a number), and one VALU instruction in this loop is about 1.5 % of the frame
-                    float hi, m;
                     if constexpr (EXACT) {
+                        const bool miss = screen_box_miss_exact(b, fox, foy, foz, fix, fiy, fiz, tminf, tmaxf);
                         nodes++;
-                        // f32 kernels: `max <= min -> miss` on the same operations as box_miss_fast (min(h, tmax) <= lo there is
-                        // h <= lo || tmax <= lo)
-                        asm("v_min_f32_e32 %0, %1, %2\n\tv_min3_f32 %0, %3, %4, %0" : "=&v"(hi) : "v"(fz), "v"(tmaxf), "v"(fx), "v"(fy));
                         CR_DIAG_HIT(dg, DG_BOX_WAVE, DG_BOX_LANE);
-                        return hi <= lo;
+                        return miss;
                     }
-                    asm("v_min_f32_e32 %0, %2, %3\n\tv_min3_f32 %0, %4, %5, %0\n\tv_max_f32_e64 %1, |%6|, |%0|"
-                        : "=&v"(hi), "=v"(m) : "v"(fz), "v"(tmaxf), "v"(fx), "v"(fy), "v"(lo));
-                    const float th = __builtin_fmaf(0x1.0p-20f, m, th0);
-                    float d = hi - lo;
+                    float th;
+                    float d = screen_box_d(b, fox, foy, foz, fix, fiy, fiz, tminf, tmaxf, th0, th);
                     nodes++;
                     CR_DIAG_HIT(dg, DG_BOX_WAVE, DG_BOX_LANE);
                     // too close to call in f32: Aabb::hit in f64 on the f64 box.  (The wave tests "any lane?" with a scalar branch and
@@ -1282,8 +1317,12 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             if constexpr (RES != RES_LDS && !ANIM) {
                 // primitives in global memory: touch the second record's lines while the first is being tested, so that its own
                 // loads hit L1 instead of waiting a second L2 round trip (teapot +1.5 %, 1M spheres +1.4 %)
+                // (the second word touched lies inside that record: byte 80 of the 96-byte f64 record, the last word of the
+                // 48-byte f32 one -- the record may be the last of an exactly sized array)
+                constexpr uint32_t touch = sizeof(Prim<real>) == 96 ? 20u : (uint32_t)(sizeof(Prim<real>) / 4 - 1);
+                static_assert((touch + 1) * 4 <= sizeof(Prim<real>), "the touched word must lie inside the record");
                 GlobPtr<uint32_t> nx = (GlobPtr<uint32_t>)(const void*)(prims + first + (count - 1));
-                const uint32_t t0 = nx[0], t1 = nx[20];
+                const uint32_t t0 = nx[0], t1 = nx[touch];
                 test(first);
                 asm volatile("" :: "v"(t0), "v"(t1));
                 if (count == 2) test(first + 1);
@@ -1668,24 +1707,32 @@ pathtrace_kernel_latency(const KernelArgs<real> A) {
 
 // The screening records of a wrapper array: boxes rounded to the nearest f32 (the band of walk_round allows for either
 // direction), links copied.  Run after every upload and after every refit of the f64 boxes.
+// A finite f64 plane beyond the f32 range becomes an infinite f32 plane, an error TH does not cover (an f32 box that
+// reaches to infinity decides hits that Aabb::hit misses): such a plane sets *overflow, and the caller then walks the tree
+// without the screen.
+CR_D void screen_plane(double b, float& f, int32_t* overflow) {
+    f = (float)b;
+    if (__builtin_fabsf(f) == __builtin_inff() && __builtin_fabs(b) != __builtin_inf()) *overflow = 1;
+}
+CR_D void screen_plane(float b, float& f, int32_t*) { f = b; }
 template <typename real>
-__global__ void __launch_bounds__(256) screen_from_entries_kernel(const Entry<real>* e, ScreenEntry* s, int32_t n) {
+__global__ void __launch_bounds__(256) screen_from_entries_kernel(const Entry<real>* e, ScreenEntry* s, int32_t n, int32_t* overflow) {
     const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
     const Entry<real> v = e[i];
     ScreenEntry o;
-    for (int k = 0; k < 6; k++) o.b[k] = (float)v.b[k];
+    for (int k = 0; k < 6; k++) screen_plane(v.b[k], o.b[k], overflow);
     o.skip = (uint32_t)v.skip << 5;
     o.hit = v.leaf < 0 ? (uint32_t)(-v.leaf) << 5 : (kScreenLeaf | (uint32_t)v.leaf);
     s[i] = o;
 }
 
-__global__ void __launch_bounds__(256) screen_from_ordered_entries_kernel(const EntryO<double>* e, ScreenEntryO* s, int32_t n) {
+__global__ void __launch_bounds__(256) screen_from_ordered_entries_kernel(const EntryO<double>* e, ScreenEntryO* s, int32_t n, int32_t* overflow) {
     const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
     const EntryO<double> v = e[i];
     ScreenEntryO o;
-    for (int k = 0; k < 6; k++) o.b[k] = (float)v.b[k];
+    for (int k = 0; k < 6; k++) screen_plane(v.b[k], o.b[k], overflow);
     if (v.leaf < 0) { o.axis = (uint32_t)(-v.leaf) & 3u; o.hit = (uint32_t)ordered_left(v.leaf) << 6; }
     else { o.axis = 3u; o.hit = kScreenLeaf | (uint32_t)v.leaf; }
     for (int k = 0; k < 8; k++) o.skip[k] = (uint32_t)v.skip[k] << 6;
