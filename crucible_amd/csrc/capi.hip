@@ -10,6 +10,7 @@
 #include "queue.hpp"
 #include "refit.hpp"
 #include "lbvh.hpp"
+#include "pack.hpp"
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -594,12 +595,7 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     bool any_keys = false, any_lists = false;
     ds.has_triangles = false; ds.has_spheres = false;
     auto make_prim = [&](const CrPrimitive& p) {
-        Prim<real> q;
-        memset(&q, 0, sizeof q);
-        for (int k = 0; k < 9; k++) q.g[k] = (real)p.v[k];
-        if (p.kind == CR_PRIM_SPHERE) q.g[4] = real(1) / q.g[3];    // 1/radius, used for the hit normal of static spheres
-        q.kind_mat = (p.kind & 1) | (p.material << 1);
-        q.key_first = p.key_first; q.key_count = p.key_count;
+        const Prim<real> q = pack_prim<real>(p);
         any_keys |= p.key_count > 0;
         ds.has_triangles |= p.kind == CR_PRIM_TRIANGLE;
         ds.has_spheres |= p.kind == CR_PRIM_SPHERE;
@@ -793,56 +789,16 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     }
     const std::vector<Entry<real>>& up_entries = (any_lists || spliced) ? dev_entries : b.entries;
 
-    // Device texture table: only textures a non-solid lambertian can reach (a solid top-level
-    // texture is folded into its material), re-indexed densely; children keep smaller indices.
-    std::vector<int32_t> tex_remap(h->textures.size(), -1);
-    {
-        std::vector<char> live(h->textures.size(), 0);
-        for (const CrMaterial& m : h->materials)
-            if (m.kind == CR_MAT_LAMBERTIAN && h->textures[m.texture].kind != CR_TEX_SOLID) live[m.texture] = 1;
-        for (size_t i = h->textures.size(); i-- > 0;)   // parents have larger indices than children
-            if (live[i] && h->textures[i].kind == CR_TEX_CHECKER) { live[h->textures[i].even] = 1; live[h->textures[i].odd] = 1; }
-        int32_t next = 0;
-        for (size_t i = 0; i < live.size(); i++) if (live[i]) tex_remap[i] = next++;
-    }
+    // Device texture table, materials, textures and keyframes (pack.hpp)
+    const std::vector<int32_t> tex_remap = live_texture_remap(h->materials.data(), h->materials.size(), h->textures.data(), h->textures.size());
     std::vector<Mat<real>> mats(h->materials.size());
-    for (size_t i = 0; i < mats.size(); i++) {
-        const CrMaterial& m = h->materials[i];
-        Mat<real>& o = mats[i];
-        memset(&o, 0, sizeof o);
-        o.kind = m.kind; o.param = (real)m.param; o.tex = -1;
-        for (int k = 0; k < 3; k++) o.albedo[k] = (real)m.albedo[k];
-        if (m.kind == CR_MAT_LAMBERTIAN) {
-            const CrTexture& t = h->textures[m.texture];
-            if (t.kind == CR_TEX_SOLID) for (int k = 0; k < 3; k++) o.albedo[k] = (real)t.color[k];
-            else o.tex = tex_remap[m.texture];
-            o.aux = real(1) / r_abs(o.param);                       // Color / f64: (1.0 / rhs.abs()) * c
-        } else if (m.kind == CR_MAT_DIELECTRIC) {
-            auto r0 = [](real ri) { real q = (real(1) - ri) / (real(1) + ri); return q * q; };   // dielectric.rs:21-23
-            o.albedo[0] = real(1) / o.param;                        // ri for a front-face hit (dielectric.rs:33-37)
-            o.albedo[1] = r0(o.albedo[0]);
-            o.albedo[2] = r0(o.param);
-        }
-    }
+    for (size_t i = 0; i < mats.size(); i++) mats[i] = pack_mat<real>(h->materials[i], h->textures.data(), tex_remap.data());
     std::vector<Tex<real>> texs;
-    for (size_t i = 0; i < h->textures.size(); i++) {
-        if (tex_remap[i] < 0) continue;
-        const CrTexture& t = h->textures[i];
-        Tex<real> o;
-        memset(&o, 0, sizeof o);
-        o.kind = t.kind; o.image = t.image; o.inv_scale = (real)t.inv_scale;
-        o.even = t.kind == CR_TEX_CHECKER ? tex_remap[t.even] : -1;
-        o.odd = t.kind == CR_TEX_CHECKER ? tex_remap[t.odd] : -1;
-        for (int k = 0; k < 3; k++) o.color[k] = (real)t.color[k];
-        texs.push_back(o);
-    }
+    for (size_t i = 0; i < h->textures.size(); i++)
+        if (tex_remap[i] >= 0) texs.push_back(pack_tex<real>(h->textures[i], tex_remap.data()));
     std::vector<Key<real>> keys(h->keys.size());
     if (!keys.empty()) memset(keys.data(), 0, keys.size() * sizeof(Key<real>));
-    for (size_t i = 0; i < h->keys.size(); i++) {
-        const CrKeyframe& k = h->keys[i];
-        keys[i].t0 = (real)k.t0; keys[i].t1 = (real)k.t1; keys[i].a = (real)k.a; keys[i].b = (real)k.b;
-        keys[i].channel = k.channel; keys[i].interp = k.interp;
-    }
+    for (size_t i = 0; i < h->keys.size(); i++) key_to_real(h->keys[i], keys[i]);
 
     auto up = [&](DevBuf& d, const void* src_p, size_t bytes, size_t front_pad = 0) -> hipError_t {
         hipError_t e = d.ensure(bytes ? bytes : 16, front_pad);
@@ -907,10 +863,6 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     ds.built = true;
     h->upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return CR_OK;
-}
-
-template <typename real> void key_to_real(const CrKeyframe& k, Key<real>& o) {
-    o.t0 = (real)k.t0; o.t1 = (real)k.t1; o.a = (real)k.a; o.b = (real)k.b; o.channel = k.channel; o.interp = k.interp;
 }
 
 template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
@@ -1306,27 +1258,11 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.n_entries = ds.n_entries; a.n_prims = ds.n_prims; a.n_mats = ds.n_mats; a.n_texs = ds.n_texs;
     a.sky_kind = h->sky_kind; a.sky_image = h->sky_image;
 
-    // camera set-up: Radians::new_from_degrees (utils.rs:51-55), fix_viewport
-    // (rendering_compute.rs:5-11) and defocus_radius (:71-73) in f64, rounded once
-    const double PI64 = 3.14159265358979323846264338327950288;
+    // camera set-up (pack.hpp)
     CamConst<real>& c = a.cam;
-    c.W = cd->image_width; c.H = cd->image_height;
-    double vfov = cd->vfov_degrees * PI64 / 180.0;
-    double hh = std::tan(vfov / 2.0);
-    double vh = 2.0 * hh * cd->focus_dist;
-    double vw = vh * ((double)cd->image_width / (double)cd->image_height);
-    double da = cd->defocus_angle_degrees * PI64 / 180.0;
-    c.viewport_height = (real)vh; c.viewport_width = (real)vw; c.focus_dist = (real)cd->focus_dist;
-    c.defocus_on = !(da <= 0.0);
-    c.defocus_radius = (real)(cd->focus_dist * std::tan(da / 2.0));
-    c.from = mk<real>((real)cd->look_from[0], (real)cd->look_from[1], (real)cd->look_from[2]);
-    c.at = mk<real>((real)cd->look_at[0], (real)cd->look_at[1], (real)cd->look_at[2]);
-    c.vup = mk<real>((real)cd->vup[0], (real)cd->vup[1], (real)cd->vup[2]);
+    pack_camera(cd, c);
     int nk = cd->from_key_count + cd->at_key_count;
-    c.animated = nk > 0;
     if ((size_t)nk > CrHandle::kMaxCamKeys) return fail(h, CR_ERR_UNSUPPORTED, "more than 512 camera keyframes");
-    c.from_key_first = 0; c.from_key_count = cd->from_key_count;
-    c.at_key_first = cd->from_key_count; c.at_key_count = cd->at_key_count;
     a.cam_keys = nullptr;
     if (nk > 0) {   // per-launch slot: never overwritten while an earlier render may still read it
         const int slot = h->cam_next;
@@ -1353,20 +1289,12 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
         a.cam_keys = (const Key<real>*)h->cam_dev[slot].p;
         h->cam_pending_slot = slot;
     }
-    {   // static camera: same expression tree the kernel would evaluate per sample
-        V3<real> from = mk<real>(real(0) + c.from.x, real(0) + c.from.y, real(0) + c.from.z);
-        V3<real> at = mk<real>(real(0) + c.at.x, real(0) + c.at.y, real(0) + c.at.z);
-        from = scale(real(1), from); at = scale(real(1), at);   // build_other_scaler(1.0): s*x
-        CamFrame<real> f = camera_frame(c, from, at);
-        if (!c.animated) c.from = f.from;
-        c.p00 = f.p00; c.pdu = f.pdu; c.pdv = f.pdv; c.ddu = f.ddu; c.ddv = f.ddv;
-    }
+    pack_camera_frame(c);   // static camera: the per-sample vectors
 
     a.sample_begin = p->sample_begin; a.sample_end = p->sample_begin + p->sample_count;
     a.samples_total = p->samples; a.max_depth = p->max_depth;
     a.seed_mixed = mix64(p->seed + RNG_GAMMA);
-    a.current_time = (real)p->frame * (real(1) / (real)p->frame_rate);                       // ray_casting.rs:77
-    a.shutter_length = ((real)p->shutter_angle / real(360)) * (real(1) / (real)p->frame_rate);   // :79
+    frame_times(p, a.current_time, a.shutter_length);   // ray_casting.rs:77-79
     a.output_sum = p->output_sum;
     if (refit) {   // refit.hpp: wrapper boxes for this frame's ray times [current_time, current_time + shutter_length]
         const size_t bytes = (size_t)ds.n_entries * ds.entry_bytes;
@@ -1733,21 +1661,10 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
     h->keys.assign(s->keys, s->keys + s->n_keys);
     h->sky_kind = s->sky_kind; h->sky_image = s->sky_image; h->bvh_mode = s->bvh_mode;
     h->s32.built = false; h->s64.built = false;
-    // images: RGB8 -> RGBA8 words, one flat texel array
-    std::vector<ImageRef> refs(s->n_images);
-    size_t total = 0;
-    for (int i = 0; i < s->n_images; i++) {
-        refs[i].w = s->images[i].width; refs[i].h = s->images[i].height; refs[i].offset = (uint32_t)total; refs[i].pad = 0;
-        total += (size_t)s->images[i].width * s->images[i].height;
-    }
-    if (total >= ((size_t)1 << 32)) return fail(h, CR_ERR_INVALID_ARG, "too many texels");
-    std::vector<uint32_t> texels(total ? total : 1);
-    for (int i = 0; i < s->n_images; i++) {
-        const uint8_t* src = s->images[i].rgb8;
-        size_t n = (size_t)refs[i].w * refs[i].h;
-        uint32_t* dst = texels.data() + refs[i].offset;
-        for (size_t k = 0; k < n; k++) dst[k] = (uint32_t)src[3 * k] | ((uint32_t)src[3 * k + 1] << 8) | ((uint32_t)src[3 * k + 2] << 16);
-    }
+    // images: RGB8 -> RGBA8 words, one flat texel array (pack.hpp)
+    std::vector<ImageRef> refs;
+    std::vector<uint32_t> texels;
+    if (!pack_images(s->images, s->n_images, refs, texels)) return fail(h, CR_ERR_INVALID_ARG, "too many texels");
     HIP_TRY(h, h->images.ensure(refs.size() * sizeof(ImageRef) + 16));
     HIP_TRY(h, h->texels.ensure(texels.size() * 4));
     if (!refs.empty()) HIP_TRY(h, hipMemcpy(h->images.p, refs.data(), refs.size() * sizeof(ImageRef), hipMemcpyHostToDevice));

@@ -750,6 +750,20 @@ template <typename T> CR_D T load_rec(const T* p, bool in_lds) {
     return out;
 }
 
+// The texture a hit at p reads: nested checkers resolved down to a solid or image texture (checker_texture.rs:38-51; at most
+// CR_MAX_CHECKER_DEPTH levels, checked at upload).  ti / tx: the material's texture index and record on entry, the leaf's
+// on exit.  The parity of the three floors is taken on their wrapping 32-bit sum, as the reference's i32 additions wrap in
+// release builds.  A macro rather than a function so that shade() compiles to the code of the loop written in place: as a
+// function (by value or by reference, with or without #pragma nounroll) the kernels' code changed and grew by ~5 %.
+// tests/shade_check.hip drives it with chosen points.
+#define CR_CHECKER_LEAF(tex_at, ti, tx, p)                                                                                          \
+    for (int guard = 0; guard < 32 && tx.kind == 1; guard++) {                                                                   \
+        int32_t s = (int32_t)((uint32_t)as_i32(r_floor(tx.inv_scale * p.x)) + (uint32_t)as_i32(r_floor(tx.inv_scale * p.y)) +   \
+                              (uint32_t)as_i32(r_floor(tx.inv_scale * p.z)));                                                      \
+        ti = (s % 2 == 0) ? tx.even : tx.odd;                                                                                    \
+        tx = tex_at(ti);                                                                                                         \
+    }
+
 // What ray_color does after the closest-hit query (ray_casting.rs:122-151) for a path whose hit is
 // (best_t, best) -- best < 0 is a miss.  Returns true when the path is finished (col = the colour the
 // outermost ray_color call returns), false when it scattered (ro/rd replaced, depth_left decremented).
@@ -778,12 +792,7 @@ CR_D bool shade(const KernelArgs<real>& A, const Prim<real>* prims, const Mat<re
         if (m.kind == 0 && m.tex >= 0) {   // only image textures read u,v
             int ti = m.tex;
             Tex<real> tx = tex_at(ti);
-            for (int guard = 0; guard < 32 && tx.kind == 1; guard++) {   // checker_texture.rs:38-51; <= CR_MAX_CHECKER_DEPTH levels by upload
-                int32_t s = (int32_t)((uint32_t)as_i32(r_floor(tx.inv_scale * loc.x)) + (uint32_t)as_i32(r_floor(tx.inv_scale * loc.y)) +
-                                      (uint32_t)as_i32(r_floor(tx.inv_scale * loc.z)));
-                ti = (s % 2 == 0) ? tx.even : tx.odd;
-                tx = tex_at(ti);
-            }
+            CR_CHECKER_LEAF(tex_at, ti, tx, loc)
             need_uv = tx.kind == 2;
             leaf_tex = ti;
         }

@@ -19,7 +19,13 @@
 // part (the winning scale key and its value) are sampled at those times INDEPENDENTLY and every combination is
 // united: between two consecutive sample times both parts are linear, so the vertex is a bilinear function of
 // (translate time, scale time) there and its coordinates are bounded by the four corner combinations, all of which
-// are among the pairs.  Conservative (a superset), never too small.
+// are among the pairs.
+//
+// Those arguments hold for the exact values.  The computed ones are rounded sums of rounded products, which can stray past
+// the values at the sample times by a few units in the last place of the largest magnitude met -- keys of opposite signs
+// on one channel, a centre moving while the radius shrinks.  Every face of a keyed primitive's box therefore moves out by
+// timeline_pad, a bound on twice that error.  And the value at a sample time is its right limit: a zero-length LERP key
+// evaluated at its own instant gives 0/0, but just after it the key is complete.  Conservative (a superset), never too small.
 //
 // On a scene without primitive keys this reproduces the construction-time boxes exactly.  The topology is never
 // changed.  (The test suite's CPU checker applies the same rule to its own tree.)
@@ -28,8 +34,9 @@
 
 namespace cr {
 
-// combine_and_compute (timeline/mod.rs:233-263) with a switch for the left limit at a key start:
-// before_start = true treats a key whose t0 equals t as not yet active.
+// combine_and_compute (timeline/mod.rs:233-263) with a switch for the one-sided limits at t: before_start = true treats a
+// key whose t0 equals t as not yet active (the left limit at a key start); false counts a key whose t1 equals t as complete
+// (the right limit: s = 1, which only a zero-length key does not already reach at t1, where it gives 0/0).
 template <typename real>
 CR_HD void timeline_eval_side(const Key<real>* keys, int n, real t, bool before_start, real& x, real& y, real& z, real& w,
                               int32_t* skind = nullptr) {
@@ -40,7 +47,7 @@ CR_HD void timeline_eval_side(const Key<real>* keys, int n, real t, bool before_
         bool started = before_start ? (k.t0 < t) : (k.t0 <= t);
         bool active = (t > k.t1) || (started && t <= k.t1);
         if (!active) continue;
-        real s = clamp01((t - k.t0) / (k.t1 - k.t0));
+        real s = (!before_start && t >= k.t1) ? real(1) : clamp01((t - k.t0) / (k.t1 - k.t0));
         if (k.channel <= 2) {
             real val = k.interp ? k.a * s : k.a;
             if (k.channel == 0) x = x + val; else if (k.channel == 1) y = y + val; else z = z + val;
@@ -50,6 +57,31 @@ CR_HD void timeline_eval_side(const Key<real>* keys, int n, real t, bool before_
         }
     }
     if (skind) *skind = sk;
+}
+
+// How far every face of a keyed primitive's box moves out (header comment): B * (4 n + 32) * 2^-p for n keys and precision p,
+// B a bound on every magnitude the evaluation meets -- G the largest initial coordinate (and radius), T the sum of the
+// translate keys' |a|, V the largest scale value (1, or a scale key's |a| or |b|): B = G + T + V for a sphere (c +- r), and
+// (V + 1) (G + T) for a triangle (v x + y).  Each channel is n rounded additions of rounded a * s terms; the bound covers
+// twice that error with room to spare.  Not a number (a key that is not): +inf, the box becomes unbounded.  Zero when no key
+// moves anything (every key NERP, a LERP translate by 0 or a LERP scale from a value to itself): the computed values are
+// then constant between key starts, and the samples take each of them exactly.
+template <typename real> CR_HD real timeline_pad(const Prim<real>& p, const Key<real>* keys) {
+    const Key<real>* k = keys + p.key_first;
+    real g = real(0), tr = real(0), v = real(1);
+    bool moving = false;
+    const int ng = p.kind() == 0 ? 4 : 9;
+    for (int i = 0; i < ng; i++) g = r_fmax(g, r_abs(p.g[i]));
+    for (int i = 0; i < p.key_count; i++) {
+        if (k[i].channel <= 2) tr = tr + r_abs(k[i].a);
+        else v = r_fmax(v, r_fmax(r_abs(k[i].a), r_abs(k[i].b)));
+        moving |= k[i].interp && (k[i].channel <= 2 ? k[i].a != real(0) : k[i].a != k[i].b);
+    }
+    if (!moving) return real(0);
+    const real b = p.kind() == 0 ? (g + tr) + v : (v + real(1)) * (g + tr);
+    const real eps = sizeof(real) == 8 ? real(0x1.0p-53) : real(0x1.0p-24);
+    const real pad = b * ((real)(4 * p.key_count + 32) * eps);
+    return pad == pad ? pad : r_inf(real(0));
 }
 
 // A sample box with a coordinate that is not a number is not united (a zero-length LERP key evaluated exactly at its
@@ -66,10 +98,11 @@ template <typename real> CR_HD void enclose(real lo[3], real hi[3], const real b
 }
 
 // Box of primitive p with its translate part taken at time t and its scale part at time ts, united into lo/hi
-// (ts = t, bs = before_start: the box at one time).  use_keys = false: the construction-time box (no keys applied).
+// (ts = t, bs = before_start: the box at one time), its faces moved out by pad.  use_keys = false: the construction-time
+// box (no keys applied; pad 0 leaves it exact).
 template <typename real>
 CR_HD void prim_box_at2(const Prim<real>& p, const Key<real>* keys, real t, bool before_start, real ts, bool bs, real lo[3], real hi[3],
-                        bool use_keys = true) {
+                        bool use_keys = true, real pad = real(0)) {
     real blo[3], bhi[3];
     const Key<real>* k = keys + p.key_first;
     const int32_t n_keys = use_keys ? p.key_count : 0;
@@ -84,15 +117,16 @@ CR_HD void prim_box_at2(const Prim<real>& p, const Key<real>* keys, real t, bool
         v[j][0] = q.x; v[j][1] = q.y; v[j][2] = q.z;
     }
     for (int a = 0; a < 3; a++) {
-        bhi[a] = r_fmax(v[0][a], r_fmax(v[1][a], v[2][a]));
-        blo[a] = r_fmin(v[0][a], r_fmin(v[1][a], v[2][a]));
+        bhi[a] = r_fmax(v[0][a], r_fmax(v[1][a], v[2][a])) + pad;
+        blo[a] = r_fmin(v[0][a], r_fmin(v[1][a], v[2][a])) - pad;
     }
     if (box_is_number(blo, bhi)) enclose(lo, hi, blo, bhi);
 }
 
 template <typename real>
-CR_HD void prim_box_at(const Prim<real>& p, const Key<real>* keys, real t, bool before_start, real lo[3], real hi[3], bool use_keys = true) {
-    if (p.kind() != 0) { prim_box_at2(p, keys, t, before_start, t, before_start, lo, hi, use_keys); return; }
+CR_HD void prim_box_at(const Prim<real>& p, const Key<real>* keys, real t, bool before_start, real lo[3], real hi[3], bool use_keys = true,
+                       real pad = real(0)) {
+    if (p.kind() != 0) { prim_box_at2(p, keys, t, before_start, t, before_start, lo, hi, use_keys, pad); return; }
     real blo[3], bhi[3];
     const Key<real>* k = keys + p.key_first;
     const int32_t n_keys = use_keys ? p.key_count : 0;
@@ -101,7 +135,7 @@ CR_HD void prim_box_at(const Prim<real>& p, const Key<real>* keys, real t, bool 
         timeline_eval_side(k, n_keys, t, before_start, c[0], c[1], c[2], r);
         for (int a = 0; a < 3; a++) {
             real l = c[a] + (-r), h = c[a] + r;
-            if (l <= h) { blo[a] = l; bhi[a] = h; } else { blo[a] = h; bhi[a] = l; }
+            if (l <= h) { blo[a] = l - pad; bhi[a] = h + pad; } else { blo[a] = h - pad; bhi[a] = l + pad; }
         }
     }
     if (box_is_number(blo, bhi)) enclose(lo, hi, blo, bhi);
@@ -121,11 +155,14 @@ CR_HD bool refit_sample(const Prim<real>& p, const Key<real>* keys, real ta, rea
     return ta < k.t1 && k.t1 < tb;
 }
 
-// Box of primitive p over ray times [ta, tb], united into lo/hi (rule in the header comment).
+// Box of primitive p over ray times [ta, tb], united into lo/hi (rule in the header comment).  use_keys = false, or no
+// keys: the construction-time box, exactly.  Every sample box is grown by timeline_pad before it is united (the same
+// bits as growing the union: rounding is monotone).
 template <typename real>
 CR_HD void prim_box_over(const Prim<real>& p, const Key<real>* keys, real ta, real tb, real lo[3], real hi[3], bool use_keys = true) {
-    prim_box_at(p, keys, ta, false, lo, hi, use_keys);
-    if (!use_keys || p.key_count == 0) return;
+    if (!use_keys || p.key_count == 0) { prim_box_at(p, keys, ta, false, lo, hi, use_keys); return; }
+    const real pad = timeline_pad(p, keys);
+    prim_box_at(p, keys, ta, false, lo, hi, true, pad);
     bool scaled = false;   // ScaleX / ScaleY / ScaleZ keys: translate and scale parts sampled independently
     for (int i = 0; i < p.key_count; i++) scaled |= keys[p.key_first + i].channel >= 4;
     if (scaled) {
@@ -135,19 +172,19 @@ CR_HD void prim_box_over(const Prim<real>& p, const Key<real>* keys, real ta, re
             if (!refit_sample(p, keys, ta, tb, i, t1, b1)) continue;
             for (int32_t j = 0; j < n; j++) {
                 real t2; bool b2;
-                if (refit_sample(p, keys, ta, tb, j, t2, b2)) prim_box_at2(p, keys, t1, b1, t2, b2, lo, hi);
+                if (refit_sample(p, keys, ta, tb, j, t2, b2)) prim_box_at2(p, keys, t1, b1, t2, b2, lo, hi, true, pad);
             }
         }
         return;
     }
-    prim_box_at(p, keys, tb, false, lo, hi);
+    prim_box_at(p, keys, tb, false, lo, hi, true, pad);
     for (int i = 0; i < p.key_count; i++) {
         const Key<real> k = keys[p.key_first + i];
         if (ta < k.t0 && k.t0 <= tb) {
-            prim_box_at(p, keys, k.t0, false, lo, hi);
-            prim_box_at(p, keys, k.t0, true, lo, hi);
+            prim_box_at(p, keys, k.t0, false, lo, hi, true, pad);
+            prim_box_at(p, keys, k.t0, true, lo, hi, true, pad);
         }
-        if (ta < k.t1 && k.t1 < tb) prim_box_at(p, keys, k.t1, false, lo, hi);
+        if (ta < k.t1 && k.t1 < tb) prim_box_at(p, keys, k.t1, false, lo, hi, true, pad);
     }
 }
 

@@ -67,6 +67,7 @@ typedef float real;
 #define LIBM_ASIN asinf
 #define LIBM_ACOS acosf
 #define R_FMIN fminf
+#define R_FMAX fmaxf
 #define R_EPSILON FLT_EPSILON
 #define R_INF HUGE_VALF
 #define ORACLE_REAL_TYPE CR_REAL_F32
@@ -79,6 +80,7 @@ typedef double real;
 #define LIBM_ASIN asin
 #define LIBM_ACOS acos
 #define R_FMIN fmin
+#define R_FMAX fmax
 #define R_EPSILON DBL_EPSILON
 #define R_INF HUGE_VAL
 #define ORACLE_REAL_TYPE CR_REAL_F64
@@ -372,8 +374,10 @@ static void scale_apply(int skind, real v, real x, real y, real z, real out[4]) 
  * build_sphere_scaler (w = radius, xyz untouched) vs the non-sphere scale
  * matrices of scale_apply.
  * side: 0 = the value at t; 1 = the left limit at a key start (a key whose t0 equals t counts as not yet
- * active) -- used by the refit rule only.  tr / sc: which parts to evaluate at this t (the refit rule samples
- * them independently): the translate part goes to xyz[0..2], the scale part to *w and *skind. */
+ * active); 2 = the right limit (a key whose t1 equals t counts as complete, s = 1: only a zero-length key, which
+ * gives 0/0 at its own instant, differs from the value) -- 1 and 2 are used by the refit rule only.  tr / sc: which
+ * parts to evaluate at this t (the refit rule samples them independently): the translate part goes to xyz[0..2], the
+ * scale part to *w and *skind. */
 static void timeline_parts(const Timeline* tl, real t, int side, real xyz[3], real* w, int* skind) {
     real x = R(0.0) + tl->init[0], y = R(0.0) + tl->init[1], z = R(0.0) + tl->init[2];
     real wv = tl->init[3];
@@ -381,12 +385,12 @@ static void timeline_parts(const Timeline* tl, real t, int side, real xyz[3], re
     for (int i = 0; i < tl->n_keys; i++) {
         const Key* k = &tl->keys[i];
         int active;
-        if (side) {
+        if (side == 1) {
             int started = k->t0 < t;
             active = (t > k->t1) || (started && t <= k->t1);
         } else active = key_active(k, t);
         if (!active) continue;
-        real s = key_scaled_time(k, t);
+        real s = (side == 2 && t >= k->t1) ? R(1.0) : key_scaled_time(k, t);
         if (k->channel <= CR_KEY_TZ) {
             real val = (k->interp == CR_KEY_LERP) ? k->a * s : k->a;
             if (k->channel == CR_KEY_TX) x = x + val;
@@ -1175,13 +1179,15 @@ EXPORT Scene* oracle_scene_create(const CrSceneDesc* d) {
  * every key end inside (ta, tb) and every key start inside (ta, tb] with the key active and not yet active; a
  * wrapper's box is aabb_from_boxes of its children.  The reference never recomputes wrapper boxes
  * (bvhwrapper.rs:47-50,102-106), so this mode is pinned by construction only: against the linear list
- * (oracle_use_list) it must give the same closest hits. */
-/* the primitive's box with its translate part taken at (t, side) and its scale part at (ts, side_s) */
+ * (oracle_use_list) it must give the same closest hits.  The value at a sample time is its right limit, and a keyed
+ * primitive's box grows by timeline_pad on every face, both as in refit.hpp. */
+/* the primitive's box with its translate part taken at (t, side) and its scale part at (ts, side_s); side 0 is the right
+ * limit at t, 1 the left limit at a key start */
 static Aabb prim_box_at2(const Hittable* h, real t, int side, real ts, int side_s) {
     real p[3], p2[3], w, w2;
     int sk, sk2;
     if (h->kind == H_SPHERE) {
-        timeline_parts(&h->tl, t, side, p, &w, &sk);
+        timeline_parts(&h->tl, t, side ? 1 : 2, p, &w, &sk);
         return sphere_bbox(v3(p[0], p[1], p[2]), w);
     }
     Timeline tl[3] = {h->tl, h->tl, h->tl};
@@ -1190,8 +1196,8 @@ static Aabb prim_box_at2(const Hittable* h, real t, int side, real ts, int side_
     Vec3 v[3];
     for (int j = 0; j < 3; j++) {
         real o[4];
-        timeline_parts(&tl[j], t, side, p, &w, &sk);
-        timeline_parts(&tl[j], ts, side_s, p2, &w2, &sk2);
+        timeline_parts(&tl[j], t, side ? 1 : 2, p, &w, &sk);
+        timeline_parts(&tl[j], ts, side_s ? 1 : 2, p2, &w2, &sk2);
         scale_apply(sk2, w2, p[0], p[1], p[2], o);
         v[j] = v3(o[0], o[1], o[2]);
     }
@@ -1214,14 +1220,44 @@ static Aabb unite_sample(Aabb acc, Aabb s) {
     if (!(s.x.min == s.x.min && s.x.max == s.x.max && s.y.min == s.y.min && s.y.max == s.y.max && s.z.min == s.z.min && s.z.max == s.z.max)) return acc;
     return aabb_from_boxes(acc, s);
 }
+/* refit.hpp timeline_pad: B * (4 n + 32) * 2^-p, B = G + T + V (sphere) or (V + 1) (G + T) (triangle); 0 when no key moves */
+static real timeline_pad(const Hittable* h) {
+    real g = R(0.0), tr = R(0.0), v = R(1.0);
+    int moving = 0;
+    if (h->kind == H_SPHERE) for (int i = 0; i < 4; i++) g = R_FMAX(g, R_FABS(h->tl.init[i]));
+    else for (int i = 0; i < 3; i++) {
+        g = R_FMAX(g, R_FABS(h->tl.init[i])); g = R_FMAX(g, R_FABS(h->vb[i])); g = R_FMAX(g, R_FABS(h->vc[i]));
+    }
+    for (int i = 0; i < h->tl.n_keys; i++) {
+        const Key* k = &h->tl.keys[i];
+        if (k->channel <= CR_KEY_TZ) tr = tr + R_FABS(k->a);
+        else v = R_FMAX(v, R_FMAX(R_FABS(k->a), R_FABS(k->b)));
+        moving |= k->interp == CR_KEY_LERP && (k->channel <= CR_KEY_TZ ? k->a != R(0.0) : k->a != k->b);
+    }
+    if (!moving) return R(0.0);
+    const real b = h->kind == H_SPHERE ? (g + tr) + v : (v + R(1.0)) * (g + tr);
+    const real eps = sizeof(real) == 8 ? R(0x1.0p-53) : R(0x1.0p-24);
+    const real pad = b * ((real)(4 * h->tl.n_keys + 32) * eps);
+    return pad == pad ? pad : R_INF;
+}
+static Aabb prim_box_samples(const Hittable* h, real ta, real tb);
 static Aabb prim_box_over(const Hittable* h, real ta, real tb) {
     if (h->kind == H_HITLIST) {   /* the visible objects' boxes, united in the list's order */
         Aabb l = aabb_empty();
         for (int i = 0; i < h->n_objs; i++) if (!h->objs[i]->hide) l = aabb_from_boxes(l, prim_box_over(h->objs[i], ta, tb));
         return l;
     }
+    if (h->tl.n_keys == 0) return unite_sample(aabb_empty(), prim_box_at(h, ta, 0));
+    Aabb b = prim_box_samples(h, ta, tb);
+    if (!(b.x.min <= b.x.max)) return b;   /* no sample was a number */
+    const real pad = timeline_pad(h);
+    b.x.min = b.x.min - pad; b.x.max = b.x.max + pad;
+    b.y.min = b.y.min - pad; b.y.max = b.y.max + pad;
+    b.z.min = b.z.min - pad; b.z.max = b.z.max + pad;
+    return b;
+}
+static Aabb prim_box_samples(const Hittable* h, real ta, real tb) {
     Aabb b = unite_sample(aabb_empty(), prim_box_at(h, ta, 0));
-    if (h->tl.n_keys == 0) return b;
     int scaled = 0;
     for (int i = 0; i < h->tl.n_keys; i++) scaled |= h->tl.keys[i].channel >= CR_KEY_SCALE_X;
     if (scaled) {   /* translate and scale parts sampled independently, every pair united (refit.hpp) */
