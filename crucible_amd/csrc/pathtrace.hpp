@@ -647,7 +647,7 @@ template <typename real> CR_D real r_acos(real x) { return soft_acos(x); }
 // unit vector with ~36 lanes drawing), and in f64 most of a round is converting three 64-bit draws to doubles just to
 // throw half of them away.  The screen uses the top 24 bits of each draw: xf = -1 + 2*(u >> 40)*2^-24 is EXACT in f32
 // and within 2^-23 of the f64 coordinate, so the f32 squared length lf differs from the f64 one by less than 2e-6
-// (3 * 2 * 2^-23 from the truncation, < 1e-6 from f32 rounding).  Hence
+// (3 * 2 * 2^-23 from the truncation; lf is one product and two FMAs, each rounded once: < 4e-7 from f32 rounding).  Hence
 //     lf > 1 + 1e-5              =>  the reference's test `lensq <= 1` fails      -> next round, nothing converted
 //     1e-5 < lf < 1 - 1e-5       =>  it passes (1e-160 < lensq <= 1)             -> leave the loop with the raw draws
 // and only a candidate inside the 2e-5 band (or with lf <= 1e-5) is decided by evaluating the reference's f64
@@ -664,7 +664,7 @@ template <typename real> CR_D V3<real> random_unit_vector_dev(uint64_t& s) {
         for (;;) {
             ux = rng_next(s); uy = rng_next(s); uz = rng_next(s);
             const float fx = screen_coord(ux), fy = screen_coord(uy), fz = screen_coord(uz);
-            const float lf = fx * fx + fy * fy + fz * fz;
+            const float lf = __builtin_fmaf(fz, fz, __builtin_fmaf(fy, fy, fx * fx));
             if (lf > 1.0f + 1e-5f) continue;
             if (lf > 1e-5f && lf < 1.0f - 1e-5f) break;
             const double x = -1.0 + 2.0 * u01(ux, 0.0), y = -1.0 + 2.0 * u01(uy, 0.0), z = -1.0 + 2.0 * u01(uz, 0.0);
@@ -688,7 +688,7 @@ template <typename real> CR_D void random_in_unit_disk_dev(uint64_t& s, real& px
         for (;;) {
             ux = rng_next(s); uy = rng_next(s);
             const float fx = screen_coord(ux), fy = screen_coord(uy);
-            const float lf = fx * fx + fy * fy;
+            const float lf = __builtin_fmaf(fy, fy, fx * fx);
             if (lf > 1.0f + 1e-5f) continue;
             if (lf < 1.0f - 1e-5f) break;
             const double x = -1.0 + 2.0 * u01(ux, 0.0), y = -1.0 + 2.0 * u01(uy, 0.0);
@@ -1081,17 +1081,31 @@ template <typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd) {
 // f32 kernels (unordered trees): the record holds the wrapper's own box and the test on it is Aabb::hit (EXACT below).
 // f64 kernels: Aabb::hit decided on the f32 screening record wherever f32 can decide it:
 // Notation: b, o, inv = an f64 box plane, the origin component and 1/direction on that axis; bf, of, if their f32
-// roundings; u = 2^-24; T = (b - o) * inv; t32 = fl(fl(bf - of) * if) the f32 slab distance.  Then
-//     |t32 - T| <= 1.01 u |inv| (|b| + |o|) + 3.01 u |t32|          (three roundings of inputs, two of operations)
-// and, because |inv| |b| <= |T| + |inv| |o|,
-//     |t32 - T| <= 4.03 u |t32| + 2.03 u |inv| |o|                   (the f64 test's own roundings, 2^-52 |T|, vanish in the slack).
-// lo32 = max(nears, 0.001) and hi32 = min(fars, tmax32): an operand can decide the f64 result only if its own value lies
-// within the two errors of the f32 winner, so the end's error is bounded by the same expression in |lo32| resp. |hi32|
-// (to first order in u); an interval end that wins was rounded once (u |end|); the subtraction rounds once more.  With
-// M = max(|lo32|, |hi32|) and Q = max over the axes of |if of|,
-//     TH = 2^-20 M + 2^-21 Q + 2^-147 max |if| + 1e-35
-// is at least 1.5 times the largest possible |(hi32 - lo32) - (hi - lo)| (10.1 u M + 4.06 u Q; the last two terms cover
-// a box plane or origin component below the normal f32 range and a product that underflows).  Hence hi32 - lo32 < -TH proves Aabb::hit's
+// roundings; u = 2^-24; T = (b - o) * inv; p = fl(of * if), computed once per ray; t32 = fl(bf * if - p), one FMA, the
+// f32 slab distance (the screen is the project's own estimate, not the reference's arithmetic: the parity rule's
+// -ffp-contract=off does not bind it, the bound below does).  For normal f32 values write bf = b (1 + B), of = o (1 + W),
+// if = inv (1 + I), p = of if (1 + P) and t32 = x (1 + F) with x = bf if - p exact inside the FMA; |B|, |W|, |I|, |P|,
+// |F| <= u.  Then
+//     x - T = b inv (B + I + B I) - o inv (W + I + P + W I + W P + I P + W I P)
+//     |x - T| <= (2u + u^2) |b inv| + (3u + 3u^2 + u^3) |o inv|,    |t32 - x| <= u |t32|       (round to nearest)
+// and with |b inv| <= |T| + |o inv| and |T| <= |t32| + E, E = |t32 - T|:  E (1 - 2u - u^2) <= (3u + u^2) |t32| +
+// (5u + 4u^2 + u^3) |o inv|, i.e.
+//     |t32 - T| <= 3.01 u |t32| + 5.02 u |p|         (|o inv| <= (1 + 3.01 u) |p|; the f64 test's own roundings, 2^-52 |T|,
+//                                                     vanish in the slack).
+// Below the normal f32 range each rounding errs by at most 2^-150 absolutely instead: bf and of add 2^-150 |if| each to
+// |x - T| (times 1 + 2u), p and the FMA 2^-150 each -- per slab at most 2^-149 (|if| + 1) (1 + 3u).
+// lo32 = max(nears, 0.001) and hi32 = min(fars, tmax32) (min and max are exact): if operand i wins in f32 and j in f64,
+// lo32 - lo <= E_i and lo - lo32 <= E_j with |t32_j| <= |lo32| + E_i + E_j, so each end errs by the bound above in
+// |lo32| resp. |hi32| (to first order in u; an end that is 0.001 or tmax32 was rounded once, u |end|, which is less).  A
+// slab distance that overflows is +-inf on the side of T: it loses to a finite end on both sides, or makes M infinite.
+// The subtraction hi32 - lo32 rounds once more (u |hi32 - lo32| <= 2u M).  With M = max(|lo32|, |hi32|) and
+// Q = max over the axes of |p|:
+//     |(hi32 - lo32) - (hi - lo)| <= (2 * 3.01 + 2) u M + 2 * 5.02 u Q + 2^-148 (max |if| + 1)  =  8.02 u M + 10.04 u Q + ...
+// and 1.5 times that is 12.03 u M + 15.06 u Q + 1.5 * 2^-148 (max |if| + 1).  The kernel uses
+//     TH = 2^-20 M + 2^-20 Q + 2^-147 max |if| + 1e-35
+// (16u M and 16u Q, each rounded in f32 at most twice: >= 15.99u; 2^-147 = 4 * 2^-149 > 1.5 * 2^-148; 1e-35 covers the rest,
+// and the 2^-147 term itself where it underflows).  A product p beyond the f32 range is inf: then TH = inf and every
+// test of the ray lands in the band.  Hence hi32 - lo32 < -TH proves Aabb::hit's
 // `max <= min` (a miss), hi32 - lo32 > TH proves a hit, and only a lane with |hi32 - lo32| <= TH evaluates Aabb::hit in f64
 // on the f64 box.  Overflow and NaN land there too (every comparison with them is false), and the round uses the screen only
 // when |if| lies in [2^-100, 2^100] and |of| <= 2^100 on every axis, on trees whose f64 planes all lie in the f32 range
@@ -1102,8 +1116,8 @@ template <typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd) {
 // The screen's pieces, one record at a time (tests/walk_check.hip runs them on the device).  of*, if*: the f32 roundings of
 // the origin and of 1/direction; mo = max |of|, pmax / pmin = max / min |if|.  screen_in_range: a ray the f64 screen may decide
 // (finite 1/direction, and the range above); screen_th0: from Q's three terms screen_q, the part of TH
-// that does not depend on the box -- 2^-21 Q, plus what rounding a box plane or an origin component BELOW the normal f32
-// range can add (2^-149 each, times |if| <= 2^100), plus a product that underflows.
+// that does not depend on the box -- 2^-20 Q, plus what rounding a box plane or an origin component BELOW the normal f32
+// range can add (2^-150 each, times |if| <= 2^100), plus a product or an FMA that underflows.
 CR_D void screen_extents(float ofx, float ofy, float ofz, float ifx, float ify, float ifz, float& mo, float& pmax, float& pmin) {
     mo = r_max(r_max(__builtin_fabsf(ofx), __builtin_fabsf(ofy)), __builtin_fabsf(ofz));
     pmax = r_max(r_max(__builtin_fabsf(ifx), __builtin_fabsf(ify)), __builtin_fabsf(ifz));
@@ -1114,7 +1128,7 @@ CR_D bool screen_in_range(bool exact_box, float mo, float pmax, float pmin) {
 }
 CR_D float screen_q(float of, float inv_f) { return __builtin_fabsf(of * inv_f); }   // |of if| on one axis
 CR_D float screen_th0(float qx, float qy, float qz, float pmax) {
-    return __builtin_fmaf(0x1.0p-21f, r_max(r_max(qx, qy), qz), __builtin_fmaf(pmax * 0x1.0p-100f, 0x1.0p-47f, 1e-35f));
+    return __builtin_fmaf(0x1.0p-20f, r_max(r_max(qx, qy), qz), __builtin_fmaf(pmax * 0x1.0p-100f, 0x1.0p-47f, 1e-35f));
 }
 // f64 kernels: hi32 - lo32 on the screening box b, and its TH in `th`.  The decision is d < -th (miss) or d > th (hit);
 // anything else (NaN included) is left to Aabb::hit in f64.
@@ -1123,9 +1137,11 @@ CR_D float screen_th0(float qx, float qy, float qz, float pmax) {
 // cannot see that it is a number), and one VALU instruction in the walk loop is about 1.5 % of the frame
 CR_D float screen_box_d(const float* b, Pair<float> fox, Pair<float> foy, Pair<float> foz, Pair<float> fix, Pair<float> fiy, Pair<float> fiz,
                         float tminf, float tmaxf, float th0, float& th) {
-    const Pair<float> tx = (Pair<float>{b[0], b[1]} - fox) * fix;
-    const Pair<float> ty = (Pair<float>{b[2], b[3]} - foy) * fiy;
-    const Pair<float> tz = (Pair<float>{b[4], b[5]} - foz) * fiz;
+    // t = fma(bf, if, -p) with p = fl(of if), the same product as screen_q: loop-invariant, so the compiler hoists it and
+    // each axis is one v_pk_fma_f32 (the bound above is derived for this form; -ffp-contract=off does not bind the screen)
+    const Pair<float> tx = __builtin_elementwise_fma(Pair<float>{b[0], b[1]}, fix, -(fox * fix));
+    const Pair<float> ty = __builtin_elementwise_fma(Pair<float>{b[2], b[3]}, fiy, -(foy * fiy));
+    const Pair<float> tz = __builtin_elementwise_fma(Pair<float>{b[4], b[5]}, fiz, -(foz * fiz));
     const float nx = r_min(tx.x, tx.y), ny = r_min(ty.x, ty.y), nz = r_min(tz.x, tz.y);
     const float fx = r_max(tx.x, tx.y), fy = r_max(ty.x, ty.y), fz = r_max(tz.x, tz.y);
     const float lo = r_max(r_max(nx, ny), r_max(nz, tminf));
