@@ -1,7 +1,7 @@
 """ctypes mirror of include/crucible_hip.h (the C ABI).  Plain data only."""
 import ctypes as C
 
-CR_ABI_VERSION = 3
+CR_ABI_VERSION = 4
 
 CR_OK, CR_ERR_INVALID_ARG, CR_ERR_NO_DEVICE, CR_ERR_HIP, CR_ERR_NO_SCENE, CR_ERR_IO, CR_ERR_NAN, CR_ERR_UNSUPPORTED, CR_ERR_PEER = range(9)
 CR_REAL_F32, CR_REAL_F64 = 0, 1
@@ -15,6 +15,7 @@ CR_KEY_TX, CR_KEY_TY, CR_KEY_TZ, CR_KEY_RADIUS, CR_KEY_SCALE_X, CR_KEY_SCALE_Y, 
 CR_MAX_CHECKER_DEPTH = 32
 CR_KEY_NERP, CR_KEY_LERP = 0, 1
 CR_SUM_DEFAULT, CR_SUM_REFERENCE_ORDER, CR_SUM_RELAXED = 0, 1, 2
+CR_OUTPUT_FIXED_SUM = 2   # CrRenderParams.output_sum: 0 mean, 1 sum in reals, 2 fixed-point words (uint64)
 
 
 class CrPrimitive(C.Structure):
@@ -96,6 +97,7 @@ SYMBOLS = {
     "cr_write_ppm_binary": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "cr_write_png": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "cr_quantize_rgb8": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "cr_fixed_sums_to_rgb": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "cr_last_error": (C.c_char_p, [C.c_void_p]),
     "cr_group_shard": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cr_group_create": (C.c_int32, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),

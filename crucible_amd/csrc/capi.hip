@@ -865,6 +865,29 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     return CR_OK;
 }
 
+// CR_SUM_RELAXED's fixed-point scale 2^S for n samples per pixel: n * 2^S < 2^63, S = 52 up to 2047 samples
+double fx_scale_for(int64_t n) {
+    int lg = 0;
+    while ((n >> (lg + 1)) > 0) lg++;
+    return std::ldexp(1.0, std::min(52, 62 - lg));
+}
+
+// fixed-point sums of a whole frame of `samples` samples per pixel -> its per-pixel means, as launch() finalizes them
+int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n, int32_t samples, bool f64, void* out) {
+    const double inv_scale = 1.0 / fx_scale_for(samples);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (f64) hipLaunchKernelGGL((fx_finalize_kernel<double>), grid, dim3(256), 0, h->stream, sums, (double*)out, n, inv_scale, (double)samples, 0);
+    else hipLaunchKernelGGL((fx_finalize_kernel<float>), grid, dim3(256), 0, h->stream, sums, (float*)out, n, inv_scale, (double)samples, 0);
+    HIP_TRY(h, hipGetLastError());
+    return CR_OK;
+}
+
+// what CrRenderParams.sum_order means on this handle: CR_SUM_DEFAULT is the handle's default in the megakernel and the
+// reference order in the alternative pipelines
+int resolve_sum_order(const CrHandle* h, const CrRenderParams* p) {
+    return p->sum_order == CR_SUM_DEFAULT ? (h->pipeline == 0 ? h->default_sum_order : CR_SUM_REFERENCE_ORDER) : p->sum_order;
+}
+
 template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
 int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats) {
     constexpr bool LDS = RES != RES_GLOBAL || RELAX;
@@ -920,7 +943,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         // the buffer holds one colour per work item of a batch: whole tiles and whole sample groups (edge padding included)
         if constexpr (RELAX) {
             if (batch <= 0) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
-            HIP_TRY(h, h->fx_acc.ensure(npix * 3 * sizeof(unsigned long long)));
+            if (args.output_sum != CR_OUTPUT_FIXED_SUM) HIP_TRY(h, h->fx_acc.ensure(npix * 3 * sizeof(unsigned long long)));
         } else {
             auto batch_bytes = [&](int32_t b) { return (size_t)tiles * ((size_t)(b + (int32_t)ns - 1) / ns) * 64u * 3u * sizeof(real); };
             while (batch > (int32_t)ns && batch_bytes(batch) > std::max(h->sample_buf_limit, batch_bytes((int32_t)ns))) batch -= (int32_t)ns;
@@ -944,13 +967,12 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         HIP_TRY(h, h->att_stack.ensure(stack_bytes));
         args.att_stack = (real*)h->att_stack.p;
     } else {
-        // n * 2^S < 2^63 for the n samples a pixel receives in this render: S = 52 up to 2047 samples
-        int lg = 0;
-        while (((int64_t)(s_end - s_begin) >> (lg + 1)) > 0) lg++;
-        const int S = std::min(52, 62 - lg);
-        args.fx_scale = std::ldexp(1.0, S);
-        args.fx_acc = (unsigned long long*)h->fx_acc.p;
-        HIP_TRY(h, hipMemsetAsync(h->fx_acc.p, 0, npix * 3 * sizeof(unsigned long long), h->stream));
+        // the scale of the n samples a pixel receives in this render; CR_OUTPUT_FIXED_SUM: of the whole frame, so the words
+        // of any shards of it add up to the frame's, and they go straight into the caller's buffer
+        const bool fixed = args.output_sum == CR_OUTPUT_FIXED_SUM;
+        args.fx_scale = fx_scale_for(fixed ? args.samples_total : s_end - s_begin);
+        args.fx_acc = fixed ? (unsigned long long*)args.out : (unsigned long long*)h->fx_acc.p;
+        HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, npix * 3 * sizeof(unsigned long long), h->stream));
     }
     HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -981,7 +1003,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
                                (real*)h->sg_acc.p, b1 - b0, b0 == s_begin ? 1 : 0, b1 == s_end ? 1 : 0);
             HIP_TRY(h, hipGetLastError());
         }
-        if constexpr (RELAX) {
+        if constexpr (RELAX) if (args.output_sum != CR_OUTPUT_FIXED_SUM) {
             const size_t n = npix * 3;
             hipLaunchKernelGGL((fx_finalize_kernel<real>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                                (const unsigned long long*)h->fx_acc.p, args.out, n, 1.0 / args.fx_scale, (double)args.samples_total, args.output_sum);
@@ -1231,10 +1253,14 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     int32_t rc = build_dev_scene<real>(h);
     if (rc != CR_OK) return rc;
     DevScene<real>& ds = dev_scene<real>(h);
+    const int sum_order = resolve_sum_order(h, p);
+    const bool fixed = p->output_sum == CR_OUTPUT_FIXED_SUM;
+    if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
+        return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
     if (p->sample_count == 0) {
         // An empty shard (more ranks than samples): the sum of no samples, and 0 / samples for the mean, are both
         // zero -- cast_ray's loop body never runs (ray_casting.rs:82).  No kernel is launched.
-        const size_t bytes = (size_t)cd->image_width * (size_t)cd->image_height * 3 * sizeof(real);
+        const size_t bytes = (size_t)cd->image_width * (size_t)cd->image_height * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
         HIP_TRY(h, hipMemsetAsync(d_out, 0, bytes, h->stream));
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -1335,7 +1361,6 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     const bool anim = ds.animated || ds.has_leaf_runs;   // keyed primitives (the ANIM kernels also follow a keyed camera)
     const bool cam_keys = c.animated;                     // camera keys alone: the static kernels' CAMK variant
     // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
-    const int sum_order = p->sum_order == CR_SUM_DEFAULT ? (h->pipeline == 0 ? h->default_sum_order : CR_SUM_REFERENCE_ORDER) : p->sum_order;
     if (sum_order == CR_SUM_RELAXED && h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_SUM_RELAXED is implemented by the megakernel pipeline only");
     const bool relax = sum_order == CR_SUM_RELAXED;
     const size_t fx_need = relax ? fx_lds_bytes(MaxBlock<real>::value, 4) : 0;   // the relaxed sums' slots share the LDS
@@ -1417,6 +1442,7 @@ int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
     if (p->max_depth < 0) return fail(h, CR_ERR_INVALID_ARG, "max_depth must be >= 0");
     if (p->real_type != CR_REAL_F32 && p->real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");
     if (p->sum_order != CR_SUM_DEFAULT && p->sum_order != CR_SUM_REFERENCE_ORDER && p->sum_order != CR_SUM_RELAXED) return fail(h, CR_ERR_INVALID_ARG, "unknown sum_order");
+    if (p->output_sum < 0 || p->output_sum > CR_OUTPUT_FIXED_SUM) return fail(h, CR_ERR_INVALID_ARG, "unknown output_sum");
     if (!(p->frame_rate > 0)) return fail(h, CR_ERR_INVALID_ARG, "frame_rate must be positive");
     if ((cam->from_key_count > 0 && !cam->from_keys) || (cam->at_key_count > 0 && !cam->at_keys) || cam->from_key_count < 0 || cam->at_key_count < 0)
         return fail(h, CR_ERR_INVALID_ARG, "camera keyframe array missing");
@@ -1696,7 +1722,7 @@ int32_t cr_render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParam
     if (!h_out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
     HIP_TRY(h, hipSetDevice(h->device));
     size_t n = (size_t)cam->image_width * cam->image_height * 3;
-    size_t bytes = n * real_size(p->real_type);
+    size_t bytes = n * (p->output_sum == CR_OUTPUT_FIXED_SUM ? sizeof(uint64_t) : real_size(p->real_type));
     HIP_TRY(h, h->out_buf.ensure(bytes));
     CrStats local;
     rc = cr_render_device(h, cam, p, h->out_buf.p, stats ? stats : &local);
@@ -1718,6 +1744,18 @@ int32_t cr_render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParam
         if (bad) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
     }
     return CR_OK;
+}
+
+int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples, int32_t real_type,
+                             void* d_out_rgb) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!d_sums || !d_out_rgb) return fail(h, CR_ERR_INVALID_ARG, "cr_fixed_sums_to_rgb: null buffer");
+    if (width < 1 || height < 1) return fail(h, CR_ERR_INVALID_ARG, "image size must be positive");
+    if ((int64_t)width * height > (int64_t)1 << 26) return fail(h, CR_ERR_INVALID_ARG, "image too large");
+    if (samples < 1) return fail(h, CR_ERR_INVALID_ARG, "The camera must have a positive number of samples.");
+    if (real_type != CR_REAL_F32 && real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return fixed_sums_to_rgb(h, (const unsigned long long*)d_sums, (size_t)width * (size_t)height * 3, samples, real_type == CR_REAL_F64, d_out_rgb);
 }
 
 static int32_t check_queue_abort(CrHandle* h) {
@@ -1877,6 +1915,7 @@ int32_t cr_group_create(const int32_t* device_ids, int32_t n_devices, CrGroup** 
     g->world = n_devices; g->first = 0;
     g->members.assign((size_t)n_devices, nullptr);
     g->partial.resize((size_t)n_devices);
+    g->flags.resize((size_t)n_devices);
     g->status.resize((size_t)n_devices);
     for (int i = 0; i < n_devices; i++) {
         int32_t rc = cr_create(device_ids[i], &g->members[(size_t)i]);
@@ -1918,6 +1957,7 @@ int32_t cr_group_create_rank(int32_t device_id, int32_t rank, int32_t world_size
     g->world = world_size; g->first = rank;
     g->members.assign(1, nullptr);
     g->partial.resize(1);
+    g->flags.resize(1);
     g->status.resize(1);
     int32_t rc = cr_create(device_id, &g->members[0]);
     if (rc != CR_OK) { g_group_create_error = g_create_error; group_free(g); return rc; }
@@ -1985,15 +2025,19 @@ static int32_t group_render_impl(CrGroup* g, const CrCameraDesc* cam, const CrRe
         int32_t rc = validate_render(h, cam, params);
         if (rc != CR_OK) { note(rc, h->error); continue; }
         if (cr_group_shard(params->samples, g->first + i, g->world, &ps[(size_t)i].sample_begin, &ps[(size_t)i].sample_count) != CR_OK) note(CR_ERR_INVALID_ARG, "samples must be >= 0");
-        ps[(size_t)i].output_sum = summed ? 1 : 0;   // one member, no collective: exactly cr_render_device
     }
+    // relaxed sums reduce exactly: the members export fixed-point words at the frame's scale, the group adds integers
+    // and the root finalizes them as cr_render_device does -- the frame of any member count is the one-device frame
+    const bool exact = summed && resolve_sum_order(g->members[0], params) == CR_SUM_RELAXED;
+    for (CrRenderParams& p : ps) p.output_sum = exact ? CR_OUTPUT_FIXED_SUM : (summed ? 1 : 0);   // one member, no collective: exactly cr_render_device
     const size_t n = local_rc == CR_OK ? (size_t)cam->image_width * (size_t)cam->image_height * 3 : 0;
     const bool f64 = params->real_type == CR_REAL_F64;
-    const size_t bytes = n * (f64 ? sizeof(double) : sizeof(float));
+    const size_t bytes = n * (exact ? sizeof(unsigned long long) : (f64 ? sizeof(double) : sizeof(float)));
     if (summed) for (int i = 0; i < local && local_rc == CR_OK; i++) {
         CrHandle* h = g->members[(size_t)i];
         if (hipSetDevice(h->device) != hipSuccess || g->partial[(size_t)i].ensure(bytes) != hipSuccess ||
-            (collective && g->status[(size_t)i].ensure(sizeof(int32_t)) != hipSuccess)) { (void)hipGetLastError(); note(CR_ERR_HIP, "cannot allocate a member's buffer of per-pixel sums"); }
+            (collective && exact && g->flags[(size_t)i].ensure(n) != hipSuccess) ||
+            (collective && g->status[(size_t)i].ensure(kStatusWords * sizeof(int32_t)) != hipSuccess)) { (void)hipGetLastError(); note(CR_ERR_HIP, "cannot allocate a member's buffer of per-pixel sums"); }
     }
     // 1. every local member renders its shard, asynchronously on its own stream
     const char* fail_member = getenv("CRUCIBLE_GROUP_FAIL_MEMBER");   // tests: this member's render reports a failure after it was launched
@@ -2011,39 +2055,42 @@ static int32_t group_render_impl(CrGroup* g, const CrCameraDesc* cam, const CrRe
         for (CrHandle* h : g->members) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
         return gfail(g, CR_ERR_HIP, what);
     };
-    // 2. do all members of the whole group stand?  (min over "1 = fine")
-    bool all_fine = local_rc == CR_OK;
+    // 2. do all members of the whole group stand?  (min over "1 = fine")  And do they all reduce the same kind of sums?
+    //    (min over exact and over -exact: equal kinds iff the two minima are opposite)
+    bool all_fine = local_rc == CR_OK, same_kind = true;
     if (collective) {
         RcclApi& api = rccl_api();
-        const int32_t mine = local_rc == CR_OK ? 1 : 0;
+        const int32_t mine[kStatusWords] = {local_rc == CR_OK ? 1 : 0, exact ? 1 : 0, exact ? -1 : 0};
         bool ok = true;
         for (int i = 0; i < local && ok; i++) {
             CrHandle* h = g->members[(size_t)i];
-            ok = hipSetDevice(h->device) == hipSuccess && g->status[(size_t)i].ensure(sizeof(int32_t)) == hipSuccess &&
-                 hipMemcpyAsync(g->status[(size_t)i].p, &mine, sizeof mine, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+            ok = hipSetDevice(h->device) == hipSuccess && g->status[(size_t)i].ensure(sizeof mine) == hipSuccess &&
+                 hipMemcpyAsync(g->status[(size_t)i].p, mine, sizeof mine, hipMemcpyHostToDevice, h->stream) == hipSuccess;
         }
         if (!ok) return poison("cannot stage the group's status word");
         ncclResult_t r = api.GroupStart();
         for (int i = 0; i < local && r == ncclSuccess; i++) {
             CrHandle* h = g->members[(size_t)i];
             (void)hipSetDevice(h->device);
-            r = api.AllReduce(g->status[(size_t)i].p, g->status[(size_t)i].p, 1, ncclInt32, ncclMin, g->comms[(size_t)i], h->stream);
+            r = api.AllReduce(g->status[(size_t)i].p, g->status[(size_t)i].p, kStatusWords, ncclInt32, ncclMin, g->comms[(size_t)i], h->stream);
         }
         if (r == ncclSuccess) r = api.GroupEnd(); else (void)api.GroupEnd();
         if (r != ncclSuccess) return poison(std::string("ncclAllReduce of the status word: ") + api.GetErrorString(r));
         int32_t agreed = 1;
         for (int i = 0; i < local; i++) {
             CrHandle* h = g->members[(size_t)i];
-            int32_t v = 0;
-            if (hipSetDevice(h->device) != hipSuccess || hipMemcpyAsync(&v, g->status[(size_t)i].p, sizeof v, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+            int32_t v[kStatusWords] = {0, 0, 0};
+            if (hipSetDevice(h->device) != hipSuccess || hipMemcpyAsync(v, g->status[(size_t)i].p, sizeof v, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
                 hipStreamSynchronize(h->stream) != hipSuccess) return poison("cannot read the group's status word");
-            agreed = std::min(agreed, v);
+            agreed = std::min(agreed, v[0]);
+            same_kind = same_kind && v[1] == -v[2];
         }
-        all_fine = agreed == 1;
+        all_fine = agreed == 1 && same_kind;
     }
     if (!all_fine) {   // every rank is here: wait for what was launched and report
         for (CrHandle* h : g->members) { (void)hipSetDevice(h->device); (void)hipStreamSynchronize(h->stream); }
         if (local_rc != CR_OK) return gfail(g, local_rc, local_err);
+        if (!same_kind) return gfail(g, CR_ERR_INVALID_ARG, "the ranks of the group resolve different summation orders (sum_order, CRUCIBLE_SUM_ORDER); nothing was reduced");
         return gfail(g, CR_ERR_PEER, "another member of the group failed its render; nothing was reduced");
     }
     // 3. one reduce of the sums to the root, then the divide there
@@ -2054,20 +2101,29 @@ static int32_t group_render_impl(CrGroup* g, const CrCameraDesc* cam, const CrRe
             for (int i = 1; i < local; i++) GHIP_TRY(g, hipStreamSynchronize(g->members[(size_t)i]->stream));
             const unsigned grid = (unsigned)((n + 255) / 256);
             for (int i = 1; i < local; i++) {
-                if (f64) hipLaunchKernelGGL((group_add_kernel<double>), dim3(grid), dim3(256), 0, root->stream, (double*)g->partial[0].p, (const double*)g->partial[(size_t)i].p, n);
+                if (exact) hipLaunchKernelGGL(group_fx_add_kernel, dim3(grid), dim3(256), 0, root->stream, (unsigned long long*)g->partial[0].p, (const unsigned long long*)g->partial[(size_t)i].p, n);
+                else if (f64) hipLaunchKernelGGL((group_add_kernel<double>), dim3(grid), dim3(256), 0, root->stream, (double*)g->partial[0].p, (const double*)g->partial[(size_t)i].p, n);
                 else hipLaunchKernelGGL((group_add_kernel<float>), dim3(grid), dim3(256), 0, root->stream, (float*)g->partial[0].p, (const float*)g->partial[(size_t)i].p, n);
             }
             GHIP_TRY(g, hipGetLastError());
         }
         if (collective) {
             RcclApi& api = rccl_api();
-            const ncclDataType_t dt = f64 ? ncclDouble : ncclFloat;
+            if (exact) for (int i = 0; i < local; i++) {   // on each member's stream, behind its render
+                CrHandle* h = g->members[(size_t)i];
+                GHIP_TRY(g, hipSetDevice(h->device));
+                hipLaunchKernelGGL(group_fx_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                                   (unsigned long long*)g->partial[(size_t)i].p, (uint8_t*)g->flags[(size_t)i].p, n);
+                GHIP_TRY(g, hipGetLastError());
+            }
+            const ncclDataType_t dt = exact ? ncclUint64 : (f64 ? ncclDouble : ncclFloat);
             ncclResult_t r = api.GroupStart();
             for (int i = 0; i < local && r == ncclSuccess; i++) {
                 CrHandle* h = g->members[(size_t)i];
                 (void)hipSetDevice(h->device);
                 void* buf = g->partial[(size_t)i].p;   // in place on the root
                 r = api.Reduce(buf, buf, n, dt, ncclSum, 0, g->comms[(size_t)i], h->stream);
+                if (exact && r == ncclSuccess) r = api.Reduce(g->flags[(size_t)i].p, g->flags[(size_t)i].p, n, ncclUint8, ncclMax, 0, g->comms[(size_t)i], h->stream);
             }
             if (r == ncclSuccess) r = api.GroupEnd(); else (void)api.GroupEnd();
             if (r != ncclSuccess) return poison(std::string("ncclReduce: ") + api.GetErrorString(r));
@@ -2075,7 +2131,12 @@ static int32_t group_render_impl(CrGroup* g, const CrCameraDesc* cam, const CrRe
         if (root_here) {
             GHIP_TRY(g, hipSetDevice(root->device));
             const unsigned grid = (unsigned)((n + 255) / 256);
-            if (f64) hipLaunchKernelGGL((group_mean_kernel<double>), dim3(grid), dim3(256), 0, root->stream, (const double*)g->partial[0].p, (double*)d_out, n, (double)params->samples);
+            if (exact) {
+                unsigned long long* sums = (unsigned long long*)g->partial[0].p;
+                if (collective) hipLaunchKernelGGL(group_fx_merge_kernel, dim3(grid), dim3(256), 0, root->stream, sums, (const uint8_t*)g->flags[0].p, n);
+                GHIP_TRY(g, hipGetLastError());
+                if (fixed_sums_to_rgb(root, sums, n, params->samples, f64, d_out) != CR_OK) return gfail(g, CR_ERR_HIP, root->error);
+            } else if (f64) hipLaunchKernelGGL((group_mean_kernel<double>), dim3(grid), dim3(256), 0, root->stream, (const double*)g->partial[0].p, (double*)d_out, n, (double)params->samples);
             else hipLaunchKernelGGL((group_mean_kernel<float>), dim3(grid), dim3(256), 0, root->stream, (const float*)g->partial[0].p, (float*)d_out, n, (float)params->samples);
             GHIP_TRY(g, hipGetLastError());
             GHIP_TRY(g, hipEventRecord(g->ev1, root->stream));

@@ -61,12 +61,40 @@ RcclApi& rccl_api() {
 
 thread_local std::string g_group_create_error;
 
+// the agreement step's words, reduced with min: 1 = my render is fine; 1 / -1 = I reduce fixed-point words (0 / 0: reals)
+constexpr int kStatusWords = 3;
+
 // Test-only stand-in for the collective when several members share ONE device (CRUCIBLE_GROUP_SAME_DEVICE=1: RCCL
 // refuses two ranks on a device): acc += part, member by member in index order.
 template <typename real>
 __global__ void __launch_bounds__(256) group_add_kernel(real* acc, const real* part, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) acc[i] = acc[i] + part[i];
+}
+
+// CR_SUM_RELAXED groups reduce the members' CR_OUTPUT_FIXED_SUM words (bits 0..62 magnitude, bit 63 the NaN flag):
+// c = ((a & M) + (b & M)) | ((a | b) & F).  The magnitudes of one frame's shards total below samples * 2^S < 2^63, so
+// the add never carries into the flag.  Same-device stand-in: acc = acc (+) part, member by member in index order.
+__global__ void __launch_bounds__(256) group_fx_add_kernel(unsigned long long* acc, const unsigned long long* part, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long a = acc[i], b = part[i];
+    acc[i] = ((a & ~kFxNaN) + (b & ~kFxNaN)) | ((a | b) & kFxNaN);
+}
+
+// RCCL has no such add: the flags leave the words as a byte plane (reduced with max), the magnitudes stay (reduced with sum)
+__global__ void __launch_bounds__(256) group_fx_split_kernel(unsigned long long* words, uint8_t* flags, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long v = words[i];
+    flags[i] = (uint8_t)(v >> 63);
+    words[i] = v & ~kFxNaN;
+}
+
+// ... and come back on the root before the finalize
+__global__ void __launch_bounds__(256) group_fx_merge_kernel(unsigned long long* words, const uint8_t* flags, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && flags[i]) words[i] |= kFxNaN;
 }
 
 template <typename real>
@@ -81,8 +109,9 @@ struct CrGroup {
     std::vector<CrHandle*> members;    // driven by this process
     std::vector<ncclComm_t> comms;     // one per local member; empty: no collective (one-member group)
     bool same_device_sum = false;      // tests: members share a device and their sums are added by group_add_kernel
-    std::vector<DevBuf> partial;       // per local member: W*H*3 raw sums of its shard
-    std::vector<DevBuf> status;        // per local member: the 4-byte "my render is fine" word of the agreement step
+    std::vector<DevBuf> partial;       // per local member: W*H*3 raw sums of its shard (reals, or fixed-point words)
+    std::vector<DevBuf> flags;         // per local member, fixed-point words over RCCL: W*H*3 NaN-flag bytes
+    std::vector<DevBuf> status;        // per local member: the agreement step's words ("my render is fine", the reduce's kind)
     bool poisoned = false;             // a collective call failed: peers may still be inside it, the communicators are gone
     int first = 0;                     // group-wide index of members[0]
     int world = 1;                     // members in the whole group
@@ -125,6 +154,7 @@ void group_free(CrGroup* g) {
         if (!g->members[i]) continue;
         (void)hipSetDevice(g->members[i]->device);
         if (i < g->partial.size()) g->partial[i].release();
+        if (i < g->flags.size()) g->flags[i].release();
         if (i < g->status.size()) g->status[i].release();
         if (i == 0) { if (g->ev0) (void)hipEventDestroy(g->ev0); if (g->ev1) (void)hipEventDestroy(g->ev1); }
         cr_destroy(g->members[i]);

@@ -78,10 +78,12 @@ class Renderer:
 
     def render(self, cam, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
                want_stats=True, sum_order=None):
-        """Render into a host array (H, W, 3) of f32/f64.  Returns (image, stats dict)."""
+        """Render into a host array (H, W, 3) of f32/f64 -- of uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM.
+        Returns (image, stats dict)."""
         cd = cam.desc()
         p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
-        out = np.empty((cam.image_height, cam.image_width, 3), dtype=np_real(real_type))
+        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
+        out = np.empty((cam.image_height, cam.image_width, 3), dtype=dtype)
         st = A.CrStats()
         self._check(self.lib.cr_render_host(self.h, C.byref(cd), C.byref(p), out.ctypes.data_as(C.c_void_p),
                                             C.byref(st) if want_stats else None))
@@ -89,13 +91,21 @@ class Renderer:
 
     def render_device(self, cam, d_ptr, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
                       output_sum=False, want_stats=False, sum_order=None):
-        """Render into device memory at `d_ptr` (W*H*3 reals).  Asynchronous unless want_stats."""
+        """Render into device memory at `d_ptr` (W*H*3 reals, or uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM).
+        Asynchronous unless want_stats."""
         cd = cam.desc()
         p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
         st = A.CrStats()
         self._check(self.lib.cr_render_device(self.h, C.byref(cd), C.byref(p), C.c_void_p(d_ptr),
                                               C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
+
+    def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
+        """cr_fixed_sums_to_rgb: summed CR_OUTPUT_FIXED_SUM words of a whole frame (device pointer, W*H*3 uint64) ->
+        its per-pixel means at device pointer `d_out` (W*H*3 reals), exactly the relaxed frame.  Asynchronous on the
+        handle's stream."""
+        self._check(self.lib.cr_fixed_sums_to_rgb(self.h, C.c_void_p(d_sums), width, height, samples, real_type,
+                                                  C.c_void_p(d_out)))
 
     def export_bvh(self, real_type=A.CR_REAL_F32):
         """The wrapper tree the device walks: (boxes (n, 6) f64, children (n, 2) i32, split_axis (n,) i32), see

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define CR_ABI_VERSION 3
+#define CR_ABI_VERSION 4
 
 #if defined(__GNUC__)
 #define CR_API __attribute__((visibility("default")))
@@ -263,8 +263,11 @@ typedef struct CrCameraDesc {
  *   CR_SUM_RELAXED          the attenuations are multiplied in path order (a_1*a_2*...*a_n*sky: the same n
  *                           multiplies, associated left to right) and a finished sample is added to its pixel as
  *                           round(colour * 2^52) in a 64-bit integer (2^51, 2^50, ... beyond 2047 samples per pixel).
- *                           Integer adds commute, so the frame is deterministic -- two runs, or any split into
- *                           shards, give the same sums.  Per channel the mean differs from the reference order by
+ *                           Integer adds commute, so the frame is deterministic: two runs give the same sums.  Any
+ *                           split into shards adds exactly when the shards export their words at the whole frame's
+ *                           scale (output_sum = CR_OUTPUT_FIXED_SUM); as reals (output_sum = 1) each shard uses the
+ *                           scale of its own sample count, which differs between shards above 2047 samples per
+ *                           pixel, and rounds once.  Per channel the mean differs from the reference order by
  *                           at most about (2 * max_depth + samples) * 2^-53: each of the two product orders rounds
  *                           max_depth times, and the reference's own sequential sum rounds once per sample where the
  *                           integer sum does not -- below 1e-13 at depth 50 and 512 samples, 1.0e-14 measured on the
@@ -275,6 +278,21 @@ typedef struct CrCameraDesc {
  *                           the environment variable CRUCIBLE_SUM_ORDER=reference|relaxed overrides it.
  */
 enum { CR_SUM_DEFAULT = 0, CR_SUM_REFERENCE_ORDER = 1, CR_SUM_RELAXED = 2 };
+
+/*
+ * CrRenderParams.output_sum = CR_OUTPUT_FIXED_SUM: the output buffer receives image_width*image_height*3 uint64_t words
+ * (row-major, RGB interleaved, for f32 and f64 alike) holding the shard's CR_SUM_RELAXED sums as they are:
+ *   bits 0..62  the magnitude, sum over the shard's samples of round(colour * 2^S)
+ *   bit 63      the NaN flag (a sample's colour was not a number)
+ * S = min(52, 62 - floor(log2(samples))) is taken from `samples`, the WHOLE frame's count, so the words of all shards of
+ * one frame are on one scale.  They combine exactly, in any order, with
+ *   c = ((a & M) + (b & M)) | ((a | b) & F),   F = 1 << 63, M = ~F
+ * -- the magnitudes of one frame's shards total below samples * 2^S < 2^63, so the add never carries into the flag --
+ * and cr_fixed_sums_to_rgb turns the combined words into exactly the frame cr_render_device writes in CR_SUM_RELAXED.
+ * Needs CR_SUM_RELAXED (after CR_SUM_DEFAULT / CRUCIBLE_SUM_ORDER are resolved) and the megakernel pipeline; otherwise
+ * CR_ERR_UNSUPPORTED.  cr_render_host copies the words back without the Color::new check.
+ */
+enum { CR_OUTPUT_FIXED_SUM = 2 };   /* CrRenderParams.output_sum: 0 mean, 1 sum in reals, 2 fixed-point words */
 
 typedef struct CrRenderParams {
     int32_t samples;
@@ -287,7 +305,9 @@ typedef struct CrRenderParams {
     double frame_rate;
     double shutter_angle;
     int32_t output_sum;     /* 0: per-pixel mean over `samples` (average_samples,
-                               ray_casting.rs:154-173); 1: raw per-pixel sum of this shard */
+                               ray_casting.rs:154-173); 1: raw per-pixel sum of this shard;
+                               CR_OUTPUT_FIXED_SUM (2): the shard's exact fixed-point sums, see below.  Other values:
+                               CR_ERR_INVALID_ARG. */
     int32_t refit_boxes;    /* 0: wrapper boxes stay the construction-time boxes, as in the reference
                                (bvhwrapper.rs:47-50) -- keyframed primitives are clipped where they leave them;
                                1: SURVEY 8(f) rows 1-2: boxes are re-derived on the device for this frame's
@@ -387,6 +407,13 @@ CR_API int32_t cr_write_png(const char* path, const void* rgb, int32_t real_type
 /* Quantise means to the bytes Display would print (3 per pixel); no file. */
 CR_API int32_t cr_quantize_rgb8(const void* rgb, int32_t real_type, int64_t n_pixels, uint8_t* out);
 
+/* The per-pixel means of a whole frame of `samples` samples per pixel from its summed CR_OUTPUT_FIXED_SUM words (device
+ * buffer of width*height*3 uint64_t): sums * 2^-S / samples, NaN where the flag is set, into d_out_rgb (width*height*3
+ * reals of real_type), exactly what cr_render_device writes in CR_SUM_RELAXED.  For callers that move the words with a
+ * transport of their own (one process per GPU, a Rust host).  Asynchronous on the handle's stream. */
+CR_API int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples,
+                                    int32_t real_type, void* d_out_rgb);
+
 /* Last error text of this handle (NULL handle: last create error). */
 CR_API const char* cr_last_error(CrHandle* h);
 
@@ -395,10 +422,16 @@ CR_API const char* cr_last_error(CrHandle* h);
  *
  * Every sample is an independent path (src/camera/ray_casting.rs:82-105) and the random stream is keyed by
  * (seed, pixel, sample), so member g of G renders sample indices cr_group_shard(samples, g, G) of EVERY pixel as raw
- * per-pixel sums (the scene is replicated), one ncclReduce(sum, f32 | f64 per real_type, count = W*H*3, root = member 0)
- * over xGMI adds them, and the root divides by `samples` (average_samples' `/= count`, ray_casting.rs:168-170).  The
- * union is the 1-GPU sample set; the image differs from the 1-GPU one only by the order of the floating-point adds
- * (a group of one member is bit-identical to cr_render_device).  This replaces the reference's worker pool
+ * per-pixel sums (the scene is replicated), one reduce over xGMI adds them on member 0, and the root turns them into
+ * the mean.  The union is the 1-GPU sample set.
+ *   CR_SUM_RELAXED          the members export CR_OUTPUT_FIXED_SUM words; ncclReduce(sum, uint64) adds the magnitudes
+ *                           and ncclReduce(max, uint8) the NaN flags (a byte plane), in one ncclGroupStart/End; the root
+ *                           finalizes them as cr_fixed_sums_to_rgb does.  The frame is the 1-GPU frame BIT FOR BIT, for
+ *                           any member count.
+ *   CR_SUM_REFERENCE_ORDER  ncclReduce(sum, f32 | f64 per real_type) of the shards' real sums, then the divide by
+ *                           `samples` (average_samples' `/= count`, ray_casting.rs:168-170): the image differs from the
+ *                           1-GPU one only by the order of the floating-point adds.
+ * A group of one member without a collective is bit-identical to cr_render_device in both orders.  This replaces the reference's worker pool
  * (src/camera/cpu_threading.rs:25-115: `thread_count` OS threads behind one mutex) across devices.
  *
  * Two ways to form a group; both end in the same cr_group_render:
@@ -432,19 +465,21 @@ CR_API CrHandle* cr_group_handle(CrGroup* g, int32_t local_member);
 /* cr_upload_scene on every local member (the scene is replicated). */
 CR_API int32_t cr_group_upload_scene(CrGroup* g, const CrSceneDesc* scene);
 
-/* Camera::render across the group.  params->sample_begin/sample_count/output_sum are ignored: the group splits
+/* Camera::render across the group.  params->sample_begin/sample_count/output_sum are ignored (output_sum must still be
+ * a valid value): the group splits
  * [0, samples) itself and returns the per-pixel MEAN.  d_out_rgb: device buffer of W*H*3 reals on the ROOT member's
  * device (member 0 = device_ids[0], or rank 0); other ranks may pass NULL.  Every rank of a rank-mode group must
  * call this with the same arguments (it is a collective).  Synchronous.  stats (may be NULL): counters summed over
  * the LOCAL members, kernel_ms = the slowest local member's render, reduce_ms in CrGroupStats.
  * Failure: arguments are validated and buffers allocated on every member before anything is launched; with a
- * collective, the members then agree (a 4-byte ncclAllReduce(min) on the render streams) that every render is fine
- * before the ncclReduce is entered -- if one is not, EVERY rank returns an error (its own, or CR_ERR_PEER) and the
+ * collective, the members then agree (a 12-byte ncclAllReduce(min) on the render streams) that every render is fine
+ * and that every rank reduces the same kind of sums (its resolved sum_order; otherwise CR_ERR_INVALID_ARG) before the
+ * ncclReduce is entered -- if one is not, EVERY rank returns an error (its own, or CR_ERR_PEER) and the
  * group stays usable.  If a collective call itself fails, the group's communicators are aborted and every later call
  * on it returns CR_ERR_PEER: destroy the group.  The calling thread's current HIP device is restored on return. */
 typedef struct CrGroupStats {
     CrStats render;        /* local members: counters summed, kernel_ms = max */
-    double reduce_ms;      /* root-side time of the ncclReduce + the divide, HIP events on the root's stream */
+    double reduce_ms;      /* root-side time of the reduce + the finalize, HIP events on the root's stream */
     int32_t members;       /* whole group */
     int32_t used_rccl;     /* 0: a one-member group rendered directly */
 } CrGroupStats;
