@@ -7,15 +7,20 @@ resident in HBM before the timed region; the output stays in HBM.  With N GPUs t
 ranks (rank r renders [r*512/N, (r+1)*512/N) of every pixel), the per-pixel sums are added on rank 0 by ONE RCCL
 reduce issued inside the library (cr_group_render) and divided by 512 there -- a fixed job, so scaling is "strong".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes the frame of the last timed step (rank 0's) to DIR as .npy
 (see dump_outputs); scenes and seeds are fixed, so two builds run with the same arguments can be compared frame for frame.
 
+A plain run does what the headline needs: scene upload, one counted launch (it loads and sizes the path the steps use, and
+its work counters feed `roofline`), the warm-up and timed steps, the dump, the line.  `--full` adds the lines measured on
+top of it, each a run of its own: `f32_fast_mode`, `reference_order`, `opt_in_tree` and the two CPU baselines (the
+`--no-...` options leave single ones out).
+
 Summation order: the library default (CR_SUM_RELAXED: the same paths, attenuations multiplied in path order, samples added
-as 64-bit fixed point -- within 1e-12 of the reference order, equal work counters; include/crucible_hip.h).  The line
-carries the reference-order (bit-exact parity mode) rate of the same frame as `reference_order` and the largest
+as 64-bit fixed point -- within 1e-12 of the reference order, equal work counters; include/crucible_hip.h).  With `--full`
+the line carries the reference-order (bit-exact parity mode) rate of the same frame as `reference_order` and the largest
 per-channel difference between the two frames, measured on the device in this run.  `--sum-order reference` makes the
 parity mode the measured one.
 
@@ -29,9 +34,9 @@ as two -- the path may not fuse (parity forbids contraction), so half of it is t
 line.  The algorithmic HBM bytes of SURVEY 8(d) and the PMC counters of the committed profile are secondary keys, the
 latter labelled as coming from profiles/.
 
-`cpu_baseline`: the f64 oracle (a port of the reference, NOT the Rust binary) on all host cores, on a bounded slice of
-the same workload; `cpu_baseline_faithful` is the same port evaluating timelines, update_bb and material clones the way
-the reference does at every hit.  Baselines, not targets.
+`cpu_baseline` (`--full`): the f64 oracle (a port of the reference, NOT the Rust binary) on all host cores, on a bounded
+slice of the same workload; `cpu_baseline_faithful` is the same port evaluating timelines, update_bb and material clones
+the way the reference does at every hit.  Baselines, not targets.
 """
 import argparse
 import json
@@ -199,9 +204,12 @@ def main():
                     help="f64 = the reference's arithmetic (the headline); f32 = the opt-in fast mode (an extra line)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--spp", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-line", action="store_true", help="skip the short f32 timing carried as `f32_fast_mode`")
-    ap.add_argument("--no-optin-line", action="store_true", help="skip the short CR_BVH_SAH_ORDERED timing carried as `opt_in_tree`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the f32 fast mode, the reference order and the opt-in tree on the same "
+                         "frame and the two CPU baselines (extra keys of the line; the --no-... options leave single ones out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-f32-line", action="store_true", help="--full: skip the short f32 timing carried as `f32_fast_mode`")
+    ap.add_argument("--no-optin-line", action="store_true", help="--full: skip the short CR_BVH_SAH_ORDERED timing carried as `opt_in_tree`")
     ap.add_argument("--workload", choices=["book1", "teapot", "million", "movie"], default="book1",
                     help="book1 = BASELINE configs[1] (the headline); teapot/million/movie = configs[2]/[3]/[4], extra lines")
     ap.add_argument("--bvh", choices=["reference", "sah", "ordered", "lbvh"], default="reference",
@@ -210,7 +218,7 @@ def main():
     ap.add_argument("--sum-order", choices=["default", "reference", "relaxed"], default="default",
                     help="CrRenderParams.sum_order of the measured renders: default = the library's (relaxed sums); reference = the "
                          "reference's own order of products and sums, bit for bit (the parity mode)")
-    ap.add_argument("--no-reference-line", action="store_true", help="skip the reference-order timing carried as `reference_order`")
+    ap.add_argument("--no-reference-line", action="store_true", help="--full: skip the reference-order timing carried as `reference_order`")
     ap.add_argument("--end-to-end", type=int, default=0, metavar="FRAMES",
                     help="--workload movie: also render FRAMES consecutive frames (240 = all of configs[4]) with file output in P3, P6 "
                          "and PNG, a writer thread encoding frame k while frame k+1 renders; reported as `end_to_end`")
@@ -383,7 +391,7 @@ def main():
 
     # the opt-in f32 mode, carried as an extra key (it is NOT the reference's arithmetic)
     f32_line = None
-    if rank == 0 and world == 1 and args.real == "f64" and not args.no_f32_line and r is not None:
+    if args.full and rank == 0 and world == 1 and args.real == "f64" and not args.no_f32_line and r is not None:
         o32 = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
         ms32 = []
         for _ in range(3):
@@ -398,7 +406,7 @@ def main():
     # the reference's own order of products and sums (the bit-exact parity mode) on the same frame, and how far the measured
     # frame is from it: largest per-channel difference, on the device
     reference_line = None
-    if rank == 0 and world == 1 and relaxed and not args.no_reference_line and r is not None and not frame_sharded:
+    if args.full and rank == 0 and world == 1 and relaxed and not args.no_reference_line and r is not None and not frame_sharded:
         fast = torch.empty_like(out)
         r.render_device(cam, fast.data_ptr(), seed=seed, real_type=real_type)
         r.last_kernel_ms()
@@ -420,7 +428,7 @@ def main():
     # the opt-in tree of SURVEY 8(f) row 1 on the same frame, carried as an extra key: the same image bit for bit
     # (checked here, on the device), fewer box tests.  The headline stays on the reference's own topology.
     optin_line = None
-    if rank == 0 and world == 1 and args.bvh == "reference" and not args.no_optin_line and r is not None and not frame_sharded:
+    if args.full and rank == 0 and world == 1 and args.bvh == "reference" and not args.no_optin_line and r is not None and not frame_sharded:
         ref_img = torch.empty_like(out)
         r.render_device(cam, ref_img.data_ptr(), seed=seed, real_type=real_type)
         r.last_kernel_ms()
@@ -580,7 +588,7 @@ def main():
             rec["f32_fast_mode"] = f32_line
         if optin_line:
             rec["opt_in_tree"] = optin_line
-        if world == 1 and not args.no_cpu_baseline and args.workload != "million":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload != "million":
             rec["cpu_baseline"] = cpu_baseline(scene, seed, 14.0, False)
             rec["cpu_baseline_faithful"] = cpu_baseline(scene, seed, 10.0, True)
         sys.stdout.flush()

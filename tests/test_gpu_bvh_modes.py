@@ -165,7 +165,7 @@ def test_opt_in_trees_render_the_reference_image_on_the_baseline_scenes(renderer
     """For static primitives with true boxes any tree returns the same closest hits (up to exact ties in t, which
     random scenes do not produce): on the four BASELINE scenes -- book1, teapot + environment map, the 1M-sphere
     field, a movie frame (keyed camera) -- CR_BVH_SAH, _ORDERED and LBVH give the reference topology's frame bit for bit.
-    bench.py repeats this check at full size (`opt_in_tree.image_identical_to_reference_topology`)."""
+    bench.py --full repeats this check at full size (`opt_in_tree.image_identical_to_reference_topology`)."""
     from crucible_amd.demo_builder import load_teapot, million_spheres, procedural_sky, teapot_orbit_movie
     if scene == "book1":
         sc = book1_end_scene(1, scene_seed=1, image_width=320, samples=8)
