@@ -88,6 +88,10 @@ SYMBOLS = {
                                      C.POINTER(CrStats)]),
     "cr_render_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_void_p,
                                    C.POINTER(CrStats)]),
+    "cr_render_frames_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
+                                            C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_frames_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
+                                          C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
     "cr_last_kernel_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),

@@ -110,7 +110,13 @@ struct CrHandle {
     hipEvent_t cam_ev[kCamSlots] = {};
     int cam_next = 0, cam_pending_slot = -1;
     DevBuf sample_buf, sg_acc;   // sample-granular megakernel: per-sample colours of a batch, running sums between batches
-    DevBuf fx_acc;               // CR_SUM_RELAXED: per-pixel fixed-point sums (3 x u64 per pixel)
+    DevBuf fx_acc;               // CR_SUM_RELAXED: per-pixel fixed-point sums (3 x u64 per pixel; per frame of a batch)
+    // cr_render_frames_*: a batch's per-frame ray times travel through one pinned host buffer, refilled only after the
+    // previous batch's copy has run (times_ev); the device table is reused in stream order
+    void* times_host = nullptr;
+    size_t times_cap = 0;
+    DevBuf times_dev;
+    hipEvent_t times_ev = nullptr;
     int screen_boxes = 1;        // f64, unordered trees: box tests decided on f32 screening records where f32 can (CRUCIBLE_SCREEN=0: never)
     int screen_lds = 1;          // ... also for scenes that sit in LDS whole (CRUCIBLE_SCREEN_LDS=0: only trees read from global memory)
     int default_sum_order = CR_SUM_RELAXED;   // what CR_SUM_DEFAULT means on this handle (CRUCIBLE_SUM_ORDER=reference|relaxed)
@@ -888,8 +894,16 @@ int resolve_sum_order(const CrHandle* h, const CrRenderParams* p) {
     return p->sum_order == CR_SUM_DEFAULT ? (h->pipeline == 0 ? h->default_sum_order : CR_SUM_REFERENCE_ORDER) : p->sum_order;
 }
 
+// The frames of one render: n frames whose ray times start at times[k] (host) and d_times[k] (the device's copy).  A
+// single render is a batch of one without a table (its times start at KernelArgs::current_time).  RELAX kernels only.
+template <typename real> struct FrameBatch {
+    int32_t n = 1;
+    const real* times = nullptr;
+    const real* d_times = nullptr;
+};
+
 template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
-int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats) {
+int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats, const FrameBatch<real>& fb) {
     constexpr bool LDS = RES != RES_GLOBAL || RELAX;
     static_assert(!LATENCY || RES == RES_TOP, "the 6-waves-per-SIMD entry point exists for RES_TOP only");
     KernelArgs<real> args = args_in;
@@ -926,6 +940,9 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     const size_t npix = (size_t)args.cam.W * (size_t)args.cam.H;
     const int32_t s_begin = args.sample_begin, s_end = args.sample_end;
     int32_t batch = 0;
+    int32_t fpl = 1;   // frames per launch (a batch of frames: as many whole frames as the work counter holds)
+    args.n_frames = 1; args.frame_times = nullptr;
+    if (fb.n > 1 && !(RELAX && (ANIM || CAMK))) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
     if ((h->sample_granular || RELAX) && s_end > s_begin) {
         const size_t per_sample = npix * 3 * sizeof(real);
         batch = (int32_t)std::min<size_t>((size_t)(s_end - s_begin), RELAX ? (size_t)INT32_MAX : std::max<size_t>(1, h->sample_buf_limit / per_sample));
@@ -943,7 +960,15 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         // the buffer holds one colour per work item of a batch: whole tiles and whole sample groups (edge padding included)
         if constexpr (RELAX) {
             if (batch <= 0) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
-            if (args.output_sum != CR_OUTPUT_FIXED_SUM) HIP_TRY(h, h->fx_acc.ensure(npix * 3 * sizeof(unsigned long long)));
+            // a frame that needs sample batches on its own renders frame by frame
+            if (batch == s_end - s_begin) fpl = (int32_t)std::min<uint64_t>((uint64_t)fb.n, max_groups / (((uint64_t)batch + ns - 1) / ns));
+            if (args.output_sum != CR_OUTPUT_FIXED_SUM) {
+                const hipError_t e = h->fx_acc.ensure((size_t)fb.n * npix * 3 * sizeof(unsigned long long));
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(h, CR_ERR_HIP, "fixed-point sums of " + std::to_string(fb.n) + " frame(s): " + hipGetErrorString(e));
+                }
+            }
         } else {
             auto batch_bytes = [&](int32_t b) { return (size_t)tiles * ((size_t)(b + (int32_t)ns - 1) / ns) * 64u * 3u * sizeof(real); };
             while (batch > (int32_t)ns && batch_bytes(batch) > std::max(h->sample_buf_limit, batch_bytes((int32_t)ns))) batch -= (int32_t)ns;
@@ -955,7 +980,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     args.sg_on = batch > 0 ? 1u : 0u;
     const uint32_t ns = args.sg_on ? (64u >> (args.sg_lw + args.sg_lh)) : 1u;
     auto groups_of = [&](int32_t n) { return (uint32_t)((n + (int32_t)ns - 1) / (int32_t)ns); };
-    uint64_t total_work = args.sg_on ? (uint64_t)args.tiles_x * args.tiles_y * groups_of(std::min(batch, s_end - s_begin)) * 64u
+    uint64_t total_work = args.sg_on ? (uint64_t)args.tiles_x * args.tiles_y * fpl * groups_of(std::min(batch, s_end - s_begin)) * 64u
                                      : (uint64_t)args.tiles_x * args.tiles_y * 64u;
     uint32_t grid = (uint32_t)(h->n_cus * per_cu);
     uint64_t need_blocks = (total_work + block - 1) / block;
@@ -972,7 +997,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         const bool fixed = args.output_sum == CR_OUTPUT_FIXED_SUM;
         args.fx_scale = fx_scale_for(fixed ? args.samples_total : s_end - s_begin);
         args.fx_acc = fixed ? (unsigned long long*)args.out : (unsigned long long*)h->fx_acc.p;
-        HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, npix * 3 * sizeof(unsigned long long), h->stream));
+        HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, (size_t)fb.n * npix * 3 * sizeof(unsigned long long), h->stream));
     }
     HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -982,29 +1007,39 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         HIP_TRY(h, hipGetLastError());
     } else {
         args.sample_buf = (real*)h->sample_buf.p;
-        for (int32_t b0 = s_begin; b0 < s_end; b0 += batch) {
-            const int32_t b1 = std::min(s_end, b0 + batch);
-            args.sample_begin = b0; args.sample_end = b1;
-            args.sg_groups = groups_of(b1 - b0);
-            args.sg_total = (uint32_t)((uint64_t)args.tiles_x * args.tiles_y * args.sg_groups * 64u);
-            {   // 1024 items per atomic keeps the counter quiet on long launches; a short launch (a small frame, or one
-                // GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most
-                // 1/128 of its share
-                const uint64_t per_wave = (uint64_t)args.sg_total / std::max<uint64_t>(1, (uint64_t)grid * block / 64);
-                const uint64_t c = h->sg_chunk_override > 0 ? (uint64_t)h->sg_chunk_override : std::min<uint64_t>(1024, std::max<uint64_t>(64, per_wave / 128));
-                args.sg_chunk = (uint32_t)((c + 63) / 64 * 64);
+        unsigned long long* const fx_frame0 = args.fx_acc;
+        for (int32_t f0 = 0; f0 < fb.n; f0 += fpl) {   // one pass for a single render
+            const int32_t fn = std::min(fpl, fb.n - f0);
+            if constexpr (RELAX) {   // frames [f0, f0 + fn) of a batch
+                args.n_frames = (uint32_t)fn;
+                args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
+                args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
+                args.fx_acc = fx_frame0 + (size_t)f0 * npix * 3;
             }
-            HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
-            HIP_TRY(h, hipGetLastError());
-            if constexpr (RELAX) continue;   // the sums stay in fx_acc until the last batch
-            const size_t fin_threads = ((size_t)args.tiles_x * args.tiles_y) << (args.sg_lw + args.sg_lh);
-            hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((fin_threads + 255) / 256)), dim3(256), 0, h->stream, args,
-                               (real*)h->sg_acc.p, b1 - b0, b0 == s_begin ? 1 : 0, b1 == s_end ? 1 : 0);
-            HIP_TRY(h, hipGetLastError());
+            for (int32_t b0 = s_begin; b0 < s_end; b0 += batch) {
+                const int32_t b1 = std::min(s_end, b0 + batch);
+                args.sample_begin = b0; args.sample_end = b1;
+                args.sg_groups = groups_of(b1 - b0);
+                args.sg_total = (uint32_t)((uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn * args.sg_groups * 64u);
+                {   // 1024 items per atomic keeps the counter quiet on long launches; a short launch (a small frame, or one
+                    // GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most
+                    // 1/128 of its share
+                    const uint64_t per_wave = (uint64_t)args.sg_total / std::max<uint64_t>(1, (uint64_t)grid * block / 64);
+                    const uint64_t c = h->sg_chunk_override > 0 ? (uint64_t)h->sg_chunk_override : std::min<uint64_t>(1024, std::max<uint64_t>(64, per_wave / 128));
+                    args.sg_chunk = (uint32_t)((c + 63) / 64 * 64);
+                }
+                HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
+                HIP_TRY(h, hipGetLastError());
+                if constexpr (RELAX) continue;   // the sums stay in fx_acc until the last batch
+                const size_t fin_threads = ((size_t)args.tiles_x * args.tiles_y) << (args.sg_lw + args.sg_lh);
+                hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((fin_threads + 255) / 256)), dim3(256), 0, h->stream, args,
+                                   (real*)h->sg_acc.p, b1 - b0, b0 == s_begin ? 1 : 0, b1 == s_end ? 1 : 0);
+                HIP_TRY(h, hipGetLastError());
+            }
         }
         if constexpr (RELAX) if (args.output_sum != CR_OUTPUT_FIXED_SUM) {
-            const size_t n = npix * 3;
+            const size_t n = (size_t)fb.n * npix * 3;   // a batch's frames follow each other in fx_acc and in the output
             hipLaunchKernelGGL((fx_finalize_kernel<real>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                                (const unsigned long long*)h->fx_acc.p, args.out, n, 1.0 / args.fx_scale, (double)args.samples_total, args.output_sum);
             HIP_TRY(h, hipGetLastError());
@@ -1022,7 +1057,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         memset(stats, 0, sizeof *stats);
         stats->kernel_ms = ms;
         stats->segments = c[0]; stats->node_tests = c[1]; stats->prim_tests = c[2]; stats->texel_fetches = c[3];
-        stats->samples = (uint64_t)args.cam.W * (uint64_t)args.cam.H * (uint64_t)(args.sample_end - args.sample_begin);
+        stats->samples = (uint64_t)args.cam.W * (uint64_t)args.cam.H * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n;
         stats->upload_ms = h->upload_ms;
         stats->bvh_entries = args.n_entries;
         stats->scene_in_lds = RES;
@@ -1237,19 +1272,41 @@ int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>&
 // Picks the kernel variant: keyed primitives (ANIM), camera keys alone (CAMK) or neither, each in the reference's
 // summation order or with relaxed sums (CrRenderParams.sum_order).
 template <typename real, int RES, bool ORD, bool LATENCY, bool SCREEN = false>
-int32_t launch_variant(CrHandle* h, const KernelArgs<real>& a, size_t lds_bytes, CrStats* stats, bool anim, bool cam_keys, bool relax) {
+int32_t launch_variant(CrHandle* h, const KernelArgs<real>& a, size_t lds_bytes, CrStats* stats, bool anim, bool cam_keys, bool relax,
+                       const FrameBatch<real>& fb) {
     if (relax) {
-        if (anim) return launch<real, RES, true, ORD, LATENCY, false, true, SCREEN>(h, a, lds_bytes, stats);
-        if (cam_keys) return launch<real, RES, false, ORD, LATENCY, true, true, SCREEN>(h, a, lds_bytes, stats);
-        return launch<real, RES, false, ORD, LATENCY, false, true, SCREEN>(h, a, lds_bytes, stats);
+        if (anim) return launch<real, RES, true, ORD, LATENCY, false, true, SCREEN>(h, a, lds_bytes, stats, fb);
+        if (cam_keys) return launch<real, RES, false, ORD, LATENCY, true, true, SCREEN>(h, a, lds_bytes, stats, fb);
+        return launch<real, RES, false, ORD, LATENCY, false, true, SCREEN>(h, a, lds_bytes, stats, fb);
     }
-    if (anim) return launch<real, RES, true, ORD, LATENCY, false, false, SCREEN>(h, a, lds_bytes, stats);
-    if (cam_keys) return launch<real, RES, false, ORD, LATENCY, true, false, SCREEN>(h, a, lds_bytes, stats);
-    return launch<real, RES, false, ORD, LATENCY, false, false, SCREEN>(h, a, lds_bytes, stats);
+    if (anim) return launch<real, RES, true, ORD, LATENCY, false, false, SCREEN>(h, a, lds_bytes, stats, fb);
+    if (cam_keys) return launch<real, RES, false, ORD, LATENCY, true, false, SCREEN>(h, a, lds_bytes, stats, fb);
+    return launch<real, RES, false, ORD, LATENCY, false, false, SCREEN>(h, a, lds_bytes, stats, fb);
 }
 
+// cr_render_frames_*: the batch's ray times through the handle's pinned staging buffer into its device table
+int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
+    if (h->times_ev) HIP_TRY(h, hipEventSynchronize(h->times_ev));   // the previous batch's copy has read the staging buffer
+    else HIP_TRY(h, hipEventCreateWithFlags(&h->times_ev, hipEventDisableTiming));
+    if (bytes > h->times_cap) {
+        if (h->times_host) (void)hipHostFree(h->times_host);
+        h->times_host = nullptr; h->times_cap = 0;
+        const hipError_t e = hipHostMalloc(&h->times_host, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { h->times_host = nullptr; (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("frame times: ") + hipGetErrorString(e)); }
+        h->times_cap = bytes;
+    }
+    const hipError_t e = h->times_dev.ensure(bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("frame times: ") + hipGetErrorString(e)); }
+    memcpy(h->times_host, times, bytes);
+    HIP_TRY(h, hipMemcpyAsync(h->times_dev.p, h->times_host, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->times_ev, h->stream));
+    return CR_OK;
+}
+
+// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*).
 template <typename real>
-int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats) {
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats,
+                     const int32_t* frames = nullptr, int32_t n_frames = 1) {
     int32_t rc = build_dev_scene<real>(h);
     if (rc != CR_OK) return rc;
     DevScene<real>& ds = dev_scene<real>(h);
@@ -1257,10 +1314,20 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     const bool fixed = p->output_sum == CR_OUTPUT_FIXED_SUM;
     if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
         return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
+    // without primitive keys the boxes would not change -- unless a HitList element's box is not its objects' union
+    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;
+    if (frames) {
+        if (sum_order != CR_SUM_RELAXED || h->pipeline != 0)
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
+                                               "sequential over samples and would need a per-sample buffer per frame)");
+        if (refit)
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
+                                               "(render such frames one at a time)");
+    }
     if (p->sample_count == 0) {
         // An empty shard (more ranks than samples): the sum of no samples, and 0 / samples for the mean, are both
         // zero -- cast_ray's loop body never runs (ray_casting.rs:82).  No kernel is launched.
-        const size_t bytes = (size_t)cd->image_width * (size_t)cd->image_height * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
+        const size_t bytes = (size_t)n_frames * (size_t)cd->image_width * (size_t)cd->image_height * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
         HIP_TRY(h, hipMemsetAsync(d_out, 0, bytes, h->stream));
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -1276,8 +1343,6 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     KernelArgs<real> a;
     memset(&a, 0, sizeof a);
     a.entries = (const Entry<real>*)ds.entries.p; a.prims = (const Prim<real>*)ds.prims.p; a.leaf_runs = ds.has_leaf_runs ? (const int32_t*)ds.leaf_runs.p : nullptr;
-    // without primitive keys the boxes would not change -- unless a HitList element's box is not its objects' union
-    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;
     a.mats = (const Mat<real>*)ds.mats.p; a.texs = (const Tex<real>*)ds.texs.p;
     a.images = (const ImageRef*)h->images.p; a.texels = (const uint32_t*)h->texels.p;
     a.keys = (const Key<real>*)ds.keys.p;
@@ -1322,6 +1387,17 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.seed_mixed = mix64(p->seed + RNG_GAMMA);
     frame_times(p, a.current_time, a.shutter_length);   // ray_casting.rs:77-79
     a.output_sum = p->output_sum;
+    FrameBatch<real> fb;
+    std::vector<real> times;
+    if (frames) {   // each frame's times as a single render of it computes them (the shutter is the same for all)
+        times.resize((size_t)n_frames);
+        CrRenderParams q = *p;
+        for (int32_t k = 0; k < n_frames; k++) { q.frame = frames[k]; frame_times(&q, times[(size_t)k], a.shutter_length); }
+        rc = stage_frame_times(h, times.data(), times.size() * sizeof(real));
+        if (rc != CR_OK) return rc;
+        a.current_time = times[0];
+        fb.n = n_frames; fb.times = times.data(); fb.d_times = (const real*)h->times_dev.p;
+    }
     if (refit) {   // refit.hpp: wrapper boxes for this frame's ray times [current_time, current_time + shutter_length]
         const size_t bytes = (size_t)ds.n_entries * ds.entry_bytes;
         HIP_TRY(h, ds.entries_refit.ensure(bytes, ds.entries.pad));
@@ -1359,7 +1435,9 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
 
     // the ANIM kernels also carry the decode of leaves that hold a HitList element (pathtrace.hpp walk_round)
     const bool anim = ds.animated || ds.has_leaf_runs;   // keyed primitives (the ANIM kernels also follow a keyed camera)
-    const bool cam_keys = c.animated;                     // camera keys alone: the static kernels' CAMK variant
+    // camera keys alone: the static kernels' CAMK variant, which also renders the batches of scenes without keys (the
+    // static kernels do not carry a batch's frame arithmetic; with an unkeyed camera CAMK computes what they compute)
+    const bool cam_keys = c.animated || frames != nullptr;
     // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
     if (sum_order == CR_SUM_RELAXED && h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_SUM_RELAXED is implemented by the megakernel pipeline only");
     const bool relax = sum_order == CR_SUM_RELAXED;
@@ -1371,9 +1449,9 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
         constexpr bool f32 = std::is_same<real, float>::value;   // the double kernel needs far more than 80 VGPRs: it halves there
         if (ds.n_entries > 0 && (plain_lds || screen_lds)) {
             a.lds_entries = ds.n_entries;
-            if constexpr (!f32) if (screen_lds) return launch_variant<real, RES_LDS, true, false, true>(h, a, lds_all_screen, stats, anim, cam_keys, relax);
+            if constexpr (!f32) if (screen_lds) return launch_variant<real, RES_LDS, true, false, true>(h, a, lds_all_screen, stats, anim, cam_keys, relax, fb);
             a.screen = nullptr;
-            return launch_variant<real, RES_LDS, true, false>(h, a, ds.lds_bytes, stats, anim, cam_keys, relax);
+            return launch_variant<real, RES_LDS, true, false>(h, a, ds.lds_bytes, stats, anim, cam_keys, relax, fb);
         }
         const bool latency = f32 && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
         const size_t window_rec = screen ? sizeof(ScreenEntryO) : sizeof(EntryO<real>);
@@ -1381,13 +1459,13 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
         if (top > 0) {
             a.lds_entries = top;
             const size_t bytes = (size_t)top * window_rec;
-            if constexpr (f32) if (latency) return launch_variant<real, RES_TOP, true, true>(h, a, bytes, stats, anim, cam_keys, relax);
-            if constexpr (!f32) if (screen) return launch_variant<real, RES_TOP, true, false, true>(h, a, bytes, stats, anim, cam_keys, relax);
-            return launch_variant<real, RES_TOP, true, false>(h, a, bytes, stats, anim, cam_keys, relax);
+            if constexpr (f32) if (latency) return launch_variant<real, RES_TOP, true, true>(h, a, bytes, stats, anim, cam_keys, relax, fb);
+            if constexpr (!f32) if (screen) return launch_variant<real, RES_TOP, true, false, true>(h, a, bytes, stats, anim, cam_keys, relax, fb);
+            return launch_variant<real, RES_TOP, true, false>(h, a, bytes, stats, anim, cam_keys, relax, fb);
         }
         a.lds_entries = 0;
-        if constexpr (!f32) if (screen) return launch_variant<real, RES_GLOBAL, true, false, true>(h, a, 0, stats, anim, cam_keys, relax);
-        return launch_variant<real, RES_GLOBAL, true, false>(h, a, 0, stats, anim, cam_keys, relax);
+        if constexpr (!f32) if (screen) return launch_variant<real, RES_GLOBAL, true, false, true>(h, a, 0, stats, anim, cam_keys, relax, fb);
+        return launch_variant<real, RES_GLOBAL, true, false>(h, a, 0, stats, anim, cam_keys, relax, fb);
     }
     if (h->pipeline == 1) return render_wavefront<real>(h, a, ds, anim || cam_keys, stats);
     if (h->pipeline == 2) {   // LDS-queue megakernel when scene + slot arrays fit in LDS, else the plain megakernel below
@@ -1405,9 +1483,9 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     }
     if (ds.n_entries > 0 && (plain_lds || screen_lds)) {
         a.lds_entries = ds.n_entries;
-        if (screen_lds) return launch_variant<real, RES_LDS, false, false, true>(h, a, lds_all_screen, stats, anim, cam_keys, relax);
+        if (screen_lds) return launch_variant<real, RES_LDS, false, false, true>(h, a, lds_all_screen, stats, anim, cam_keys, relax, fb);
         a.screen = nullptr;
-        return launch_variant<real, RES_LDS, false, false>(h, a, ds.lds_bytes, stats, anim, cam_keys, relax);
+        return launch_variant<real, RES_LDS, false, false>(h, a, ds.lds_bytes, stats, anim, cam_keys, relax, fb);
     }
     constexpr bool f32 = std::is_same<real, float>::value;   // the double kernel needs far more than 80 VGPRs: it halves there
     const bool latency = f32 && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
@@ -1421,13 +1499,13 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
         // (the 6-waves-per-SIMD entry point runs three 512-thread groups per CU: window, side tables and the relaxed sums' slots of all three share 160 KB)
         const size_t side_cap = latency ? (((size_t)160 * 1024 / 3 - 16 > bytes + fx_lds_bytes(LatencyBlock, 4)) ? (size_t)160 * 1024 / 3 - 16 - bytes - fx_lds_bytes(LatencyBlock, 4) : 0) : h->lds_side_limit;
         if (side <= std::min(h->lds_side_limit, side_cap)) { a.lds_side = 1; bytes = ((bytes + 15) & ~(size_t)15) + side; }
-        if constexpr (f32) if (latency) return launch_variant<real, RES_TOP, false, true>(h, a, bytes, stats, anim, cam_keys, relax);
-        if (screen) return launch_variant<real, RES_TOP, false, false, true>(h, a, bytes, stats, anim, cam_keys, relax);
-        return launch_variant<real, RES_TOP, false, false>(h, a, bytes, stats, anim, cam_keys, relax);
+        if constexpr (f32) if (latency) return launch_variant<real, RES_TOP, false, true>(h, a, bytes, stats, anim, cam_keys, relax, fb);
+        if (screen) return launch_variant<real, RES_TOP, false, false, true>(h, a, bytes, stats, anim, cam_keys, relax, fb);
+        return launch_variant<real, RES_TOP, false, false>(h, a, bytes, stats, anim, cam_keys, relax, fb);
     }
     a.lds_entries = 0;
-    if (screen) return launch_variant<real, RES_GLOBAL, false, false, true>(h, a, 0, stats, anim, cam_keys, relax);
-    return launch_variant<real, RES_GLOBAL, false, false>(h, a, 0, stats, anim, cam_keys, relax);
+    if (screen) return launch_variant<real, RES_GLOBAL, false, false, true>(h, a, 0, stats, anim, cam_keys, relax, fb);
+    return launch_variant<real, RES_GLOBAL, false, false>(h, a, 0, stats, anim, cam_keys, relax, fb);
 }
 
 int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p) {
@@ -1584,6 +1662,9 @@ void cr_destroy(CrHandle* h) {
         h->cam_dev[i].release();
         if (h->cam_ev[i]) (void)hipEventDestroy(h->cam_ev[i]);
     }
+    if (h->times_host) (void)hipHostFree(h->times_host);
+    h->times_dev.release();
+    if (h->times_ev) (void)hipEventDestroy(h->times_ev);
     if (h->wf_ring_host) { (void)hipHostFree(h->wf_ring_host); for (int i = 0; i < 8; i++) if (h->wf_ev[i]) (void)hipEventDestroy(h->wf_ev[i]); }
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1701,13 +1782,17 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
     return CR_OK;
 }
 
-int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats) {
-    int32_t rc = validate_render(h, cam, p);
-    if (rc != CR_OK) return rc;
-    if (!d_out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
+}   // extern "C"
+
+namespace {
+
+// cr_render_device / cr_render_frames_device after their own argument checks (frames == nullptr: params->frame)
+int32_t render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats,
+                      const int32_t* frames, int32_t n_frames) {
     HIP_TRY(h, hipSetDevice(h->device));
     h->cam_pending_slot = -1;
-    rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats) : render_typed<float>(h, cam, p, d_out, stats);
+    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames)
+                                             : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames);
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
         hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
         h->cam_pending_slot = -1;
@@ -1716,34 +1801,91 @@ int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderPar
     return rc;
 }
 
+// Color::new asserts 0 <= c <= 1 on every mean (ray_casting.rs:172): the pixels of a host frame that would panic there
+uint64_t bad_pixels(const void* rgb, int32_t real_type, size_t n_pix) {
+    uint64_t bad = 0;
+    for (size_t i = 0; i < n_pix; i++) {
+        bool ok = true;
+        for (int k = 0; k < 3; k++) {
+            double v = real_type == CR_REAL_F64 ? ((const double*)rgb)[3 * i + k] : (double)((const float*)rgb)[3 * i + k];
+            ok = ok && (v >= 0.0 && v <= 1.0);
+        }
+        bad += ok ? 0 : 1;
+    }
+    return bad;
+}
+
+// cr_render_host / cr_render_frames_host: render into the handle's buffer, copy back, check the means frame by frame
+int32_t render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* h_out, CrStats* stats,
+                    const int32_t* frames, int32_t n_frames) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)cam->image_width * cam->image_height * 3;   // reals (or words) per frame
+    const size_t frame_bytes = n * (p->output_sum == CR_OUTPUT_FIXED_SUM ? sizeof(uint64_t) : real_size(p->real_type));
+    const size_t bytes = frame_bytes * (size_t)n_frames;
+    const hipError_t e = h->out_buf.ensure(bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
+    CrStats local;
+    int32_t rc = render_device(h, cam, p, h->out_buf.p, stats ? stats : &local, frames, n_frames);
+    if (rc != CR_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!p->output_sum) {
+        uint64_t bad = 0;
+        int32_t first_bad = -1;
+        for (int32_t k = 0; k < n_frames; k++) {
+            const uint64_t b = bad_pixels((const char*)h_out + (size_t)k * frame_bytes, p->real_type, n / 3);
+            if (b && first_bad < 0) first_bad = k;
+            bad += b;
+        }
+        if (stats) stats->nan_pixels = bad;
+        if (bad && !frames) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+        if (bad)
+            return fail(h, CR_ERR_NAN, "frame " + std::to_string(frames[first_bad]) + " (entry " + std::to_string(first_bad) +
+                                           " of the batch): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+    }
+    return CR_OK;
+}
+
+int32_t validate_frames(CrHandle* h, const int32_t* frames, int32_t n_frames) {
+    if (!frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
+    if (n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
+    return CR_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats) {
+    int32_t rc = validate_render(h, cam, p);
+    if (rc != CR_OK) return rc;
+    if (!d_out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
+    return render_device(h, cam, p, d_out, stats, nullptr, 1);
+}
+
 int32_t cr_render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* h_out, CrStats* stats) {
     int32_t rc = validate_render(h, cam, p);
     if (rc != CR_OK) return rc;
     if (!h_out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
-    HIP_TRY(h, hipSetDevice(h->device));
-    size_t n = (size_t)cam->image_width * cam->image_height * 3;
-    size_t bytes = n * (p->output_sum == CR_OUTPUT_FIXED_SUM ? sizeof(uint64_t) : real_size(p->real_type));
-    HIP_TRY(h, h->out_buf.ensure(bytes));
-    CrStats local;
-    rc = cr_render_device(h, cam, p, h->out_buf.p, stats ? stats : &local);
+    return render_host(h, cam, p, h_out, stats, nullptr, 1);
+}
+
+int32_t cr_render_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
+                                void* d_out, CrStats* stats) {
+    int32_t rc = validate_render(h, cam, p);
+    if (rc == CR_OK) rc = validate_frames(h, frames, n_frames);
     if (rc != CR_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!p->output_sum) {   // Color::new asserts 0 <= c <= 1 on every mean (ray_casting.rs:172)
-        uint64_t bad = 0;
-        size_t n_pix = n / 3;
-        for (size_t i = 0; i < n_pix; i++) {
-            bool ok = true;
-            for (int k = 0; k < 3; k++) {
-                double v = p->real_type == CR_REAL_F64 ? ((const double*)h_out)[3 * i + k] : (double)((const float*)h_out)[3 * i + k];
-                ok = ok && (v >= 0.0 && v <= 1.0);
-            }
-            bad += ok ? 0 : 1;
-        }
-        if (stats) stats->nan_pixels = bad;
-        if (bad) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
-    }
-    return CR_OK;
+    if (!d_out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
+    return render_device(h, cam, p, d_out, stats, frames, n_frames);
+}
+
+int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
+                              void* h_out, CrStats* stats) {
+    int32_t rc = validate_render(h, cam, p);
+    if (rc == CR_OK) rc = validate_frames(h, frames, n_frames);
+    if (rc != CR_OK) return rc;
+    if (!h_out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
+    return render_host(h, cam, p, h_out, stats, frames, n_frames);
 }
 
 int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples, int32_t real_type,

@@ -310,7 +310,18 @@ template <typename real> struct KernelArgs {
     double fx_scale;              // 2^S, S = 52 for up to 2047 samples per pixel
     uint32_t fx_lds_off;          // byte offset of the waves' LDS accumulators: 2 slots per wave, each one work tile
                                   // (2^(sg_lw + sg_lh) pixels x 3 channels) of 64-bit words
+    // A batch of frames in one launch (cr_render_frames_*: the RELAX kernels with keys, see pathtrace_body).  The tile rows of the n_frames frames
+    // follow each other -- frame f owns the tile rows [f * tiles_y, (f + 1) * tiles_y) -- so a work item's pix_j counts
+    // the rows of the whole batch (tiles_y << sg_lh per frame, edge padding included) and no tile straddles two frames.
+    // Frame f's ray times start at frame_times[f] and its sums sit at fx_acc + f * W * H * 3.  n_frames = 1: a single
+    // render, whose times start at current_time (frame_times is not read).
+    uint32_t n_frames;
+    const real* frame_times;
 };
+// the frame of the batch that a batch-wide pixel row belongs to (0 in a single render)
+template <typename real> CR_HD uint32_t batch_frame(const KernelArgs<real>& A, uint32_t pix_j) {
+    return A.n_frames > 1u ? (pix_j >> A.sg_lh) / A.tiles_y : 0u;
+}
 constexpr unsigned long long kFxNaN = 0x8000000000000000ull;
 constexpr size_t fx_lds_bytes(int block, uint32_t tile_log2) { return (size_t)(block / 64) * 2 * ((size_t)3 << tile_log2) * sizeof(unsigned long long); }
 
@@ -704,13 +715,14 @@ template <typename real> CR_D void random_in_unit_disk_dev(uint64_t& s, real& px
 // static-primitive kernels with the camera keys compiled in -- a movie that only moves the camera keeps the static walk
 // (the teapot orbit frame: +6.5 % in f64 over running it on the ANIM kernels; folding the camera code into the plain
 // static kernels instead cost book1 0.9 % f64 / 1.8 % f32, so it is a variant of its own).
+// `current_time`: the frame's first ray time (a frame of a batch has its own; pix_j is then the row within that frame).
 template <typename real, bool ANIM, bool CAMK = false>
 CR_D void camera_ray(const KernelArgs<real>& A, uint32_t pix_i, uint32_t pix_j, int32_t sample, uint64_t& rng, V3<real>& ro, V3<real>& rd,
-                     real& rtime) {
+                     real& rtime, real current_time) {
     const CamConst<real>& cam = A.cam;
     uint32_t pixel = pix_j * (uint32_t)cam.W + pix_i;
     rng = rng_key(A.seed_mixed, pixel, (uint32_t)sample);
-    real ts = A.current_time + rng_range<real>(rng, real(0), A.shutter_length);
+    real ts = current_time + rng_range<real>(rng, real(0), A.shutter_length);
     real ox = rng_uniform<real>(rng) - real(0.5);   // sample_square, camera/mod.rs:368-376
     real oy = rng_uniform<real>(rng) - real(0.5);
     CamFrame<real> f;
@@ -731,6 +743,11 @@ CR_D void camera_ray(const KernelArgs<real>& A, uint32_t pix_i, uint32_t pix_j, 
         orig = add(add(f.from, scale(px, f.ddu)), scale(py, f.ddv));
     }
     ro = orig; rd = sub(ps, orig); rtime = ts;
+}
+template <typename real, bool ANIM, bool CAMK = false>
+CR_D void camera_ray(const KernelArgs<real>& A, uint32_t pix_i, uint32_t pix_j, int32_t sample, uint64_t& rng, V3<real>& ro, V3<real>& rd,
+                     real& rtime) {
+    camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j, sample, rng, ro, rd, rtime, A.current_time);
 }
 
 // A record of a table that sits either in LDS or in global memory (RES_TOP's materials and textures, decided per
@@ -1386,9 +1403,13 @@ template <typename real> struct MaxBlock { static constexpr int value = 1024; };
 // -- about 48 global atomics per 1024 samples instead of 3 per sample (global atomics execute at the memory side, one
 // request per lane when the lanes' addresses are scattered).  A straggler whose tile has already been flushed adds to
 // the global sums directly.
+// BATCH: the kernels that render a batch of frames (KernelArgs::n_frames) -- the RELAX kernels movies run on, with a keyed
+// camera (CAMK) or keyed primitives (ANIM); a batch of a scene without keys runs on the CAMK kernel.  The static kernels
+// (the stills, the headline among them) do not carry the frame arithmetic: in them it moved the register allocation.
 template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
 CR_D void pathtrace_body(const KernelArgs<real>& A) {
     using EntryT = typename EntryOf<real, ORD>::type;
+    constexpr bool BATCH = RELAX && (ANIM || CAMK);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifdef CR_HOLD_VCC
     unsigned long long vcc_hold;
@@ -1460,7 +1481,10 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         if constexpr (RELAX) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             if (tile != kFxNoTile) {
-                const uint32_t ti = (tile % A.tiles_x) << A.sg_lw, tj = (tile / A.tiles_x) << A.sg_lh;
+                const uint32_t ti = (tile % A.tiles_x) << A.sg_lw;
+                uint32_t tj = (tile / A.tiles_x) << A.sg_lh;
+                // BATCH: the tile's first row in fx_acc, where a batch's frames are H rows apart (tiles_y << sg_lh in pix_j)
+                if constexpr (BATCH) tj -= batch_frame(A, tj) * ((A.tiles_y << A.sg_lh) - (uint32_t)A.cam.H);
                 for (uint32_t k = lane; k < fx_words; k += 64) {   // 48 words for the usual 4 x 4 tile: one pass
                     unsigned long long* w = fx_slots + slot * fx_words + k;
                     const unsigned long long v = *w;
@@ -1533,7 +1557,9 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                     pix_i = ((tile % A.tiles_x) << A.sg_lw) + px;
                     pix_j = ((tile / A.tiles_x) << A.sg_lh) + py;
                     sample = A.sample_begin + (int32_t)(sg * (64u >> (A.sg_lw + A.sg_lh)) + ds);
-                    if (pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H && sample < A.sample_end) state = ST_NEED_SAMPLE;
+                    uint32_t row = pix_j;   // BATCH: pix_j counts the rows of a whole batch; the frame's own row decides
+                    if constexpr (BATCH) row -= batch_frame(A, pix_j) * (A.tiles_y << A.sg_lh);
+                    if (pix_i < (uint32_t)cam.W && row < (uint32_t)cam.H && sample < A.sample_end) state = ST_NEED_SAMPLE;
                     // else: padding of an edge tile or of the last sample group, ask again next round
                 }
             }
@@ -1577,7 +1603,11 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         // ---------------- regeneration: camera rays (cast_ray, ray_casting.rs:82-105)
         if (state == ST_NEED_SAMPLE) {
             CR_DIAG_HIT(dgp, DG_REGEN_WAVE, DG_REGEN_LANE);
-            camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
+            if constexpr (BATCH) {   // a frame of a batch: its own row and its own ray times
+                const uint32_t f = batch_frame(A, pix_j);
+                camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j - f * (A.tiles_y << A.sg_lh), sample, rng, ro, rd, rtime,
+                                             A.n_frames > 1u ? A.frame_times[f] : A.current_time);
+            } else camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
             depth_left = A.max_depth; stack_n = 0;
             if constexpr (RELAX) thr = mk<real>(1, 1, 1);
             state = ST_TRACE;
@@ -1639,7 +1669,11 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                     bool in_lds = true;
                     if (tile == fx_tile0) dst = fx_slots + px * 3u;
                     else if (tile == fx_tile1) dst = fx_slots + fx_words + px * 3u;
-                    else { dst = A.fx_acc + ((size_t)pix_j * (size_t)cam.W + pix_i) * 3; in_lds = false; }
+                    else {
+                        uint32_t row = pix_j;   // fx_acc's row
+                        if constexpr (BATCH) row -= batch_frame(A, pix_j) * ((A.tiles_y << A.sg_lh) - (uint32_t)cam.H);
+                        dst = A.fx_acc + ((size_t)row * (size_t)cam.W + pix_i) * 3; in_lds = false;
+                    }
                     if (!nan) {
                         if (in_lds) {
                             auto d = (__attribute__((address_space(3))) unsigned long long*)dst;   // ds_add_u64, not a flat atomic

@@ -430,6 +430,7 @@ public:
     int device = 0;
     int gpus = 1;            // > 1 (or use_group): still images split their samples over devices 0..gpus-1 through cr_group_*;
     bool use_group = false;  // movies give frame f to device f % gpus (scene/mod.rs:307-316: frames are independent)
+    size_t frames_per_launch = 1;   // movies: > 1 renders that many frames per cr_render_frames_host call (relaxed sums)
 
     Scene(double aspect, uint32_t width, size_t rate, double shutter, size_t threads)
         : scene_cam(aspect, width, (double)rate, shutter, threads), frame_rate(rate) {}
@@ -592,17 +593,27 @@ public:
         buf.resize((size_t)scene_cam.image_width * scene_cam.image_height * 3);
         return cr_render_host(h, &cd, &p, buf.data(), stats);
     }
+    // The frames `frs` in one call: frame k at k * W*H*3 reals of `real_type` in `buf`.
+    int32_t render_frames(CrHandle* h, std::vector<double>& buf, const std::vector<int32_t>& frs, CrStats* stats) const {
+        std::vector<CrKeyframe> fk, ak;
+        CrCameraDesc cd = camera_desc(fk, ak);
+        CrRenderParams p = render_params(0);   // the frame indices come from frs
+        buf.resize((size_t)scene_cam.image_width * scene_cam.image_height * 3 * frs.size());
+        return cr_render_frames_host(h, &cd, &p, frs.data(), (int32_t)frs.size(), buf.data(), stats);
+    }
+    size_t frame_bytes() const { return (size_t)scene_cam.image_width * scene_cam.image_height * 3 * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float)); }
     // The file: "ppm" = the reference's ASCII P3 (camera/mod.rs:286,306-311); "p6" / "png" = SURVEY 8(f) row 3,
     // the same per-channel bytes in binary PPM / PNG.
-    int32_t write_frame(const std::string& fname, const std::vector<double>& buf) const {
+    int32_t write_frame(const std::string& fname, const void* rgb) const {
         const Camera& c = scene_cam;
         const std::string path = fname + (frame_format == "png" ? ".png" : ".ppm");
-        int32_t rc = frame_format == "png" ? cr_write_png(path.c_str(), buf.data(), real_type, c.image_width, c.image_height)
-                   : frame_format == "p6" ? cr_write_ppm_binary(path.c_str(), buf.data(), real_type, c.image_width, c.image_height)
-                                          : cr_write_ppm(path.c_str(), buf.data(), real_type, c.image_width, c.image_height);
+        int32_t rc = frame_format == "png" ? cr_write_png(path.c_str(), rgb, real_type, c.image_width, c.image_height)
+                   : frame_format == "p6" ? cr_write_ppm_binary(path.c_str(), rgb, real_type, c.image_width, c.image_height)
+                                          : cr_write_ppm(path.c_str(), rgb, real_type, c.image_width, c.image_height);
         if (rc == CR_OK && !quiet) fprintf(stderr, "Successful render! Image stored at: %s\n", path.c_str());
         return rc;
     }
+    int32_t write_frame(const std::string& fname, const std::vector<double>& buf) const { return write_frame(fname, (const void*)buf.data()); }
     bool quiet = false;   // no "Successful render!" line per frame
     int32_t render_image(CrHandle* h, const std::string& fname, CrStats* stats = nullptr) {
         std::vector<double> buf;
@@ -625,10 +636,12 @@ public:
         if (stats) *stats = gs.render;
         return rc;
     }
-    // render_movie (scene/mod.rs:295-322) for the frames first, first + step, ... on one handle: frame k is encoded and
-    // written by a helper thread while frame k+1 renders (two buffers; SURVEY 8(f) row 3 -- the reference formats and
-    // writes each frame before starting the next).  render_ms: time this thread spent inside renders; write_ms: time the
-    // helper threads spent encoding and writing (overlapped, so it is not part of the wall clock unless it is the longer one).
+    // render_movie (scene/mod.rs:295-322) for the frames first, first + step, ... on one handle, frames_per_launch of
+    // them per call (cr_render_frames_host; a library that refuses the batch -- reference order, refit boxes -- gets one
+    // frame per call, the same files).  Batch b is encoded and written by a helper thread while batch b+1 renders (two
+    // buffers; SURVEY 8(f) row 3 -- the reference formats and writes each frame before starting the next).  render_ms:
+    // time this thread spent inside renders; write_ms: time the helper threads spent encoding and writing (overlapped,
+    // so it is not part of the wall clock unless it is the longer one).
     int32_t render_movie_frames(CrHandle* h, const std::string& fname, size_t first, size_t step, size_t frames, size_t digits,
                                 CrStats* stats, Timing* tm) const {
         std::vector<double> bufs[2];
@@ -636,22 +649,33 @@ public:
         int32_t write_rc[2] = {CR_OK, CR_OK};
         double write_ms[2] = {0, 0};
         int32_t rc = CR_OK;
+        bool batched = frames_per_launch > 1;
         size_t k = 0;
-        for (size_t fr = first; rc == CR_OK && fr < frames; fr += step, k++) {
+        for (size_t fr = first; rc == CR_OK && fr < frames; k++) {
             const int slot = (int)(k & 1);
             if (writers[slot].joinable()) { writers[slot].join(); if (write_rc[slot] != CR_OK) { rc = write_rc[slot]; break; } }
-            std::string num = std::to_string(fr);
-            num = std::string(digits - num.size(), '0') + num;
+            std::vector<int32_t> batch;   // fr, fr + step, ...
+            for (size_t f = fr; f < frames && batch.size() < (batched ? frames_per_launch : 1); f += step) batch.push_back((int32_t)f);
             CrStats st;
             const double t0 = now_ms();
-            rc = render_frame(h, bufs[slot], &st, (int64_t)fr);
-            if (tm) { tm->render_ms += now_ms() - t0; tm->kernel_ms += st.kernel_ms; tm->frames++; }
+            if (batched) {
+                rc = render_frames(h, bufs[slot], batch, &st);
+                if (rc == CR_ERR_UNSUPPORTED) { batched = false; batch.resize(1); }
+            }
+            if (!batched) rc = render_frame(h, bufs[slot], &st, (int64_t)batch[0]);
+            if (tm) { tm->render_ms += now_ms() - t0; tm->kernel_ms += st.kernel_ms; tm->frames += batch.size(); }
             if (stats) *stats = st;
             if (rc != CR_OK) break;
-            const std::string stem = fname + "/artifacts/image" + num;
-            writers[slot] = std::thread([this, stem, slot, &bufs, &write_rc, &write_ms] {
+            std::vector<std::string> stems;
+            for (int32_t f : batch) {
+                std::string num = std::to_string(f);
+                stems.push_back(fname + "/artifacts/image" + std::string(digits - num.size(), '0') + num);
+            }
+            fr = (size_t)batch.back() + step;
+            writers[slot] = std::thread([this, stems, slot, &bufs, &write_rc, &write_ms] {
                 const double w0 = now_ms();
-                write_rc[slot] = write_frame(stem, bufs[slot]);
+                for (size_t i = 0; i < stems.size() && write_rc[slot] == CR_OK; i++)
+                    write_rc[slot] = write_frame(stems[i], (const char*)bufs[slot].data() + i * frame_bytes());
                 write_ms[slot] += now_ms() - w0;
             });
         }

@@ -8,6 +8,7 @@
 // the wrapper boxes per frame so keyframed primitives are not clipped; the reference does not),
 // --dump-desc FILE (write the flattened scene description and exit; used by the tests to check
 // this mirror against the Python one), --sum-order reference|relaxed (CrRenderParams.sum_order; default: the library's),
+// --frames-per-launch N (movies: N frames per library call through cr_render_frames_host, relaxed sums; default 1),
 // --repeat N --timing (measurement: render_scene N times in this process, one JSON line of wall-clock phases each --
 // the shape of the reference's criterion benchmark, benches/renderer_benchmark.rs:16-42 -- the first is the cold one).
 #include "crucible.hpp"
@@ -46,6 +47,7 @@ int main(int argc, char** argv) {
     std::string bvh = "reference", sky, format = "ppm";
     bool refit = false, use_group = false, timing = false;
     int gpus = 1, repeat = 1;
+    long frames_per_launch = 1;
     std::string sum_order = "default";
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -70,6 +72,7 @@ int main(int argc, char** argv) {
         else if (a == "--group") use_group = true;
         else if (a == "--timing") timing = true;
         else if (a == "--repeat") repeat = std::max(1, atoi(next()));
+        else if (a == "--frames-per-launch") frames_per_launch = atol(next());
         else if (a == "--sum-order") sum_order = next();
         else if (a == "--dump-desc") dump = next();
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -112,6 +115,8 @@ int main(int argc, char** argv) {
         scene.bvh_mode = bvh == "sah" ? CR_BVH_SAH : (bvh == "ordered" ? CR_BVH_SAH_ORDERED : (bvh == "lbvh" ? CR_BVH_LBVH : CR_BVH_REFERENCE));
         scene.refit_boxes = refit;
         scene.gpus = std::max(1, gpus); scene.use_group = use_group;
+        if (frames_per_launch < 1) { fprintf(stderr, "--frames-per-launch takes a positive count\n"); return 2; }
+        scene.frames_per_launch = (size_t)frames_per_launch;
         if (format != "ppm" && format != "p6" && format != "png") { fprintf(stderr, "--format takes ppm, p6 or png\n"); return 2; }
         scene.frame_format = format;
         if (sum_order != "default" && sum_order != "reference" && sum_order != "relaxed") { fprintf(stderr, "--sum-order takes default, reference or relaxed\n"); return 2; }

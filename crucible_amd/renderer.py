@@ -100,6 +100,34 @@ class Renderer:
                                               C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    def render_frames(self, cam, frames, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                      output_sum=False, want_stats=True, sum_order=None):
+        """cr_render_frames_host: the frames `frames` (frame indices; cam.frame is not used) in one launch, as an
+        (F, H, W, 3) host array of f32/f64 -- of uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM.  Frame k equals
+        render() at frame frames[k] bit for bit.  Needs CR_SUM_RELAXED.  Returns (frames array, stats dict)."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
+        out = np.empty((max(1, fr.size), cam.image_height, cam.image_width, 3), dtype=dtype)
+        st = A.CrStats()
+        self._check(self.lib.cr_render_frames_host(self.h, C.byref(cd), C.byref(p), fr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   fr.size, out.ctypes.data_as(C.c_void_p),
+                                                   C.byref(st) if want_stats else None))
+        return out, st.as_dict()
+
+    def render_frames_device(self, cam, frames, d_ptr, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
+                             sample_count=None, output_sum=False, want_stats=False, sum_order=None):
+        """cr_render_frames_device: the frames `frames` into device memory at `d_ptr` (F*W*H*3 reals, or uint64 words
+        with output_sum=A.CR_OUTPUT_FIXED_SUM), frame after frame.  Asynchronous unless want_stats."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        st = A.CrStats()
+        self._check(self.lib.cr_render_frames_device(self.h, C.byref(cd), C.byref(p), fr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     fr.size, C.c_void_p(d_ptr), C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
         """cr_fixed_sums_to_rgb: summed CR_OUTPUT_FIXED_SUM words of a whole frame (device pointer, W*H*3 uint64) ->
         its per-pixel means at device pointer `d_out` (W*H*3 reals), exactly the relaxed frame.  Asynchronous on the

@@ -475,6 +475,7 @@ class Scene:
         self.real_type = A.CR_REAL_F32
         self.device = 0
         self.bvh_mode = A.CR_BVH_REFERENCE   # A.CR_BVH_SAH: the quality builder (include/crucible_hip.h)
+        self.frames_per_launch = 1   # render_movie: N > 1 renders N frames per call through Renderer.render_frames
 
     @classmethod
     def new_image(cls, aspect_ratio, image_width, frame_rate, shutter_angle, thread_count):
@@ -677,7 +678,7 @@ class Scene:
                 f"{fname}/movie.mp4"]
 
     def render_movie(self, fname):
-        from .renderer import Renderer
+        from .renderer import CrucibleError, Renderer
         os.mkdir(fname)   # scene/mod.rs:296: fails if it exists
         os.mkdir(os.path.join(fname, "artifacts"))
         frames = self.compute_frame_count()
@@ -685,9 +686,26 @@ class Scene:
         r = Renderer(self.device)
         try:
             r.upload_scene(self.flatten())
-            for frame in range(frames):
-                img, _ = r.render(self.scene_cam, seed=self.seed, real_type=self.real_type)
-                r.write_ppm(os.path.join(fname, "artifacts", f"image{frame:0{digits}d}.ppm"), img)
-                self.scene_cam.next_frame()
+            n = max(1, int(self.frames_per_launch))
+            batched = n > 1
+            frame = 0
+            while frame < frames:
+                if batched:
+                    # the camera's frame counter for each file, as the one-frame loop advances it
+                    batch = [self.scene_cam.frame + k for k in range(min(n, frames - frame))]
+                    try:
+                        imgs, _ = r.render_frames(self.scene_cam, batch, seed=self.seed, real_type=self.real_type)
+                    except CrucibleError as e:
+                        if e.code != A.CR_ERR_UNSUPPORTED:
+                            raise
+                        batched = False   # reference order or refit boxes: one frame per call, the same files
+                        continue
+                else:
+                    img, _ = r.render(self.scene_cam, seed=self.seed, real_type=self.real_type)
+                    imgs = img[None]
+                for img in imgs:
+                    r.write_ppm(os.path.join(fname, "artifacts", f"image{frame:0{digits}d}.ppm"), img)
+                    self.scene_cam.next_frame()
+                    frame += 1
         finally:
             r.close()

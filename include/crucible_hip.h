@@ -369,6 +369,35 @@ CR_API int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRe
 CR_API int32_t cr_render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
                        void* h_out_rgb, CrStats* stats);
 
+/*
+ * A batch of movie frames in one launch: the frames frames[0..n_frames-1] of one camera and one set of params.
+ * frames[k] is the frame index params->frame would carry for frame k (params->frame itself is ignored); any list
+ * works -- consecutive, strided (m, m+n, ... for one device of several), descending or repeated.  The output holds
+ * n_frames consecutive frames, frame k at k * image_width*image_height*3 elements, each laid out as cr_render_device
+ * writes one frame: reals for output_sum 0 and 1, uint64_t words at the whole frame's scale for CR_OUTPUT_FIXED_SUM.
+ * sample_begin / sample_count mean what they mean for a single render.
+ *
+ * Frame k is bit for bit what cr_render_device writes for the same camera and params with frame = frames[k], in f32
+ * and in f64: the frames differ only in their ray times (computed on the host as for a single render), the RNG streams
+ * are keyed by the frame's own pixel index, and CR_SUM_RELAXED sums are integer sums that do not depend on the order
+ * of the work.  `stats` covers the whole call: the counters and `samples` summed over the frames, one kernel_ms.
+ *
+ * Needs CR_SUM_RELAXED (after CR_SUM_DEFAULT / CRUCIBLE_SUM_ORDER are resolved) and the megakernel pipeline, and no
+ * box refit (refit_boxes with keyed primitives or HitList elements: the boxes are per frame, a batch shares one set):
+ * otherwise CR_ERR_UNSUPPORTED, and the caller renders those frames one at a time.  A null `frames`, n_frames < 1 or
+ * anything cr_render_device rejects: CR_ERR_INVALID_ARG.  The handle keeps fixed-point sums for all frames (24 bytes
+ * per pixel per frame); a batch too large for device memory fails with CR_ERR_HIP.  A batch that would overflow the
+ * 32-bit work counter runs as several launches of whole frames; a frame that alone needs sample batches runs frame by
+ * frame.  Asynchronous unless `stats` is non-NULL, like cr_render_device.
+ */
+CR_API int32_t cr_render_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                       const int32_t* frames, int32_t n_frames, void* d_out, CrStats* stats);
+
+/* Same, into a HOST buffer of n_frames frames (synchronous).  The Color::new check of cr_render_host applies frame by
+ * frame; CR_ERR_NAN's message names the first frame that fails it (stats->nan_pixels counts all frames). */
+CR_API int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                     const int32_t* frames, int32_t n_frames, void* h_out, CrStats* stats);
+
 /* The wrapper tree the device walks for `real_type`, as BVHWrapper's shape (src/objects/bvhwrapper.rs:7-11):
  * wrapper k has boxes[6k..6k+5] = xmin,xmax,ymin,ymax,zmin,zmax (exact values of `real_type`) and
  * children[2k], children[2k+1] = left, right: >= 0 another wrapper's index, < 0 the bitwise complement of a
