@@ -932,6 +932,20 @@ static int material_scatter(const Scene* sc, const Ray* r_in, const HitRecord* r
 
 /* ------------------------------------------------------------------ ray_color */
 
+/* the colour of a ray that missed everything (ray_casting.rs:133-151) */
+static Color sky_color(const Scene* sc, Ray r, Counters* cn) {
+    Vec3 ud = v_unit(r.direction);
+    if (sc->sky_kind == CR_SKY_SPHERICAL) {
+        real theta = R_ATAN2(ud.x, ud.z);
+        real phi = R_ASIN(ud.y);
+        real u = (theta / (R(2.0) * R_PI)) + R(0.5);
+        real v = (phi / R_PI) + R(0.5);
+        return image_lookup(sc, sc->sky_image, u, v, cn);
+    }
+    real a = R(0.5) * (ud.y + R(1.0));
+    return c_add(c_scale(R(1.0) - a, c3(1, 1, 1)), c_scale(a, c3(R(0.5), R(0.7), R(1.0))));
+}
+
 static Color ray_color(const Scene* sc, Ray r, uint32_t depth, Rng* rng, Counters* cn) {   /* ray_casting.rs:112-152 */
     if (depth == 0) return c3(0, 0, 0);
     Interval iv = {R(0.001), R_INF};
@@ -944,16 +958,31 @@ static Color ray_color(const Scene* sc, Ray r, uint32_t depth, Rng* rng, Counter
             return c_mul(attenuation, ray_color(sc, s, depth - 1, rng, cn));
         return c3(0, 0, 0);
     }
-    Vec3 ud = v_unit(r.direction);
-    if (sc->sky_kind == CR_SKY_SPHERICAL) {
-        real theta = R_ATAN2(ud.x, ud.z);
-        real phi = R_ASIN(ud.y);
-        real u = (theta / (R(2.0) * R_PI)) + R(0.5);
-        real v = (phi / R_PI) + R(0.5);
-        return image_lookup(sc, sc->sky_image, u, v, cn);
+    return sky_color(sc, r, cn);
+}
+
+/* CR_SUM_RELAXED (not in the reference; include/crucible_hip.h): the same path as ray_color -- same draws, same walks,
+ * same counters -- with the attenuations multiplied in path order, thr = ((1 * a_1) * a_2) * ..., per component and
+ * without Color's clamp (every factor is in [0, 1] or NaN).  A dielectric's attenuation is exactly (1, 1, 1) and is
+ * skipped.  A miss gives thr * sky; a path whose depth runs out or whose scatter returns None gives black. */
+static Color ray_color_relaxed(const Scene* sc, Ray r, uint32_t depth, Rng* rng, Counters* cn) {
+    Color thr = c3(R(1.0), R(1.0), R(1.0));
+    for (; depth > 0; depth--) {
+        Interval iv = {R(0.001), R_INF};
+        HitRecord h;
+        cn->segments++;
+        if (!hittable_hit(sc->world, &r, iv, &h, cn)) {
+            Color sky = sky_color(sc, r, cn);
+            return c3(thr.r * sky.r, thr.g * sky.g, thr.b * sky.b);
+        }
+        Color attenuation = c3(0, 0, 0);
+        Ray s;
+        if (!material_scatter(sc, &r, &h, &attenuation, &s, rng, cn)) return c3(0, 0, 0);
+        if (sc->materials[h.mat].kind != CR_MAT_DIELECTRIC)
+            thr = c3(thr.r * attenuation.r, thr.g * attenuation.g, thr.b * attenuation.b);
+        r = s;
     }
-    real a = R(0.5) * (ud.y + R(1.0));
-    return c_add(c_scale(R(1.0) - a, c3(1, 1, 1)), c_scale(a, c3(R(0.5), R(0.7), R(1.0))));
+    return c3(0, 0, 0);
 }
 
 /* ------------------------------------------------------------------ camera */
@@ -1033,28 +1062,71 @@ static void camera_setup(Camera* c, const CrCameraDesc* d) {
     c->vup = v3((real)d->vup[0], (real)d->vup[1], (real)d->vup[2]);
 }
 
-/* Camera::cast_ray (ray_casting.rs:64-108) restricted to sample indices
- * [s0, s0+n): returns the running sum in draw order (average_samples :154-173 sums
- * sequentially); the caller divides. */
-static void cast_ray_sum(const Scene* sc, const Camera* cam, const CrRenderParams* p, uint32_t i, uint32_t j,
-                         real sum[3], Counters* cn) {
+/* Camera::cast_ray (ray_casting.rs:64-108) for the sample index s: its primary ray, then its colour with the
+ * attenuations multiplied in the params' sum order. */
+static Color cast_ray(const Scene* sc, const Camera* cam, const CrRenderParams* p, uint32_t i, uint32_t j, int s,
+                      Counters* cn) {
     real current_time = (real)p->frame * (R(1.0) / (real)p->frame_rate);
     real shutter_length = ((real)p->shutter_angle / R(360.0)) * (R(1.0) / (real)p->frame_rate);
-    real r_tot = R(0.0), g_tot = R(0.0), b_tot = R(0.0);
     uint32_t pixel = j * (uint32_t)cam->W + i;
+    Rng rng = rng_for_sample(p->seed, pixel, (uint32_t)s);
+    real time_sample = current_time + rng_range(&rng, R(0.0), shutter_length);
+    Vec3 cc = cam_from(cam, time_sample);
+    real ox = rng_uniform(&rng) - R(0.5);            /* sample_square, camera/mod.rs:368-376 */
+    real oy = rng_uniform(&rng) - R(0.5);
+    Vec3 ps = get_pixel_pos(cam, i, j, v3(ox, oy, R(0.0)), time_sample);
+    Vec3 orig = cam->defocus_on ? defocus_disk_sample(cam, time_sample, &rng) : cc;
+    Ray ray = {orig, v_sub(ps, orig), time_sample};
+    if (p->sum_order == CR_SUM_RELAXED) return ray_color_relaxed(sc, ray, (uint32_t)p->max_depth, &rng, cn);
+    return ray_color(sc, ray, (uint32_t)p->max_depth, &rng, cn);
+}
+
+/* The reference order: the running sum in draw order (average_samples :154-173 sums sequentially); the caller
+ * divides. */
+static void cast_ray_sum(const Scene* sc, const Camera* cam, const CrRenderParams* p, uint32_t i, uint32_t j,
+                         real sum[3], Counters* cn) {
+    real r_tot = R(0.0), g_tot = R(0.0), b_tot = R(0.0);
     for (int s = p->sample_begin; s < p->sample_begin + p->sample_count; s++) {
-        Rng rng = rng_for_sample(p->seed, pixel, (uint32_t)s);
-        real time_sample = current_time + rng_range(&rng, R(0.0), shutter_length);
-        Vec3 cc = cam_from(cam, time_sample);
-        real ox = rng_uniform(&rng) - R(0.5);            /* sample_square, camera/mod.rs:368-376 */
-        real oy = rng_uniform(&rng) - R(0.5);
-        Vec3 ps = get_pixel_pos(cam, i, j, v3(ox, oy, R(0.0)), time_sample);
-        Vec3 orig = cam->defocus_on ? defocus_disk_sample(cam, time_sample, &rng) : cc;
-        Ray ray = {orig, v_sub(ps, orig), time_sample};
-        Color c = ray_color(sc, ray, (uint32_t)p->max_depth, &rng, cn);
+        Color c = cast_ray(sc, cam, p, i, j, s, cn);
         r_tot += c.r; g_tot += c.g; b_tot += c.b;
     }
     sum[0] = r_tot; sum[1] = g_tot; sum[2] = b_tot;
+}
+
+/* CR_SUM_RELAXED's fixed-point scale: S = min(52, 62 - floor(log2 n)), so that n samples of at most 1.0 sum below
+ * 2^63.  n < 1 (an empty shard) adds nothing at any scale. */
+static int fixed_scale_log2(int64_t n) {
+    int lg = 0;
+    while (n >= ((int64_t)2 << lg)) lg++;
+    return 62 - lg < 52 ? 62 - lg : 52;
+}
+
+/* CR_SUM_RELAXED: the pixel's words over sample indices [s0, s0+n).  Each sample adds round_half_even(c * 2^S) per
+ * channel (c in [0, 1], so the product is exact and rint rounds once); a channel that is not a number sets bit 63,
+ * the pixel's NaN flag.  A black sample adds nothing. */
+static void cast_ray_fixed(const Scene* sc, const Camera* cam, const CrRenderParams* p, uint32_t i, uint32_t j, int S,
+                           uint64_t w[3], Counters* cn) {
+    const uint64_t F = (uint64_t)1 << 63;
+    w[0] = w[1] = w[2] = 0;
+    for (int s = p->sample_begin; s < p->sample_begin + p->sample_count; s++) {
+        Color c = cast_ray(sc, cam, p, i, j, s, cn);
+        double x[3] = {(double)c.r, (double)c.g, (double)c.b};
+        for (int k = 0; k < 3; k++) {
+            if (x[k] != x[k]) w[k] |= F;
+            else w[k] += (uint64_t)rint(ldexp(x[k], S));
+        }
+    }
+}
+
+/* A pixel's words -> its reals: m = w & ~2^63 converted to double (correctly rounded), times 2^-S; divided by the
+ * frame's sample count for a mean (output_sum 0), kept as the shard's sum for output_sum 1; NaN where the flag is set;
+ * then rounded once to `real`. */
+static real fixed_to_real(uint64_t w, int S, const CrRenderParams* p) {
+    const uint64_t F = (uint64_t)1 << 63;
+    double s = ldexp((double)(w & ~F), -S);
+    if (p->output_sum == 0) s = s / (double)p->samples;
+    if (w & F) s = NAN;
+    return (real)s;
 }
 
 /* ------------------------------------------------------------------ exported API */
@@ -1298,7 +1370,8 @@ static void scene_prepare_boxes(Scene* sc, int refit, real ta, real tb) {
 
 typedef struct {
     const Scene* sc; const Camera* cam; const CrRenderParams* p;
-    real* out; int64_t pix_begin, pix_end;
+    void* out; int64_t pix_begin, pix_end;
+    int fx_s;                /* CR_SUM_RELAXED: the fixed-point scale's log2 */
     volatile int64_t* next;
     Counters cn; uint64_t nan_pixels;
 } Job;
@@ -1324,9 +1397,21 @@ static void* worker(void* arg) {   /* one pixel per work item, cpu_threading.rs:
         if (pix >= jb->pix_end) break;
         uint32_t i = (uint32_t)(pix % W), j = (uint32_t)(pix / W);
         real sum[3];
-        cast_ray_sum(jb->sc, jb->cam, jb->p, i, j, sum, &jb->cn);
-        real* o = jb->out + (pix - jb->pix_begin) * 3;
-        if (jb->p->output_sum) { o[0] = sum[0]; o[1] = sum[1]; o[2] = sum[2]; }
+        if (jb->p->sum_order == CR_SUM_RELAXED) {
+            uint64_t w[3];
+            cast_ray_fixed(jb->sc, jb->cam, jb->p, i, j, jb->fx_s, w, &jb->cn);
+            if (jb->p->output_sum == CR_OUTPUT_FIXED_SUM) {
+                uint64_t* o = (uint64_t*)jb->out + (pix - jb->pix_begin) * 3;
+                o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+                continue;
+            }
+            for (int k = 0; k < 3; k++) sum[k] = fixed_to_real(w[k], jb->fx_s, jb->p);
+        } else cast_ray_sum(jb->sc, jb->cam, jb->p, i, j, sum, &jb->cn);
+        real* o = (real*)jb->out + (pix - jb->pix_begin) * 3;
+        if (jb->p->sum_order == CR_SUM_RELAXED && jb->p->output_sum == 0) {   /* already the mean */
+            o[0] = sum[0]; o[1] = sum[1]; o[2] = sum[2];
+            for (int k = 0; k < 3; k++) if (!(o[k] >= R(0.0) && o[k] <= R(1.0))) { jb->nan_pixels++; break; }
+        } else if (jb->p->output_sum) { o[0] = sum[0]; o[1] = sum[1]; o[2] = sum[2]; }
         else {
             real cnt = (real)jb->p->samples;   /* `/= sample_count as f64`, ray_casting.rs:168-170 */
             o[0] = sum[0] / cnt; o[1] = sum[1] / cnt; o[2] = sum[2] / cnt;
@@ -1338,10 +1423,15 @@ static void* worker(void* arg) {   /* one pixel per work item, cpu_threading.rs:
 }
 
 /* Renders pixels [pix_begin, pix_end) in row-major order (pix = j*W + i) into
- * out[(pix-pix_begin)*3..].  n_threads OS threads pull pixels from one counter. */
+ * out[(pix-pix_begin)*3..]: reals, or uint64_t words for CR_SUM_RELAXED with CR_OUTPUT_FIXED_SUM.  n_threads OS
+ * threads pull pixels from one counter.  sum_order CR_SUM_RELAXED is the library's relaxed frame; CR_SUM_DEFAULT and
+ * CR_SUM_REFERENCE_ORDER are the reference's order (the oracle has no handle default). */
 EXPORT int32_t oracle_render(const Scene* sc, const CrCameraDesc* cd, const CrRenderParams* p, int64_t pix_begin,
-                             int64_t pix_end, real* out, int32_t n_threads, CrStats* stats) {
+                             int64_t pix_end, void* out, int32_t n_threads, CrStats* stats) {
     if (p->real_type != ORACLE_REAL_TYPE) return CR_ERR_INVALID_ARG;
+    if (p->output_sum == CR_OUTPUT_FIXED_SUM && p->sum_order != CR_SUM_RELAXED) return CR_ERR_INVALID_ARG;
+    /* the scale: of the whole frame's `samples` for fixed words (so shards add up), else of the shard's own count */
+    const int fx_s = fixed_scale_log2(p->output_sum == CR_OUTPUT_FIXED_SUM ? p->samples : p->sample_count);
     Camera cam;
     camera_setup(&cam, cd);
     if (n_threads < 1) n_threads = 1;
@@ -1356,7 +1446,7 @@ EXPORT int32_t oracle_render(const Scene* sc, const CrCameraDesc* cd, const CrRe
     pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)n_threads);
     for (int t = 0; t < n_threads; t++) {
         jobs[t].sc = sc; jobs[t].cam = &cam; jobs[t].p = p; jobs[t].out = out;
-        jobs[t].pix_begin = pix_begin; jobs[t].pix_end = pix_end; jobs[t].next = &next;
+        jobs[t].pix_begin = pix_begin; jobs[t].pix_end = pix_end; jobs[t].next = &next; jobs[t].fx_s = fx_s;
         if (n_threads > 1) pthread_create(&th[t], NULL, worker, &jobs[t]);
     }
     if (n_threads == 1) worker(&jobs[0]);

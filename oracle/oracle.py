@@ -133,13 +133,16 @@ class Oracle:
         assert rc == 0, "malformed wrapper tree"
 
     def render(self, scene_h, cam, *, seed, sample_begin=0, sample_count=None, output_sum=False, pix_begin=0,
-               pix_end=None, n_threads=None):
-        """Returns (H*W*3 array reshaped (n_pix,3) of reals, stats dict)."""
+               pix_end=None, n_threads=None, sum_order=A.CR_SUM_REFERENCE_ORDER):
+        """Returns (H*W*3 array reshaped (n_pix,3) of reals, stats dict).  sum_order=A.CR_SUM_RELAXED: the library's
+        relaxed frame (CR_SUM_DEFAULT is the reference order here); with output_sum=A.CR_OUTPUT_FIXED_SUM the array
+        holds its uint64 words."""
         cd = cam.desc()
-        p = cam.params(seed, self.real_type, sample_begin, sample_count, output_sum)
+        p = cam.params(seed, self.real_type, sample_begin, sample_count, output_sum, sum_order)
         n_pix_total = cam.image_width * cam.image_height
         pix_end = n_pix_total if pix_end is None else pix_end
-        out = np.zeros((pix_end - pix_begin, 3), dtype=self.np_real)
+        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else self.np_real
+        out = np.zeros((pix_end - pix_begin, 3), dtype=dtype)
         st = A.CrStats()
         if n_threads is None:
             n_threads = os.cpu_count() or 1
@@ -150,7 +153,7 @@ class Oracle:
 
     def render_image(self, scene, *, seed, n_threads=None, tree=None, linear_list=False, **kw):
         """tree: walk this exported wrapper tree; linear_list: no BVH at all (HitList::hit over the visible
-        primitives) -- the ground truth for closest hits."""
+        primitives) -- the ground truth for closest hits.  sum_order / output_sum as in render()."""
         flat = scene.flatten()
         h = self.scene_create(flat)
         try:

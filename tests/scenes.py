@@ -286,3 +286,54 @@ def wrapped_scene(width=96, samples=6, frame=0, depth=8, variant="mixed"):
     sc.add_element(BVHWrapper.new_wrapper(HitList.new(cluster(4.5, 2.0, 3))), "third")
     sc.translate_point((0.0, 0.0, 1.0), 1.0, LERP, LOCAL, "glass")
     return sc
+
+
+def deep_metal_scene(width=8, samples=4, depth=50, sky=True):
+    """Paths that bounce many times: a ring of near-white mirrors around the camera between a mirror floor and a
+    mirror ceiling, one matte and one glass sphere among them -- long attenuation products, the case where the two product orders of
+    CR_SUM_REFERENCE_ORDER and CR_SUM_RELAXED differ most."""
+    sc = Scene.new_image(2.0, width, 24, 180.0, 1)
+    cam = sc.scene_cam
+    cam.set_samples(samples)
+    cam.set_max_depth(depth)
+    cam.look_from((0.0, 1.0, 0.0))
+    cam.look_at((0.0, 1.0, -1.0))
+    cam.set_vfov(70.0)
+    sc.add_element(Sphere.new((0.0, -1000.0, 0.0), 1000.0, Metal.new((0.97, 0.95, 0.99), 0.02)), "floor")
+    sc.add_element(Sphere.new((0.0, 103.0, 0.0), 100.0, Metal.new((0.98, 0.97, 0.99), 0.05)), "ceiling")
+    for k in range(8):
+        a = 2.0 * np.pi * k / 8.0
+        mat = Metal.new((0.99, 0.9 + 0.01 * k, 0.95), 0.01 * (k % 3))
+        if k == 3:
+            mat = Lambertian.new_from_color((0.9, 0.8, 0.7), 1.0)
+        if k == 6:
+            mat = Dielectric.new(1.5)
+        sc.add_element(Sphere.new((3.0 * np.sin(a), 1.0, -3.0 * np.cos(a)), 1.4, mat), f"m{k}")
+    if sky:
+        rs = np.random.RandomState(5)
+        sc.load_spherical_skybox(RTWImage(rs.randint(100, 256, size=(8, 16, 3)).astype(np.uint8)))
+    return sc
+
+
+def white_sky_scene(width=2, samples=1):
+    """Nothing but a uniform white spherical sky (every texel 255, so every sample's colour is exactly 1.0): the largest
+    fixed-point words each scale allows."""
+    sc = Scene.new_image(2.0, width, 24, 180.0, 1)
+    cam = sc.scene_cam
+    cam.set_samples(samples)
+    cam.set_max_depth(4)
+    sc.load_spherical_skybox(RTWImage(np.full((4, 8, 3), 255, dtype=np.uint8)))
+    return sc
+
+
+# (real_type, tag, sum_order) cases of the bit-exact GPU suites: both precisions in the reference order (ids "f64" and
+# "f32", as the suites had them) and in CR_SUM_RELAXED, the library default ("f64-relaxed", "f32-relaxed"), each held to
+# the oracle in the same order.  Use as @pytest.mark.parametrize("rt,tag,order", REAL_ORDERS, ids=REAL_ORDER_IDS).
+def _real_orders():
+    from crucible_amd import _abi as A
+    reals = [(A.CR_REAL_F64, "f64"), (A.CR_REAL_F32, "f32")]
+    cases = [(rt, tag, A.CR_SUM_REFERENCE_ORDER) for rt, tag in reals] + [(rt, tag, A.CR_SUM_RELAXED) for rt, tag in reals]
+    return cases, [tag if order == A.CR_SUM_REFERENCE_ORDER else tag + "-relaxed" for _, tag, order in cases]
+
+
+REAL_ORDERS, REAL_ORDER_IDS = _real_orders()

@@ -95,7 +95,7 @@ def test_sah_tree_is_well_formed(renderer, rt, tag, build, mode):
         assert (axis == -1).all()
 
 
-@pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
+@pytest.mark.parametrize("rt,tag,order", scenes.REAL_ORDERS, ids=scenes.REAL_ORDER_IDS)
 @pytest.mark.parametrize("name,build,seed", [
     ("book1", lambda: book1_end_scene(1, scene_seed=3, image_width=160, samples=6), 77),
     ("checkered", lambda: checkered_spheres(1, image_width=64, samples=4), SEED),
@@ -105,12 +105,13 @@ def test_sah_tree_is_well_formed(renderer, rt, tag, build, mode):
     ("few9", lambda: scenes.few_spheres(9), SEED),
 ])
 @pytest.mark.parametrize("mode", [A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED, A.CR_BVH_LBVH], ids=["sah", "ordered", "lbvh"])
-def test_sah_mode_bit_exact_against_oracle_on_the_same_tree(renderer, oracles, rt, tag, name, build, seed, mode):
+def test_sah_mode_bit_exact_against_oracle_on_the_same_tree(renderer, oracles, rt, tag, order, name, build, seed, mode):
+    """In both sum orders; the relaxed CR_BVH_SAH_ORDERED renders are the ordered walk's RELAX kernels."""
     sc = build()
     flat = upload(renderer, sc, mode)
-    img, st = renderer.render(sc.scene_cam, seed=seed, real_type=rt)
+    img, st = renderer.render(sc.scene_cam, seed=seed, real_type=rt, sum_order=order)
     tree = renderer.export_bvh(rt) if visible(flat) else None
-    ref, rst = oracles[rt].render_image(sc, seed=seed, tree=tree)
+    ref, rst = oracles[rt].render_image(sc, seed=seed, tree=tree, sum_order=order)
     assert np.array_equal(img, ref), f"differing px = {(img != ref).any(axis=2).sum()}"
     for k in COUNTERS:
         assert st[k] == rst[k], (k, st[k], rst[k])

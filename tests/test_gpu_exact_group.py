@@ -65,10 +65,33 @@ def finalize(renderer, words, cam, rt, samples):
     return out.cpu().numpy()
 
 
+# words where the finalize can go wrong: the 32-bit halves of the conversion, the first words that do not fit a double
+# (2^53 + 1 ties to even downwards, 2^53 + 3 upwards), the largest magnitude and flagged words
+CRAFTED = [0, 1, (1 << 32) - 1, 1 << 32, (1 << 53) - 1, (1 << 53) + 1, (1 << 53) + 3, (1 << 63) - 1,
+           1 << 63, (1 << 63) | 5, (1 << 63) | ((1 << 63) - 1), (1 << 63) | (1 << 53) + 1]
+
+
+@pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
+@pytest.mark.parametrize("samples", [1, 3, 2047, 2048, 4095, 4096, 1 << 20, (1 << 31) - 1])
+def test_finalize_of_crafted_words_is_plain_arithmetic(renderer, rt, tag, samples):
+    """cr_fixed_sums_to_rgb against the header's finalize in plain Python (tests/test_oracle_relaxed.py: float(int),
+    ldexp, the divide, np.float32), bit for bit, at every scale the sample count selects."""
+    from types import SimpleNamespace
+
+    from test_oracle_relaxed import bits, finalize as plain_finalize
+    words = np.array(CRAFTED, dtype=np.uint64).reshape(1, len(CRAFTED) // 3, 3)
+    cam = SimpleNamespace(image_width=words.shape[1], image_height=1)
+    got = finalize(renderer, words, cam, rt, samples)
+    want = plain_finalize(words, samples, rt)
+    assert got.dtype == want.dtype
+    assert np.array_equal(bits(got), bits(want)), (got.reshape(-1), want.reshape(-1))
+
+
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
 @pytest.mark.parametrize("members,spp", [(2, 6), (3, 10), (4, 10), (8, 5)])
-def test_same_device_group_equals_the_single_relaxed_frame(renderer, monkeypatch, rt, tag, members, spp):
-    """(8, 5): three members have empty shards and contribute zero words."""
+def test_same_device_group_equals_the_single_relaxed_frame(renderer, oracles, monkeypatch, rt, tag, members, spp):
+    """(8, 5): three members have empty shards and contribute zero words.  The group's frame and counters are also the
+    relaxed oracle's, bit for bit."""
     monkeypatch.setenv("CRUCIBLE_GROUP_SAME_DEVICE", "1")
     sc = book1_end_scene(1, scene_seed=1, image_width=80, samples=spp)
     cam = sc.scene_cam
@@ -85,6 +108,10 @@ def test_same_device_group_equals_the_single_relaxed_frame(renderer, monkeypatch
         assert st["samples"] == 80 * 45 * spp
         dev, _ = group_device_frame(g, cam, rt)
         assert np.array_equal(dev, single)
+        want, wst = oracles[rt].render_image(sc, seed=SEED, sum_order=RELAX)
+        assert np.array_equal(img, want)
+        for k in COUNTERS:
+            assert st[k] == wst[k], k
     finally:
         g.close()
 
@@ -137,9 +164,10 @@ def test_one_member_group_through_rccl_is_exact(renderer, monkeypatch, rt, tag, 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
 @pytest.mark.parametrize("spp,splits", [(12, [(0, 5), (5, 0), (5, 4), (9, 3)]), (3000, [(0, 1000), (1000, 0), (1000, 2000)])],
                          ids=["12spp", "3000spp"])
-def test_fixed_sum_words_of_shards_add_to_the_frame(renderer, rt, tag, spp, splits):
+def test_fixed_sum_words_of_shards_add_to_the_frame(renderer, oracles, rt, tag, spp, splits):
     """Shard words combined with the header's rule equal the whole frame's words, and cr_fixed_sums_to_rgb of them is the
-    relaxed frame bit for bit.  3000 spp: the frame's scale 2^51 is not the one a 1000- or 2000-sample shard would take."""
+    relaxed frame bit for bit.  3000 spp: the frame's scale 2^51 is not the one a 1000- or 2000-sample shard would take.
+    Every shard's words are the relaxed oracle's."""
     sc = book1_end_scene(1, scene_seed=1, image_width=80 if spp < 100 else 16, samples=spp)
     cam = sc.scene_cam
     renderer.upload_scene(sc.flatten())
@@ -151,6 +179,8 @@ def test_fixed_sum_words_of_shards_add_to_the_frame(renderer, rt, tag, spp, spli
         part, pst = renderer.render(cam, seed=SEED, real_type=rt, sum_order=RELAX, output_sum=FIXED, sample_begin=b, sample_count=n)
         if n == 0:
             assert not part.any()
+        want, _ = oracles[rt].render_image(sc, seed=SEED, sum_order=RELAX, output_sum=FIXED, sample_begin=b, sample_count=n)
+        assert np.array_equal(part, want), (b, n)
         acc = combine(acc, part)
     assert np.array_equal(acc, whole)
     frame, fst = renderer.render(cam, seed=SEED, real_type=rt, sum_order=RELAX)

@@ -1,8 +1,8 @@
-"""cr_render_frames_device / cr_render_frames_host: a batch of movie frames in one launch.  The contract is bit-exact
-and needs no oracle: frame k of a batch is, byte for byte, the frame a single render writes with frame = frames[k], and
-the batch's work counters are the sum of those single renders' counters -- in f32 and in f64, for any frame list,
-every output_sum mode, a sample shard, a batch the 32-bit work counter splits into several launches, and every scene
-residency.  Batches need CR_SUM_RELAXED (tests/conftest.py makes the reference order the suite default, so every render
+"""cr_render_frames_device / cr_render_frames_host: a batch of movie frames in one launch.  The contract is bit-exact:
+frame k of a batch is, byte for byte, the frame a single render writes with frame = frames[k] and the relaxed oracle's
+frame of frames[k], and the batch's work counters are the sum of those single renders' counters (and of the oracle's) --
+in f32 and in f64, for any frame list, every output_sum mode, a sample shard, a batch the 32-bit work counter splits into
+several launches, and every scene residency.  Batches need CR_SUM_RELAXED (tests/conftest.py makes the reference order the suite default, so every render
 here names its sum order)."""
 import ctypes as C
 import filecmp
@@ -40,8 +40,31 @@ def singles(r, sc, frames, rt, **kw):
     return out, sts
 
 
+_ORACLES = {}
+
+
+def oracle_frames(sc, frames, rt, **kw):
+    """The relaxed oracle's frame for each entry of the list: (frames, summed counters)."""
+    from oracle.oracle import Oracle
+    o = _ORACLES.setdefault(rt, Oracle(rt))
+    cam = sc.scene_cam
+    keep = cam.frame
+    out, tot = [], {c: 0 for c in COUNTERS}
+    try:
+        for f in frames:
+            cam.frame = f
+            img, st = o.render_image(sc, seed=SEED, sum_order=RELAX, **kw)
+            out.append(img)
+            for c in COUNTERS:
+                tot[c] += st[c]
+    finally:
+        cam.frame = keep
+    return out, tot
+
+
 def check_batch(r, sc, frames, rt, **kw):
-    """The batch equals the single renders bit for bit, and its counters are theirs summed.  Returns the batch stats."""
+    """The batch equals the single renders bit for bit, and its counters are theirs summed; each frame is also the
+    relaxed oracle's frame of frames[k], bit for bit.  Returns the batch stats."""
     r.upload_scene(sc.flatten())
     got, st = r.render_frames(sc.scene_cam, frames, seed=SEED, real_type=rt, sum_order=RELAX, **kw)
     refs, rsts = singles(r, sc, frames, rt, **kw)
@@ -53,6 +76,12 @@ def check_batch(r, sc, frames, rt, **kw):
     for c in COUNTERS + ("samples",):
         assert st[c] == sum(s[c] for s in rsts), (c, st[c], [s[c] for s in rsts])
     assert st["kernel_ms"] > 0
+    want, wst = oracle_frames(sc, frames, rt, **kw)
+    for k, ref in enumerate(want):
+        assert got[k].dtype == ref.dtype
+        assert got[k].tobytes() == ref.tobytes(), f"frame {frames[k]} (entry {k}) differs from the relaxed oracle"
+    for c in COUNTERS:
+        assert st[c] == wst[c], (c, st[c], wst[c])
     return st
 
 

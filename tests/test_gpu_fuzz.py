@@ -2,7 +2,9 @@
 triangles, all three materials, solid / nested checker / image textures, default or spherical sky, hidden primitives,
 translate / radius / ScaleX-Y-Z keys (LERP and NERP) on primitives and camera, defocus on or off, odd image sizes,
 shallow and deep paths, HitList elements (seeds from 100) -- rendered by the HIP library and by the oracle: bit-equal images and equal work counters, f64
-and f32, with the reference's tree and (every third scene) with refit or an exported opt-in tree."""
+and f32, with the reference's tree and (every third scene) with refit or an exported opt-in tree.  Every scene runs in
+the reference order; a fixed subset (even random seeds, the three named hostile seeds and every third of the rest, all
+big scenes) runs in CR_SUM_RELAXED too, bit for bit against the relaxed oracle."""
 import numpy as np
 import pytest
 
@@ -15,6 +17,18 @@ pytestmark = pytest.mark.gpu
 
 COUNTERS = ("segments", "node_tests", "prim_tests", "texel_fetches")
 REALS = [(A.CR_REAL_F64, "f64"), (A.CR_REAL_F32, "f32")]
+
+
+def seeds_in_both_orders(seeds, relaxed):
+    """(seed, sum_order) cases: every seed in the reference order (ids as they were) and the seeds of `relaxed` in
+    CR_SUM_RELAXED, the library default, against the relaxed oracle walking the same tree."""
+    return ([pytest.param(s, A.CR_SUM_REFERENCE_ORDER, id=str(s)) for s in seeds]
+            + [pytest.param(s, A.CR_SUM_RELAXED, id=f"{s}-relaxed") for s in relaxed])
+
+
+RANDOM_SEEDS = list(range(36)) + list(range(100, 124)) + list(range(200, 224))
+HOSTILE_SEEDS = [300052, 309589, 400541] + list(range(300000, 300045)) + list(range(1200000, 1200008))
+BIG_SEEDS = list(range(500000, 500012))
 
 
 def random_scene(seed, lists=False, wrappers=False):
@@ -301,8 +315,8 @@ def big_scene(seed, lists=False, wrappers=False):
 
 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
-@pytest.mark.parametrize("seed", list(range(36)) + list(range(100, 124)) + list(range(200, 224)))
-def test_random_scene_bit_exact(renderer, oracles, rt, tag, seed):
+@pytest.mark.parametrize("seed,order", seeds_in_both_orders(RANDOM_SEEDS, [s for s in RANDOM_SEEDS if s % 2 == 0]))
+def test_random_scene_bit_exact(renderer, oracles, rt, tag, seed, order):
     sc = random_scene(1000 + seed, lists=seed >= 100, wrappers=seed >= 200)   # seeds from 100: with HitList elements, from 200: and BVHWrapper elements
     variant = seed % 3
     if variant == 1:
@@ -311,13 +325,13 @@ def test_random_scene_bit_exact(renderer, oracles, rt, tag, seed):
         sc.bvh_mode = [A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED, A.CR_BVH_LBVH][(seed // 3) % 3]
     renderer.upload_scene(sc.flatten())
     try:
-        img, st = renderer.render(sc.scene_cam, seed=4000 + seed, real_type=rt)
+        img, st = renderer.render(sc.scene_cam, seed=4000 + seed, real_type=rt, sum_order=order)
         gpu_nan = False
     except Exception as e:   # CR_ERR_NAN: the reference would panic in Color::new; the oracle must see the same pixels
         assert getattr(e, "code", None) == A.CR_ERR_NAN, e
         gpu_nan = True
     tree = renderer.export_bvh(rt) if variant == 2 else None
-    ref, rst = oracles[rt].render_image(sc, seed=4000 + seed, tree=tree)
+    ref, rst = oracles[rt].render_image(sc, seed=4000 + seed, tree=tree, sum_order=order)
     if gpu_nan:
         assert rst["nan_pixels"] > 0
         return
@@ -328,8 +342,8 @@ def test_random_scene_bit_exact(renderer, oracles, rt, tag, seed):
 
 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
-@pytest.mark.parametrize("seed", [300052, 309589, 400541] + list(range(300000, 300045)) + list(range(1200000, 1200008)))
-def test_hostile_scene_bit_exact(renderer, oracles, rt, tag, seed):
+@pytest.mark.parametrize("seed,order", seeds_in_both_orders(HOSTILE_SEEDS, HOSTILE_SEEDS[:3] + HOSTILE_SEEDS[3::3]))
+def test_hostile_scene_bit_exact(renderer, oracles, rt, tag, seed, order):
     """Degenerate inputs (hostile_scene): the same equalities.  300052 / 309589: zero-length radius keys at the frame time
     under refit_boxes (0/0 at the key's own start -- the refit rule skips that sample); 400541: an opt-in tree over a
     scene whose only element is a list without visible objects.  scripts/fuzz_campaign.py runs tens of thousands more."""
@@ -344,14 +358,14 @@ def test_hostile_scene_bit_exact(renderer, oracles, rt, tag, seed):
         sc.bvh_mode = [A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED, A.CR_BVH_LBVH][(seed // 3) % 3]
     renderer.upload_scene(sc.flatten())
     try:
-        img, st = renderer.render(sc.scene_cam, seed=seed, real_type=rt)
+        img, st = renderer.render(sc.scene_cam, seed=seed, real_type=rt, sum_order=order)
         gpu_nan = False
     except Exception as e:
         assert getattr(e, "code", None) == A.CR_ERR_NAN, e
         gpu_nan = True
     tree = renderer.export_bvh(rt) if variant == 2 else None
     empty = tree is not None and len(tree[1]) == 0
-    ref, rst = oracles[rt].render_image(sc, seed=seed, tree=None if empty else tree, linear_list=empty)
+    ref, rst = oracles[rt].render_image(sc, seed=seed, tree=None if empty else tree, linear_list=empty, sum_order=order)
     assert gpu_nan == (rst["nan_pixels"] > 0)
     if gpu_nan:
         return
@@ -361,8 +375,8 @@ def test_hostile_scene_bit_exact(renderer, oracles, rt, tag, seed):
 
 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
-@pytest.mark.parametrize("seed", range(500000, 500012))
-def test_big_scene_bit_exact(renderer, oracles, rt, tag, seed):
+@pytest.mark.parametrize("seed,order", seeds_in_both_orders(BIG_SEEDS, BIG_SEEDS))
+def test_big_scene_bit_exact(renderer, oracles, rt, tag, seed, order):
     """big_scene: trees outside LDS, with and without lists, refit and the opt-in trees by the same rota as above."""
     sc = big_scene(seed, lists=seed % 2 == 1)
     variant = seed % 3
@@ -370,9 +384,9 @@ def test_big_scene_bit_exact(renderer, oracles, rt, tag, seed):
     if variant == 2:
         sc.bvh_mode = [A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED, A.CR_BVH_LBVH][(seed // 3) % 3]
     renderer.upload_scene(sc.flatten())
-    img, st = renderer.render(sc.scene_cam, seed=seed, real_type=rt)
+    img, st = renderer.render(sc.scene_cam, seed=seed, real_type=rt, sum_order=order)
     tree = renderer.export_bvh(rt) if variant == 2 else None
-    ref, rst = oracles[rt].render_image(sc, seed=seed, tree=tree)
+    ref, rst = oracles[rt].render_image(sc, seed=seed, tree=tree, sum_order=order)
     assert np.array_equal(img, ref), f"seed {seed}: {(img != ref).any(axis=2).sum()} pixels differ"
     for k in COUNTERS:
         assert st[k] == rst[k], (seed, k, st[k], rst[k])

@@ -20,12 +20,12 @@ COUNTERS = ("segments", "node_tests", "prim_tests", "texel_fetches")
 SEED = 60606
 
 
-def render(renderer, sc, rt, mode=A.CR_BVH_REFERENCE, refit=False):
+def render(renderer, sc, rt, mode=A.CR_BVH_REFERENCE, refit=False, order=A.CR_SUM_DEFAULT):
     sc.bvh_mode = mode
     sc.scene_cam.refit_boxes = refit
     flat = sc.flatten()
     renderer.upload_scene(flat)
-    return renderer.render(sc.scene_cam, seed=SEED, real_type=rt)
+    return renderer.render(sc.scene_cam, seed=SEED, real_type=rt, sum_order=order)
 
 
 def same(img, st, ref, rst):
@@ -34,14 +34,15 @@ def same(img, st, ref, rst):
         assert st[k] == rst[k], (k, st[k], rst[k])
 
 
-@pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
+@pytest.mark.parametrize("rt,tag,order", scenes.REAL_ORDERS, ids=scenes.REAL_ORDER_IDS)
 @pytest.mark.parametrize("refit", [False, True], ids=["stale-boxes", "refit"])
 @pytest.mark.parametrize("variant,frame", [("mixed", 0), ("mixed", 1), ("mixed", 3), ("only_lists", 0), ("only_lists", 1),
                                            ("one_list", 0), ("one_list", 1)])
-def test_list_elements_bit_exact(renderer, oracles, rt, tag, refit, variant, frame):
+def test_list_elements_bit_exact(renderer, oracles, rt, tag, order, refit, variant, frame):
+    """In both sum orders: the relaxed frame's leaf-run decode is that of the ANIM kernels with RELAX = true."""
     sc = scenes.list_scene(96, 4, frame=frame, variant=variant)
-    img, st = render(renderer, sc, rt, refit=refit)
-    ref, rst = oracles[rt].render_image(sc, seed=SEED)
+    img, st = render(renderer, sc, rt, refit=refit, order=order)
+    ref, rst = oracles[rt].render_image(sc, seed=SEED, sum_order=order)
     same(img, st, ref, rst)
 
 
@@ -63,10 +64,10 @@ def test_list_elements_in_the_other_pipelines(oracles, monkeypatch, rt, tag, pip
         r.close()
 
 
-@pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
+@pytest.mark.parametrize("rt,tag,order", scenes.REAL_ORDERS, ids=scenes.REAL_ORDER_IDS)
 @pytest.mark.parametrize("env", [{"CRUCIBLE_LDS_LIMIT": "0", "CRUCIBLE_LDS_TOP_KB": "0"}, {"CRUCIBLE_LDS_LIMIT": "0"},
                                  {"CRUCIBLE_LDS_LIMIT": "0", "CRUCIBLE_LDS_TOP_KB": "1"}], ids=["global", "top-levels", "top-1KB"])
-def test_list_elements_outside_lds(oracles, monkeypatch, rt, tag, env):
+def test_list_elements_outside_lds(oracles, monkeypatch, rt, tag, order, env):
     """The scene-in-LDS path is what the small scenes above take; the same scene with the tree in HBM (and with only
     its top levels staged) reads the leaf runs the same way."""
     from crucible_amd.renderer import Renderer
@@ -75,9 +76,9 @@ def test_list_elements_outside_lds(oracles, monkeypatch, rt, tag, env):
     r = Renderer(0)
     try:
         sc = scenes.list_scene(80, 3, frame=0)
-        img, st = render(r, sc, rt)
+        img, st = render(r, sc, rt, order=order)
         assert st["scene_in_lds"] != 1   # 1 = the whole scene staged in LDS
-        ref, rst = oracles[rt].render_image(sc, seed=SEED)
+        ref, rst = oracles[rt].render_image(sc, seed=SEED, sum_order=order)
         same(img, st, ref, rst)
     finally:
         r.close()
@@ -222,13 +223,13 @@ def test_descriptor_rules(renderer):
 
 
 # ---- BVHWrapper elements (scene/mod.rs:161-163)
-@pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
+@pytest.mark.parametrize("rt,tag,order", scenes.REAL_ORDERS, ids=scenes.REAL_ORDER_IDS)
 @pytest.mark.parametrize("refit", [False, True], ids=["stale-boxes", "refit"])
 @pytest.mark.parametrize("variant,frame", [("mixed", 0), ("mixed", 1), ("only", 0), ("pair", 0), ("pair", 1), ("small", 0)])
-def test_wrapper_elements_bit_exact(renderer, oracles, rt, tag, refit, variant, frame):
+def test_wrapper_elements_bit_exact(renderer, oracles, rt, tag, order, refit, variant, frame):
     sc = scenes.wrapped_scene(96, 4, frame=frame, variant=variant)
-    img, st = render(renderer, sc, rt, refit=refit)
-    ref, rst = oracles[rt].render_image(sc, seed=SEED)
+    img, st = render(renderer, sc, rt, refit=refit, order=order)
+    ref, rst = oracles[rt].render_image(sc, seed=SEED, sum_order=order)
     same(img, st, ref, rst)
 
 
@@ -250,17 +251,17 @@ def test_wrapper_elements_in_the_other_pipelines(oracles, monkeypatch, rt, tag, 
         r.close()
 
 
-@pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
+@pytest.mark.parametrize("rt,tag,order", scenes.REAL_ORDERS, ids=scenes.REAL_ORDER_IDS)
 @pytest.mark.parametrize("mode", [A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED, A.CR_BVH_LBVH], ids=["sah", "ordered", "lbvh"])
-def test_wrapper_elements_in_the_other_bvh_modes(renderer, oracles, rt, tag, mode):
+def test_wrapper_elements_in_the_other_bvh_modes(renderer, oracles, rt, tag, order, mode):
     """There the wrappers' visible objects are primitives of the one tree."""
     sc = scenes.wrapped_scene(80, 3, frame=1)
-    img, st = render(renderer, sc, rt, mode=mode, refit=True)
+    img, st = render(renderer, sc, rt, mode=mode, refit=True, order=order)
     tree = renderer.export_bvh(rt)
     flat = sc.flatten()
     named = sorted({~c for c in tree[1].ravel() if c < 0})
     assert named == [i for i, p in enumerate(flat.prims) if p.kind in (A.CR_PRIM_SPHERE, A.CR_PRIM_TRIANGLE) and not (p.flags & A.CR_PRIM_HIDDEN)]
-    ref, rst = oracles[rt].render_image(sc, seed=SEED, tree=tree)
+    ref, rst = oracles[rt].render_image(sc, seed=SEED, tree=tree, sum_order=order)
     same(img, st, ref, rst)
 
 

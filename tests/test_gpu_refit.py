@@ -19,22 +19,23 @@ COUNTERS = ("segments", "node_tests", "prim_tests", "texel_fetches")
 SEED = 4242
 
 
-def render(renderer, sc, rt, mode, refit):
+def render(renderer, sc, rt, mode, refit, order=A.CR_SUM_DEFAULT):
     sc.bvh_mode = mode
     sc.scene_cam.refit_boxes = refit
     renderer.upload_scene(sc.flatten())
-    return renderer.render(sc.scene_cam, seed=SEED, real_type=rt)
+    return renderer.render(sc.scene_cam, seed=SEED, real_type=rt, sum_order=order)
 
 
-@pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
+@pytest.mark.parametrize("rt,tag,order", scenes.REAL_ORDERS, ids=scenes.REAL_ORDER_IDS)
 @pytest.mark.parametrize("mode", [A.CR_BVH_REFERENCE, A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED, A.CR_BVH_LBVH],
                          ids=["reference", "sah", "ordered", "lbvh"])
 @pytest.mark.parametrize("frame", [0, 1, 2, 5])
-def test_refit_bit_exact_against_oracle_refit(renderer, oracles, rt, tag, mode, frame):
+def test_refit_bit_exact_against_oracle_refit(renderer, oracles, rt, tag, order, mode, frame):
+    """In both sum orders: the relaxed kernels screen the refitted boxes too."""
     sc = scenes.moving_scene(96, 4, frame=frame)
-    img, st = render(renderer, sc, rt, mode, True)
+    img, st = render(renderer, sc, rt, mode, True, order)
     tree = renderer.export_bvh(rt) if mode != A.CR_BVH_REFERENCE else None
-    ref, rst = oracles[rt].render_image(sc, seed=SEED, tree=tree)
+    ref, rst = oracles[rt].render_image(sc, seed=SEED, tree=tree, sum_order=order)
     assert np.array_equal(img, ref), f"differing px = {(img != ref).any(axis=2).sum()}"
     for k in COUNTERS:
         assert st[k] == rst[k], (k, st[k], rst[k])

@@ -1,7 +1,8 @@
 """CrRenderParams.sum_order = CR_SUM_RELAXED (the library default): the SAME paths as the reference order -- same draws,
 same walks, hence EQUAL work counters -- with the attenuations multiplied in path order and the finished samples added to
 their pixel as 64-bit fixed-point integers (include/crucible_hip.h).  Nothing of the reference pins this mode; it is
-pinned against the oracle's reference-order frame: per channel within 1e-12 in f64 (the documented bound is about
+pinned bit for bit (frame and counters) against the oracle's own relaxed frame, which restates the header; and against the
+oracle's reference-order frame: per channel within 1e-12 in f64 (the documented bound is about
 (2 * max_depth + samples) * 2^-53: below 1e-13 at depth 50 and 512 samples), equal quantised PPM bytes, and -- because integer adds commute -- frames that do
 not depend on scheduling at all: two runs, every tile shape, every workgroup size and any split into shards agree bit
 for bit.  The f32 mode is compared with its own f32 oracle within the f32 rounding of a sequential sum."""
@@ -48,7 +49,9 @@ def same_bytes(img, ref):
         assert bad.sum() <= max(2, bad.size // 2000), bad.sum()
 
 
-def check(img, st, ref, rst, rt):
+def check(img, st, ref, rst, rt, exact=None):
+    """Against the reference-order frame `ref`: equal counters, within TOL, equal bytes (the header's claim).  exact:
+    the relaxed oracle's (frame, stats) -- then the frame is also bit-equal to it, with equal counters."""
     assert img.dtype == ref.dtype and img.shape == ref.shape
     for k in COUNTERS:
         assert st[k] == rst[k], (k, st[k], rst[k])   # path identity: the product never feeds a branch
@@ -56,6 +59,17 @@ def check(img, st, ref, rst, rt):
     assert d <= TOL[rt], d
     if rt == A.CR_REAL_F64:
         same_bytes(img, ref)
+    if exact is not None:
+        xref, xst = exact
+        assert xref.dtype == img.dtype and xref.shape == img.shape
+        assert np.array_equal(img, xref, equal_nan=True), f"differing px = {(img != xref).any(axis=-1).sum()}"
+        for k in COUNTERS:
+            assert st[k] == xst[k], (k, st[k], xst[k])
+
+
+def relaxed_oracle(oracle, sc, **kw):
+    """The oracle's own CR_SUM_RELAXED frame: what the device must write bit for bit."""
+    return oracle.render_image(sc, seed=kw.pop("seed", SEED), sum_order=RELAX, **kw)
 
 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
@@ -71,7 +85,7 @@ def test_relaxed_against_the_oracle(renderer, oracles, rt, tag, name, build):
     sc = build()
     img, st = relaxed(renderer, sc, rt)
     ref, rst = oracles[rt].render_image(sc, seed=SEED)
-    check(img, st, ref, rst, rt)
+    check(img, st, ref, rst, rt, exact=relaxed_oracle(oracles[rt], sc))
 
 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
@@ -81,7 +95,7 @@ def test_relaxed_ragged_sizes_and_sample_counts(renderer, oracles, rt, tag, widt
     sc = book1_end_scene(1, scene_seed=1, image_width=width, samples=samples)
     img, st = relaxed(renderer, sc, rt)
     ref, rst = oracles[rt].render_image(sc, seed=SEED)
-    check(img, st, ref, rst, rt)
+    check(img, st, ref, rst, rt, exact=relaxed_oracle(oracles[rt], sc))
 
 
 @pytest.mark.parametrize("depth", [0, 1, 2, 50])
@@ -90,7 +104,7 @@ def test_relaxed_depth_limits(renderer, o64, depth):
     sc.scene_cam.set_max_depth(depth)
     img, st = relaxed(renderer, sc, A.CR_REAL_F64)
     ref, rst = o64.render_image(sc, seed=SEED)
-    check(img, st, ref, rst, A.CR_REAL_F64)
+    check(img, st, ref, rst, A.CR_REAL_F64, exact=relaxed_oracle(o64, sc))
     if depth == 0:
         assert not img.any()
 
@@ -101,13 +115,14 @@ def test_relaxed_baseline_config0(renderer, o64):
     sc.scene_cam.set_max_depth(50)
     img, st = relaxed(renderer, sc, A.CR_REAL_F64)
     ref, rst = o64.render_image(sc, seed=SEED)
-    check(img, st, ref, rst, A.CR_REAL_F64)
+    check(img, st, ref, rst, A.CR_REAL_F64, exact=relaxed_oracle(o64, sc))
 
 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
-def test_relaxed_is_deterministic_and_shards_add_up(renderer, rt, tag):
+def test_relaxed_is_deterministic_and_shards_add_up(renderer, oracles, rt, tag):
     """Integer sums: two runs are bit-identical; the raw sums of a split of the sample indices add up to the whole within
-    the one rounding each u64 -> real conversion makes (a sum of n samples has up to 52 + log2(n) bits)."""
+    the one rounding each u64 -> real conversion makes (a sum of n samples has up to 52 + log2(n) bits).  Every shard's
+    real sums and fixed-point words are the relaxed oracle's, bit for bit."""
     sc = book1_end_scene(1, scene_seed=1, image_width=128, samples=12)
     cam = sc.scene_cam
     renderer.upload_scene(sc.flatten())
@@ -123,6 +138,16 @@ def test_relaxed_is_deterministic_and_shards_add_up(renderer, rt, tag):
     else:
         assert np.abs(parts[0] + parts[2] + parts[3] - whole).max() <= 12 * 2.0 ** -22
     assert not parts[1].any()
+    o = oracles[rt]
+    assert np.array_equal(whole, relaxed_oracle(o, sc, output_sum=True)[0])
+    words = np.zeros((cam.image_height, cam.image_width, 3), dtype=np.uint64)
+    for s0, n in ((0, 5), (5, 0), (5, 4), (9, 3)):
+        got = renderer.render(cam, seed=SEED, real_type=rt, sum_order=RELAX, sample_begin=s0, sample_count=n, output_sum=A.CR_OUTPUT_FIXED_SUM)[0]
+        assert np.array_equal(got, relaxed_oracle(o, sc, sample_begin=s0, sample_count=n, output_sum=A.CR_OUTPUT_FIXED_SUM)[0]), (s0, n)
+        words += got
+    assert np.array_equal(words, relaxed_oracle(o, sc, output_sum=A.CR_OUTPUT_FIXED_SUM)[0])
+    for part, (s0, n) in zip(parts, ((0, 5), (5, 0), (5, 4), (9, 3))):
+        assert np.array_equal(part, relaxed_oracle(o, sc, sample_begin=s0, sample_count=n, output_sum=True)[0]), (s0, n)
 
 
 @pytest.mark.parametrize("env", [{"CRUCIBLE_SG_TILE": "8x8"}, {"CRUCIBLE_SG_TILE": "2x2"}, {"CRUCIBLE_SG_TILE": "1x1", "CRUCIBLE_BLOCK": "512"},
@@ -217,7 +242,7 @@ def test_relaxed_is_the_library_default(monkeypatch, o64):
     assert e.value.code == A.CR_ERR_INVALID_ARG
 
 
-def test_relaxed_nan_policy(renderer):
+def test_relaxed_nan_policy(renderer, oracles):
     """A colour that is not a number sets the pixel's NaN flag: the frame reports CR_ERR_NAN like the reference order
     (the reference itself panics in Color::new)."""
     sc = scenes.few_spheres(2, width=24, samples=2)
@@ -230,19 +255,22 @@ def test_relaxed_nan_policy(renderer):
         assert e.value.code == A.CR_ERR_NAN
         sums, _ = renderer.render(sc.scene_cam, seed=SEED, real_type=rt, sum_order=RELAX, output_sum=True)
         assert np.isnan(sums).all()
+        words, _ = renderer.render(sc.scene_cam, seed=SEED, real_type=rt, sum_order=RELAX, output_sum=A.CR_OUTPUT_FIXED_SUM)
+        assert np.array_equal(words, relaxed_oracle(oracles[rt], sc, output_sum=A.CR_OUTPUT_FIXED_SUM)[0])
 
 
 @pytest.mark.parametrize("rt,tag", REALS, ids=["f64", "f32"])
 @pytest.mark.parametrize("bvh", [A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED, A.CR_BVH_LBVH], ids=["sah", "ordered", "lbvh"])
-def test_relaxed_with_the_opt_in_trees(renderer, rt, tag, bvh):
+def test_relaxed_with_the_opt_in_trees(renderer, oracles, rt, tag, bvh):
     """Same frame and counters as the reference order on the same tree (the GPU's own reference-order render, which
-    tests/test_gpu_bvh_modes.py pins against the oracle walking the exported tree)."""
+    tests/test_gpu_bvh_modes.py pins against the oracle walking the exported tree), and bit for bit the relaxed oracle
+    walking that tree."""
     sc = book1_end_scene(1, scene_seed=2, image_width=96, samples=5)
     sc.bvh_mode = bvh
     renderer.upload_scene(sc.flatten())
     ref, rst = renderer.render(sc.scene_cam, seed=SEED, real_type=rt, sum_order=A.CR_SUM_REFERENCE_ORDER)
     img, st = renderer.render(sc.scene_cam, seed=SEED, real_type=rt, sum_order=RELAX)
-    check(img, st, ref, rst, rt)
+    check(img, st, ref, rst, rt, exact=relaxed_oracle(oracles[rt], sc, tree=renderer.export_bvh(rt)))
 
 
 @pytest.mark.parametrize("name,build,rows", [
@@ -266,6 +294,9 @@ def test_relaxed_full_size_frames(renderer, o64, name, build, rows):
         for row in rows:
             want, _ = o64.render(h, cam, seed=SEED, pix_begin=row * cam.image_width, pix_end=(row + 1) * cam.image_width)
             assert np.abs(img[row] - want).max() <= 1e-12, row
+            exact, _ = o64.render(h, cam, seed=SEED, pix_begin=row * cam.image_width, pix_end=(row + 1) * cam.image_width,
+                                  sum_order=RELAX)
+            assert np.array_equal(img[row], exact), row
     finally:
         o64.scene_destroy(h)
 
@@ -283,6 +314,8 @@ def test_relaxed_headline_sample_count(renderer, o64):
         for row in (3, 600):
             want, _ = o64.render(h, cam, seed=SEED, pix_begin=row * 1920, pix_end=(row + 1) * 1920)
             assert np.abs(img[row] - want).max() <= 1e-12, row
+            exact, _ = o64.render(h, cam, seed=SEED, pix_begin=row * 1920, pix_end=(row + 1) * 1920, sum_order=RELAX)
+            assert np.array_equal(img[row], exact), row
             same_bytes(img[row:row + 1], want.reshape(1, 1920, 3))
     finally:
         o64.scene_destroy(h)
@@ -293,7 +326,7 @@ def test_relaxed_many_samples_scale_down(renderer, o64):
     sc = book1_end_scene(1, scene_seed=1, image_width=16, samples=5000)
     img, st = relaxed(renderer, sc, A.CR_REAL_F64)
     ref, rst = o64.render_image(sc, seed=SEED)
-    check(img, st, ref, rst, A.CR_REAL_F64)
+    check(img, st, ref, rst, A.CR_REAL_F64, exact=relaxed_oracle(o64, sc))
 
 
 def test_relaxed_needs_no_sample_buffer():
