@@ -1,9 +1,11 @@
 // CPU validation of the Karras construction in crucible_amd/csrc/lbvh.hpp (built and run by tests/test_lbvh_host.py):
 // random keys with many duplicates and all-equal keys, several sizes -- every leaf reached exactly once, every
-// internal node referenced exactly once, sibling ranges adjacent, the root covering everything.
+// internal node referenced exactly once, sibling ranges adjacent, the root covering everything.  Two more modes hand
+// lbvh_children and lbvh_key of given inputs to tests/test_lbvh_model_host.py (children_mode, keys_mode below).
 #include "lbvh.hpp"
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <random>
 #include <vector>
 using namespace cr;
@@ -45,7 +47,49 @@ static bool check(const std::vector<uint64_t>& keys) {
     if (range[0].lo != 0 || range[0].hi != n - 1) { printf("root range wrong\n"); return false; }
     return true;
 }
-int main() {
+// The whole of a binary file, as 8-byte words
+static bool read_words(const char* path, std::vector<uint64_t>& w) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    uint64_t buf[4096];
+    size_t got;
+    while ((got = fread(buf, 8, 4096, f)) > 0) w.insert(w.end(), buf, buf + got);
+    fclose(f);
+    return true;
+}
+// `lbvh_check children FILE`: FILE holds key sets, each a count n (u64) followed by n sorted u64 keys; writes, per set,
+// lbvh_children of its n - 1 internal nodes as int32 pairs (left, right) to stdout.  tests/test_lbvh_model_host.py
+// compares them with the radix tree of tests/lbvh_model.py.
+static int children_mode(const char* path) {
+    std::vector<uint64_t> w;
+    if (!read_words(path, w)) return 2;
+    for (size_t at = 0; at < w.size();) {
+        const uint64_t n = w[at++];
+        if (n < 1 || n > (uint64_t)INT32_MAX || at + n > w.size()) return 3;
+        std::vector<int32_t> ch(2 * (size_t)(n - 1));
+        for (int32_t i = 0; i < (int32_t)n - 1; i++) lbvh_children(w.data() + at, (int32_t)n, i, ch[2 * i], ch[2 * i + 1]);
+        if (!ch.empty() && fwrite(ch.data(), 4, ch.size(), stdout) != ch.size()) return 4;
+        at += n;
+    }
+    return 0;
+}
+// `lbvh_check keys FILE`: FILE holds rows of nine doubles (centroid, lo, inv_ext); writes lbvh_key of each row as u64.
+static int keys_mode(const char* path) {
+    std::vector<uint64_t> w;
+    if (!read_words(path, w) || w.size() % 9) return 2;
+    std::vector<uint64_t> out(w.size() / 9);
+    for (size_t r = 0; r < out.size(); r++) {
+        double d[9];
+        memcpy(d, w.data() + 9 * r, sizeof d);
+        out[r] = lbvh_key(d, d + 3, d + 6);
+    }
+    if (!out.empty() && fwrite(out.data(), 8, out.size(), stdout) != out.size()) return 4;
+    return 0;
+}
+int main(int argc, char** argv) {
+    if (argc == 3 && !strcmp(argv[1], "children")) return children_mode(argv[2]);
+    if (argc == 3 && !strcmp(argv[1], "keys")) return keys_mode(argv[2]);
+    if (argc != 1) { fprintf(stderr, "usage: lbvh_check [children FILE | keys FILE]\n"); return 2; }
     std::mt19937_64 rng(7);
     long ok = 0;
     for (int trial = 0; trial < 4000; trial++) {

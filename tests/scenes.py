@@ -326,6 +326,46 @@ def white_sky_scene(width=2, samples=1):
     return sc
 
 
+class ArrayScene(Scene):
+    """A scene given as arrays of CrPrimitive fields: kind (n,), v (n, 9) and flags (n,), every sphere and triangle with
+    one of two materials (matte, metal).  For the tree tests, which need tens of thousands of primitives, list records
+    with chosen flags, and values the Sphere / Triangle classes refuse; `elements` stays empty."""
+
+    def __init__(self, kind, v, flags=None, width=48, samples=2):
+        import ctypes as C
+
+        from crucible_amd import _abi as A
+        from crucible_amd.scene import FlatScene
+        super().__init__(16.0 / 9.0, width, 24, 180.0, 1)
+        cam = self.scene_cam
+        cam.set_samples(samples)
+        cam.set_max_depth(6)
+        n = len(kind)
+        dt = np.dtype([("kind", "<i4"), ("material", "<i4"), ("flags", "<i4"), ("key_first", "<i4"), ("key_count", "<i4"),
+                       ("_pad", "<i4"), ("v", "<f8", 9)])
+        recs = np.zeros(max(1, n), dtype=dt)
+        recs["kind"][:n] = kind
+        recs["v"][:n] = v
+        recs["flags"][:n] = 0 if flags is None else flags
+        recs["material"][:n] = np.where(np.asarray(kind) <= 1, np.arange(n) % 2, 0)
+        flat = FlatScene.__new__(FlatScene)
+        flat._np = recs
+        flat.prims = (A.CrPrimitive * len(recs)).from_buffer(recs)
+        flat.textures = (A.CrTexture * 1)(A.CrTexture(A.CR_TEX_SOLID, -1, -1, -1, (C.c_double * 3)(0.7, 0.4, 0.3), 0.0))
+        flat.materials = (A.CrMaterial * 2)(A.CrMaterial(A.CR_MAT_LAMBERTIAN, 0, (C.c_double * 3)(0, 0, 0), 1.0),
+                                            A.CrMaterial(A.CR_MAT_METAL, -1, (C.c_double * 3)(0.8, 0.8, 0.9), 0.1))
+        flat.images = (A.CrImage * 1)()
+        flat.keys = (A.CrKeyframe * 1)()
+        flat._image_arrays = []
+        flat.desc = A.CrSceneDesc(n, 2, 1, 0, 0, A.CR_SKY_DEFAULT, -1, 0, flat.prims, flat.materials, flat.textures,
+                                  flat.images, flat.keys)
+        self._flat = flat
+
+    def flatten(self):
+        self._flat.desc.bvh_mode = self.bvh_mode
+        return self._flat
+
+
 # (real_type, tag, sum_order) cases of the bit-exact GPU suites: both precisions in the reference order (ids "f64" and
 # "f32", as the suites had them) and in CR_SUM_RELAXED, the library default ("f64-relaxed", "f32-relaxed"), each held to
 # the oracle in the same order.  Use as @pytest.mark.parametrize("rt,tag,order", REAL_ORDERS, ids=REAL_ORDER_IDS).
