@@ -15,6 +15,7 @@ CR_KEY_TX, CR_KEY_TY, CR_KEY_TZ, CR_KEY_RADIUS, CR_KEY_SCALE_X, CR_KEY_SCALE_Y, 
 CR_MAX_CHECKER_DEPTH = 32
 CR_KEY_NERP, CR_KEY_LERP = 0, 1
 CR_SUM_DEFAULT, CR_SUM_REFERENCE_ORDER, CR_SUM_RELAXED = 0, 1, 2
+CR_UPDATE_REFIT, CR_UPDATE_REBUILD = 0, 1   # cr_update_primitives flags
 CR_OUTPUT_FIXED_SUM = 2   # CrRenderParams.output_sum: 0 mean, 1 sum in reals, 2 fixed-point words (uint64)
 
 
@@ -94,6 +95,7 @@ SYMBOLS = {
                                           C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
+    "cr_update_primitives": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]),
     "cr_last_kernel_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "cr_synchronize": (C.c_int32, [C.c_void_p]),
     "cr_stream": (C.c_void_p, [C.c_void_p]),
@@ -113,6 +115,8 @@ SYMBOLS = {
     "cr_group_rank": (C.c_int32, [C.c_void_p]),
     "cr_group_handle": (C.c_void_p, [C.c_void_p, C.c_int32]),
     "cr_group_upload_scene": (C.c_int32, [C.c_void_p, C.POINTER(CrSceneDesc)]),
+    "cr_group_update_primitives": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,
+                                               C.c_int32]),
     "cr_group_render": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_void_p,
                                     C.POINTER(CrGroupStats)]),
     "cr_group_render_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_void_p,

@@ -11,6 +11,7 @@
 #include "refit.hpp"
 #include "lbvh.hpp"
 #include "pack.hpp"
+#include "update.hpp"
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -76,7 +77,11 @@ template <typename real> struct DevScene {
     std::vector<int32_t> level_begin;        // entries of tree level l are [level_begin[l], level_begin[l+1])
     std::vector<Entry<real>> host_entries;   // the tree over the scene's objects (for cr_export_bvh); the device copy names primitive runs
     std::vector<int32_t> leaf_desc;          // leaf-order position -> index in the caller's primitive list
-    void release() { entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
+    DevBuf desc_pos;                         // the inverse, on the device: index in the caller's primitive list -> position of its record in
+                                             // `prims`, -1 where it has none (hidden); scenes without list elements only (cr_update_primitives)
+    bool desc_pos_valid = false;
+    bool side_tables = false;                // mats / texs / keys hold the uploaded scene's (a rebuild after cr_update_primitives keeps them)
+    void release() { desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
 };
 
 }   // namespace
@@ -94,6 +99,8 @@ struct CrHandle {
     std::vector<CrTexture> textures;
     std::vector<CrKeyframe> keys;
     int32_t sky_kind = 0, sky_image = -1, bvh_mode = 0;
+    bool has_list_elements = false;   // some CR_PRIM_LIST / CR_PRIM_BVH record: cr_update_primitives does not apply
+    DevBuf update_stage;              // cr_update_primitives: the call's rows (9 doubles each), then its indices
     // images are precision independent
     DevBuf images, texels;
     int32_t n_images = 0;
@@ -840,9 +847,18 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     ds.has_leaf_runs = !leaf_runs.empty();
     ds.has_lists = any_lists;
     HIP_TRY(h, up(ds.prims, leaf_prims.data(), leaf_prims.size() * sizeof(Prim<real>)));
-    HIP_TRY(h, up(ds.mats, mats.data(), mats.size() * sizeof(Mat<real>)));
-    HIP_TRY(h, up(ds.texs, texs.data(), texs.size() * sizeof(Tex<real>)));
-    HIP_TRY(h, up(ds.keys, keys.data(), keys.size() * sizeof(Key<real>)));
+    if (!ds.side_tables) {   // a rebuild after cr_update_primitives: these still hold the uploaded scene's
+        HIP_TRY(h, up(ds.mats, mats.data(), mats.size() * sizeof(Mat<real>)));
+        HIP_TRY(h, up(ds.texs, texs.data(), texs.size() * sizeof(Tex<real>)));
+        HIP_TRY(h, up(ds.keys, keys.data(), keys.size() * sizeof(Key<real>)));
+        ds.side_tables = true;
+    }
+    ds.desc_pos_valid = !any_lists && !spliced && !h->has_list_elements;
+    if (ds.desc_pos_valid) {   // every object is one primitive: record i of leaf_prims is objs[b.order[i]]
+        std::vector<int32_t> pos(h->prims.size(), -1);
+        for (int32_t i = 0; i < n; i++) pos[(size_t)objs[b.order[i]].desc] = i;
+        HIP_TRY(h, up(ds.desc_pos, pos.data(), pos.size() * sizeof(int32_t)));
+    }
     ds.n_entries = (int32_t)b.entries.size(); ds.n_prims = (int32_t)leaf_prims.size(); ds.n_mats = (int32_t)mats.size(); ds.n_texs = (int32_t)texs.size();
     ds.n_scene_keys = (int32_t)h->keys.size();
     auto r16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -1652,7 +1668,7 @@ void cr_destroy(CrHandle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->s32.release(); h->s64.release();
+    h->s32.release(); h->s64.release(); h->update_stage.release();
     h->images.release(); h->texels.release(); h->work_counter.release(); h->counters.release();
     h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release();
     h->wf_job.release(); h->wf_rng.release(); h->wf_ray.release(); h->wf_depth.release(); h->wf_hit_t.release(); h->wf_hit_prim.release();
@@ -1768,6 +1784,9 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
     h->keys.assign(s->keys, s->keys + s->n_keys);
     h->sky_kind = s->sky_kind; h->sky_image = s->sky_image; h->bvh_mode = s->bvh_mode;
     h->s32.built = false; h->s64.built = false;
+    h->s32.side_tables = false; h->s64.side_tables = false;
+    h->has_list_elements = false;
+    for (const CrPrimitive& p : h->prims) h->has_list_elements |= p.kind == CR_PRIM_LIST || p.kind == CR_PRIM_BVH;
     // images: RGB8 -> RGBA8 words, one flat texel array (pack.hpp)
     std::vector<ImageRef> refs;
     std::vector<uint32_t> texels;
@@ -1852,9 +1871,102 @@ int32_t validate_frames(CrHandle* h, const int32_t* frames, int32_t n_frames) {
     return CR_OK;
 }
 
+// ---------------------------------------------------------------- cr_update_primitives (update.hpp)
+// Everything that can refuse the call, before anything changes.
+int32_t validate_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (n < 0) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: negative count");
+    if (n > 0 && !v) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: null values");
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_update_primitives before cr_upload_scene");
+    if (flags != CR_UPDATE_REFIT && flags != CR_UPDATE_REBUILD) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: unknown flags");
+    const int64_t n_desc = (int64_t)h->prims.size();
+    if (prim_index) {
+        for (int32_t k = 0; k < n; k++)
+            if (prim_index[k] < 0 || prim_index[k] >= n_desc) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: primitive index out of range");
+        std::vector<int32_t> sorted(prim_index, prim_index + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: a primitive is named twice");
+    } else if (n > n_desc) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: primitive index out of range");
+    auto finite = [](double x) { return x == x && x != HUGE_VAL && x != -HUGE_VAL; };
+    for (int32_t k = 0; k < n; k++) {
+        const CrPrimitive& p = h->prims[(size_t)(prim_index ? prim_index[k] : k)];
+        if (p.kind == CR_PRIM_LIST || p.kind == CR_PRIM_BVH) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: a list element has no coordinates to update");
+        const double* row = v + (size_t)k * 9;
+        const int nv = p.kind == CR_PRIM_SPHERE ? 4 : 9;
+        for (int j = 0; j < nv; j++) if (!finite(row[j])) return fail(h, CR_ERR_INVALID_ARG, "primitive coordinate is not finite");
+        if (p.kind == CR_PRIM_SPHERE && !(row[3] >= 0.0)) return fail(h, CR_ERR_INVALID_ARG, "Cannot make a sphere with negative radius");   // sphere.rs:26
+    }
+    // the construction-time box of a HitList / BVHWrapper element is not the union of its objects' boxes: a refit would not
+    // reproduce it
+    if (h->has_list_elements) return fail(h, CR_ERR_UNSUPPORTED, "cr_update_primitives: the scene holds a HitList or BVHWrapper element");
+    return CR_OK;
+}
+
+// CR_UPDATE_REFIT on one built precision: the staged rows into the primitive records, then the construction-time boxes of
+// every wrapper bottom-up, the screening records, and the host's copy of the tree.  The topology stays.
+template <typename real>
+int32_t refit_updated(CrHandle* h, const int32_t* d_index, const double* d_rows, int32_t n) {
+    DevScene<real>& ds = dev_scene<real>(h);
+    if (!ds.built || ds.n_prims == 0) return CR_OK;
+    if (!ds.desc_pos_valid) return fail(h, CR_ERR_UNSUPPORTED, "cr_update_primitives: the scene holds a HitList or BVHWrapper element");
+    hipLaunchKernelGGL((update_prims_kernel<real>), dim3((unsigned)((n + kUpdateBlock - 1) / kUpdateBlock)), dim3(kUpdateBlock), 0, h->stream,
+                       (Prim<real>*)ds.prims.p, ds.n_prims, (const int32_t*)ds.desc_pos.p, (int32_t)h->prims.size(), d_index, d_rows, n);
+    HIP_TRY(h, hipGetLastError());
+    if (ds.n_entries == 0) return CR_OK;
+    int32_t rc = run_box_kernels<real>(h, ds, ds.entries.p, real(0), real(0), false);
+    if (rc != CR_OK) return rc;
+    rc = make_screen(h, ds, ds.entries.p, ds.screen, &ds.screen_usable);
+    if (rc != CR_OK) return rc;
+    if (ds.host_entries.size() != (size_t)ds.n_entries) return CR_OK;   // nothing to export (a scene with a BVHWrapper element; not reached)
+    if (!ds.ordered) {   // the device records are the host's, box for box and link for link
+        HIP_TRY(h, hipMemcpyAsync(ds.host_entries.data(), ds.entries.p, (size_t)ds.n_entries * sizeof(Entry<real>), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    } else {             // EntryO records: only their boxes go into the host's Entry records
+        std::vector<EntryO<real>> eo((size_t)ds.n_entries);
+        HIP_TRY(h, hipMemcpyAsync(eo.data(), ds.entries.p, eo.size() * sizeof(EntryO<real>), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < eo.size(); i++) for (int k = 0; k < 6; k++) ds.host_entries[i].b[k] = eo[i].b[k];
+    }
+    return CR_OK;
+}
+
+// After validate_update: the edit itself.
+int32_t apply_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
+    if (n == 0) return CR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const bool refit = flags == CR_UPDATE_REFIT && (h->s32.built || h->s64.built);
+    if (refit) {   // one staged buffer: the rows, then the indices; the stream orders the copy after earlier renders
+        const size_t row_bytes = (size_t)n * 9 * sizeof(double), idx_bytes = prim_index ? (size_t)n * sizeof(int32_t) : 0;
+        HIP_TRY(h, h->update_stage.ensure(row_bytes + idx_bytes));
+        HIP_TRY(h, hipMemcpyAsync(h->update_stage.p, v, row_bytes, hipMemcpyHostToDevice, h->stream));
+        if (prim_index) HIP_TRY(h, hipMemcpyAsync((char*)h->update_stage.p + row_bytes, prim_index, idx_bytes, hipMemcpyHostToDevice, h->stream));
+    } else HIP_TRY(h, hipStreamSynchronize(h->stream));   // a rebuild frees and refills what an earlier render may still read
+    for (int32_t k = 0; k < n; k++) {   // the host copy: what a rebuild, a precision not built yet and a hidden primitive see
+        CrPrimitive& p = h->prims[(size_t)(prim_index ? prim_index[k] : k)];
+        const int nv = p.kind == CR_PRIM_SPHERE ? 4 : 9;
+        for (int j = 0; j < nv; j++) p.v[j] = v[(size_t)k * 9 + j];
+    }
+    if (flags == CR_UPDATE_REBUILD) { h->s32.built = false; h->s64.built = false; return CR_OK; }
+    if (!refit) return CR_OK;
+    const double* d_rows = (const double*)h->update_stage.p;
+    const int32_t* d_index = prim_index ? (const int32_t*)((const char*)h->update_stage.p + (size_t)n * 9 * sizeof(double)) : nullptr;
+    int32_t rc = refit_updated<float>(h, d_index, d_rows, n);
+    if (rc == CR_OK) rc = refit_updated<double>(h, d_index, d_rows, n);
+    hipError_t e = hipStreamSynchronize(h->stream);   // the caller's arrays and the staged buffer are free from here on
+    if (e != hipSuccess && rc == CR_OK) { h->error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); rc = CR_ERR_HIP; }
+    return rc;
+}
+
 }   // namespace
 
 extern "C" {
+
+int32_t cr_update_primitives(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
+    int32_t rc = validate_update(h, prim_index, v, n, flags);
+    if (rc != CR_OK) return rc;
+    return apply_update(h, prim_index, v, n, flags);
+}
 
 int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats) {
     int32_t rc = validate_render(h, cam, p);
@@ -2132,6 +2244,20 @@ int32_t cr_group_upload_scene(CrGroup* g, const CrSceneDesc* scene) {
     DeviceGuard guard;
     for (CrHandle* h : g->members) {
         int32_t rc = cr_upload_scene(h, scene);
+        if (rc != CR_OK) return gfail(g, rc, h->error);
+    }
+    return CR_OK;
+}
+
+int32_t cr_group_update_primitives(CrGroup* g, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
+    if (!g) return CR_ERR_INVALID_ARG;
+    DeviceGuard guard;
+    for (CrHandle* h : g->members) {   // every member is validated before any is changed
+        int32_t rc = validate_update(h, prim_index, v, n, flags);
+        if (rc != CR_OK) return gfail(g, rc, h->error);
+    }
+    for (CrHandle* h : g->members) {
+        int32_t rc = apply_update(h, prim_index, v, n, flags);
         if (rc != CR_OK) return gfail(g, rc, h->error);
     }
     return CR_OK;

@@ -11,7 +11,7 @@ root, the root divides by the sample count.  Two ways to build one:
 import ctypes as C
 
 from . import _abi as A
-from .renderer import CrucibleError, load_library
+from .renderer import CrucibleError, load_library, update_arrays
 
 
 def shard(samples, member, n_members):
@@ -85,6 +85,13 @@ class RenderGroup:
 
     def upload_scene(self, flat):
         self._check(self.lib.cr_group_upload_scene(self.g, C.byref(flat.desc)))
+
+    def update_primitives(self, indices, values, rebuild=False):
+        """cr_group_update_primitives: Renderer.update_primitives on every local member (all validated before any
+        changes)."""
+        idx, v, n = update_arrays(indices, values)
+        self._check(self.lib.cr_group_update_primitives(self.g, idx, v.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                                        A.CR_UPDATE_REBUILD if rebuild else A.CR_UPDATE_REFIT))
 
     def render(self, cam, *, seed, real_type=A.CR_REAL_F64, sum_order=A.CR_SUM_DEFAULT):
         """Collective: returns (image (H, W, 3) on the root -- zeros elsewhere --, stats dict)."""

@@ -45,6 +45,20 @@ def np_real(real_type):
     return np.float64 if real_type == A.CR_REAL_F64 else np.float32
 
 
+def update_arrays(indices, values):
+    """(index pointer or None, contiguous (n, 9) float64 rows, n) for cr_update_primitives; the index array stays
+    alive through the returned pointer object."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, 9)
+    if indices is None:
+        return None, v, len(v)
+    idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+    if idx.size != len(v):
+        raise ValueError(f"update_primitives: {idx.size} indices for {len(v)} rows")
+    ptr = idx.ctypes.data_as(C.POINTER(C.c_int32))
+    ptr._keep = idx
+    return ptr, v, len(v)
+
+
 class Renderer:
     """One CrHandle (one HIP device).  Mirrors the call `Camera::render(&skybox, &world, fname)`
     (reference src/camera/mod.rs:270) split into upload_scene / render / write_ppm."""
@@ -75,6 +89,15 @@ class Renderer:
 
     def upload_scene(self, flat):
         self._check(self.lib.cr_upload_scene(self.h, C.byref(flat.desc)))
+
+    def update_primitives(self, indices, values, rebuild=False):
+        """cr_update_primitives: new CrPrimitive.v rows (n, 9) for the primitives `indices` (positions in the uploaded
+        description; None: 0..n-1) of the scene on this handle.  A sphere reads four values of its row.
+        rebuild=False refits the boxes of the trees already built, topology unchanged; rebuild=True has the trees
+        rebuilt at next use, as a fresh upload of the edited scene would."""
+        idx, v, n = update_arrays(indices, values)
+        self._check(self.lib.cr_update_primitives(self.h, idx, v.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                                  A.CR_UPDATE_REBUILD if rebuild else A.CR_UPDATE_REFIT))
 
     def render(self, cam, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
                want_stats=True, sum_order=None):

@@ -409,6 +409,39 @@ CR_API int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const
 CR_API int32_t cr_export_bvh(CrHandle* h, int32_t real_type, double* boxes, int32_t* children, int32_t* split_axis,
                              int32_t capacity, int32_t* n_wrappers);
 
+/*
+ * Edit primitives of the uploaded scene in place: new coordinates for n spheres / triangles, without another
+ * cr_upload_scene.  prim_index[k] is an index into the CrSceneDesc.prims of the last upload (NULL: 0..n-1) and
+ * v + 9k its new CrPrimitive.v: a sphere reads v[0..3] (what it stores beyond them is kept), a triangle all nine.
+ * Kind, material, flags, key range and list membership cannot be changed; for a keyed primitive the new values are the
+ * initial transform its keys apply to.  The caller's arrays are free on return.  The call is ordered on the handle's
+ * stream after earlier renders (an asynchronous render launched before it sees the scene as it was) and may synchronise.
+ *
+ *   CR_UPDATE_REFIT    every precision already built on the handle: the device record of each named visible primitive
+ *                      becomes what an upload of the edited description packs, bit for bit (1/radius included), and
+ *                      every wrapper box becomes what a fresh build computes for the SAME topology -- a leaf the union
+ *                      of its primitives' construction-time boxes, an inner wrapper the tight_enclose of its children
+ *                      (src/objects/bvh.rs:67-73) -- on the device, bottom-up; the screening records follow.  Links, LDS
+ *                      sizing and kernel selection do not change; cr_export_bvh returns the same children and
+ *                      split_axis with the new boxes.  The tree is as good as the edit is small: primitives that
+ *                      travel far leave large, overlapping boxes (correct, slower to walk).  A precision not built yet
+ *                      builds at first use from the edited description; a hidden primitive changes in the host copy
+ *                      only.  refit_boxes and the stale-box default behave as after an upload of the edited description.
+ *   CR_UPDATE_REBUILD  the same edit, after which the trees are rebuilt by the scene's bvh_mode builder at next use: the
+ *                      handle is then what a cr_upload_scene of the edited description leaves, without re-uploading
+ *                      images, materials, textures and keys.
+ *
+ * Everything is checked before anything changes -- after an error the next render is what it would have been:
+ * CR_ERR_INVALID_ARG for a null handle, n < 0, null v with n > 0, unknown flags, an index out of range, repeated within
+ * the call or naming a CR_PRIM_LIST / CR_PRIM_BVH record, a non-finite coordinate or a negative radius (cr_upload_scene's
+ * messages); CR_ERR_NO_SCENE before an upload; CR_ERR_UNSUPPORTED for a scene that holds a CR_PRIM_LIST or CR_PRIM_BVH
+ * element (their construction-time boxes are not the union of their objects' boxes, so a refit does not reproduce them).
+ * n == 0 is CR_OK and does nothing.
+ */
+enum { CR_UPDATE_REFIT = 0, CR_UPDATE_REBUILD = 1 };
+CR_API int32_t cr_update_primitives(CrHandle* h, const int32_t* prim_index, const double* v,
+                                    int32_t n, int32_t flags);
+
 /* Wait for the last render launched on this handle and return its kernel time in
  * milliseconds, measured with HIP events recorded on the handle's stream around the
  * launch (no counters are copied back). */
@@ -493,6 +526,11 @@ CR_API CrHandle* cr_group_handle(CrGroup* g, int32_t local_member);
 
 /* cr_upload_scene on every local member (the scene is replicated). */
 CR_API int32_t cr_group_upload_scene(CrGroup* g, const CrSceneDesc* scene);
+
+/* cr_update_primitives on every local member.  Every member is validated before any is changed; the first member's
+ * error wins.  In rank mode every rank calls it with the same arguments (no collective is involved). */
+CR_API int32_t cr_group_update_primitives(CrGroup* g, const int32_t* prim_index, const double* v,
+                                          int32_t n, int32_t flags);
 
 /* Camera::render across the group.  params->sample_begin/sample_count/output_sum are ignored (output_sum must still be
  * a valid value): the group splits
