@@ -1,0 +1,256 @@
+// api.hip -- the handle's life and the render entry points of include/crucible_hip.h: cr_create reads the CRUCIBLE_*
+// knobs, cr_render_* validate and hand over to render_typed (render.hip); the error strings behind cr_last_error.
+//
+// Nothing here falls back to a CPU renderer: without a HIP device cr_create fails.
+#include "handle.hpp"
+
+namespace cr {
+
+static thread_local std::string g_create_error;
+
+int32_t fail(CrHandle* h, int32_t code, const std::string& msg) {
+    if (h) h->error = msg; else g_create_error = msg;
+    return code;
+}
+
+// fixed-point sums of a whole frame of `samples` samples per pixel -> its per-pixel means, as launch() finalizes them
+int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n, int32_t samples, bool f64, void* out) {
+    const double inv_scale = 1.0 / fx_scale_for(samples);
+    return f64 ? fx_finalize<double>(h, sums, (double*)out, n, inv_scale, (double)samples, 0) : fx_finalize<float>(h, sums, (float*)out, n, inv_scale, (double)samples, 0);
+}
+
+int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!cam || !p) return fail(h, CR_ERR_INVALID_ARG, "null camera or params");
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_render before cr_upload_scene");
+    if (cam->image_width < 1 || cam->image_height < 1) return fail(h, CR_ERR_INVALID_ARG, "image size must be positive");
+    if ((int64_t)cam->image_width * cam->image_height > (int64_t)1 << 26) return fail(h, CR_ERR_INVALID_ARG, "image too large");
+    if (p->samples < 1) return fail(h, CR_ERR_INVALID_ARG, "The camera must have a positive number of samples.");   // camera/mod.rs:235-238
+    if (p->sample_begin < 0 || p->sample_count < 0 || p->sample_begin + p->sample_count > p->samples)
+        return fail(h, CR_ERR_INVALID_ARG, "sample range outside [0, samples)");
+    if (p->max_depth < 0) return fail(h, CR_ERR_INVALID_ARG, "max_depth must be >= 0");
+    if (p->real_type != CR_REAL_F32 && p->real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");
+    if (p->sum_order != CR_SUM_DEFAULT && p->sum_order != CR_SUM_REFERENCE_ORDER && p->sum_order != CR_SUM_RELAXED) return fail(h, CR_ERR_INVALID_ARG, "unknown sum_order");
+    if (p->output_sum < 0 || p->output_sum > CR_OUTPUT_FIXED_SUM) return fail(h, CR_ERR_INVALID_ARG, "unknown output_sum");
+    if (!(p->frame_rate > 0)) return fail(h, CR_ERR_INVALID_ARG, "frame_rate must be positive");
+    if ((cam->from_key_count > 0 && !cam->from_keys) || (cam->at_key_count > 0 && !cam->at_keys) || cam->from_key_count < 0 || cam->at_key_count < 0)
+        return fail(h, CR_ERR_INVALID_ARG, "camera keyframe array missing");
+    for (int i = 0; i < cam->from_key_count + cam->at_key_count; i++) {   // cam_translate_* only (scene_animator.rs)
+        const CrKeyframe& k = i < cam->from_key_count ? cam->from_keys[i] : cam->at_keys[i - cam->from_key_count];
+        if (k.channel < CR_KEY_TX || k.channel > CR_KEY_TZ || (k.interp != CR_KEY_NERP && k.interp != CR_KEY_LERP))
+            return fail(h, CR_ERR_INVALID_ARG, "camera keyframes are translations (channels 0..2)");
+    }
+    return CR_OK;
+}
+
+// cr_render_device / cr_render_frames_device after their own argument checks (frames == nullptr: params->frame)
+static int32_t render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats,
+                      const int32_t* frames, int32_t n_frames) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    h->cam_pending_slot = -1;
+    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames)
+                                             : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames);
+    if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
+        hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
+        h->cam_pending_slot = -1;
+        if (e != hipSuccess && rc == CR_OK) { h->error = std::string("hipEventRecord: ") + hipGetErrorString(e); rc = CR_ERR_HIP; }
+    }
+    return rc;
+}
+
+// Color::new asserts 0 <= c <= 1 on every mean (ray_casting.rs:172): the pixels of a host frame that would panic there
+uint64_t bad_pixels(const void* rgb, int32_t real_type, size_t n_pix) {
+    uint64_t bad = 0;
+    for (size_t i = 0; i < n_pix; i++) {
+        bool ok = true;
+        for (int k = 0; k < 3; k++) {
+            double v = real_type == CR_REAL_F64 ? ((const double*)rgb)[3 * i + k] : (double)((const float*)rgb)[3 * i + k];
+            ok = ok && (v >= 0.0 && v <= 1.0);
+        }
+        bad += ok ? 0 : 1;
+    }
+    return bad;
+}
+
+// cr_render_host / cr_render_frames_host: render into the handle's buffer, copy back, check the means frame by frame
+static int32_t render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* h_out, CrStats* stats,
+                    const int32_t* frames, int32_t n_frames) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)cam->image_width * cam->image_height * 3;   // reals (or words) per frame
+    const size_t frame_bytes = n * (p->output_sum == CR_OUTPUT_FIXED_SUM ? sizeof(uint64_t) : real_size(p->real_type));
+    const size_t bytes = frame_bytes * (size_t)n_frames;
+    const hipError_t e = h->out_buf.ensure(bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
+    CrStats local;
+    int32_t rc = render_device(h, cam, p, h->out_buf.p, stats ? stats : &local, frames, n_frames);
+    if (rc != CR_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (!p->output_sum) {
+        uint64_t bad = 0;
+        int32_t first_bad = -1;
+        for (int32_t k = 0; k < n_frames; k++) {
+            const uint64_t b = bad_pixels((const char*)h_out + (size_t)k * frame_bytes, p->real_type, n / 3);
+            if (b && first_bad < 0) first_bad = k;
+            bad += b;
+        }
+        if (stats) stats->nan_pixels = bad;
+        if (bad && !frames) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+        if (bad)
+            return fail(h, CR_ERR_NAN, "frame " + std::to_string(frames[first_bad]) + " (entry " + std::to_string(first_bad) +
+                                           " of the batch): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+    }
+    return CR_OK;
+}
+
+// The four cr_render_* entry points: their argument checks in one order, then the render (batch: `frames` is checked too)
+static int32_t render_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, bool batch, const int32_t* frames, int32_t n_frames,
+                            bool host, void* out, CrStats* stats) {
+    int32_t rc = validate_render(h, cam, p);
+    if (rc != CR_OK) return rc;
+    if (batch && !frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
+    if (batch && n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
+    if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
+    return (host ? render_host : render_device)(h, cam, p, out, stats, frames, n_frames);
+}
+
+}   // namespace cr
+
+using namespace cr;
+
+extern "C" {
+
+int32_t cr_abi_version(void) { return CR_ABI_VERSION; }
+
+int32_t cr_create(int32_t device_id, CrHandle** out) {
+    if (!out) return fail(nullptr, CR_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    int n_dev = 0;
+    hipError_t e = hipGetDeviceCount(&n_dev);
+    if (e != hipSuccess || n_dev < 1) return fail(nullptr, CR_ERR_NO_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
+    if (device_id < 0 || device_id >= n_dev) return fail(nullptr, CR_ERR_INVALID_ARG, "device_id out of range");
+    CrHandle* h = new CrHandle();
+    h->device = device_id;
+    auto bail = [&](const char* what, hipError_t err) {
+        g_create_error = std::string(what) + ": " + hipGetErrorString(err);
+        delete h;
+        return CR_ERR_HIP;
+    };
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return bail("hipSetDevice", e);
+    hipDeviceProp_t prop;
+    if ((e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess) return bail("hipGetDeviceProperties", e);
+    h->n_cus = prop.multiProcessorCount;
+    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = hipEventCreate(&h->ev0)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = hipEventCreate(&h->ev1)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = h->work_counter.ensure(16)) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = h->counters.ensure(64 * sizeof(uint64_t))) != hipSuccess) return bail("hipMalloc", e);
+    if (const char* s = getenv("CRUCIBLE_LDS_LIMIT")) h->lds_limit = (size_t)atol(s);
+    if (const char* s = getenv("CRUCIBLE_SAMPLE_GRANULAR")) h->sample_granular = atoi(s) != 0;
+    if (const char* s = getenv("CRUCIBLE_SCREEN")) h->screen_boxes = atoi(s) != 0;
+    if (const char* s = getenv("CRUCIBLE_SCREEN_LDS")) h->screen_lds = atoi(s) != 0;
+    if (const char* s = getenv("CRUCIBLE_SUM_ORDER")) h->default_sum_order = strcmp(s, "reference") == 0 ? CR_SUM_REFERENCE_ORDER : CR_SUM_RELAXED;
+    if (const char* s = getenv("CRUCIBLE_SAMPLE_BUF_MB")) h->sample_buf_limit = (size_t)std::max(0L, atol(s)) << 20;
+    if (const char* s = getenv("CRUCIBLE_SG_CHUNK")) h->sg_chunk_override = std::max(0, atoi(s));
+    if (const char* s = getenv("CRUCIBLE_WORK_COUNTER_MAX")) h->work_counter_max = std::min<uint64_t>(0xF0000000ull, (uint64_t)std::max(64LL, atoll(s)));
+    if (const char* s = getenv("CRUCIBLE_SG_TILE")) {
+        int tw = 0, th = 0;
+        if (sscanf(s, "%dx%d", &tw, &th) == 2 && tw > 0 && th > 0 && (tw & (tw - 1)) == 0 && (th & (th - 1)) == 0 && tw * th <= 64) {
+            h->sg_lw = __builtin_ctz((unsigned)tw); h->sg_lh = __builtin_ctz((unsigned)th);
+        }
+    }
+    if (const char* s = getenv("CRUCIBLE_LATENCY_ENTRIES")) h->latency_entries = (int32_t)std::max(0L, atol(s));
+    if (const char* s = getenv("CRUCIBLE_LATENCY_TOP_KB")) h->latency_top_bytes = (size_t)std::max(0L, atol(s)) * 1024;
+    if (const char* s = getenv("CRUCIBLE_LDS_SIDE_KB")) h->lds_side_limit = (size_t)std::max(0L, atol(s)) * 1024;
+    if (const char* s = getenv("CRUCIBLE_LDS_TOP_KB")) { h->lds_top_bytes = (size_t)std::max(0L, atol(s)) * 1024; h->lds_top_set = true; }
+    if (const char* s = getenv("CRUCIBLE_BLOCKS_PER_CU")) h->blocks_per_cu_override = atoi(s);
+    if (const char* s = getenv("CRUCIBLE_BLOCK")) h->block_override = atoi(s);
+    if (const char* s = getenv("CRUCIBLE_WALK_ROUND")) h->walk_round_steps = std::max(0, atoi(s));
+    if (const char* s = getenv("CRUCIBLE_WALK_EXIT")) h->walk_exit_lanes = std::min(64, std::max(1, atoi(s)));
+    if (const char* s = getenv("CRUCIBLE_WALK_LEAF_MIN")) h->walk_leaf_min = std::min(64, std::max(0, atoi(s)));
+    if (const char* s = getenv("CRUCIBLE_PIPELINE")) h->pipeline = strcmp(s, "mega") == 0 ? 0 : (strcmp(s, "queue") == 0 ? 2 : 1);
+    if (const char* s = getenv("CRUCIBLE_QUEUE_BATCH")) h->queue_min_batch = std::min(64, std::max(1, atoi(s)));
+    if (const char* s = getenv("CRUCIBLE_QUEUE_PATIENCE")) h->queue_patience = std::max(0, atoi(s));
+    if (const char* s = getenv("CRUCIBLE_QUEUE_WALKERS")) h->queue_walk_waves = std::min(15, std::max(1, atoi(s)));
+    if (const char* s = getenv("CRUCIBLE_WF_SLOTS")) h->wf_slots = (uint32_t)std::max(64L, atol(s));
+    if (const char* s = getenv("CRUCIBLE_WF_SAMPLE_MB")) h->wf_sample_bytes = (size_t)std::max(1L, atol(s)) << 20;
+    *out = h;
+    return CR_OK;
+}
+
+void cr_destroy(CrHandle* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->s32.release(); h->s64.release(); h->update_stage.release();
+    h->images.release(); h->texels.release(); h->work_counter.release(); h->counters.release();
+    h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release();
+    h->wf_job.release(); h->wf_rng.release(); h->wf_ray.release(); h->wf_depth.release(); h->wf_hit_t.release(); h->wf_hit_prim.release();
+    h->wf_chunk.release(); h->wf_ctrl.release(); h->wf_samples.release(); h->wf_acc.release();
+    for (int i = 0; i < CrHandle::kCamSlots; i++) {
+        if (h->cam_host[i]) (void)hipHostFree(h->cam_host[i]);
+        h->cam_dev[i].release();
+        if (h->cam_ev[i]) (void)hipEventDestroy(h->cam_ev[i]);
+    }
+    if (h->times_host) (void)hipHostFree(h->times_host);
+    h->times_dev.release();
+    if (h->times_ev) (void)hipEventDestroy(h->times_ev);
+    if (h->wf_ring_host) { (void)hipHostFree(h->wf_ring_host); for (int i = 0; i < 8; i++) if (h->wf_ev[i]) (void)hipEventDestroy(h->wf_ev[i]); }
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats) {
+    return render_entry(h, cam, p, false, nullptr, 1, false, d_out, stats);
+}
+
+int32_t cr_render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* h_out, CrStats* stats) {
+    return render_entry(h, cam, p, false, nullptr, 1, true, h_out, stats);
+}
+
+int32_t cr_render_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
+                                void* d_out, CrStats* stats) {
+    return render_entry(h, cam, p, true, frames, n_frames, false, d_out, stats);
+}
+
+int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
+                              void* h_out, CrStats* stats) {
+    return render_entry(h, cam, p, true, frames, n_frames, true, h_out, stats);
+}
+
+int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples, int32_t real_type,
+                             void* d_out_rgb) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!d_sums || !d_out_rgb) return fail(h, CR_ERR_INVALID_ARG, "cr_fixed_sums_to_rgb: null buffer");
+    if (width < 1 || height < 1) return fail(h, CR_ERR_INVALID_ARG, "image size must be positive");
+    if ((int64_t)width * height > (int64_t)1 << 26) return fail(h, CR_ERR_INVALID_ARG, "image too large");
+    if (samples < 1) return fail(h, CR_ERR_INVALID_ARG, "The camera must have a positive number of samples.");
+    if (real_type != CR_REAL_F32 && real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return fixed_sums_to_rgb(h, (const unsigned long long*)d_sums, (size_t)width * (size_t)height * 3, samples, real_type == CR_REAL_F64, d_out_rgb);
+}
+
+int32_t cr_last_kernel_ms(CrHandle* h, double* out_ms) {
+    if (!h || !out_ms) return CR_ERR_INVALID_ARG;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipEventSynchronize(h->ev1));
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    *out_ms = ms;
+    return check_queue_abort(h);
+}
+
+int32_t cr_synchronize(CrHandle* h) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return check_queue_abort(h);
+}
+
+void* cr_stream(CrHandle* h) { return h ? (void*)h->stream : nullptr; }
+
+const char* cr_last_error(CrHandle* h) { return h ? h->error.c_str() : g_create_error.c_str(); }
+
+}   // extern "C"

@@ -1,6 +1,6 @@
 // group.hpp -- several GPUs of one node behind the C ABI: samples-per-pixel sharding, one
-// ncclReduce(sum) of the W*H*3 per-pixel sums over xGMI, the divide by `samples` on the root.  Included by capi.hip
-// (one translation unit).  RCCL is loaded with dlopen on first use: the library has no link-time dependency on it,
+// ncclReduce(sum) of the W*H*3 per-pixel sums over xGMI, the divide by `samples` on the root.  Included by group.hip
+// alone (its kernels are emitted there).  RCCL is loaded with dlopen on first use: the library has no link-time dependency on it,
 // and a group of one member never touches it.
 //
 // What it replaces in the reference: the worker pool of src/camera/cpu_threading.rs:25-115 (thread_count OS threads
@@ -165,16 +165,7 @@ void group_free(CrGroup* g) {
 // Counters and kernel time of the member's last (asynchronous) render, read after its stream went idle.
 int32_t member_stats(CrHandle* h, int64_t samples, CrStats* st) {
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipEventSynchronize(h->ev1));
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    uint64_t c[4] = {0, 0, 0, 0};
-    if (samples > 0) HIP_TRY(h, hipMemcpy(c, h->counters.p, sizeof c, hipMemcpyDeviceToHost));
-    memset(st, 0, sizeof *st);
-    st->kernel_ms = ms; st->samples = (uint64_t)samples;
-    st->segments = c[0]; st->node_tests = c[1]; st->prim_tests = c[2]; st->texel_fetches = c[3];
-    st->upload_ms = h->upload_ms;
-    return CR_OK;
+    return finish_stats(h, st, (uint64_t)samples, 0, 0);
 }
 
 }   // namespace

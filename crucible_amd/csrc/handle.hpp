@@ -1,0 +1,241 @@
+// handle.hpp -- what the translation units of libcrucible_hip.so share: the handle behind the C ABI of
+// include/crucible_hip.h, a precision's device copy of the scene, and the internal functions one unit calls in another.
+// Those are hidden-visibility functions of cr:: (exports.map keeps the dynamic table to the ABI); each is defined in
+// the unit its declaration names.  A kernel instantiation is emitted by exactly one unit:
+//   build.hip          host BVH builders, the LBVH driver (lbvh.hpp, hipcub), build_dev_scene, cr_export_bvh
+//   scene.hip          cr_upload_scene, refit.hpp's box kernels, the screening records, cr_update_primitives (update.hpp)
+//   render.hip         render_typed: a render's kernel arguments up to the choice of ladder; the stats epilogue
+//   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder)
+//   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
+//   api.hip            cr_create / cr_destroy, cr_render_*, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
+#pragma once
+#include "../../include/crucible_hip.h"
+#include "pathtrace.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace cr {
+
+struct DevBuf {
+    void* p = nullptr;      // what users address: raw + pad
+    void* raw = nullptr;    // the allocation (hipMalloc aligns it to 256 bytes)
+    size_t bytes = 0, pad = 0;
+    // pad: bytes skipped at the front, so that p is deliberately MISaligned by that much (see entry_pad)
+    hipError_t ensure(size_t n, size_t front_pad = 0) {
+        if (n <= bytes && front_pad == pad) return hipSuccess;
+        if (raw) (void)hipFree(raw);
+        p = raw = nullptr; bytes = 0; pad = 0;
+        hipError_t e = hipMalloc(&raw, n + front_pad);
+        if (e == hipSuccess) { bytes = n; pad = front_pad; p = (char*)raw + front_pad; }
+        return e;
+    }
+    void release() { if (raw) (void)hipFree(raw); p = raw = nullptr; bytes = 0; pad = 0; }
+};
+// Sibling wrappers are adjacent in the level-order array and start at ODD indices (1,2), (3,4), ...  Skipping one
+// entry at the front of the allocation puts every pair on one 2*sizeof(Entry) boundary: the two children of a
+// wrapper then share a cache line (f64: exactly one 128-byte line), so the walk's left-then-right visits touch it once.
+template <typename E> constexpr size_t entry_pad() { return (sizeof(E) & (sizeof(E) - 1)) == 0 ? sizeof(E) : 0; }
+
+template <typename real> struct DevScene {
+    bool built = false;
+    DevBuf entries, prims, mats, texs, keys;
+    DevBuf leaf_runs;                        // (first, count) of the primitive runs that leaves holding a list name
+    int32_t n_entries = 0, n_prims = 0, n_mats = 0, n_texs = 0, n_scene_keys = 0;
+    size_t lds_bytes = 0;
+    bool animated = false;
+    bool has_triangles = false;
+    bool has_spheres = false;
+    bool has_leaf_runs = false;              // some leaf names its primitives through leaf_runs (a HitList element)
+    bool has_bvh_elements = false;           // CR_BVH_REFERENCE over a BVHWrapper element: the records are not the reference's wrappers one to one (no export)
+    bool has_lists = false;                  // the tree was built over at least one HitList element: its construction-time box
+                                             // (empty, or grown over hidden objects too) is not what refit derives
+    DevBuf entries_refit;                    // working copy whose boxes refit_level_kernel rewrites per frame
+    DevBuf screen, screen_refit;             // f64, unordered trees: the f32 screening records of entries / entries_refit
+    DevBuf screen_overflow;                  // f64: one int, set by the record kernels when a box plane lies beyond the f32 range
+    bool screen_usable = true;               // f64: `screen` may be walked on (no box plane beyond the f32 range)
+    bool ordered = false;                    // CR_BVH_SAH_ORDERED: `entries` holds EntryO records
+    size_t entry_bytes = sizeof(Entry<real>);
+    std::vector<int8_t> host_axis;           // ordered: split axis per wrapper (-1 leaf), same order as host_entries
+    std::vector<int32_t> level_begin;        // entries of tree level l are [level_begin[l], level_begin[l+1])
+    std::vector<Entry<real>> host_entries;   // the tree over the scene's objects (for cr_export_bvh); the device copy names primitive runs
+    std::vector<int32_t> leaf_desc;          // leaf-order position -> index in the caller's primitive list
+    DevBuf desc_pos;                         // the inverse, on the device: index in the caller's primitive list -> position of its record in
+                                             // `prims`, -1 where it has none (hidden); scenes without list elements only (cr_update_primitives)
+    bool desc_pos_valid = false;
+    bool side_tables = false;                // mats / texs / keys hold the uploaded scene's (a rebuild after cr_update_primitives keeps them)
+    void release() { desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
+};
+
+}   // namespace cr
+
+using cr::DevBuf;
+using cr::DevScene;
+
+struct CrHandle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int n_cus = 0;
+    std::string error;
+    // host copy of the scene description
+    bool has_scene = false;
+    std::vector<CrPrimitive> prims;
+    std::vector<CrMaterial> materials;
+    std::vector<CrTexture> textures;
+    std::vector<CrKeyframe> keys;
+    int32_t sky_kind = 0, sky_image = -1, bvh_mode = 0;
+    bool has_list_elements = false;   // some CR_PRIM_LIST / CR_PRIM_BVH record: cr_update_primitives does not apply
+    DevBuf update_stage;              // cr_update_primitives: the call's rows (9 doubles each), then its indices
+    // images are precision independent
+    DevBuf images, texels;
+    int32_t n_images = 0;
+    DevScene<float> s32;
+    DevScene<double> s64;
+    DevBuf work_counter, counters, att_stack, out_buf;
+    // Camera keyframes of a render travel in a ring of per-launch slots: a pinned host slot is filled, copied to its
+    // device slot on the handle's stream and kept until that copy's event has fired, so back-to-back asynchronous
+    // renders (a movie's frames) never see each other's keys.
+    static constexpr int kCamSlots = 4;
+    static constexpr size_t kMaxCamKeys = 512;
+    void* cam_host[kCamSlots] = {};
+    DevBuf cam_dev[kCamSlots];
+    hipEvent_t cam_ev[kCamSlots] = {};
+    int cam_next = 0, cam_pending_slot = -1;
+    DevBuf sample_buf, sg_acc;   // sample-granular megakernel: per-sample colours of a batch, running sums between batches
+    DevBuf fx_acc;               // CR_SUM_RELAXED: per-pixel fixed-point sums (3 x u64 per pixel; per frame of a batch)
+    // cr_render_frames_*: a batch's per-frame ray times travel through one pinned host buffer, refilled only after the
+    // previous batch's copy has run (times_ev); the device table is reused in stream order
+    void* times_host = nullptr;
+    size_t times_cap = 0;
+    DevBuf times_dev;
+    hipEvent_t times_ev = nullptr;
+    int screen_boxes = 1;        // f64, unordered trees: box tests decided on f32 screening records where f32 can (CRUCIBLE_SCREEN=0: never)
+    int screen_lds = 1;          // ... also for scenes that sit in LDS whole (CRUCIBLE_SCREEN_LDS=0: only trees read from global memory)
+    int default_sum_order = CR_SUM_RELAXED;   // what CR_SUM_DEFAULT means on this handle (CRUCIBLE_SUM_ORDER=reference|relaxed)
+    // wavefront pipeline state (wavefront.hpp)
+    DevBuf wf_job, wf_rng, wf_ray, wf_depth, wf_hit_t, wf_hit_prim, wf_chunk, wf_ctrl, wf_samples, wf_acc;
+    uint32_t* wf_ring_host = nullptr;   // host-mapped ring the extend kernel reports its queue length into
+    uint32_t* wf_ring_dev = nullptr;
+    hipEvent_t wf_ev[8] = {};
+    int pipeline = 0;                   // 0 = megakernel (default), 1 = wavefront kernels, 2 = LDS-queue megakernel (CRUCIBLE_PIPELINE=mega|wavefront|queue)
+    int queue_walk_waves = 9, queue_min_batch = 48, queue_patience = 64;
+    uint32_t wf_slots = 1u << 21;
+    size_t wf_sample_bytes = (size_t)1600 << 20;
+    int wf_last_iterations = 0;
+    double upload_ms = 0;
+    size_t lds_limit = 160 * 1024;
+    // Sample-granular scheduling of the megakernel (pathtrace.hpp, KernelArgs::sg_on): on by default; the per-sample
+    // colour buffer may take up to sample_buf_limit bytes (more samples than fit are rendered in batches).
+    int sample_granular = 1;             // CRUCIBLE_SAMPLE_GRANULAR=0: a lane owns a pixel (no buffer)
+    size_t sample_buf_limit = (size_t)40 << 30;   // CRUCIBLE_SAMPLE_BUF_MB (MI355X: 288 GB of HBM)
+    int sg_chunk_override = 0;           // CRUCIBLE_SG_CHUNK: items per atomic (default: by launch size)
+    uint64_t work_counter_max = 0xF0000000ull;   // work items one launch may hand out (32-bit counter); more samples run as consecutive launches
+                                         // (CRUCIBLE_WORK_COUNTER_MAX: tests shrink it to reach that path on small frames)
+    int sg_lw = -1, sg_lh = -1;          // CRUCIBLE_SG_TILE=WxH (powers of two, W*H <= 64); default 4x4 pixels x 4 samples
+    // f32 trees with more than latency_entries wrappers run on pathtrace_kernel_latency (6 waves/SIMD) with a
+    // latency_top_bytes LDS window, three 512-thread groups per CU.  CRUCIBLE_LATENCY_ENTRIES (0 = never).
+    int32_t latency_entries = 0;         // (round 3: never by default -- with relaxed sums, the early touch of the leaf's second primitive and the deferred
+                                         //  leaf phases the regular kernel is 6.7 % faster on the 1M-sphere tree: 1770 against 1658 Msamples/s)
+    size_t latency_top_bytes = 48 * 1024;
+    size_t lds_side_limit = 16 * 1024;   // RES_TOP: materials + textures join the LDS window up to this size (CRUCIBLE_LDS_SIDE_KB; 0 = never)
+    size_t lds_top_bytes = 128 * 1024;  // LDS spent on the top of a tree that does not fit whole (CRUCIBLE_LDS_TOP_KB; 0 = none): 4096 32-byte records
+                                        // (f32 wrappers, or the f64 kernels' screening records) -- one 1024-thread workgroup per CU has the LDS to itself; teapot +2.5 %
+    bool lds_top_set = false;           // CRUCIBLE_LDS_TOP_KB given
+    int blocks_per_cu_override = 0;
+    int block_override = 0;
+    // Wave scheduling of the walk (speed only).  -1 = chosen per scene: sphere scenes 10 / 56, scenes with triangles 8 / 40 --
+    // a triangle test is ~1.5x a sphere test, so parked lanes are dearer and the sweeps (gpurun_out/exp7.txt, exp8.txt:
+    // teapot +9 % in f64 and f32 at 8 / 40; book1 and the 1M-sphere scene lose 1-2 % there) favour shorter rounds and
+    // an earlier exit.  CRUCIBLE_WALK_ROUND / CRUCIBLE_WALK_EXIT override.
+    int walk_round_steps = -1;         // wrappers a lane may step through per round; 0 = until every walking lane found a leaf or ran out
+    int walk_exit_lanes = -1;          // leave the walk phase once this many lanes are not walking (64 = wait for all)
+    int walk_leaf_min = -1;            // CRUCIBLE_WALK_LEAF_MIN: parked lanes a leaf phase waits for while others can still step (0 = every round; default 8:
+                                       // book1 +1.5 %, movie frame +1.5 %, 1M spheres +2.9 %, profiles/experiments/r03_leaf_min.txt)
+    int last_block = 0, last_grid = 0;
+    bool check_abort = false;          // the last launch was a queue kernel whose abort word has not been read yet
+};
+
+namespace cr {
+
+#define HIP_TRY(h, expr)                                                                      \
+    do {                                                                                      \
+        hipError_t _e = (expr);                                                               \
+        if (_e != hipSuccess) {                                                               \
+            (h)->error = std::string(#expr) + ": " + hipGetErrorString(_e);                   \
+            return CR_ERR_HIP;                                                                \
+        }                                                                                     \
+    } while (0)
+
+int32_t fail(CrHandle* h, int32_t code, const std::string& msg);   // api.hip (h == nullptr: cr_create's error)
+
+template <typename real> DevScene<real>& dev_scene(CrHandle* h);
+template <> inline DevScene<float>& dev_scene<float>(CrHandle* h) { return h->s32; }
+template <> inline DevScene<double>& dev_scene<double>(CrHandle* h) { return h->s64; }
+
+inline size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
+inline size_t real_size(int32_t real_type) { return real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float); }
+
+// CR_SUM_RELAXED's fixed-point scale 2^S for n samples per pixel: n * 2^S < 2^63, S = 52 up to 2047 samples
+inline double fx_scale_for(int64_t n) {
+    int lg = 0;
+    while ((n >> (lg + 1)) > 0) lg++;
+    return std::ldexp(1.0, std::min(52, 62 - lg));
+}
+
+// what CrRenderParams.sum_order means on this handle: CR_SUM_DEFAULT is the handle's default in the megakernel and the
+// reference order in the alternative pipelines
+inline int resolve_sum_order(const CrHandle* h, const CrRenderParams* p) {
+    return p->sum_order == CR_SUM_DEFAULT ? (h->pipeline == 0 ? h->default_sum_order : CR_SUM_REFERENCE_ORDER) : p->sum_order;
+}
+
+// The frames of one render: n frames whose ray times start at times[k] (host) and d_times[k] (the device's copy).  A
+// single render is a batch of one without a table (its times start at KernelArgs::current_time).  RELAX kernels only.
+template <typename real> struct FrameBatch {
+    int32_t n = 1;
+    const real* times = nullptr;
+    const real* d_times = nullptr;
+};
+
+// What render_typed settled before the residency ladder (render.hpp)
+struct WalkChoice {
+    bool anim, cam_keys;            // the kernel kind: keyed primitives, camera keys alone, neither
+    bool screen;                    // walk on the f32 screening records (a.screen is set)
+    bool screen_lds, plain_lds;     // the whole scene fits in LDS with screening records / with its wrappers
+    size_t lds_all_screen;          // LDS bytes of the whole scene with screening records in the wrappers' place
+};
+
+// build.hip
+template <typename real> int32_t build_dev_scene(CrHandle* h);
+// scene.hip
+template <typename real> int32_t run_box_kernels(CrHandle* h, DevScene<real>& ds, void* entries, real ta, real tb, bool use_keys);
+int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevBuf& out, bool* usable);
+int32_t make_screen(CrHandle* h, DevScene<float>& ds, const void* entries, DevBuf& out, bool* usable);
+int32_t validate_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags);
+int32_t apply_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags);
+// render.hip
+int32_t finish_stats(CrHandle* h, CrStats* stats, uint64_t samples, int32_t bvh_entries, int32_t scene_in_lds);
+int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_large_override, size_t lds_base, size_t lds_per_wave,
+                   const char* what, int& block, int& per_cu);
+template <typename real>
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames);
+// render_f32_reference.hip, render_f32_relaxed.hip, render_f64_reference.hip, render_f64_relaxed.hip (render.hpp)
+template <typename real, bool ORD, bool RELAX>
+int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb);
+template <typename real>   // the relaxed units: fixed-point sums -> means (or raw sums) of `count` samples
+int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size_t n, double inv_scale, double count, int32_t output_sum);
+// alt_pipelines.hip
+template <typename real> int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>& ds, bool anim, CrStats* stats);
+template <typename real> int32_t render_queue(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, bool anim, CrStats* stats, bool* launched);
+int32_t check_queue_abort(CrHandle* h);
+// api.hip
+int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p);
+int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n, int32_t samples, bool f64, void* out);
+uint64_t bad_pixels(const void* rgb, int32_t real_type, size_t n_pix);   // pixels of a host frame with a mean outside [0,1] or NaN
+
+}   // namespace cr

@@ -1126,7 +1126,7 @@ template <typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd) {
 // `max <= min` (a miss), hi32 - lo32 > TH proves a hit, and only a lane with |hi32 - lo32| <= TH evaluates Aabb::hit in f64
 // on the f64 box.  Overflow and NaN land there too (every comparison with them is false), and the round uses the screen only
 // when |if| lies in [2^-100, 2^100] and |of| <= 2^100 on every axis, on trees whose f64 planes all lie in the f32 range
-// (screen_from_entries_kernel reports any other; capi.hip then walks without the screen).  The decisions -- hence the walk, the counters and the image -- are those of the f64 test.
+// (screen_from_entries_kernel reports any other; render.hip then walks without the screen).  The decisions -- hence the walk, the counters and the image -- are those of the f64 test.
 // SCREEN is a kernel variant of its own: a kernel that carried both the f32 loop and the f64 min/max loop lost 5 % on the
 // teapot frames to register pressure.  In a SCREEN kernel a ray whose
 // 1/direction is infinite, or outside the f32 range above, walks with Aabb::hit's compare/select form (valid for every ray).
@@ -1352,7 +1352,7 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             }
             if (h) { w.best_t = t; w.best = pi; }
         };
-        // Scenes with a HitList element run the ANIM kernels (capi.hip), so the static kernels -- the headline's -- keep
+        // Scenes with a HitList element run the ANIM kernels (render.hip), so the static kernels -- the headline's -- keep
         // the one-or-two-record loop alone; A.leaf_runs is null unless such an element exists (a scalar test)
         if (!ANIM || A.leaf_runs == nullptr || !(leaf & kLeafRun)) {
             const int32_t first = leaf >> 1, count = (leaf & 1) + 1;
@@ -1764,39 +1764,15 @@ pathtrace_kernel_latency(const KernelArgs<real> A) {
     pathtrace_body<real, RES_TOP, ANIM, ORD, CAMK, RELAX>(A);
 }
 
-// The screening records of a wrapper array: boxes rounded to the nearest f32 (the band of walk_round allows for either
-// direction), links copied.  Run after every upload and after every refit of the f64 boxes.
-// A finite f64 plane beyond the f32 range becomes an infinite f32 plane, an error TH does not cover (an f32 box that
-// reaches to infinity decides hits that Aabb::hit misses): such a plane sets *overflow, and the caller then walks the tree
-// without the screen.
+// One plane of a screening record (screen.hpp's kernels make the records): the f64 plane rounded to the nearest f32 (the
+// band of walk_round allows for either direction).  A finite f64 plane beyond the f32 range becomes an infinite f32 plane,
+// an error TH does not cover (an f32 box that reaches to infinity decides hits that Aabb::hit misses): such a plane sets
+// *overflow, and the caller then walks the tree without the screen.
 CR_D void screen_plane(double b, float& f, int32_t* overflow) {
     f = (float)b;
     if (__builtin_fabsf(f) == __builtin_inff() && __builtin_fabs(b) != __builtin_inf()) *overflow = 1;
 }
 CR_D void screen_plane(float b, float& f, int32_t*) { f = b; }
-template <typename real>
-__global__ void __launch_bounds__(256) screen_from_entries_kernel(const Entry<real>* e, ScreenEntry* s, int32_t n, int32_t* overflow) {
-    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= n) return;
-    const Entry<real> v = e[i];
-    ScreenEntry o;
-    for (int k = 0; k < 6; k++) screen_plane(v.b[k], o.b[k], overflow);
-    o.skip = (uint32_t)v.skip << 5;
-    o.hit = v.leaf < 0 ? (uint32_t)(-v.leaf) << 5 : (kScreenLeaf | (uint32_t)v.leaf);
-    s[i] = o;
-}
-
-__global__ void __launch_bounds__(256) screen_from_ordered_entries_kernel(const EntryO<double>* e, ScreenEntryO* s, int32_t n, int32_t* overflow) {
-    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= n) return;
-    const EntryO<double> v = e[i];
-    ScreenEntryO o;
-    for (int k = 0; k < 6; k++) screen_plane(v.b[k], o.b[k], overflow);
-    if (v.leaf < 0) { o.axis = (uint32_t)(-v.leaf) & 3u; o.hit = (uint32_t)ordered_left(v.leaf) << 6; }
-    else { o.axis = 3u; o.hit = kScreenLeaf | (uint32_t)v.leaf; }
-    for (int k = 0; k < 8; k++) o.skip[k] = (uint32_t)v.skip[k] << 6;
-    s[i] = o;
-}
 
 // CR_SUM_RELAXED: the fixed-point sums become the frame -- sum * 2^-S, divided by the sample count unless the raw
 // sum of the shard is asked for; a set NaN flag gives NaN (the reference would have panicked in Color::new).

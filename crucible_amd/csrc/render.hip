@@ -1,0 +1,218 @@
+// render.hip -- a render up to its kernel: render_typed fills the kernel arguments (camera, frame times, refitted boxes,
+// screening records) and hands them to the residency ladder of the precision and sum order (render.hpp, render_*.hip)
+// or to a cross-check pipeline (alt_pipelines.hip).  Also what every launch path shares: the workgroup-size choice and
+// the stats epilogue.  No kernel is emitted here.
+#include "handle.hpp"
+#include "pack.hpp"
+
+namespace cr {
+
+// After ev1 was recorded behind a render of `samples` samples: its time and work counters into *stats.  No samples (an
+// empty shard): no kernel ran, the counters are an earlier render's and stay unread.
+int32_t finish_stats(CrHandle* h, CrStats* stats, uint64_t samples, int32_t bvh_entries, int32_t scene_in_lds) {
+    HIP_TRY(h, hipEventSynchronize(h->ev1));
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    uint64_t c[4] = {0, 0, 0, 0};
+    if (samples > 0) HIP_TRY(h, hipMemcpy(c, h->counters.p, sizeof c, hipMemcpyDeviceToHost));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    stats->segments = c[0]; stats->node_tests = c[1]; stats->prim_tests = c[2]; stats->texel_fetches = c[3];
+    stats->samples = samples;
+    stats->upload_ms = h->upload_ms;
+    stats->bvh_entries = bvh_entries;
+    stats->scene_in_lds = scene_in_lds;
+    return CR_OK;
+}
+
+// Workgroup size and workgroups per CU of `kern`: the candidate that keeps the most waves resident per CU (a larger
+// workgroup shares one LDS copy of the scene among more waves); ties go to the larger.  A workgroup of w waves asks for
+// lds_base + w * lds_per_wave bytes of LDS.  CRUCIBLE_BLOCK narrows the candidates to one; the two callers differ in an
+// override above max_block: the megakernel ignores it (ignore_large_override), the wavefront driver is left without a
+// candidate and reports that the kernel does not fit.
+int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_large_override, size_t lds_base, size_t lds_per_wave,
+                   const char* what, int& block, int& per_cu) {
+    int best_waves = 0;
+    block = 256; per_cu = 1;
+    for (int cand : {1024, 512, 256}) {
+        if (cand > max_block) continue;
+        if (h->block_override > 0 && cand != h->block_override && !(ignore_large_override && h->block_override > max_block)) continue;
+        int n = 0;
+        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, cand, lds_base + (size_t)(cand / 64) * lds_per_wave));
+        if (n * cand / 64 > best_waves) { best_waves = n * cand / 64; block = cand; per_cu = n; }
+    }
+    if (best_waves == 0) return fail(h, CR_ERR_HIP, what);
+    if (h->blocks_per_cu_override > 0) per_cu = h->blocks_per_cu_override;
+    return CR_OK;
+}
+
+// cr_render_frames_*: the batch's ray times through the handle's pinned staging buffer into its device table
+static int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
+    if (h->times_ev) HIP_TRY(h, hipEventSynchronize(h->times_ev));   // the previous batch's copy has read the staging buffer
+    else HIP_TRY(h, hipEventCreateWithFlags(&h->times_ev, hipEventDisableTiming));
+    if (bytes > h->times_cap) {
+        if (h->times_host) (void)hipHostFree(h->times_host);
+        h->times_host = nullptr; h->times_cap = 0;
+        const hipError_t e = hipHostMalloc(&h->times_host, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { h->times_host = nullptr; (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("frame times: ") + hipGetErrorString(e)); }
+        h->times_cap = bytes;
+    }
+    const hipError_t e = h->times_dev.ensure(bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("frame times: ") + hipGetErrorString(e)); }
+    memcpy(h->times_host, times, bytes);
+    HIP_TRY(h, hipMemcpyAsync(h->times_dev.p, h->times_host, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(h->times_ev, h->stream));
+    return CR_OK;
+}
+
+// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*).
+template <typename real>
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames) {
+    int32_t rc = build_dev_scene<real>(h);
+    if (rc != CR_OK) return rc;
+    DevScene<real>& ds = dev_scene<real>(h);
+    const int sum_order = resolve_sum_order(h, p);
+    const bool fixed = p->output_sum == CR_OUTPUT_FIXED_SUM;
+    if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
+        return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
+    // without primitive keys the boxes would not change -- unless a HitList element's box is not its objects' union
+    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;
+    if (frames) {
+        if (sum_order != CR_SUM_RELAXED || h->pipeline != 0)
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
+                                               "sequential over samples and would need a per-sample buffer per frame)");
+        if (refit)
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
+                                               "(render such frames one at a time)");
+    }
+    if (p->sample_count == 0) {
+        // An empty shard (more ranks than samples): the sum of no samples, and 0 / samples for the mean, are both
+        // zero -- cast_ray's loop body never runs (ray_casting.rs:82).  No kernel is launched.
+        const size_t bytes = (size_t)n_frames * (size_t)cd->image_width * (size_t)cd->image_height * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        HIP_TRY(h, hipMemsetAsync(d_out, 0, bytes, h->stream));
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        return stats ? finish_stats(h, stats, 0, ds.n_entries, 0) : CR_OK;
+    }
+    KernelArgs<real> a;
+    memset(&a, 0, sizeof a);
+    a.entries = (const Entry<real>*)ds.entries.p; a.prims = (const Prim<real>*)ds.prims.p; a.leaf_runs = ds.has_leaf_runs ? (const int32_t*)ds.leaf_runs.p : nullptr;
+    a.mats = (const Mat<real>*)ds.mats.p; a.texs = (const Tex<real>*)ds.texs.p;
+    a.images = (const ImageRef*)h->images.p; a.texels = (const uint32_t*)h->texels.p;
+    a.keys = (const Key<real>*)ds.keys.p;
+    a.n_entries = ds.n_entries; a.n_prims = ds.n_prims; a.n_mats = ds.n_mats; a.n_texs = ds.n_texs;
+    a.sky_kind = h->sky_kind; a.sky_image = h->sky_image;
+
+    // camera set-up (pack.hpp)
+    CamConst<real>& c = a.cam;
+    pack_camera(cd, c);
+    int nk = cd->from_key_count + cd->at_key_count;
+    if ((size_t)nk > CrHandle::kMaxCamKeys) return fail(h, CR_ERR_UNSUPPORTED, "more than 512 camera keyframes");
+    a.cam_keys = nullptr;
+    if (nk > 0) {   // per-launch slot: never overwritten while an earlier render may still read it
+        const int slot = h->cam_next;
+        h->cam_next = (slot + 1) % CrHandle::kCamSlots;
+        const size_t slot_bytes = CrHandle::kMaxCamKeys * sizeof(Key<double>);
+        if (!h->cam_host[slot]) {   // the slot's three resources together, or none of them (a later render tries again)
+            void* host = nullptr;
+            hipEvent_t ev = nullptr;
+            hipError_t e = hipHostMalloc(&host, slot_bytes, hipHostMallocDefault);
+            if (e == hipSuccess) e = h->cam_dev[slot].ensure(slot_bytes);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            if (e != hipSuccess) {
+                if (host) (void)hipHostFree(host);
+                h->cam_dev[slot].release();
+                (void)hipGetLastError();
+                return fail(h, CR_ERR_HIP, std::string("camera keyframe slot: ") + hipGetErrorString(e));
+            }
+            h->cam_host[slot] = host; h->cam_ev[slot] = ev;
+        } else HIP_TRY(h, hipEventSynchronize(h->cam_ev[slot]));   // the slot's previous user has finished with it
+        Key<real>* ck = (Key<real>*)h->cam_host[slot];
+        for (int i = 0; i < cd->from_key_count; i++) key_to_real(cd->from_keys[i], ck[i]);
+        for (int i = 0; i < cd->at_key_count; i++) key_to_real(cd->at_keys[i], ck[cd->from_key_count + i]);
+        HIP_TRY(h, hipMemcpyAsync(h->cam_dev[slot].p, ck, nk * sizeof(Key<real>), hipMemcpyHostToDevice, h->stream));
+        a.cam_keys = (const Key<real>*)h->cam_dev[slot].p;
+        h->cam_pending_slot = slot;
+    }
+    pack_camera_frame(c);   // static camera: the per-sample vectors
+
+    a.sample_begin = p->sample_begin; a.sample_end = p->sample_begin + p->sample_count;
+    a.samples_total = p->samples; a.max_depth = p->max_depth;
+    a.seed_mixed = mix64(p->seed + RNG_GAMMA);
+    frame_times(p, a.current_time, a.shutter_length);   // ray_casting.rs:77-79
+    a.output_sum = p->output_sum;
+    FrameBatch<real> fb;
+    std::vector<real> times;
+    if (frames) {   // each frame's times as a single render of it computes them (the shutter is the same for all)
+        times.resize((size_t)n_frames);
+        CrRenderParams q = *p;
+        for (int32_t k = 0; k < n_frames; k++) { q.frame = frames[k]; frame_times(&q, times[(size_t)k], a.shutter_length); }
+        rc = stage_frame_times(h, times.data(), times.size() * sizeof(real));
+        if (rc != CR_OK) return rc;
+        a.current_time = times[0];
+        fb.n = n_frames; fb.times = times.data(); fb.d_times = (const real*)h->times_dev.p;
+    }
+    if (refit) {   // refit.hpp: wrapper boxes for this frame's ray times [current_time, current_time + shutter_length]
+        const size_t bytes = (size_t)ds.n_entries * ds.entry_bytes;
+        HIP_TRY(h, ds.entries_refit.ensure(bytes, ds.entries.pad));
+        HIP_TRY(h, hipMemcpyAsync(ds.entries_refit.p, ds.entries.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+        { int32_t rc = run_box_kernels<real>(h, ds, ds.entries_refit.p, a.current_time, a.current_time + a.shutter_length, true); if (rc != CR_OK) return rc; }
+        a.entries = (const Entry<real>*)ds.entries_refit.p;
+    }
+    // f64 megakernel on an unordered tree: the walk decides its box tests on the f32 screening records (half the bytes
+    // per step), see walk_round (A/B in profiles/experiments/r03_screen_ab.txt).
+    // (not on a tree with a box plane beyond the f32 range: make_screen)
+    bool screen = h->pipeline == 0 && ds.screen.p != nullptr && ds.n_entries > 0 && h->screen_boxes && ds.n_entries < (ds.ordered ? kScreenMaxEntriesO : kScreenMaxEntries);
+    if (screen) {
+        a.screen = ds.screen.p;
+        bool usable = ds.screen_usable;
+        if (refit) {
+            int32_t rc = make_screen(h, ds, ds.entries_refit.p, ds.screen_refit, &usable);
+            if (rc != CR_OK) return rc;
+            a.screen = ds.screen_refit.p;
+        }
+        if (!usable) { screen = false; a.screen = nullptr; }
+    }
+    // a SCREEN kernel stages screening records where the others stage wrappers
+    const size_t screen_rec = ds.ordered ? sizeof(ScreenEntryO) : sizeof(ScreenEntry);
+    WalkChoice w;
+    w.screen = screen;
+    w.lds_all_screen = ds.lds_bytes - r16((size_t)ds.n_entries * ds.entry_bytes) + r16((size_t)ds.n_entries * screen_rec);
+    a.tiles_x = (uint32_t)(c.W + 7) / 8u; a.tiles_y = (uint32_t)(c.H + 7) / 8u;
+    a.work_counter = (uint32_t*)h->work_counter.p;
+    a.counters = (uint64_t*)h->counters.p;
+    a.out = (real*)d_out;
+    a.uniform_kind = (ds.has_spheres && !ds.has_triangles) ? 0 : ((ds.has_triangles && !ds.has_spheres) ? 1 : -1);
+    a.walk_exit_lanes = (uint32_t)(h->walk_exit_lanes >= 0 ? h->walk_exit_lanes : (ds.has_triangles ? 40 : 56));
+    a.walk_round_steps = (uint32_t)(h->walk_round_steps >= 0 ? h->walk_round_steps : (ds.has_triangles ? 8 : 10));
+    a.walk_leaf_min = h->pipeline == 0 ? (uint32_t)(h->walk_leaf_min >= 0 ? h->walk_leaf_min : 8) : 0u;   // the other pipelines test a leaf in the round that found it
+    a.sg_on = 0; a.sg_lw = a.sg_lh = 3; a.sg_groups = 0; a.sg_total = 0; a.sample_buf = nullptr;   // set by launch()
+
+    // the ANIM kernels also carry the decode of leaves that hold a HitList element (pathtrace.hpp walk_round)
+    w.anim = ds.animated || ds.has_leaf_runs;   // keyed primitives (the ANIM kernels also follow a keyed camera)
+    // camera keys alone: the static kernels' CAMK variant, which also renders the batches of scenes without keys (the
+    // static kernels do not carry a batch's frame arithmetic; with an unkeyed camera CAMK computes what they compute)
+    w.cam_keys = c.animated || frames != nullptr;
+    // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
+    if (sum_order == CR_SUM_RELAXED && h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_SUM_RELAXED is implemented by the megakernel pipeline only");
+    const bool relax = sum_order == CR_SUM_RELAXED;
+    const size_t fx_need = relax ? fx_lds_bytes(MaxBlock<real>::value, 4) : 0;   // the relaxed sums' slots share the LDS
+    w.screen_lds = screen && h->screen_lds && w.lds_all_screen + fx_need <= h->lds_limit;
+    w.plain_lds = ds.lds_bytes + fx_need <= h->lds_limit;
+    if (ds.ordered) {   // near-child-first walk: megakernel only
+        if (h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_BVH_SAH_ORDERED is implemented by the megakernel pipeline only");
+        return relax ? walk_ladder<real, true, true>(h, a, ds, w, stats, fb) : walk_ladder<real, true, false>(h, a, ds, w, stats, fb);
+    }
+    if (h->pipeline == 1) return render_wavefront<real>(h, a, ds, w.anim || w.cam_keys, stats);
+    if (h->pipeline == 2) {   // the LDS-queue megakernel where it fits, else the plain megakernel below
+        bool launched = false;
+        rc = render_queue<real>(h, a, ds, w.anim || w.cam_keys, stats, &launched);
+        if (launched || rc != CR_OK) return rc;
+    }
+    return relax ? walk_ladder<real, false, true>(h, a, ds, w, stats, fb) : walk_ladder<real, false, false>(h, a, ds, w, stats, fb);
+}
+
+template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t);
+template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t);
+
+}   // namespace cr

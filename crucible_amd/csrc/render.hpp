@@ -1,0 +1,226 @@
+// render.hpp -- the megakernel's host side for one precision and one sum order: launch() sets a pathtrace.hpp kernel up
+// and runs it, launch_variant() picks the kernel kind, walk_ladder() picks the scene's residency.  Included by the
+// render_*.hip units only, each of which instantiates walk_ladder (both tree orders) for its <real, RELAX>, so the
+// kernels of the four combinations compile side by side and no kernel is emitted twice.
+#pragma once
+#include "handle.hpp"
+
+#include <type_traits>
+
+namespace cr {
+
+template <typename real>
+int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size_t n, double inv_scale, double count, int32_t output_sum) {
+    hipLaunchKernelGGL((fx_finalize_kernel<real>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, sums, out, n, inv_scale, count, output_sum);
+    HIP_TRY(h, hipGetLastError());
+    return CR_OK;
+}
+
+template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
+int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats, const FrameBatch<real>& fb) {
+    constexpr bool LDS = RES != RES_GLOBAL || RELAX;
+    static_assert(!LATENCY || RES == RES_TOP, "the 6-waves-per-SIMD entry point exists for RES_TOP only");
+    KernelArgs<real> args = args_in;
+    void (*kern)(const KernelArgs<real>) = pathtrace_kernel<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>;
+    if constexpr (LATENCY) kern = pathtrace_kernel_latency<real, ANIM, ORD, CAMK, RELAX>;
+    const int max_block = LATENCY ? LatencyBlock : MaxBlock<real>::value;
+    // The work tile (sample-granular hand-out): 2^lw x 2^lh pixels times 64 >> (lw + lh) consecutive samples; by default
+    // 4 x 4 x 4, wider tiles of fewer samples when fewer than 4 samples are rendered.
+    const int32_t n_samples = args.sample_end - args.sample_begin;
+    int tile_lw = h->sg_lw, tile_lh = h->sg_lh;
+    if (tile_lw < 0) { const int ns = n_samples >= 4 ? 4 : (n_samples >= 2 ? 2 : 1); tile_lw = ns == 4 ? 2 : 3; tile_lh = ns == 1 ? 3 : 2; }
+    // RELAX: the waves' accumulator slots follow the scene in LDS (2 x 384 B per wave for a 16-pixel tile); a tile too
+    // large for what the scene leaves free falls back to 16 pixels (the surplus sample slots of its groups stay empty)
+    const size_t fx_off = RES != RES_GLOBAL ? ((scene_lds_bytes + 15) & ~(size_t)15) : 0;
+    if (RELAX && fx_off + fx_lds_bytes(max_block, (uint32_t)(tile_lw + tile_lh)) > (size_t)160 * 1024) { tile_lw = 2; tile_lh = 2; }
+    auto lds_for = [&](int block) { return RELAX ? fx_off + fx_lds_bytes(block, (uint32_t)(tile_lw + tile_lh)) : scene_lds_bytes; };
+    args.fx_lds_off = (uint32_t)fx_off;
+    if (LDS) HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_for(max_block)));
+    int block = 256, per_cu = 1;   // an override above max_block is ignored here (the latency entry point's 512 under CRUCIBLE_BLOCK=1024)
+    const size_t lds_base = RELAX ? fx_off : (LDS ? scene_lds_bytes : 0), lds_per_wave = RELAX ? fx_lds_bytes(64, (uint32_t)(tile_lw + tile_lh)) : 0;
+    { int32_t rc = pick_block(h, (const void*)kern, max_block, true, lds_base, lds_per_wave, "kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
+    const size_t lds_bytes = lds_for(block);
+    // Sample-granular mode: batches of samples whose colours fit the buffer; each batch is one launch of the
+    // path tracer followed by the ordered sum (sg_finalize_kernel).
+    const size_t npix = (size_t)args.cam.W * (size_t)args.cam.H;
+    const int32_t s_begin = args.sample_begin, s_end = args.sample_end;
+    int32_t batch = 0;
+    int32_t fpl = 1;   // frames per launch (a batch of frames: as many whole frames as the work counter holds)
+    args.n_frames = 1; args.frame_times = nullptr;
+    if (fb.n > 1 && !(RELAX && (ANIM || CAMK))) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
+    if ((h->sample_granular || RELAX) && s_end > s_begin) {
+        const size_t per_sample = npix * 3 * sizeof(real);
+        batch = (int32_t)std::min<size_t>((size_t)(s_end - s_begin), RELAX ? (size_t)INT32_MAX : std::max<size_t>(1, h->sample_buf_limit / per_sample));
+        int lw = tile_lw, lh = tile_lh;
+        if (!RELAX && h->sg_lw < 0) { const int ns = batch >= 4 ? 4 : (batch >= 2 ? 2 : 1); lw = ns == 4 ? 2 : 3; lh = ns == 1 ? 3 : 2; }   // by the batch, which the buffer may have cut
+        const uint32_t ns = 64u >> (lw + lh);
+        args.sg_lw = (uint32_t)lw; args.sg_lh = (uint32_t)lh;
+        args.tiles_x = ((uint32_t)args.cam.W + (1u << lw) - 1) >> lw;
+        args.tiles_y = ((uint32_t)args.cam.H + (1u << lh) - 1) >> lh;
+        const uint64_t tiles = (uint64_t)args.tiles_x * args.tiles_y;
+        // the 32-bit work counter must hold tiles * groups * 64 plus one chunk per wave
+        const uint64_t max_groups = h->work_counter_max / (tiles * 64);
+        if (max_groups < 1) batch = 0;
+        else batch = (int32_t)std::min<uint64_t>((uint64_t)batch, max_groups * ns);
+        // the buffer holds one colour per work item of a batch: whole tiles and whole sample groups (edge padding included)
+        if constexpr (RELAX) {
+            if (batch <= 0) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
+            // a frame that needs sample batches on its own renders frame by frame
+            if (batch == s_end - s_begin) fpl = (int32_t)std::min<uint64_t>((uint64_t)fb.n, max_groups / (((uint64_t)batch + ns - 1) / ns));
+            if (args.output_sum != CR_OUTPUT_FIXED_SUM) {
+                const hipError_t e = h->fx_acc.ensure((size_t)fb.n * npix * 3 * sizeof(unsigned long long));
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(h, CR_ERR_HIP, "fixed-point sums of " + std::to_string(fb.n) + " frame(s): " + hipGetErrorString(e));
+                }
+            }
+        } else {
+            auto batch_bytes = [&](int32_t b) { return (size_t)tiles * ((size_t)(b + (int32_t)ns - 1) / ns) * 64u * 3u * sizeof(real); };
+            while (batch > (int32_t)ns && batch_bytes(batch) > std::max(h->sample_buf_limit, batch_bytes((int32_t)ns))) batch -= (int32_t)ns;
+            if (batch > 0 && h->sample_buf.ensure(batch_bytes(batch)) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
+            if (batch > 0 && batch < s_end - s_begin && h->sg_acc.ensure(per_sample) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
+            if (batch == 0) { args.tiles_x = args_in.tiles_x; args.tiles_y = args_in.tiles_y; }   // fall back: a lane owns a pixel
+        }
+    }
+    args.sg_on = batch > 0 ? 1u : 0u;
+    const uint32_t ns = args.sg_on ? (64u >> (args.sg_lw + args.sg_lh)) : 1u;
+    auto groups_of = [&](int32_t n) { return (uint32_t)((n + (int32_t)ns - 1) / (int32_t)ns); };
+    uint64_t total_work = args.sg_on ? (uint64_t)args.tiles_x * args.tiles_y * fpl * groups_of(std::min(batch, s_end - s_begin)) * 64u
+                                     : (uint64_t)args.tiles_x * args.tiles_y * 64u;
+    uint32_t grid = (uint32_t)(h->n_cus * per_cu);
+    uint64_t need_blocks = (total_work + block - 1) / block;
+    if ((uint64_t)grid > need_blocks) grid = (uint32_t)need_blocks;
+    if (grid < 1) grid = 1;
+    args.n_threads = grid * (uint32_t)block;
+    if constexpr (!RELAX) {
+        size_t stack_bytes = (size_t)3 * (size_t)(args.max_depth > 0 ? args.max_depth : 1) * args.n_threads * sizeof(real);
+        HIP_TRY(h, h->att_stack.ensure(stack_bytes));
+        args.att_stack = (real*)h->att_stack.p;
+    } else {
+        // the scale of the n samples a pixel receives in this render; CR_OUTPUT_FIXED_SUM: of the whole frame, so the words
+        // of any shards of it add up to the frame's, and they go straight into the caller's buffer
+        const bool fixed = args.output_sum == CR_OUTPUT_FIXED_SUM;
+        args.fx_scale = fx_scale_for(fixed ? args.samples_total : s_end - s_begin);
+        args.fx_acc = fixed ? (unsigned long long*)args.out : (unsigned long long*)h->fx_acc.p;
+        HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, (size_t)fb.n * npix * 3 * sizeof(unsigned long long), h->stream));
+    }
+    HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    if (!args.sg_on) {
+        HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
+        HIP_TRY(h, hipGetLastError());
+    } else {
+        args.sample_buf = (real*)h->sample_buf.p;
+        unsigned long long* const fx_frame0 = args.fx_acc;
+        for (int32_t f0 = 0; f0 < fb.n; f0 += fpl) {   // one pass for a single render
+            const int32_t fn = std::min(fpl, fb.n - f0);
+            if constexpr (RELAX) {   // frames [f0, f0 + fn) of a batch
+                args.n_frames = (uint32_t)fn;
+                args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
+                args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
+                args.fx_acc = fx_frame0 + (size_t)f0 * npix * 3;
+            }
+            for (int32_t b0 = s_begin; b0 < s_end; b0 += batch) {
+                const int32_t b1 = std::min(s_end, b0 + batch);
+                args.sample_begin = b0; args.sample_end = b1;
+                args.sg_groups = groups_of(b1 - b0);
+                args.sg_total = (uint32_t)((uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn * args.sg_groups * 64u);
+                {   // 1024 items per atomic keeps the counter quiet on long launches; a short launch (a small frame, or one
+                    // GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most
+                    // 1/128 of its share
+                    const uint64_t per_wave = (uint64_t)args.sg_total / std::max<uint64_t>(1, (uint64_t)grid * block / 64);
+                    const uint64_t c = h->sg_chunk_override > 0 ? (uint64_t)h->sg_chunk_override : std::min<uint64_t>(1024, std::max<uint64_t>(64, per_wave / 128));
+                    args.sg_chunk = (uint32_t)((c + 63) / 64 * 64);
+                }
+                HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
+                HIP_TRY(h, hipGetLastError());
+                if constexpr (!RELAX) {   // (relaxed: the sums stay in fx_acc until the last batch)
+                    const size_t fin_threads = ((size_t)args.tiles_x * args.tiles_y) << (args.sg_lw + args.sg_lh);
+                    hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((fin_threads + 255) / 256)), dim3(256), 0, h->stream, args,
+                                       (real*)h->sg_acc.p, b1 - b0, b0 == s_begin ? 1 : 0, b1 == s_end ? 1 : 0);
+                    HIP_TRY(h, hipGetLastError());
+                }
+            }
+        }
+        if constexpr (RELAX) if (args.output_sum != CR_OUTPUT_FIXED_SUM) {   // a batch's frames follow each other in fx_acc and in the output
+            int32_t rc = fx_finalize<real>(h, (const unsigned long long*)h->fx_acc.p, args.out, (size_t)fb.n * npix * 3, 1.0 / args.fx_scale, (double)args.samples_total, args.output_sum);
+            if (rc != CR_OK) return rc;
+        }
+        args.sample_begin = s_begin; args.sample_end = s_end;
+    }
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    h->last_block = block; h->last_grid = (int)grid;
+    if (stats) {
+        int32_t rc = finish_stats(h, stats, (uint64_t)args.cam.W * (uint64_t)args.cam.H * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, RES);
+        if (rc != CR_OK) return rc;
+#ifdef CR_DIAG
+        {
+            uint64_t d[64];
+            HIP_TRY(h, hipMemcpy(d, h->counters.p, sizeof d, hipMemcpyDeviceToHost));
+            const char* names[] = {"box_wave", "box_lane", "prim_wave", "prim_lane", "round_wave", "round_lane", "leafph_wave", "leafph_lane",
+                                   "shade_wave", "shade_lane", "lamb_lane", "metal_lane", "diel_lane", "sky_lane", "ruv_wave", "ruv_lane",
+                                   "regen_wave", "regen_lane", "outer_wave", "unwind_wave", "unwind_lane", "hitsh_wave", "hitsh_lane", "band_wave", "band_lane"};
+            fprintf(stderr, "[diag] block=%d grid=%u clk_regen=%llu clk_trace=%llu clk_shade=%llu clk_total=%llu", block, grid,
+                    (unsigned long long)d[9], (unsigned long long)d[10], (unsigned long long)d[11], (unsigned long long)d[12]);
+            for (int i = 0; i < DG_N; i++) fprintf(stderr, " %s=%llu", names[i], (unsigned long long)d[16 + i]);
+            fprintf(stderr, "\n");
+        }
+#endif
+    }
+    return CR_OK;
+}
+
+// Picks the kernel kind: keyed primitives (ANIM), camera keys alone (CAMK) or neither.  The ANIM kernels follow a keyed
+// camera themselves, so ANIM with CAMK is never instantiated.
+template <typename real, int RES, bool ORD, bool LATENCY, bool RELAX, bool SCREEN = false>
+int32_t launch_variant(CrHandle* h, const KernelArgs<real>& a, size_t lds_bytes, CrStats* stats, const WalkChoice& w, const FrameBatch<real>& fb) {
+    if (w.anim) return launch<real, RES, true, ORD, LATENCY, false, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
+    if (w.cam_keys) return launch<real, RES, false, ORD, LATENCY, true, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
+    return launch<real, RES, false, ORD, LATENCY, false, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
+}
+
+// The residency ladder: the whole scene in LDS, else a window of the tree's top there (RES_TOP), else everything through
+// L2.  ORD: the near-child-first walk over EntryO / ScreenEntryO records.  What the tree orders really differ in: an ordered
+// f32 tree has no screening records (make_screen), so its SCREEN kernels do not exist; the window's record type; and
+// the side tables join the window on unordered trees only.
+template <typename real, bool ORD, bool RELAX>
+int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb) {
+    constexpr bool f32 = std::is_same<real, float>::value;   // the double kernel needs far more than 80 VGPRs: it halves there
+    constexpr bool can_screen = !(ORD && f32);
+    if (ds.n_entries > 0 && (w.plain_lds || w.screen_lds)) {
+        a.lds_entries = ds.n_entries;
+        if constexpr (can_screen) if (w.screen_lds) return launch_variant<real, RES_LDS, ORD, false, RELAX, true>(h, a, w.lds_all_screen, stats, w, fb);
+        a.screen = nullptr;
+        return launch_variant<real, RES_LDS, ORD, false, RELAX>(h, a, ds.lds_bytes, stats, w, fb);
+    }
+    const bool latency = f32 && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
+    // a window of screening records holds twice the wrappers
+    const size_t window_rec = w.screen ? sizeof(std::conditional_t<ORD, ScreenEntryO, ScreenEntry>) : sizeof(typename EntryOf<real, ORD>::type);
+    const int32_t top = (int32_t)std::min<size_t>((size_t)ds.n_entries, (latency ? h->latency_top_bytes : h->lds_top_bytes) / window_rec);
+    if (top > 0) {   // large scene: the top levels of the tree in LDS, everything else through L2
+        a.lds_entries = top;
+        size_t bytes = (size_t)top * window_rec;
+        if constexpr (!ORD) {   // materials and textures ride along when they are small (the tree can be large with two materials)
+            const size_t side = r16((size_t)ds.n_mats * sizeof(Mat<real>)) + r16((size_t)ds.n_texs * sizeof(Tex<real>));
+            // (the 6-waves-per-SIMD entry point runs three 512-thread groups per CU: window, side tables and the relaxed sums' slots of all three share 160 KB)
+            const size_t third = (size_t)160 * 1024 / 3 - 16, used = bytes + fx_lds_bytes(LatencyBlock, 4);
+            const size_t side_cap = latency ? (third > used ? third - used : 0) : h->lds_side_limit;
+            if (side <= std::min(h->lds_side_limit, side_cap)) { a.lds_side = 1; bytes = r16(bytes) + side; }
+        }
+        if constexpr (f32) if (latency) return launch_variant<real, RES_TOP, ORD, true, RELAX>(h, a, bytes, stats, w, fb);
+        if constexpr (can_screen) if (w.screen) return launch_variant<real, RES_TOP, ORD, false, RELAX, true>(h, a, bytes, stats, w, fb);
+        return launch_variant<real, RES_TOP, ORD, false, RELAX>(h, a, bytes, stats, w, fb);
+    }
+    a.lds_entries = 0;
+    if constexpr (can_screen) if (w.screen) return launch_variant<real, RES_GLOBAL, ORD, false, RELAX, true>(h, a, 0, stats, w, fb);
+    return launch_variant<real, RES_GLOBAL, ORD, false, RELAX>(h, a, 0, stats, w, fb);
+}
+
+// a unit's instantiations: the ladders of both tree orders, and with them every kernel of <real, RELAX>
+#define CR_RENDER_UNIT(real, RELAX)                                                                                                                            \
+    template int32_t cr::walk_ladder<real, false, RELAX>(CrHandle*, KernelArgs<real>&, const DevScene<real>&, const WalkChoice&, CrStats*, const FrameBatch<real>&); \
+    template int32_t cr::walk_ladder<real, true, RELAX>(CrHandle*, KernelArgs<real>&, const DevScene<real>&, const WalkChoice&, CrStats*, const FrameBatch<real>&);
+
+}   // namespace cr

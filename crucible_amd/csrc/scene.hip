@@ -1,0 +1,275 @@
+// scene.hip -- the scene on the handle: cr_upload_scene validates and deep-copies the description; the device steps
+// that upload, refit and update share (wrapper boxes bottom-up, refit.hpp; the f32 screening records); and
+// cr_update_primitives (update.hpp).
+#include "handle.hpp"
+#include "refit.hpp"
+#include "screen.hpp"
+#include "pack.hpp"
+#include "update.hpp"
+
+#include <chrono>
+
+namespace cr {
+
+// Boxes of every wrapper of `entries` (a device copy of the tree), bottom-up by level: for the ray times [ta, tb]
+// of a frame (use_keys) or the construction-time boxes (!use_keys).
+template <typename real>
+int32_t run_box_kernels(CrHandle* h, DevScene<real>& ds, void* entries, real ta, real tb, bool use_keys) {
+    for (size_t l = ds.level_begin.size() - 1; l-- > 0;) {
+        const int32_t begin = ds.level_begin[l], end = ds.level_begin[l + 1];
+        if (end <= begin) continue;
+        const dim3 grid((unsigned)((end - begin + 255) / 256)), block(256);
+        if (ds.ordered) hipLaunchKernelGGL((refit_level_kernel<real, true>), grid, block, 0, h->stream, (EntryO<real>*)entries, begin, end,
+                                           (const Prim<real>*)ds.prims.p, (const Key<real>*)ds.keys.p, ta, tb, use_keys ? 1 : 0, (const int32_t*)ds.leaf_runs.p);
+        else hipLaunchKernelGGL((refit_level_kernel<real, false>), grid, block, 0, h->stream, (Entry<real>*)entries, begin, end,
+                                (const Prim<real>*)ds.prims.p, (const Key<real>*)ds.keys.p, ta, tb, use_keys ? 1 : 0, (const int32_t*)ds.leaf_runs.p);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return CR_OK;
+}
+
+// The f32 screening records of a (possibly refitted) f64 wrapper array, in the layout of the tree (ScreenEntry / ScreenEntryO).
+// *usable = false when a finite f64 plane lies beyond the f32 range (screen_from_entries_kernel): the walk must not screen
+// on these records.  Synchronises the stream.
+int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevBuf& out, bool* usable) {
+    const size_t rec = ds.ordered ? sizeof(ScreenEntryO) : sizeof(ScreenEntry);
+    HIP_TRY(h, out.ensure((size_t)ds.n_entries * rec, ds.ordered ? entry_pad<ScreenEntryO>() : entry_pad<ScreenEntry>()));
+    HIP_TRY(h, ds.screen_overflow.ensure(sizeof(int32_t)));
+    HIP_TRY(h, hipMemsetAsync(ds.screen_overflow.p, 0, sizeof(int32_t), h->stream));
+    const dim3 grid((unsigned)((ds.n_entries + 255) / 256));
+    int32_t* flag = (int32_t*)ds.screen_overflow.p;
+    if (ds.ordered) hipLaunchKernelGGL(screen_from_ordered_entries_kernel, grid, dim3(256), 0, h->stream, (const EntryO<double>*)entries, (ScreenEntryO*)out.p, ds.n_entries, flag);
+    else hipLaunchKernelGGL(screen_from_entries_kernel<double>, grid, dim3(256), 0, h->stream, (const Entry<double>*)entries, (ScreenEntry*)out.p, ds.n_entries, flag);
+    HIP_TRY(h, hipGetLastError());
+    int32_t overflow = 0;
+    HIP_TRY(h, hipMemcpyAsync(&overflow, flag, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *usable = overflow == 0;
+    return CR_OK;
+}
+// f32 scenes: the same boxes in ScreenEntry's link layout (the walk's inner loop reads that one), unordered trees only
+int32_t make_screen(CrHandle* h, DevScene<float>& ds, const void* entries, DevBuf& out, bool* usable) {
+    *usable = true;
+    if (ds.ordered) { out.release(); return CR_OK; }
+    HIP_TRY(h, out.ensure((size_t)ds.n_entries * sizeof(ScreenEntry), entry_pad<ScreenEntry>()));
+    hipLaunchKernelGGL(screen_from_entries_kernel<float>, dim3((unsigned)((ds.n_entries + 255) / 256)), dim3(256), 0, h->stream, (const Entry<float>*)entries, (ScreenEntry*)out.p, ds.n_entries, (int32_t*)nullptr);
+    HIP_TRY(h, hipGetLastError());
+    return CR_OK;
+}
+
+// ---------------------------------------------------------------- cr_update_primitives (update.hpp)
+// Everything that can refuse the call, before anything changes.
+int32_t validate_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (n < 0) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: negative count");
+    if (n > 0 && !v) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: null values");
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_update_primitives before cr_upload_scene");
+    if (flags != CR_UPDATE_REFIT && flags != CR_UPDATE_REBUILD) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: unknown flags");
+    const int64_t n_desc = (int64_t)h->prims.size();
+    if (prim_index) {
+        for (int32_t k = 0; k < n; k++)
+            if (prim_index[k] < 0 || prim_index[k] >= n_desc) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: primitive index out of range");
+        std::vector<int32_t> sorted(prim_index, prim_index + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: a primitive is named twice");
+    } else if (n > n_desc) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: primitive index out of range");
+    auto finite = [](double x) { return x == x && x != HUGE_VAL && x != -HUGE_VAL; };
+    for (int32_t k = 0; k < n; k++) {
+        const CrPrimitive& p = h->prims[(size_t)(prim_index ? prim_index[k] : k)];
+        if (p.kind == CR_PRIM_LIST || p.kind == CR_PRIM_BVH) return fail(h, CR_ERR_INVALID_ARG, "cr_update_primitives: a list element has no coordinates to update");
+        const double* row = v + (size_t)k * 9;
+        const int nv = p.kind == CR_PRIM_SPHERE ? 4 : 9;
+        for (int j = 0; j < nv; j++) if (!finite(row[j])) return fail(h, CR_ERR_INVALID_ARG, "primitive coordinate is not finite");
+        if (p.kind == CR_PRIM_SPHERE && !(row[3] >= 0.0)) return fail(h, CR_ERR_INVALID_ARG, "Cannot make a sphere with negative radius");   // sphere.rs:26
+    }
+    // the construction-time box of a HitList / BVHWrapper element is not the union of its objects' boxes: a refit would not
+    // reproduce it
+    if (h->has_list_elements) return fail(h, CR_ERR_UNSUPPORTED, "cr_update_primitives: the scene holds a HitList or BVHWrapper element");
+    return CR_OK;
+}
+
+// CR_UPDATE_REFIT on one built precision: the staged rows into the primitive records, then the construction-time boxes of
+// every wrapper bottom-up, the screening records, and the host's copy of the tree.  The topology stays.
+template <typename real>
+static int32_t refit_updated(CrHandle* h, const int32_t* d_index, const double* d_rows, int32_t n) {
+    DevScene<real>& ds = dev_scene<real>(h);
+    if (!ds.built || ds.n_prims == 0) return CR_OK;
+    if (!ds.desc_pos_valid) return fail(h, CR_ERR_UNSUPPORTED, "cr_update_primitives: the scene holds a HitList or BVHWrapper element");
+    hipLaunchKernelGGL((update_prims_kernel<real>), dim3((unsigned)((n + kUpdateBlock - 1) / kUpdateBlock)), dim3(kUpdateBlock), 0, h->stream,
+                       (Prim<real>*)ds.prims.p, ds.n_prims, (const int32_t*)ds.desc_pos.p, (int32_t)h->prims.size(), d_index, d_rows, n);
+    HIP_TRY(h, hipGetLastError());
+    if (ds.n_entries == 0) return CR_OK;
+    int32_t rc = run_box_kernels<real>(h, ds, ds.entries.p, real(0), real(0), false);
+    if (rc != CR_OK) return rc;
+    rc = make_screen(h, ds, ds.entries.p, ds.screen, &ds.screen_usable);
+    if (rc != CR_OK) return rc;
+    if (ds.host_entries.size() != (size_t)ds.n_entries) return CR_OK;   // nothing to export (a scene with a BVHWrapper element; not reached)
+    if (!ds.ordered) {   // the device records are the host's, box for box and link for link
+        HIP_TRY(h, hipMemcpyAsync(ds.host_entries.data(), ds.entries.p, (size_t)ds.n_entries * sizeof(Entry<real>), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    } else {             // EntryO records: only their boxes go into the host's Entry records
+        std::vector<EntryO<real>> eo((size_t)ds.n_entries);
+        HIP_TRY(h, hipMemcpyAsync(eo.data(), ds.entries.p, eo.size() * sizeof(EntryO<real>), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < eo.size(); i++) for (int k = 0; k < 6; k++) ds.host_entries[i].b[k] = eo[i].b[k];
+    }
+    return CR_OK;
+}
+
+// After validate_update: the edit itself.
+int32_t apply_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
+    if (n == 0) return CR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const bool refit = flags == CR_UPDATE_REFIT && (h->s32.built || h->s64.built);
+    if (refit) {   // one staged buffer: the rows, then the indices; the stream orders the copy after earlier renders
+        const size_t row_bytes = (size_t)n * 9 * sizeof(double), idx_bytes = prim_index ? (size_t)n * sizeof(int32_t) : 0;
+        HIP_TRY(h, h->update_stage.ensure(row_bytes + idx_bytes));
+        HIP_TRY(h, hipMemcpyAsync(h->update_stage.p, v, row_bytes, hipMemcpyHostToDevice, h->stream));
+        if (prim_index) HIP_TRY(h, hipMemcpyAsync((char*)h->update_stage.p + row_bytes, prim_index, idx_bytes, hipMemcpyHostToDevice, h->stream));
+    } else HIP_TRY(h, hipStreamSynchronize(h->stream));   // a rebuild frees and refills what an earlier render may still read
+    for (int32_t k = 0; k < n; k++) {   // the host copy: what a rebuild, a precision not built yet and a hidden primitive see
+        CrPrimitive& p = h->prims[(size_t)(prim_index ? prim_index[k] : k)];
+        const int nv = p.kind == CR_PRIM_SPHERE ? 4 : 9;
+        for (int j = 0; j < nv; j++) p.v[j] = v[(size_t)k * 9 + j];
+    }
+    if (flags == CR_UPDATE_REBUILD) { h->s32.built = false; h->s64.built = false; return CR_OK; }
+    if (!refit) return CR_OK;
+    const double* d_rows = (const double*)h->update_stage.p;
+    const int32_t* d_index = prim_index ? (const int32_t*)((const char*)h->update_stage.p + (size_t)n * 9 * sizeof(double)) : nullptr;
+    int32_t rc = refit_updated<float>(h, d_index, d_rows, n);
+    if (rc == CR_OK) rc = refit_updated<double>(h, d_index, d_rows, n);
+    hipError_t e = hipStreamSynchronize(h->stream);   // the caller's arrays and the staged buffer are free from here on
+    if (e != hipSuccess && rc == CR_OK) { h->error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); rc = CR_ERR_HIP; }
+    return rc;
+}
+
+template int32_t run_box_kernels<float>(CrHandle*, DevScene<float>&, void*, float, float, bool);
+template int32_t run_box_kernels<double>(CrHandle*, DevScene<double>&, void*, double, double, bool);
+
+}   // namespace cr
+
+using namespace cr;
+
+extern "C" {
+
+int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!s) return fail(h, CR_ERR_INVALID_ARG, "scene is null");
+    if (s->n_prims < 0 || s->n_materials < 0 || s->n_textures < 0 || s->n_images < 0 || s->n_keys < 0)
+        return fail(h, CR_ERR_INVALID_ARG, "negative count");
+    if (s->n_prims >= (1 << 29)) return fail(h, CR_ERR_INVALID_ARG, "too many primitives");
+    if ((s->n_prims > 0 && !s->prims) || (s->n_materials > 0 && !s->materials) || (s->n_textures > 0 && !s->textures) ||
+        (s->n_images > 0 && !s->images) || (s->n_keys > 0 && !s->keys))
+        return fail(h, CR_ERR_INVALID_ARG, "a descriptor array is null although its count is not zero");
+    auto finite = [](double x) { return x == x && x != HUGE_VAL && x != -HUGE_VAL; };
+    for (int i = 0; i < s->n_textures; i++) {
+        const CrTexture& t = s->textures[i];
+        if (t.kind < CR_TEX_SOLID || t.kind > CR_TEX_IMAGE) return fail(h, CR_ERR_INVALID_ARG, "unknown texture kind");
+        // children before parents keeps the texture graph acyclic (Arc<Textures> cannot cycle either)
+        if (t.kind == CR_TEX_CHECKER && (t.even < 0 || t.even >= i || t.odd < 0 || t.odd >= i))
+            return fail(h, CR_ERR_INVALID_ARG, "checker sub-textures must have smaller indices");
+        if (t.kind == CR_TEX_IMAGE && (t.image < 0 || t.image >= s->n_images)) return fail(h, CR_ERR_INVALID_ARG, "texture image index out of range");
+        if (t.kind == CR_TEX_SOLID) for (int k = 0; k < 3; k++) if (!(t.color[k] >= 0.0 && t.color[k] <= 1.0))
+            return fail(h, CR_ERR_INVALID_ARG, "colour component outside [0,1]");   // Color::new, utils.rs:345-350
+    }
+    {   // the device resolves a checker chain iteratively with a bound of 32 levels (pathtrace.hpp, shade)
+        std::vector<int32_t> depth((size_t)s->n_textures, 0);
+        for (int i = 0; i < s->n_textures; i++) {
+            const CrTexture& t = s->textures[i];
+            if (t.kind != CR_TEX_CHECKER) continue;
+            depth[i] = 1 + std::max(depth[t.even], depth[t.odd]);
+            if (depth[i] > CR_MAX_CHECKER_DEPTH) return fail(h, CR_ERR_UNSUPPORTED, "checker textures nested deeper than CR_MAX_CHECKER_DEPTH (32)");
+        }
+    }
+    for (int i = 0; i < s->n_materials; i++) {
+        const CrMaterial& m = s->materials[i];
+        if (m.kind < CR_MAT_LAMBERTIAN || m.kind > CR_MAT_DIELECTRIC) return fail(h, CR_ERR_INVALID_ARG, "unknown material kind");
+        if (m.kind == CR_MAT_LAMBERTIAN && (m.texture < 0 || m.texture >= s->n_textures)) return fail(h, CR_ERR_INVALID_ARG, "material texture index out of range");
+        if (m.kind == CR_MAT_METAL) {
+            if (!(m.param <= 1.0)) return fail(h, CR_ERR_INVALID_ARG, "A metal cannot have a fuzz factor above 1.0");   // metal.rs:21
+            if (!(m.param >= 0.0)) return fail(h, CR_ERR_INVALID_ARG, "A metal cannot have a fuzz factor below 0.0");   // metal.rs:22
+            for (int k = 0; k < 3; k++) if (!(m.albedo[k] >= 0.0 && m.albedo[k] <= 1.0)) return fail(h, CR_ERR_INVALID_ARG, "colour component outside [0,1]");
+        }
+        if (!finite(m.param)) return fail(h, CR_ERR_INVALID_ARG, "material parameter is not finite");
+    }
+    for (int i = 0; i < s->n_keys; i++) {
+        const CrKeyframe& k = s->keys[i];
+        if (k.channel < CR_KEY_TX || k.channel > CR_KEY_SCALE_Z || (k.interp != CR_KEY_NERP && k.interp != CR_KEY_LERP))
+            return fail(h, CR_ERR_INVALID_ARG, "bad keyframe");
+    }
+    {   // lists (CR_PRIM_LIST): whole-number ranges of flagged spheres/triangles, every flagged primitive in exactly one
+        std::vector<char> owned((size_t)std::max(0, s->n_prims), 0);
+        for (int i = 0; i < s->n_prims; i++) {
+            const CrPrimitive& p = s->prims[i];
+            if (p.kind != CR_PRIM_LIST && p.kind != CR_PRIM_BVH) continue;
+            if (p.flags & (CR_PRIM_MEMBER | CR_PRIM_HIDDEN)) return fail(h, CR_ERR_INVALID_ARG, "a list is a scene element: it cannot be hidden or be an object of a list");
+            if (p.kind == CR_PRIM_BVH && (p.flags & CR_LIST_EMPTY_BOX)) return fail(h, CR_ERR_INVALID_ARG, "CR_LIST_EMPTY_BOX applies to lists");
+            const double first = p.v[0], count = p.v[1];
+            if (!(first >= 0.0 && count >= 0.0 && first == std::floor(first) && count == std::floor(count) && first + count <= (double)s->n_prims))
+                return fail(h, CR_ERR_INVALID_ARG, "list object range out of bounds");
+            for (int64_t k = (int64_t)first; k < (int64_t)(first + count); k++) {
+                const CrPrimitive& m = s->prims[k];
+                if ((m.kind != CR_PRIM_SPHERE && m.kind != CR_PRIM_TRIANGLE) || !(m.flags & CR_PRIM_MEMBER))
+                    return fail(h, CR_ERR_INVALID_ARG, "a list's objects must be spheres or triangles flagged CR_PRIM_MEMBER");
+                if (owned[(size_t)k]) return fail(h, CR_ERR_INVALID_ARG, "a primitive is an object of two lists");
+                owned[(size_t)k] = 1;
+            }
+        }
+        for (int i = 0; i < s->n_prims; i++)
+            if ((s->prims[i].flags & CR_PRIM_MEMBER) && !owned[(size_t)i]) return fail(h, CR_ERR_INVALID_ARG, "a primitive flagged CR_PRIM_MEMBER belongs to no list");
+    }
+    for (int i = 0; i < s->n_prims; i++) {
+        const CrPrimitive& p = s->prims[i];
+        if (p.kind == CR_PRIM_LIST || p.kind == CR_PRIM_BVH) continue;
+        if (p.kind != CR_PRIM_SPHERE && p.kind != CR_PRIM_TRIANGLE) return fail(h, CR_ERR_INVALID_ARG, "unknown primitive kind");
+        if (p.material < 0 || p.material >= s->n_materials) return fail(h, CR_ERR_INVALID_ARG, "primitive material index out of range");
+        if (p.key_count < 0 || p.key_first < 0 || p.key_first + p.key_count > s->n_keys) return fail(h, CR_ERR_INVALID_ARG, "primitive keyframe range out of bounds");
+        for (int k = 0; k < p.key_count; k++) {   // the Scene API type-checks scale keys (scene_animator.rs:38-183)
+            const int32_t ch = s->keys[p.key_first + k].channel;
+            if (p.kind == CR_PRIM_SPHERE && ch > CR_KEY_RADIUS) return fail(h, CR_ERR_INVALID_ARG, "ScaleX/ScaleY/ScaleZ cannot apply to Spheres");
+            if (p.kind == CR_PRIM_TRIANGLE && ch == CR_KEY_RADIUS) return fail(h, CR_ERR_INVALID_ARG, "ScaleR can only be applied to Spheres");
+        }
+        int nv = p.kind == CR_PRIM_SPHERE ? 4 : 9;
+        for (int k = 0; k < nv; k++) if (!finite(p.v[k])) return fail(h, CR_ERR_INVALID_ARG, "primitive coordinate is not finite");
+        if (p.kind == CR_PRIM_SPHERE && !(p.v[3] >= 0.0)) return fail(h, CR_ERR_INVALID_ARG, "Cannot make a sphere with negative radius");   // sphere.rs:26
+    }
+    if (s->sky_kind != CR_SKY_DEFAULT && s->sky_kind != CR_SKY_SPHERICAL) return fail(h, CR_ERR_INVALID_ARG, "unknown sky kind");
+    if (s->bvh_mode < CR_BVH_REFERENCE || s->bvh_mode > CR_BVH_LBVH) return fail(h, CR_ERR_INVALID_ARG, "unknown bvh_mode");
+    if (s->sky_kind == CR_SKY_SPHERICAL && (s->sky_image < 0 || s->sky_image >= s->n_images)) return fail(h, CR_ERR_INVALID_ARG, "sky image index out of range");
+    for (int i = 0; i < s->n_images; i++)
+        if (s->images[i].width < 1 || s->images[i].height < 1 || !s->images[i].rgb8) return fail(h, CR_ERR_INVALID_ARG, "bad image");
+
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    auto t_begin = std::chrono::steady_clock::now();
+    h->prims.assign(s->prims, s->prims + s->n_prims);
+    h->materials.assign(s->materials, s->materials + s->n_materials);
+    h->textures.assign(s->textures, s->textures + s->n_textures);
+    h->keys.assign(s->keys, s->keys + s->n_keys);
+    h->sky_kind = s->sky_kind; h->sky_image = s->sky_image; h->bvh_mode = s->bvh_mode;
+    h->s32.built = false; h->s64.built = false;
+    h->s32.side_tables = false; h->s64.side_tables = false;
+    h->has_list_elements = false;
+    for (const CrPrimitive& p : h->prims) h->has_list_elements |= p.kind == CR_PRIM_LIST || p.kind == CR_PRIM_BVH;
+    // images: RGB8 -> RGBA8 words, one flat texel array (pack.hpp)
+    std::vector<ImageRef> refs;
+    std::vector<uint32_t> texels;
+    if (!pack_images(s->images, s->n_images, refs, texels)) return fail(h, CR_ERR_INVALID_ARG, "too many texels");
+    HIP_TRY(h, h->images.ensure(refs.size() * sizeof(ImageRef) + 16));
+    HIP_TRY(h, h->texels.ensure(texels.size() * 4));
+    if (!refs.empty()) HIP_TRY(h, hipMemcpy(h->images.p, refs.data(), refs.size() * sizeof(ImageRef), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->texels.p, texels.data(), texels.size() * 4, hipMemcpyHostToDevice));
+    h->n_images = s->n_images;
+    h->has_scene = true;
+    h->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return CR_OK;
+}
+
+int32_t cr_update_primitives(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
+    int32_t rc = validate_update(h, prim_index, v, n, flags);
+    if (rc != CR_OK) return rc;
+    return apply_update(h, prim_index, v, n, flags);
+}
+
+}   // extern "C"

@@ -1,10 +1,10 @@
-"""Every megakernel variant render_typed (crucible_amd/csrc/capi.hip) can select, in both sum orders, bit for bit against
+"""Every megakernel variant render_typed (crucible_amd/csrc/render.hip) and its walk_ladder (render.hpp) can select, in both sum orders, bit for bit against
 the oracle in the same order: images and work counters.
 
 A kernel is pathtrace_kernel<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN> (or the 6-waves-per-SIMD entry point,
 LATENCY).  The handle's knobs pick RES / SCREEN / LATENCY (they are read in cr_create, so every cell makes a fresh
 Renderer), the scene picks ANIM / CAMK, CrRenderParams.sum_order picks RELAX and the tree mode picks ORD.  SELECTIONS
-below has one row per launch_variant call of render_typed (10 per tree order); CELLS crosses them with the scene kinds and
+below has one row per launch_variant selection of walk_ladder (10 per tree order); CELLS crosses them with the scene kinds and
 the two orders.  The relaxed ANIM / CAMK cells also render a 3-frame batch (cr_render_frames_host), each frame against
 the relaxed oracle."""
 import collections
