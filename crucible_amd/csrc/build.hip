@@ -148,6 +148,11 @@ template <typename real> struct SahBuilder {
         return 2.0 * (dx * dy + dy * dz + dz * dx);
     }
 
+    // Bin of t = (cen - clo) * (kBins / ext), clamped in floating point BEFORE the conversion: when ext is so small that
+    // kBins / ext overflows, t is inf, or 0 * inf = NaN for the centroid at clo, and converting either to int is undefined.
+    // t >= kBins (inf included) is the last bin, anything that is not >= 0 (NaN included) the first.
+    static int bin_of(double t) { return t >= (double)kBins ? kBins - 1 : (t >= 0.0 ? (int)t : 0); }
+
     void build_root(int32_t n) {
         nodes.assign((size_t)std::max(1, 2 * n), Node());
         next = 1;
@@ -186,8 +191,7 @@ template <typename real> struct SahBuilder {
             for (int32_t i = start; i < end; i++) {
                 const int32_t p = ord[i];
                 const double cen = 0.5 * ((double)bmin[a][p] + (double)bmax[a][p]);
-                int k = (int)((cen - clo[a]) * scale);
-                k = k < 0 ? 0 : (k >= kBins ? kBins - 1 : k);
+                const int k = bin_of((cen - clo[a]) * scale);
                 cnt[k]++;
                 for (int d = 0; d < 3; d++) { blo[k][d] = std::min(blo[k][d], (double)bmin[d][p]); bhi[k][d] = std::max(bhi[k][d], (double)bmax[d][p]); }
             }
@@ -219,9 +223,7 @@ template <typename real> struct SahBuilder {
             const double scale = (double)kBins / (chi[a] - clo[a]);
             auto it = std::stable_partition(ord.begin() + start, ord.begin() + end, [&](int32_t p) {
                 const double cen = 0.5 * ((double)bmin[a][p] + (double)bmax[a][p]);
-                int k = (int)((cen - clo[a]) * scale);
-                k = k < 0 ? 0 : (k >= kBins ? kBins - 1 : k);
-                return k <= best_plane;
+                return bin_of((cen - clo[a]) * scale) <= best_plane;
             });
             mid = (int32_t)(it - ord.begin());
         }

@@ -366,6 +366,53 @@ class ArrayScene(Scene):
         return self._flat
 
 
+def sah_spheres(centres, radii):
+    centres = np.asarray(centres, dtype=np.float64)
+    v = np.zeros((len(centres), 9))
+    v[:, 0:3] = centres
+    v[:, 3] = radii
+    return ArrayScene(np.zeros(len(centres), dtype=np.int32), v)
+
+
+# ---- binned-SAH trees worked out by hand (tests/test_sah_model_host.py, tests/test_gpu_sah_build.py): per scene its
+# maker, then children, split_axis (CR_BVH_SAH_ORDERED) and the winning plane of every wrapper in walk order.
+# Spheres of radius 1/4 on small dyadic coordinates: every box, centroid, area and cost below is exact in f32 and f64.
+# area of a run of j unit-spaced spheres along one axis: the box is (j - 1/2) x 1/2 x 1/2, area 2 j - 1/2.
+SAH_HAND = {
+    # ext 2, 16 / ext = 8: bins 0, 8, 16 -> 15.  {0}|{1,2} costs 1.5 + 2 * 3.5 = 8.5 at planes 0..7, {0,1}|{2} costs 8.5 at
+    # planes 8..14: the tie goes to plane 0.
+    "collinear3": (lambda: sah_spheres([[0, 0, 0], [1, 0, 0], [2, 0, 0]], 0.25),
+                   [[1, 2], [~0, ~0], [~1, ~2]], [0, -1, -1], [0, -1, -1]),
+    # x: {p0,p2}|{p1,p3} at every plane, z: {p0,p1}|{p2,p3}; either side is 1/2 x 1/2 x 3/2, area 3.5, cost 14: x wins
+    "square_xz": (lambda: sah_spheres([[0, 0, 0], [1, 0, 0], [0, 0, 1], [1, 0, 1]], 0.25),
+                  [[1, 2], [~0, ~2], [~1, ~3]], [0, -1, -1], [0, -1, -1]),
+    # bins 0, 4, 8, 12, 15.  1|4: 1.5 + 4 * 7.5 = 31.5; 2|3 (planes 4..7): 2 * 3.5 + 3 * 5.5 = 23.5; 3|2 (planes 8..11): 23.5;
+    # 4|1: 31.5.  The lower plane, 4: {0,1}|{2,3,4}; then {2,3,4} is collinear3 again.
+    "line5": (lambda: sah_spheres([[k, 0, 0] for k in range(5)], 0.25),
+              [[1, 2], [~0, ~1], [3, 4], [~2, ~2], [~3, ~4]], [0, -1, 0, -1, -1], [4, -1, 0, -1, -1]),
+    # one centre, radii 1/4 .. 1: no axis has an extent, mid = start + span // 2, split_axis 0
+    "one_centre3": (lambda: sah_spheres([[0.5, -1.25, 2.0]] * 3, [0.25, 0.5, 0.75]),
+                    [[1, 2], [~0, ~0], [~1, ~2]], [0, -1, -1], [-1, -1, -1]),
+    "one_centre4": (lambda: sah_spheres([[0.5, -1.25, 2.0]] * 4, [0.25, 0.5, 0.75, 1.0]),
+                    [[1, 2], [~0, ~1], [~2, ~3]], [0, -1, -1], [-1, -1, -1]),
+    # y = 0, 1.875, 2: t = 0, 15, 16.  The centroid at chi is clamped into bin 15 beside its neighbour: no plane parts them.
+    "at_chi": (lambda: sah_spheres([[0, 2.0, 0], [0, 0, 0], [0, 1.875, 0]], 0.25),
+               [[1, 2], [~1, ~1], [~0, ~2]], [1, -1, -1], [0, -1, -1]),
+}
+
+
+def subnormal_extent_scene():
+    """Six triangles flat along x, at x = 0 (thin in y) and x = 1e-310 (tall in y) alternately, all long in z with
+    centroids a unit apart.  In f64 the x extent of the centroids is 1e-310 and 16 / ext overflows: t = 0 * inf = NaN for
+    the first group (bin 0) and inf for the second (bin 15).  That split -- thin | tall -- is the cheapest, so the tree
+    rests on bin_index's two clamps.  In f32 both x are 0 and only z is a candidate."""
+    rows = []
+    for i in range(6):
+        x, h, z = (0.0, 1.0, float(i // 2)) if i % 2 == 0 else (1e-310, 5.0, float(i // 2))
+        rows.append([x, -h, z, x, h, z, x, -h, z + 10.0])
+    return ArrayScene(np.full(6, 1, dtype=np.int32), np.array(rows))
+
+
 # (real_type, tag, sum_order) cases of the bit-exact GPU suites: both precisions in the reference order (ids "f64" and
 # "f32", as the suites had them) and in CR_SUM_RELAXED, the library default ("f64-relaxed", "f32-relaxed"), each held to
 # the oracle in the same order.  Use as @pytest.mark.parametrize("rt,tag,order", REAL_ORDERS, ids=REAL_ORDER_IDS).

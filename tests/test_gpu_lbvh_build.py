@@ -308,8 +308,9 @@ def test_export_order_and_rebuilds(renderer):
 @pytest.mark.parametrize("mode", [A.CR_BVH_SAH, A.CR_BVH_SAH_ORDERED], ids=["sah", "ordered"])
 @pytest.mark.parametrize("name", ["mixed", "book1", "mixed_scene", "teapot", "moving"])
 def test_sah_boxes_are_the_unions_of_their_primitives(renderer, name, mode, rt, real):
-    """The topology of CR_BVH_SAH / _ORDERED is a host builder's, pinned by its node-test bar; the boxes it exports are
-    recomputed here from its own `children`: every wrapper's box is the union of its primitives' boxes in the real type."""
+    """The topology of CR_BVH_SAH / _ORDERED is a host builder's, pinned wrapper for wrapper by its own model
+    (tests/sah_model.py, tests/test_gpu_sah_build.py); independently of that model, the boxes it exports are recomputed
+    here from its own `children`: every wrapper's box is the union of its primitives' boxes in the real type."""
     sc = SCENES[name]()
     flat, (boxes, kids, axis) = export(renderer, sc, mode, rt)
     recs = M.prim_records(flat)
