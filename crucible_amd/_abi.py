@@ -16,6 +16,10 @@ CR_MAX_CHECKER_DEPTH = 32
 CR_KEY_NERP, CR_KEY_LERP = 0, 1
 CR_SUM_DEFAULT, CR_SUM_REFERENCE_ORDER, CR_SUM_RELAXED = 0, 1, 2
 CR_UPDATE_REFIT, CR_UPDATE_REBUILD = 0, 1   # cr_update_primitives flags
+CR_AOV_ALBEDO, CR_AOV_NORMAL, CR_AOV_DEPTH, CR_AOV_COVERAGE = 1, 2, 4, 8   # cr_render_aov_* layers
+CR_AOV_ALL = 15
+# the planes of a guide-layer buffer in their order (ascending bit): name, bit, channels
+AOV_LAYERS = (("albedo", CR_AOV_ALBEDO, 3), ("normal", CR_AOV_NORMAL, 3), ("depth", CR_AOV_DEPTH, 1), ("coverage", CR_AOV_COVERAGE, 1))
 CR_OUTPUT_FIXED_SUM = 2   # CrRenderParams.output_sum: 0 mean, 1 sum in reals, 2 fixed-point words (uint64)
 
 
@@ -93,6 +97,10 @@ SYMBOLS = {
                                             C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_frames_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
                                           C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32, C.c_void_p,
+                                         C.POINTER(CrStats)]),
+    "cr_render_aov_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32, C.c_void_p,
+                                       C.POINTER(CrStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
     "cr_update_primitives": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]),
@@ -102,6 +110,7 @@ SYMBOLS = {
     "cr_write_ppm": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "cr_write_ppm_binary": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "cr_write_png": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "cr_write_pfm": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "cr_quantize_rgb8": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "cr_fixed_sums_to_rgb": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "cr_last_error": (C.c_char_p, [C.c_void_p]),

@@ -1,0 +1,92 @@
+// aov.hip -- the guide pass behind cr_render_aov_*: first-hit albedo, normal, depth and coverage per pixel (aov.hpp has the
+// accumulator layout, include/crucible_hip.h the definition of every layer).  aov_typed sets a launch up through the
+// render's own prepare_args (camera-key slot, ray times, refitted boxes, screening records: render.hip), runs the first-hit
+// kernel of the scene's residency (aov_f32.hip / aov_f64.hip) and turns the accumulators into the requested planes.
+#include "aov.hpp"
+
+namespace cr {
+
+// The accumulators of pixel i into the planes that were asked for, in ascending bit order.  A sum becomes a real as
+// fx_finalize_kernel turns a relaxed sum into one -- the word's magnitude in two exact halves, one rounding in their add,
+// times 2^-S, divided by the frame's sample count unless the shard's sum is asked for -- with the word's sign put back;
+// a flagged channel is NaN.  Depth: the complement of the largest word, +inf where no sample hit.
+template <typename real>
+__global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long long* acc, const uint32_t* flags, real* out, size_t npix, int32_t layers,
+                                                           double inv_scale, double count, int32_t output_sum) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const unsigned long long* w = acc + i * kAovWords;
+    const uint32_t bad = flags[i];
+    auto value = [&](uint32_t c) -> real {
+        const long long v = (long long)w[c];
+        const unsigned long long m = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+        double s = ((double)(uint32_t)(m >> 32) * 4294967296.0 + (double)(uint32_t)m) * inv_scale;
+        if (!output_sum) s = s / count;
+        if (v < 0) s = -s;
+        if ((bad >> c) & 1u) s = __builtin_nan("");
+        return (real)s;
+    };
+    real* o = out;
+    if (layers & CR_AOV_ALBEDO) { for (uint32_t c = 0; c < 3; c++) o[i * 3 + c] = value(c); o += npix * 3; }
+    if (layers & CR_AOV_NORMAL) { for (uint32_t c = 0; c < 3; c++) o[i * 3 + c] = value(3 + c); o += npix * 3; }
+    if (layers & CR_AOV_DEPTH) {
+        const unsigned long long d = w[kAovDepth];
+        real r = r_inf(real(0));
+        if (d) {
+            if constexpr (sizeof(real) == 8) r = __builtin_bit_cast(double, ~d);
+            else r = __builtin_bit_cast(float, (uint32_t)~d);
+        }
+        o[i] = r;
+        o += npix;
+    }
+    if (layers & CR_AOV_COVERAGE) o[i] = value(kAovCoverage);
+}
+
+template <typename real>
+int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats) {
+    int32_t rc = build_dev_scene<real>(h);
+    if (rc != CR_OK) return rc;
+    DevScene<real>& ds = dev_scene<real>(h);
+    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;   // as a render decides it
+    const size_t npix = (size_t)cd->image_width * (size_t)cd->image_height;
+    hipError_t e = h->aov_acc.ensure(npix * kAovWords * sizeof(unsigned long long));
+    if (e == hipSuccess) e = h->aov_flags.ensure(npix * sizeof(uint32_t));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("guide accumulators: ") + hipGetErrorString(e)); }
+    AovArgs<real> a;
+    memset(&a, 0, sizeof a);
+    WalkChoice w;
+    int res = 0;
+    if (p->sample_count > 0) {   // (an empty shard: no kernel, sums of nothing and no hit)
+        FrameBatch<real> fb;
+        std::vector<real> times;
+        // the walk is the megakernel's under every pipeline setting: the cross-check pipelines have no guide pass of their own
+        rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, nullptr, 1, times, a.k, w, fb);
+        if (rc != CR_OK) return rc;
+        a.k.tiles_x = ((uint32_t)cd->image_width + 3u) >> 2; a.k.tiles_y = ((uint32_t)cd->image_height + 3u) >> 2;
+        a.k.fx_scale = fx_scale_for(p->samples);   // of the whole frame, so that the words of shards add up
+        a.acc = (unsigned long long*)h->aov_acc.p; a.flags = (uint32_t*)h->aov_flags.p;
+        a.layers = layers;
+        a.groups = ((uint32_t)p->sample_count + 3u) >> 2;
+        const size_t need = aov_lds_bytes(MaxBlock<real>::value);   // the waves' slots share the LDS
+        w.screen_lds = w.screen && h->screen_lds && w.lds_all_screen + need <= h->lds_limit;
+        w.plain_lds = ds.lds_bytes + need <= h->lds_limit;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->aov_acc.p, 0, npix * kAovWords * sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->aov_flags.p, 0, npix * sizeof(uint32_t), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    if (p->sample_count > 0) {
+        rc = aov_ladder<real>(h, a, ds, w, &res);
+        if (rc != CR_OK) return rc;
+    }
+    hipLaunchKernelGGL((aov_finalize_kernel<real>), dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (const unsigned long long*)h->aov_acc.p,
+                       (const uint32_t*)h->aov_flags.p, (real*)d_out, npix, layers, 1.0 / fx_scale_for(p->samples), (double)p->samples, p->output_sum);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    return stats ? finish_stats(h, stats, (uint64_t)npix * (uint64_t)p->sample_count, ds.n_entries, res) : CR_OK;
+}
+
+template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*);
+template int32_t aov_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*);
+
+}   // namespace cr

@@ -1,0 +1,41 @@
+// aov.hpp -- the guide pass (cr_render_aov_*): first-hit albedo, normal, depth and coverage per pixel.  What its units
+// share: the kernel's arguments, the accumulator layout and the entry into the kernels' residency ladder.  The kernels
+// themselves are in aov_kernel.hpp (aov_f32.hip and aov_f64.hip emit them), the host side and the finalize kernel in aov.hip.
+//
+// A work item is one (pixel, sample): 64 consecutive items are a 4 x 4 pixel tile times 4 consecutive samples, one wave's
+// round.  A wave takes a UNIT from the launch's work counter -- `unit_groups` consecutive sample groups of one tile --, adds
+// the rounds' values into its LDS slot (16 pixels x 8 words) and sends the slot's non-zero words to the global
+// accumulators once per unit.  Per pixel the accumulators are kAovWords 64-bit words:
+//   0..2 albedo, 3..5 encoded normal, 6 coverage: sums of rint(x * 2^S) as signed integers (two's complement adds);
+//   7 depth: the maximum of ~bits(depth) over the samples that hit, 0 = none did -- positive reals order as their bit
+//     patterns, so this is the minimum depth, and a zeroed buffer is the empty state of every word.
+// A value that is not finite (or too large for a word) sets the channel's bit in the pixel's flag word instead.
+#pragma once
+#include "handle.hpp"
+
+namespace cr {
+
+constexpr uint32_t kAovWords = 8, kAovDepth = 7, kAovCoverage = 6;
+constexpr uint32_t kAovTileLog2 = 4;                                            // 4 x 4 pixels
+constexpr uint32_t kAovSlotWords = kAovWords << kAovTileLog2;                   // one wave's LDS slot
+constexpr size_t aov_lds_bytes(int block) { return (size_t)(block / 64) * kAovSlotWords * sizeof(unsigned long long); }
+
+template <typename real> struct AovArgs {
+    KernelArgs<real> k;             // what the walk, the camera and the texture code read (prepare_args, render.hip)
+    unsigned long long* acc;        // [H * W * kAovWords], zeroed before the launch
+    uint32_t* flags;                // [H * W]: bit c set = channel c (0..5) met a value that is not finite
+    int32_t layers;                 // CR_AOV_* mask: layers that were not asked for are not computed
+    uint32_t groups;                // sample groups (of 4) that cover [sample_begin, sample_end)
+    uint32_t unit_groups;           // groups per unit
+    uint32_t unit_chunks;           // units per tile
+    uint32_t n_units;
+    uint32_t acc_lds_off;           // byte offset of the waves' slots in LDS (behind the staged scene)
+};
+
+// aov_f32.hip, aov_f64.hip: the residency ladder of the guide kernels (the render's own choices, render.hpp walk_ladder:
+// the whole scene in LDS, the top window, global memory; screening records where the render walks on them).  The trace
+// kernel is launched on the handle's stream; *res receives the residency (CrStats.scene_in_lds).
+template <typename real>
+int32_t aov_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res);
+
+}   // namespace cr

@@ -1,0 +1,314 @@
+// aov_kernel.hpp -- the guide pass's first-hit kernels for gfx950 and their launch: made of the megakernel's parts
+// (pathtrace.hpp: camera_ray, walk_begin / walk_round, CR_CHECKER_LEAF, image_lookup, shade's sky) around a much
+// smaller body -- a primary ray per work item, its closest hit, four values, no path state.  Included by aov_f32.hip
+// and aov_f64.hip only, each of which instantiates aov_ladder for its precision, so no kernel is emitted twice.
+#pragma once
+#include "aov.hpp"
+
+#include <type_traits>
+
+namespace cr {
+
+#if defined(__HIPCC__)
+
+// rint(x * 2^S) as a signed word (x * 2^S is exact: a power of two scales); false for a value that is not finite or
+// whose word would not leave room for a sum
+CR_D bool aov_word(double x, double scale, long long& v) {
+    const double y = __builtin_rint(x * scale);
+    if (!(__builtin_fabs(y) < 0x1.0p62)) return false;
+    v = (long long)y;
+    return true;
+}
+
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+CR_D void aov_body(const AovArgs<real>& G) {
+    using EntryT = typename EntryOf<real, ORD>::type;
+    const KernelArgs<real>& A = G.k;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Entry<real>* lds_entries = nullptr;
+    const void* lds_screen = nullptr;
+    const Prim<real>* prims = A.prims;
+    const Mat<real>* mats = A.mats;
+    const Tex<real>* texs = A.texs;
+    if (RES != RES_GLOBAL) {   // the scene's LDS copy, laid out as pathtrace_body lays it out (the walk's fetches expect that)
+        auto copy = [&](const void* src, size_t off, size_t bytes) {
+            const uint32_t* s = (const uint32_t*)src;
+            uint32_t* d = (uint32_t*)(smem + off);
+            for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) d[i] = s[i];
+        };
+        using ScreenT = typename ScreenOf<ORD>::type;
+        constexpr size_t window_rec = SCREEN ? sizeof(ScreenT) : sizeof(EntryT);
+        copy(SCREEN ? A.screen : (const void*)A.entries, 0, (size_t)A.lds_entries * window_rec);
+        lds_entries = (const Entry<real>*)smem;
+        if (SCREEN) lds_screen = (const void*)smem;
+        if (RES == RES_LDS) {   // entries | prims | mats | texs, each 16-B aligned
+            size_t o1 = (((size_t)A.n_entries * window_rec + 15) & ~(size_t)15);
+            size_t o2 = o1 + (((size_t)A.n_prims * sizeof(Prim<real>) + 15) & ~(size_t)15);
+            size_t o3 = o2 + (((size_t)A.n_mats * sizeof(Mat<real>) + 15) & ~(size_t)15);
+            copy(A.prims, o1, (size_t)A.n_prims * sizeof(Prim<real>));
+            copy(A.mats, o2, (size_t)A.n_mats * sizeof(Mat<real>));
+            copy(A.texs, o3, (size_t)A.n_texs * sizeof(Tex<real>));
+            prims = (const Prim<real>*)(smem + o1);
+            mats = (const Mat<real>*)(smem + o2);
+            texs = (const Tex<real>*)(smem + o3);
+            if constexpr (SCREEN) {   // links of the staged screening records become LDS addresses (fetch_screen)
+                __syncthreads();
+                const uint32_t base = screen_lds_base<RES>(smem);
+                ScreenT* rec = (ScreenT*)smem;
+                for (int32_t i = (int32_t)threadIdx.x; i < A.n_entries; i += (int32_t)blockDim.x) {
+                    if constexpr (ORD) { for (int k = 0; k < 8; k++) rec[i].skip[k] += base; }
+                    else rec[i].skip += base;
+                    if (!(rec[i].hit & kScreenLeaf)) rec[i].hit += base;
+                }
+            }
+        } else if (A.lds_side) {   // RES_TOP: entry window | mats | texs
+            size_t o2 = (((size_t)A.lds_entries * window_rec + 15) & ~(size_t)15);
+            size_t o3 = o2 + (((size_t)A.n_mats * sizeof(Mat<real>) + 15) & ~(size_t)15);
+            copy(A.mats, o2, (size_t)A.n_mats * sizeof(Mat<real>));
+            copy(A.texs, o3, (size_t)A.n_texs * sizeof(Tex<real>));
+            mats = (const Mat<real>*)(smem + o2);
+            texs = (const Tex<real>*)(smem + o3);
+        }
+        __syncthreads();
+    }
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const CamConst<real>& cam = A.cam;
+    const int32_t n_entries = A.n_entries;
+    // this wave's slot: the words of one tile, emptied by every flush
+    unsigned long long* slot = (unsigned long long*)(smem + G.acc_lds_off) + (size_t)(threadIdx.x >> 6) * kAovSlotWords;
+    for (uint32_t k = lane; k < kAovSlotWords; k += 64) slot[k] = 0ull;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    auto slot_word = [&](uint32_t k) { return (__attribute__((address_space(3))) unsigned long long*)(slot + k); };
+
+    uint32_t c_seg = 0, c_prim = 0, c_tex = 0;
+    unsigned long long c_node = 0;
+    const bool want_albedo = (G.layers & CR_AOV_ALBEDO) != 0, want_normal = (G.layers & CR_AOV_NORMAL) != 0;
+    const bool want_depth = (G.layers & CR_AOV_DEPTH) != 0, want_cover = (G.layers & CR_AOV_COVERAGE) != 0;
+    const double fxs = A.fx_scale;
+
+    for (;;) {
+        uint32_t wu = 0;
+        if (lane == 0) wu = atomicAdd(A.work_counter, 1u);
+        wu = (uint32_t)__builtin_amdgcn_readfirstlane((int)wu);
+        if (wu >= G.n_units) break;
+        const uint32_t tile = wu / G.unit_chunks, chunk = wu - tile * G.unit_chunks;
+        const uint32_t g0 = chunk * G.unit_groups, g1 = g0 + G.unit_groups < G.groups ? g0 + G.unit_groups : G.groups;
+        const uint32_t px = lane & 15u;
+        const uint32_t pix_i = ((tile % A.tiles_x) << 2) + (px & 3u), pix_j = ((tile / A.tiles_x) << 2) + (px >> 2);
+        const bool in_image = pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H;
+        for (uint32_t g = g0; g < g1; g++) {
+            const int32_t sample = A.sample_begin + (int32_t)(g * 4u + (lane >> 4));
+            const bool active = in_image && sample < A.sample_end;   // else: padding of an edge tile or of the last group
+            V3<real> ro = mk<real>(0, 0, 0), rd = mk<real>(0, 0, 1);
+            real rtime = 0;
+            uint64_t rng = 0;
+            WalkState<real> ws;
+            ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.best_t = 0; ws.best = -1; ws.idx = n_entries; ws.exact_box = false; ws.oct = 0; ws.pending = -1;
+            bool walking = false;
+            if (active) {   // cast_ray's primary ray (the keyed camera is a per-launch, wave-uniform branch of camera_ray)
+                camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
+                c_seg++;
+                walk_begin(ws, rd);
+                walking = n_entries > 0;
+            }
+            // Hittables::hit on (0.001, inf): rounds of the walk until every lane has its closest hit
+            while (__ballot(walking)) {
+                walk_round<real, RES, ANIM, ORD, SCREEN>(A, lds_entries, prims, ro, rd, rtime, ws, walking, A.walk_round_steps, c_node, c_prim, nullptr, lds_screen);
+                if (walking && ws.idx >= n_entries && ws.pending < 0) walking = false;
+            }
+            if (active) {
+            V3<real> alb = mk<real>(0, 0, 0), n = mk<real>(0, 0, 0);
+            real depth = r_inf(real(0));
+            const bool hit = ws.best >= 0;
+            if (hit) {
+                const Prim<real>& p = prims[ws.best];
+                const V3<real> loc = add(ro, scale(ws.best_t, rd));   // Ray::at
+                if (want_depth) depth = r_sqrt(len2(sub(loc, ro)));
+                if (want_albedo || want_normal) {
+                    auto mat_at = [&](int32_t i) { return RES == RES_TOP ? load_rec(mats + i, A.lds_side != 0) : mats[i]; };
+                    auto tex_at = [&](int32_t i) { return RES == RES_TOP ? load_rec(texs + i, A.lds_side != 0) : texs[i]; };
+                    const Mat<real> m = mat_at(p.mat());
+                    bool need_uv = false;
+                    int32_t leaf_tex = -1;
+                    if (want_albedo && m.kind == 0 && m.tex >= 0) {   // only image textures read u,v
+                        int ti = m.tex;
+                        Tex<real> tx = tex_at(ti);
+                        CR_CHECKER_LEAF(tex_at, ti, tx, loc)
+                        need_uv = tx.kind == 2;
+                        leaf_tex = ti;
+                    }
+                    // the HitRecord's normal and u, v, as shade() forms them
+                    real tu = 0, tv = 0;
+                    if (p.kind() == 0) {
+                        real g0s = p.g[0], g1s = p.g[1], g2s = p.g[2], g3s = p.g[3];
+                        if (ANIM && p.key_count) {
+                            timeline_eval(A.keys + p.key_first, p.key_count, rtime, g0s, g1s, g2s, g3s);
+                            n = divs(sub(loc, mk<real>(g0s, g1s, g2s)), g3s);   // sphere.rs:97
+                        } else n = scale(p.g[4], sub(loc, mk<real>(g0s, g1s, g2s)));   // p.g[4] = 1/radius
+                        if (need_uv) {                                  // get_sphere_uv, sphere.rs:41-46
+                            real theta = r_acos(-n.y);
+                            real phi = r_atan2(-n.z, n.x) + RealTraits<real>::pi;
+                            tu = phi / (real(2) * RealTraits<real>::pi);
+                            tv = theta / RealTraits<real>::pi;
+                        }
+                    } else {
+                        V3<real> a = mk<real>(p.g[0], p.g[1], p.g[2]), b = mk<real>(p.g[3], p.g[4], p.g[5]), c = mk<real>(p.g[6], p.g[7], p.g[8]);
+                        if (ANIM && p.key_count) {
+                            a = timeline_vertex(A.keys + p.key_first, p.key_count, rtime, a);
+                            b = timeline_vertex(A.keys + p.key_first, p.key_count, rtime, b);
+                            c = timeline_vertex(A.keys + p.key_first, p.key_count, rtime, c);
+                        }
+                        n = unit(cross(sub(b, a), sub(c, a)));          // safe_new, objects/mod.rs:76
+                    }
+                    if (!(dot(rd, n) < real(0))) n = neg(n);            // HitRecord::new
+                    if (want_albedo) {
+                        if (m.kind == 0) {                              // Lambertian: tex.value(u, v, position)
+                            if (m.tex < 0) alb = mk<real>(m.albedo[0], m.albedo[1], m.albedo[2]);
+                            else {
+                                const Tex<real> lt = tex_at(leaf_tex);
+                                if (need_uv) alb = image_lookup(A.images, A.texels, lt.image, tu, tv, c_tex);
+                                else alb = mk<real>(lt.color[0], lt.color[1], lt.color[2]);
+                            }
+                        } else if (m.kind == 1) alb = mk<real>(m.albedo[0], m.albedo[1], m.albedo[2]);
+                        else alb = mk<real>(1, 1, 1);
+                    }
+                }
+            } else if (want_albedo) {   // the sky ray_color returns for this ray: shade()'s miss branch with a unit throughput
+                int32_t depth_left = 1, stack_n = 0;
+                V3<real> thr = mk<real>(1, 1, 1);
+                (void)shade<real, false, RES == RES_TOP, true>(A, prims, mats, texs, ro, rd, rtime, rng, depth_left, stack_n, ws.best_t, -1, 0u, 0u, c_tex, alb,
+                                                               nullptr, &thr);
+            }
+            const real half = real(0.5);
+            const real vals[7] = {alb.x, alb.y, alb.z, half * n.x + half, half * n.y + half, half * n.z + half, hit ? real(1) : real(0)};
+            const bool want[7] = {want_albedo, want_albedo, want_albedo, want_normal, want_normal, want_normal, want_cover};
+            uint32_t bad = 0;
+#pragma unroll
+            for (uint32_t c = 0; c < 7; c++) {
+                if (!want[c]) continue;
+                long long v = 0;
+                if (!aov_word((double)vals[c], fxs, v)) bad |= 1u << c;
+                else if (v) (void)__hip_atomic_fetch_add(slot_word(px * kAovWords + c), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            if (bad) atomicOr(G.flags + ((size_t)pix_j * (size_t)cam.W + pix_i), bad);
+            if (want_depth && hit) {
+                unsigned long long bits, inf_bits;
+                if constexpr (std::is_same<real, double>::value) { bits = __builtin_bit_cast(unsigned long long, depth); inf_bits = 0x7ff0000000000000ull; }
+                else { bits = (unsigned long long)__builtin_bit_cast(uint32_t, depth); inf_bits = 0x7f800000ull; }
+                if (bits < inf_bits)   // (a NaN's pattern lies above +inf's: the minimum over bit patterns never picks it)
+                    (void)__hip_atomic_fetch_max(slot_word(px * kAovWords + kAovDepth), ~bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            }   // active
+        }
+        // the unit's words into the global accumulators
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (uint32_t k = lane; k < kAovSlotWords; k += 64) {
+            const unsigned long long v = slot[k];
+            if (v) {   // (only pixels inside the image ever add)
+                slot[k] = 0ull;
+                const uint32_t q = k / kAovWords, ch = k - q * kAovWords;
+                const uint32_t pi = ((tile % A.tiles_x) << 2) + (q & 3u), pj = ((tile / A.tiles_x) << 2) + (q >> 2);
+                auto g = (__attribute__((address_space(1))) unsigned long long*)(G.acc + ((size_t)pj * (size_t)cam.W + pi) * kAovWords + ch);
+                if (ch == kAovDepth) (void)__hip_atomic_fetch_max(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else (void)__hip_atomic_fetch_add(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+
+    // work counters: one atomic per counter per wave
+    auto wave_sum = [&](unsigned long long v) -> unsigned long long {
+        unsigned long long s = v;
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+        return s;
+    };
+    const unsigned long long s0 = wave_sum(c_seg), s1 = wave_sum(c_node), s2 = wave_sum(c_prim), s3 = wave_sum(c_tex);
+    if (lane == 0) {
+        atomicAdd((unsigned long long*)&A.counters[0], s0);
+        atomicAdd((unsigned long long*)&A.counters[1], s1);
+        atomicAdd((unsigned long long*)&A.counters[2], s2);
+        atomicAdd((unsigned long long*)&A.counters[3], s3);
+    }
+}
+
+// (the arguments are read through the kernarg segment where they are used, as pathtrace_kernel reads its own)
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+__global__ void __launch_bounds__(MaxBlock<real>::value) aov_kernel(const AovArgs<real> G) {
+    aov_body<real, RES, ANIM, ORD, SCREEN>(*(const AovArgs<real>*)(const __attribute__((address_space(4))) AovArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
+#endif   // __HIPCC__
+
+// One launch: persistent workgroups (one LDS copy of the scene each), the waves' slots behind the scene, units handed
+// out by the work counter -- about eight per resident wave, so that the tail is short and a unit still flushes rarely.
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* res) {
+    void (*kern)(const AovArgs<real>) = aov_kernel<real, RES, ANIM, ORD, SCREEN>;
+    const int max_block = MaxBlock<real>::value;
+    const size_t off = RES != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
+    a.acc_lds_off = (uint32_t)off;
+    HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(off + aov_lds_bytes(max_block))));
+    int block = 256, per_cu = 1;
+    { int32_t rc = pick_block(h, (const void*)kern, max_block, true, off, aov_lds_bytes(64), "guide kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
+    const uint64_t tiles = (uint64_t)a.k.tiles_x * a.k.tiles_y;
+    const uint64_t resident = (uint64_t)h->n_cus * per_cu * (block / 64);
+    uint64_t ug = std::min<uint64_t>(a.groups, std::max<uint64_t>(1, tiles * a.groups / (8 * resident)));
+    const uint64_t max_units = 0xF0000000ull;   // the 32-bit work counter
+    if (tiles * ((a.groups + ug - 1) / ug) > max_units) ug = (a.groups + max_units / tiles - 1) / (max_units / tiles);
+    a.unit_groups = (uint32_t)ug;
+    a.unit_chunks = (uint32_t)((a.groups + ug - 1) / ug);
+    a.n_units = (uint32_t)(tiles * a.unit_chunks);
+    uint32_t grid = (uint32_t)(h->n_cus * per_cu);
+    const uint64_t need_blocks = ((uint64_t)a.n_units + (block / 64) - 1) / (block / 64);
+    if ((uint64_t)grid > need_blocks) grid = (uint32_t)need_blocks;
+    if (grid < 1) grid = 1;
+    HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), off + aov_lds_bytes(block), h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    h->last_block = block; h->last_grid = (int)grid;
+    *res = RES;
+    return CR_OK;
+}
+
+// keyed primitives and leaves that hold a list walk with the ANIM decode (render.hip); a keyed camera needs no kernel of its own here
+template <typename real, int RES, bool ORD, bool SCREEN>
+int32_t aov_variant(CrHandle* h, AovArgs<real>& a, size_t lds_bytes, const WalkChoice& w, int* res) {
+    return w.anim ? aov_launch<real, RES, true, ORD, SCREEN>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN>(h, a, lds_bytes, res);
+}
+
+// walk_ladder's choices (render.hpp) for the guide kernels; the 6-waves-per-SIMD entry point has no counterpart here
+template <typename real, bool ORD>
+int32_t aov_ladder_ord(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
+    constexpr bool f32 = std::is_same<real, float>::value;
+    constexpr bool can_screen = !(ORD && f32);   // an ordered f32 tree has no screening records
+    KernelArgs<real>& k = a.k;
+    if (ds.n_entries > 0 && (w.plain_lds || w.screen_lds)) {
+        k.lds_entries = ds.n_entries;
+        if constexpr (can_screen) if (w.screen_lds) return aov_variant<real, RES_LDS, ORD, true>(h, a, w.lds_all_screen, w, res);
+        k.screen = nullptr;
+        return aov_variant<real, RES_LDS, ORD, false>(h, a, ds.lds_bytes, w, res);
+    }
+    const size_t window_rec = w.screen ? sizeof(std::conditional_t<ORD, ScreenEntryO, ScreenEntry>) : sizeof(typename EntryOf<real, ORD>::type);
+    const int32_t top = (int32_t)std::min<size_t>((size_t)ds.n_entries, h->lds_top_bytes / window_rec);
+    if (top > 0) {
+        k.lds_entries = top;
+        size_t bytes = (size_t)top * window_rec;
+        if constexpr (!ORD) {
+            const size_t side = r16((size_t)ds.n_mats * sizeof(Mat<real>)) + r16((size_t)ds.n_texs * sizeof(Tex<real>));
+            if (side <= h->lds_side_limit) { k.lds_side = 1; bytes = r16(bytes) + side; }
+        }
+        if constexpr (can_screen) if (w.screen) return aov_variant<real, RES_TOP, ORD, true>(h, a, bytes, w, res);
+        return aov_variant<real, RES_TOP, ORD, false>(h, a, bytes, w, res);
+    }
+    k.lds_entries = 0;
+    if constexpr (can_screen) if (w.screen) return aov_variant<real, RES_GLOBAL, ORD, true>(h, a, 0, w, res);
+    return aov_variant<real, RES_GLOBAL, ORD, false>(h, a, 0, w, res);
+}
+
+template <typename real>
+int32_t aov_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
+    return ds.ordered ? aov_ladder_ord<real, true>(h, a, ds, w, res) : aov_ladder_ord<real, false>(h, a, ds, w, res);
+}
+
+}   // namespace cr

@@ -1,5 +1,5 @@
 // api.hip -- the handle's life and the render entry points of include/crucible_hip.h: cr_create reads the CRUCIBLE_*
-// knobs, cr_render_* validate and hand over to render_typed (render.hip); the error strings behind cr_last_error.
+// knobs, cr_render_* validate and hand over to render_typed (render.hip) or aov_typed (aov.hip); the error strings behind cr_last_error.
 //
 // Nothing here falls back to a CPU renderer: without a HIP device cr_create fails.
 #include "handle.hpp"
@@ -44,12 +44,15 @@ int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
 }
 
 // cr_render_device / cr_render_frames_device after their own argument checks (frames == nullptr: params->frame)
+// layers != 0: the guide pass of cr_render_aov_* instead of the render
 static int32_t render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats,
-                      const int32_t* frames, int32_t n_frames) {
+                      const int32_t* frames, int32_t n_frames, int32_t layers = 0) {
     HIP_TRY(h, hipSetDevice(h->device));
     h->cam_pending_slot = -1;
-    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames)
-                                             : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames);
+    int32_t rc;
+    if (layers) rc = p->real_type == CR_REAL_F64 ? aov_typed<double>(h, cam, p, layers, d_out, stats) : aov_typed<float>(h, cam, p, layers, d_out, stats);
+    else rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames)
+                                          : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames);
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
         hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
         h->cam_pending_slot = -1;
@@ -111,7 +114,28 @@ static int32_t render_entry(CrHandle* h, const CrCameraDesc* cam, const CrRender
     if (batch && !frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
     if (batch && n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
     if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
-    return (host ? render_host : render_device)(h, cam, p, out, stats, frames, n_frames);
+    return host ? render_host(h, cam, p, out, stats, frames, n_frames) : render_device(h, cam, p, out, stats, frames, n_frames);
+}
+
+// cr_render_aov_*: a render's argument checks, then the pass's own; the host form goes through the handle's output buffer
+static int32_t aov_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, bool host, void* out, CrStats* stats) {
+    int32_t rc = validate_render(h, cam, p);
+    if (rc != CR_OK) return rc;
+    const int32_t all = CR_AOV_ALBEDO | CR_AOV_NORMAL | CR_AOV_DEPTH | CR_AOV_COVERAGE;
+    if (layers == 0 || (layers & ~all)) return fail(h, CR_ERR_INVALID_ARG, "layers must be a non-empty mask of CR_AOV_*");
+    if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
+    if (p->output_sum == CR_OUTPUT_FIXED_SUM) return fail(h, CR_ERR_UNSUPPORTED, "guide layers come as reals (output_sum 0 or 1), not as fixed-point words");
+    if (!host) return render_device(h, cam, p, out, stats, nullptr, 1, layers);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t channels = (layers & CR_AOV_ALBEDO ? 3 : 0) + (layers & CR_AOV_NORMAL ? 3 : 0) + (layers & CR_AOV_DEPTH ? 1 : 0) + (layers & CR_AOV_COVERAGE ? 1 : 0);
+    const size_t bytes = (size_t)cam->image_width * cam->image_height * channels * real_size(p->real_type);
+    const hipError_t e = h->out_buf.ensure(bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
+    rc = render_device(h, cam, p, h->out_buf.p, stats, nullptr, 1, layers);
+    if (rc != CR_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CR_OK;
 }
 
 }   // namespace cr
@@ -184,7 +208,7 @@ void cr_destroy(CrHandle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->s32.release(); h->s64.release(); h->update_stage.release();
     h->images.release(); h->texels.release(); h->work_counter.release(); h->counters.release();
-    h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release();
+    h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release(); h->aov_acc.release(); h->aov_flags.release();
     h->wf_job.release(); h->wf_rng.release(); h->wf_ray.release(); h->wf_depth.release(); h->wf_hit_t.release(); h->wf_hit_prim.release();
     h->wf_chunk.release(); h->wf_ctrl.release(); h->wf_samples.release(); h->wf_acc.release();
     for (int i = 0; i < CrHandle::kCamSlots; i++) {
@@ -218,6 +242,14 @@ int32_t cr_render_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRe
 int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
                               void* h_out, CrStats* stats) {
     return render_entry(h, cam, p, true, frames, n_frames, true, h_out, stats);
+}
+
+int32_t cr_render_aov_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats) {
+    return aov_entry(h, cam, p, layers, false, d_out, stats);
+}
+
+int32_t cr_render_aov_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, void* h_out, CrStats* stats) {
+    return aov_entry(h, cam, p, layers, true, h_out, stats);
 }
 
 int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples, int32_t real_type,

@@ -68,6 +68,25 @@ int32_t cr_write_ppm_binary(const char* path, const void* rgb, int32_t real_type
     return ok ? CR_OK : CR_ERR_IO;
 }
 
+int32_t cr_write_pfm(const char* path, const void* data, int32_t real_type, int32_t w, int32_t hgt, int32_t channels) {
+    if (!path || !data || w < 1 || hgt < 1 || (channels != 1 && channels != 3) || (real_type != CR_REAL_F32 && real_type != CR_REAL_F64))
+        return CR_ERR_INVALID_ARG;
+    FILE* f = fopen(path, "wb");
+    if (!f) return CR_ERR_IO;
+    bool ok = fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", w, hgt) > 0;
+    const size_t row = (size_t)w * (size_t)channels;
+    std::vector<float> line(row);
+    for (int32_t j = hgt - 1; ok && j >= 0; j--) {   // rows bottom to top
+        if (real_type == CR_REAL_F64) { const double* s = (const double*)data + (size_t)j * row; for (size_t k = 0; k < row; k++) line[k] = (float)s[k]; }
+        else memcpy(line.data(), (const float*)data + (size_t)j * row, row * sizeof(float));
+        if (__BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__)
+            for (size_t k = 0; k < row; k++) { uint32_t u; memcpy(&u, &line[k], 4); u = __builtin_bswap32(u); memcpy(&line[k], &u, 4); }
+        ok = fwrite(line.data(), sizeof(float), row, f) == row;
+    }
+    ok = (fclose(f) == 0) && ok;
+    return ok ? CR_OK : CR_ERR_IO;
+}
+
 int32_t cr_write_png(const char* path, const void* rgb, int32_t real_type, int32_t w, int32_t hgt) {
     if (!path || !rgb || w < 1 || hgt < 1 || (real_type != CR_REAL_F32 && real_type != CR_REAL_F64)) return CR_ERR_INVALID_ARG;
     const size_t row = (size_t)w * 3;

@@ -6,6 +6,8 @@
 //   scene.hip          cr_upload_scene, refit.hpp's box kernels, the screening records, cr_update_primitives (update.hpp)
 //   render.hip         render_typed: a render's kernel arguments up to the choice of ladder; the stats epilogue
 //   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder)
+//   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
+//   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
 //   api.hip            cr_create / cr_destroy, cr_render_*, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
 #pragma once
@@ -108,6 +110,7 @@ struct CrHandle {
     hipEvent_t cam_ev[kCamSlots] = {};
     int cam_next = 0, cam_pending_slot = -1;
     DevBuf sample_buf, sg_acc;   // sample-granular megakernel: per-sample colours of a batch, running sums between batches
+    DevBuf aov_acc, aov_flags;   // cr_render_aov_*: per pixel 8 x u64 (albedo, normal, coverage sums; depth) and the channels' NaN bits
     DevBuf fx_acc;               // CR_SUM_RELAXED: per-pixel fixed-point sums (3 x u64 per pixel; per frame of a batch)
     // cr_render_frames_*: a batch's per-frame ray times travel through one pinned host buffer, refilled only after the
     // previous batch's copy has run (times_ev); the device table is reused in stream order
@@ -224,6 +227,9 @@ int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_lar
                    const char* what, int& block, int& per_cu);
 template <typename real>
 int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames);
+template <typename real>
+int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, DevScene<real>& ds, bool refit, bool mega, void* d_out,
+                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb);
 // render_f32_reference.hip, render_f32_relaxed.hip, render_f64_reference.hip, render_f64_relaxed.hip (render.hpp)
 template <typename real, bool ORD, bool RELAX>
 int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb);
@@ -233,6 +239,9 @@ int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size
 template <typename real> int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>& ds, bool anim, CrStats* stats);
 template <typename real> int32_t render_queue(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, bool anim, CrStats* stats, bool* launched);
 int32_t check_queue_abort(CrHandle* h);
+// aov.hip: the guide pass (cr_render_aov_*) after its argument checks; aov_f32.hip, aov_f64.hip: its kernels (aov.hpp)
+template <typename real>
+int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats);
 // api.hip
 int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p);
 int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n, int32_t samples, bool f64, void* out);

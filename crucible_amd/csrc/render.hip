@@ -1,5 +1,5 @@
-// render.hip -- a render up to its kernel: render_typed fills the kernel arguments (camera, frame times, refitted boxes,
-// screening records) and hands them to the residency ladder of the precision and sum order (render.hpp, render_*.hip)
+// render.hip -- a render up to its kernel: render_typed has prepare_args fill the kernel arguments (camera, frame times,
+// refitted boxes, screening records) and hands them to the residency ladder of the precision and sum order (render.hpp, render_*.hip)
 // or to a cross-check pipeline (alt_pipelines.hip).  Also what every launch path shares: the workgroup-size choice and
 // the stats epilogue.  No kernel is emitted here.
 #include "handle.hpp"
@@ -65,36 +65,13 @@ static int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
     return CR_OK;
 }
 
-// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*).
+// What a render settles before its kernels are chosen, shared with the guide pass (aov.hip): the kernel arguments (scene
+// tables, camera and its key slot, sample range, ray times -- of a batch's frames too --, this frame's refitted boxes and
+// screening records, the walk's scheduling knobs) and the kernel kind.  mega: the walk runs in a megakernel-style kernel
+// (screening records, parked leaves); the cross-check pipelines walk without either.
 template <typename real>
-int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames) {
-    int32_t rc = build_dev_scene<real>(h);
-    if (rc != CR_OK) return rc;
-    DevScene<real>& ds = dev_scene<real>(h);
-    const int sum_order = resolve_sum_order(h, p);
-    const bool fixed = p->output_sum == CR_OUTPUT_FIXED_SUM;
-    if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
-        return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
-    // without primitive keys the boxes would not change -- unless a HitList element's box is not its objects' union
-    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;
-    if (frames) {
-        if (sum_order != CR_SUM_RELAXED || h->pipeline != 0)
-            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
-                                               "sequential over samples and would need a per-sample buffer per frame)");
-        if (refit)
-            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
-                                               "(render such frames one at a time)");
-    }
-    if (p->sample_count == 0) {
-        // An empty shard (more ranks than samples): the sum of no samples, and 0 / samples for the mean, are both
-        // zero -- cast_ray's loop body never runs (ray_casting.rs:82).  No kernel is launched.
-        const size_t bytes = (size_t)n_frames * (size_t)cd->image_width * (size_t)cd->image_height * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
-        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-        HIP_TRY(h, hipMemsetAsync(d_out, 0, bytes, h->stream));
-        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-        return stats ? finish_stats(h, stats, 0, ds.n_entries, 0) : CR_OK;
-    }
-    KernelArgs<real> a;
+int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, DevScene<real>& ds, bool refit, bool mega, void* d_out,
+                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb) {
     memset(&a, 0, sizeof a);
     a.entries = (const Entry<real>*)ds.entries.p; a.prims = (const Prim<real>*)ds.prims.p; a.leaf_runs = ds.has_leaf_runs ? (const int32_t*)ds.leaf_runs.p : nullptr;
     a.mats = (const Mat<real>*)ds.mats.p; a.texs = (const Tex<real>*)ds.texs.p;
@@ -141,13 +118,11 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.seed_mixed = mix64(p->seed + RNG_GAMMA);
     frame_times(p, a.current_time, a.shutter_length);   // ray_casting.rs:77-79
     a.output_sum = p->output_sum;
-    FrameBatch<real> fb;
-    std::vector<real> times;
     if (frames) {   // each frame's times as a single render of it computes them (the shutter is the same for all)
         times.resize((size_t)n_frames);
         CrRenderParams q = *p;
         for (int32_t k = 0; k < n_frames; k++) { q.frame = frames[k]; frame_times(&q, times[(size_t)k], a.shutter_length); }
-        rc = stage_frame_times(h, times.data(), times.size() * sizeof(real));
+        int32_t rc = stage_frame_times(h, times.data(), times.size() * sizeof(real));
         if (rc != CR_OK) return rc;
         a.current_time = times[0];
         fb.n = n_frames; fb.times = times.data(); fb.d_times = (const real*)h->times_dev.p;
@@ -162,7 +137,7 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     // f64 megakernel on an unordered tree: the walk decides its box tests on the f32 screening records (half the bytes
     // per step), see walk_round (A/B in profiles/experiments/r03_screen_ab.txt).
     // (not on a tree with a box plane beyond the f32 range: make_screen)
-    bool screen = h->pipeline == 0 && ds.screen.p != nullptr && ds.n_entries > 0 && h->screen_boxes && ds.n_entries < (ds.ordered ? kScreenMaxEntriesO : kScreenMaxEntries);
+    bool screen = mega && ds.screen.p != nullptr && ds.n_entries > 0 && h->screen_boxes && ds.n_entries < (ds.ordered ? kScreenMaxEntriesO : kScreenMaxEntries);
     if (screen) {
         a.screen = ds.screen.p;
         bool usable = ds.screen_usable;
@@ -175,7 +150,6 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     }
     // a SCREEN kernel stages screening records where the others stage wrappers
     const size_t screen_rec = ds.ordered ? sizeof(ScreenEntryO) : sizeof(ScreenEntry);
-    WalkChoice w;
     w.screen = screen;
     w.lds_all_screen = ds.lds_bytes - r16((size_t)ds.n_entries * ds.entry_bytes) + r16((size_t)ds.n_entries * screen_rec);
     a.tiles_x = (uint32_t)(c.W + 7) / 8u; a.tiles_y = (uint32_t)(c.H + 7) / 8u;
@@ -185,7 +159,7 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.uniform_kind = (ds.has_spheres && !ds.has_triangles) ? 0 : ((ds.has_triangles && !ds.has_spheres) ? 1 : -1);
     a.walk_exit_lanes = (uint32_t)(h->walk_exit_lanes >= 0 ? h->walk_exit_lanes : (ds.has_triangles ? 40 : 56));
     a.walk_round_steps = (uint32_t)(h->walk_round_steps >= 0 ? h->walk_round_steps : (ds.has_triangles ? 8 : 10));
-    a.walk_leaf_min = h->pipeline == 0 ? (uint32_t)(h->walk_leaf_min >= 0 ? h->walk_leaf_min : 8) : 0u;   // the other pipelines test a leaf in the round that found it
+    a.walk_leaf_min = mega ? (uint32_t)(h->walk_leaf_min >= 0 ? h->walk_leaf_min : 8) : 0u;   // the other pipelines test a leaf in the round that found it
     a.sg_on = 0; a.sg_lw = a.sg_lh = 3; a.sg_groups = 0; a.sg_total = 0; a.sample_buf = nullptr;   // set by launch()
 
     // the ANIM kernels also carry the decode of leaves that hold a HitList element (pathtrace.hpp walk_round)
@@ -193,11 +167,49 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     // camera keys alone: the static kernels' CAMK variant, which also renders the batches of scenes without keys (the
     // static kernels do not carry a batch's frame arithmetic; with an unkeyed camera CAMK computes what they compute)
     w.cam_keys = c.animated || frames != nullptr;
+    return CR_OK;
+}
+
+// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*).
+template <typename real>
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames) {
+    int32_t rc = build_dev_scene<real>(h);
+    if (rc != CR_OK) return rc;
+    DevScene<real>& ds = dev_scene<real>(h);
+    const int sum_order = resolve_sum_order(h, p);
+    const bool fixed = p->output_sum == CR_OUTPUT_FIXED_SUM;
+    if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
+        return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
+    // without primitive keys the boxes would not change -- unless a HitList element's box is not its objects' union
+    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;
+    if (frames) {
+        if (sum_order != CR_SUM_RELAXED || h->pipeline != 0)
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
+                                               "sequential over samples and would need a per-sample buffer per frame)");
+        if (refit)
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
+                                               "(render such frames one at a time)");
+    }
+    if (p->sample_count == 0) {
+        // An empty shard (more ranks than samples): the sum of no samples, and 0 / samples for the mean, are both
+        // zero -- cast_ray's loop body never runs (ray_casting.rs:82).  No kernel is launched.
+        const size_t bytes = (size_t)n_frames * (size_t)cd->image_width * (size_t)cd->image_height * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        HIP_TRY(h, hipMemsetAsync(d_out, 0, bytes, h->stream));
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        return stats ? finish_stats(h, stats, 0, ds.n_entries, 0) : CR_OK;
+    }
+    KernelArgs<real> a;
+    WalkChoice w;
+    FrameBatch<real> fb;
+    std::vector<real> times;
+    rc = prepare_args<real>(h, cd, p, ds, refit, h->pipeline == 0, d_out, frames, n_frames, times, a, w, fb);
+    if (rc != CR_OK) return rc;
     // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
     if (sum_order == CR_SUM_RELAXED && h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_SUM_RELAXED is implemented by the megakernel pipeline only");
     const bool relax = sum_order == CR_SUM_RELAXED;
     const size_t fx_need = relax ? fx_lds_bytes(MaxBlock<real>::value, 4) : 0;   // the relaxed sums' slots share the LDS
-    w.screen_lds = screen && h->screen_lds && w.lds_all_screen + fx_need <= h->lds_limit;
+    w.screen_lds = w.screen && h->screen_lds && w.lds_all_screen + fx_need <= h->lds_limit;
     w.plain_lds = ds.lds_bytes + fx_need <= h->lds_limit;
     if (ds.ordered) {   // near-child-first walk: megakernel only
         if (h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_BVH_SAH_ORDERED is implemented by the megakernel pipeline only");
@@ -212,6 +224,8 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     return relax ? walk_ladder<real, false, true>(h, a, ds, w, stats, fb) : walk_ladder<real, false, false>(h, a, ds, w, stats, fb);
 }
 
+template int32_t prepare_args<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<float>&, bool, bool, void*, const int32_t*, int32_t, std::vector<float>&, KernelArgs<float>&, WalkChoice&, FrameBatch<float>&);
+template int32_t prepare_args<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<double>&, bool, bool, void*, const int32_t*, int32_t, std::vector<double>&, KernelArgs<double>&, WalkChoice&, FrameBatch<double>&);
 template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t);
 template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t);
 

@@ -601,6 +601,33 @@ public:
         buf.resize((size_t)scene_cam.image_width * scene_cam.image_height * 3 * frs.size());
         return cr_render_frames_host(h, &cd, &p, frs.data(), (int32_t)frs.size(), buf.data(), stats);
     }
+    // Guide layers (cr_render_aov_host): the planes of `aov_layers` for the frame, one after the other, into `buf`.
+    int32_t aov_layers = 0;   // CR_AOV_* mask: > 0 writes <frame>.<layer>.pfm next to every frame file
+    size_t aov_reals() const {
+        const size_t ch = (aov_layers & CR_AOV_ALBEDO ? 3 : 0) + (aov_layers & CR_AOV_NORMAL ? 3 : 0) + (aov_layers & CR_AOV_DEPTH ? 1 : 0) + (aov_layers & CR_AOV_COVERAGE ? 1 : 0);
+        return (size_t)scene_cam.image_width * scene_cam.image_height * ch;
+    }
+    int32_t render_aov(CrHandle* h, void* planes, CrStats* stats = nullptr, int64_t frame = -1) const {
+        std::vector<CrKeyframe> fk, ak;
+        CrCameraDesc cd = camera_desc(fk, ak);
+        CrRenderParams p = render_params(frame < 0 ? (size_t)scene_cam.frame : (size_t)frame);
+        return cr_render_aov_host(h, &cd, &p, aov_layers, planes, stats);
+    }
+    // <fname>.albedo.pfm, .normal.pfm, .depth.pfm, .coverage.pfm: the requested planes of one frame
+    int32_t write_aov(const std::string& fname, const void* planes) const {
+        static const struct { int32_t bit; const char* name; int32_t ch; } layer[4] = {
+            {CR_AOV_ALBEDO, "albedo", 3}, {CR_AOV_NORMAL, "normal", 3}, {CR_AOV_DEPTH, "depth", 1}, {CR_AOV_COVERAGE, "coverage", 1}};
+        const Camera& c = scene_cam;
+        const size_t rs = real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float);
+        const char* at = (const char*)planes;
+        for (const auto& l : layer) {
+            if (!(aov_layers & l.bit)) continue;
+            const int32_t rc = cr_write_pfm((fname + "." + l.name + ".pfm").c_str(), at, real_type, c.image_width, c.image_height, l.ch);
+            if (rc != CR_OK) return rc;
+            at += (size_t)c.image_width * c.image_height * (size_t)l.ch * rs;
+        }
+        return CR_OK;
+    }
     size_t frame_bytes() const { return (size_t)scene_cam.image_width * scene_cam.image_height * 3 * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float)); }
     // The file: "ppm" = the reference's ASCII P3 (camera/mod.rs:286,306-311); "p6" / "png" = SURVEY 8(f) row 3,
     // the same per-channel bytes in binary PPM / PNG.
@@ -622,6 +649,11 @@ public:
         double t1 = now_ms();
         timing.render_ms += t1 - t0;
         if (rc == CR_OK) { rc = write_frame(fname, buf); timing.write_ms += now_ms() - t1; timing.frames++; }
+        if (rc == CR_OK && aov_layers) {
+            std::vector<double> planes(aov_reals());
+            rc = render_aov(h, planes.data());
+            if (rc == CR_OK) rc = write_aov(fname, planes.data());
+        }
         return rc;
     }
     // Camera::render across several devices: cr_group_render_host splits the sample indices, adds the per-pixel sums with
@@ -644,7 +676,7 @@ public:
     // so it is not part of the wall clock unless it is the longer one).
     int32_t render_movie_frames(CrHandle* h, const std::string& fname, size_t first, size_t step, size_t frames, size_t digits,
                                 CrStats* stats, Timing* tm) const {
-        std::vector<double> bufs[2];
+        std::vector<double> bufs[2], guides[2];   // guides: the batch's guide planes, frame after frame
         std::thread writers[2];
         int32_t write_rc[2] = {CR_OK, CR_OK};
         double write_ms[2] = {0, 0};
@@ -665,6 +697,10 @@ public:
             if (!batched) rc = render_frame(h, bufs[slot], &st, (int64_t)batch[0]);
             if (tm) { tm->render_ms += now_ms() - t0; tm->kernel_ms += st.kernel_ms; tm->frames += batch.size(); }
             if (stats) *stats = st;
+            if (rc == CR_OK && aov_layers) {
+                guides[slot].resize(aov_reals() * batch.size());
+                for (size_t i = 0; i < batch.size() && rc == CR_OK; i++) rc = render_aov(h, (void*)((char*)guides[slot].data() + i * aov_reals() * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float))), nullptr, (int64_t)batch[i]);
+            }
             if (rc != CR_OK) break;
             std::vector<std::string> stems;
             for (int32_t f : batch) {
@@ -672,10 +708,13 @@ public:
                 stems.push_back(fname + "/artifacts/image" + std::string(digits - num.size(), '0') + num);
             }
             fr = (size_t)batch.back() + step;
-            writers[slot] = std::thread([this, stems, slot, &bufs, &write_rc, &write_ms] {
+            writers[slot] = std::thread([this, stems, slot, &bufs, &guides, &write_rc, &write_ms] {
                 const double w0 = now_ms();
-                for (size_t i = 0; i < stems.size() && write_rc[slot] == CR_OK; i++)
+                const size_t guide_bytes = aov_reals() * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float));
+                for (size_t i = 0; i < stems.size() && write_rc[slot] == CR_OK; i++) {
                     write_rc[slot] = write_frame(stems[i], (const char*)bufs[slot].data() + i * frame_bytes());
+                    if (write_rc[slot] == CR_OK && aov_layers) write_rc[slot] = write_aov(stems[i], (const char*)guides[slot].data() + i * guide_bytes);
+                }
                 write_ms[slot] += now_ms() - w0;
             });
         }

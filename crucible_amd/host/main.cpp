@@ -9,6 +9,7 @@
 // --dump-desc FILE (write the flattened scene description and exit; used by the tests to check
 // this mirror against the Python one), --sum-order reference|relaxed (CrRenderParams.sum_order; default: the library's),
 // --frames-per-launch N (movies: N frames per library call through cr_render_frames_host, relaxed sums; default 1),
+// --aov albedo,normal,depth,coverage (guide layers through cr_render_aov_host: <frame>.<layer>.pfm next to every frame file),
 // --repeat N --timing (measurement: render_scene N times in this process, one JSON line of wall-clock phases each --
 // the shape of the reference's criterion benchmark, benches/renderer_benchmark.rs:16-42 -- the first is the cold one).
 #include "crucible.hpp"
@@ -48,7 +49,7 @@ int main(int argc, char** argv) {
     bool refit = false, use_group = false, timing = false;
     int gpus = 1, repeat = 1;
     long frames_per_launch = 1;
-    std::string sum_order = "default";
+    std::string sum_order = "default", aov;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -74,6 +75,7 @@ int main(int argc, char** argv) {
         else if (a == "--repeat") repeat = std::max(1, atoi(next()));
         else if (a == "--frames-per-launch") frames_per_launch = atol(next());
         else if (a == "--sum-order") sum_order = next();
+        else if (a == "--aov") aov = next();
         else if (a == "--dump-desc") dump = next();
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -121,6 +123,14 @@ int main(int argc, char** argv) {
         scene.frame_format = format;
         if (sum_order != "default" && sum_order != "reference" && sum_order != "relaxed") { fprintf(stderr, "--sum-order takes default, reference or relaxed\n"); return 2; }
         scene.sum_order = sum_order == "reference" ? CR_SUM_REFERENCE_ORDER : (sum_order == "relaxed" ? CR_SUM_RELAXED : CR_SUM_DEFAULT);
+        for (size_t at = 0; !aov.empty() && at <= aov.size();) {   // a comma-separated list of layer names
+            const size_t end = std::min(aov.find(',', at), aov.size());
+            const std::string name = aov.substr(at, end - at);
+            const int32_t bit = name == "albedo" ? CR_AOV_ALBEDO : name == "normal" ? CR_AOV_NORMAL : name == "depth" ? CR_AOV_DEPTH : name == "coverage" ? CR_AOV_COVERAGE : 0;
+            if (!bit) { fprintf(stderr, "--aov takes a list of albedo, normal, depth, coverage\n"); return 2; }
+            scene.aov_layers |= bit;
+            at = end + 1;
+        }
         if (!dump.empty()) { dump_desc(scene.flatten(), dump.c_str()); return 0; }
         int32_t rc = CR_OK;
         for (int rep = 0; rep < repeat && rc == CR_OK; rep++) {

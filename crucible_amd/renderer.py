@@ -151,6 +151,38 @@ class Renderer:
                                                      fr.size, C.c_void_p(d_ptr), C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    def render_aov(self, cam, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                   output_sum=False, want_stats=True):
+        """cr_render_aov_host: the first-hit guide layers `layers` (a CR_AOV_* mask, or names such as
+        ("albedo", "depth")) of the primary rays of render() with the same camera and params.  Returns (dict of host
+        arrays keyed "albedo" (H, W, 3), "normal" (H, W, 3; decode 2 e - 1), "depth" (H, W), "coverage" (H, W) -- the
+        requested ones --, stats dict)."""
+        layers = aov_mask(layers)
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        H, W = cam.image_height, cam.image_width
+        planes = [(n, c) for n, bit, c in A.AOV_LAYERS if layers & bit]
+        buf = np.empty(max(1, W * H * sum(c for _, c in planes)), dtype=np_real(real_type))
+        st = A.CrStats()
+        self._check(self.lib.cr_render_aov_host(self.h, C.byref(cd), C.byref(p), layers, buf.ctypes.data_as(C.c_void_p),
+                                                C.byref(st) if want_stats else None))
+        out, o = {}, 0
+        for n, c in planes:
+            out[n] = buf[o:o + W * H * c].reshape((H, W, 3) if c == 3 else (H, W))
+            o += W * H * c
+        return out, st.as_dict()
+
+    def render_aov_device(self, cam, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
+                          sample_count=None, output_sum=False, want_stats=False):
+        """cr_render_aov_device: the requested planes, one after the other in ascending bit order, into device memory at
+        `d_ptr`.  Asynchronous unless want_stats."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        st = A.CrStats()
+        self._check(self.lib.cr_render_aov_device(self.h, C.byref(cd), C.byref(p), aov_mask(layers), C.c_void_p(d_ptr),
+                                                  C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
         """cr_fixed_sums_to_rgb: summed CR_OUTPUT_FIXED_SUM words of a whole frame (device pointer, W*H*3 uint64) ->
         its per-pixel means at device pointer `d_out` (W*H*3 reals), exactly the relaxed frame.  Asynchronous on the
@@ -197,6 +229,28 @@ class Renderer:
         rc = fn(path.encode(), img.ctypes.data_as(C.c_void_p), rt, img.shape[1], img.shape[0])
         if rc != A.CR_OK:
             raise CrucibleError(rc, "cannot write " + path)
+
+
+def aov_mask(layers):
+    """A CR_AOV_* mask from a mask or from layer names."""
+    if isinstance(layers, (int, np.integer)):
+        return int(layers)
+    bits = {n: bit for n, bit, _ in A.AOV_LAYERS}
+    return sum(bits[n] for n in set(layers))
+
+
+def write_pfm(path, plane):
+    """cr_write_pfm: a (H, W) or (H, W, 3) f32 / f64 array as a portable float map (needs no GPU)."""
+    lib = load_library()
+    a = np.ascontiguousarray(plane)
+    if a.dtype != np.float64:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim not in (2, 3):
+        raise ValueError("write_pfm: a plane is (H, W) or (H, W, 3)")
+    rt = A.CR_REAL_F64 if a.dtype == np.float64 else A.CR_REAL_F32
+    rc = lib.cr_write_pfm(path.encode(), a.ctypes.data_as(C.c_void_p), rt, a.shape[1], a.shape[0], 1 if a.ndim == 2 else a.shape[2])
+    if rc != A.CR_OK:
+        raise CrucibleError(rc, "cannot write " + path)
 
 
 def quantize_rgb8(img):

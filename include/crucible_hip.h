@@ -398,6 +398,46 @@ CR_API int32_t cr_render_frames_device(CrHandle* h, const CrCameraDesc* cam, con
 CR_API int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
                                      const int32_t* frames, int32_t n_frames, void* h_out, CrStats* stats);
 
+/*
+ * First-hit guide layers (what a denoiser or a compositor reads beside the beauty frame): per pixel the surface albedo,
+ * the shading normal, the depth and the coverage of the PRIMARY rays of cr_render_device for the same camera and
+ * params -- the stream rng_key(seed, j*W+i, s) and cast_ray's draws (time, two offsets, defocus disk), keyed cameras
+ * included -- and Hittables::hit on [0.001, inf) over the tree that render walks (bvh_mode; refit_boxes as in a render).
+ *
+ * `layers` is a mask of CR_AOV_*.  The output holds the requested layers as planes, one after the other in ascending
+ * bit order: albedo W*H*3 reals, normal W*H*3, depth W*H, coverage W*H; row-major, three-channel planes interleaved,
+ * reals of params->real_type; layers that were not requested take no space.
+ *
+ * Per sample s in [sample_begin, sample_begin + sample_count):
+ *   coverage  1 on a hit, 0 on a miss;
+ *   albedo    on a hit: Lambertian tex.value(u, v, position) (the scatter's attenuation before the divide by
+ *             scatter_prob), Metal its albedo, Dielectric (1, 1, 1); on a miss the sky colour ray_color returns;
+ *   normal    e = 0.5 * n + 0.5 per component in `real`, n the HitRecord's normal (turned against the ray as
+ *             HitRecord::new does), n = (0, 0, 0) on a miss; decode with 2 e - 1;
+ *   depth     |position - origin|, position = origin + t * direction: the difference formed as position + (-origin),
+ *             the squares added x, y, z, one square root, all in `real`.
+ * Per pixel: albedo, normal and coverage are exact fixed-point sums -- a sample adds rint(x * 2^S), evaluated in f64,
+ * to a signed 64-bit word, S that of CR_SUM_RELAXED for params->samples -- turned into the mean over `samples`
+ * (output_sum 0) or the shard's sum in reals (output_sum 1) as a relaxed render's sums are; a value that is not finite
+ * gives NaN.  Depth is the MINIMUM over the shard's samples that hit, +inf where none did, whatever output_sum says.
+ * Integer adds and minima commute: the planes do not depend on scheduling, and the words of shards add up.
+ *
+ * CR_OUTPUT_FIXED_SUM: CR_ERR_UNSUPPORTED.  layers == 0 or an unknown bit: CR_ERR_INVALID_ARG.  Everything
+ * cr_render_device rejects is rejected alike; max_depth and sum_order are validated and otherwise not read.  Works
+ * under every CRUCIBLE_PIPELINE setting.  A refused call leaves the handle as it was.
+ * stats: samples rendered, segments == samples, node_tests / prim_tests of the walk (those of a max_depth = 1 render),
+ * texel_fetches, nan_pixels = 0; kernel_ms, bvh_entries, scene_in_lds as for a render.
+ * The handle keeps 64 bytes of accumulators per pixel (+ 4 of flags), grown on demand, freed by cr_destroy.
+ * Asynchronous unless `stats` is non-NULL.
+ */
+enum { CR_AOV_ALBEDO = 1, CR_AOV_NORMAL = 2, CR_AOV_DEPTH = 4, CR_AOV_COVERAGE = 8 };
+CR_API int32_t cr_render_aov_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                    void* d_out, CrStats* stats);
+
+/* Same, into a HOST buffer (synchronous).  No Color::new check applies: the planes are not colours of a frame. */
+CR_API int32_t cr_render_aov_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                  void* h_out, CrStats* stats);
+
 /* The wrapper tree the device walks for `real_type`, as BVHWrapper's shape (src/objects/bvhwrapper.rs:7-11):
  * wrapper k has boxes[6k..6k+5] = xmin,xmax,ymin,ymax,zmin,zmax (exact values of `real_type`) and
  * children[2k], children[2k+1] = left, right: >= 0 another wrapper's index, < 0 the bitwise complement of a
@@ -465,6 +505,13 @@ CR_API int32_t cr_write_ppm_binary(const char* path, const void* rgb, int32_t re
                                    int32_t image_width, int32_t image_height);
 CR_API int32_t cr_write_png(const char* path, const void* rgb, int32_t real_type,
                             int32_t image_width, int32_t image_height);
+
+/* Portable float map, the file a guide layer travels in: the header "Pf" (channels 1) or "PF" (channels 3), a line with
+ * width and height, the line "-1.0" (little-endian), then width*height*channels little-endian f32, rows BOTTOM to top.
+ * `data` is a host plane of `real_type`, row-major top to bottom; f64 is rounded to f32, +-inf passes through.  Needs
+ * no GPU.  Another `channels`: CR_ERR_INVALID_ARG; a file that cannot be written: CR_ERR_IO. */
+CR_API int32_t cr_write_pfm(const char* path, const void* data, int32_t real_type,
+                            int32_t width, int32_t height, int32_t channels /* 1 | 3 */);
 
 /* Quantise means to the bytes Display would print (3 per pixel); no file. */
 CR_API int32_t cr_quantize_rgb8(const void* rgb, int32_t real_type, int64_t n_pixels, uint8_t* out);
