@@ -84,11 +84,12 @@ int32_t wf_run(CrHandle* h, WfArgs<real>& W, size_t lds_bytes, int32_t s_begin, 
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     int iterations = 0;
     const int LAG = 4, RING = 8;
-    for (int32_t b0 = s_begin; b0 < s_begin + s_count; b0 += batch_cap) {
-        W.batch_begin = b0;
-        W.batch_samples = std::min(batch_cap, s_begin + s_count - b0);
+    const int64_t s_end = (int64_t)s_begin + s_count;
+    for (int64_t b0 = s_begin; b0 < s_end; b0 += batch_cap) {   // (64 bits: b0 + batch_cap may pass INT32_MAX)
+        W.batch_begin = (int32_t)b0;
+        W.batch_samples = (int32_t)std::min<int64_t>(batch_cap, s_end - b0);
         W.n_jobs = (uint32_t)W.batch_samples * W.total_work;
-        W.last_batch = (b0 + W.batch_samples >= s_begin + s_count) ? 1 : 0;
+        W.last_batch = (b0 + W.batch_samples >= s_end) ? 1 : 0;
         HIP_TRY(h, hipMemsetAsync(h->wf_ctrl.p, 0, 1024, h->stream));
         HIP_TRY(h, hipMemsetAsync(h->wf_chunk.p, 0, ((size_t)W.n_slots / 64 + 1) * 8, h->stream));
         for (int it = 0;; it++) {
@@ -143,7 +144,7 @@ int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>&
     HIP_TRY(h, h->wf_job.ensure(N * 4));
     HIP_TRY(h, h->wf_rng.ensure(N * 8));
     HIP_TRY(h, h->wf_ray.ensure(N * 7 * sizeof(real)));
-    HIP_TRY(h, h->wf_depth.ensure(N * 4));
+    HIP_TRY(h, h->wf_depth.ensure(N * 8));
     HIP_TRY(h, h->wf_hit_t.ensure(N * sizeof(real)));
     HIP_TRY(h, h->wf_hit_prim.ensure(N * 4));
     HIP_TRY(h, h->wf_chunk.ensure((N / 64 + 1) * 8));
@@ -183,6 +184,8 @@ int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>&
 template <typename real>
 int32_t render_queue(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, bool anim, CrStats* stats, bool* launched) {
     const size_t budget = 160 * 1024, state = queue_state_bytes<real>();
+    // a slot packs its pixel as i | j << 16 and its counters as depth_left | stack_n << 16 (stack_n <= max_depth)
+    if (a.cam.W > kQueueMaxExtent || a.cam.H > kQueueMaxExtent || a.max_depth > kQueueMaxDepth) { *launched = false; return CR_OK; }
     *launched = true;
     if (ds.n_entries > 0 && ds.lds_bytes + 16 + state <= budget) {
         a.lds_entries = ds.n_entries;

@@ -98,8 +98,9 @@ CR_D void aov_body(const AovArgs<real>& G) {
         const uint32_t pix_i = ((tile % A.tiles_x) << 2) + (px & 3u), pix_j = ((tile / A.tiles_x) << 2) + (px >> 2);
         const bool in_image = pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H;
         for (uint32_t g = g0; g < g1; g++) {
-            const int32_t sample = A.sample_begin + (int32_t)(g * 4u + (lane >> 4));
-            const bool active = in_image && sample < A.sample_end;   // else: padding of an edge tile or of the last group
+            const uint32_t s_off = g * 4u + (lane >> 4);   // begin + offset may pass INT32_MAX in the last group's padding: the offset decides
+            const int32_t sample = (int32_t)((uint32_t)A.sample_begin + s_off);
+            const bool active = in_image && s_off < (uint32_t)(A.sample_end - A.sample_begin);   // else: padding of an edge tile or of the last group
             V3<real> ro = mk<real>(0, 0, 0), rd = mk<real>(0, 0, 1);
             real rtime = 0;
             uint64_t rng = 0;

@@ -26,7 +26,7 @@ int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
     if (cam->image_width < 1 || cam->image_height < 1) return fail(h, CR_ERR_INVALID_ARG, "image size must be positive");
     if ((int64_t)cam->image_width * cam->image_height > (int64_t)1 << 26) return fail(h, CR_ERR_INVALID_ARG, "image too large");
     if (p->samples < 1) return fail(h, CR_ERR_INVALID_ARG, "The camera must have a positive number of samples.");   // camera/mod.rs:235-238
-    if (p->sample_begin < 0 || p->sample_count < 0 || p->sample_begin + p->sample_count > p->samples)
+    if (p->sample_begin < 0 || p->sample_count < 0 || (int64_t)p->sample_begin + p->sample_count > p->samples)   // (in 64 bits: the sum of two int32 may pass 2^31)
         return fail(h, CR_ERR_INVALID_ARG, "sample range outside [0, samples)");
     if (p->max_depth < 0) return fail(h, CR_ERR_INVALID_ARG, "max_depth must be >= 0");
     if (p->real_type != CR_REAL_F32 && p->real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");

@@ -1556,10 +1556,12 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                     const uint32_t ds = in >> (A.sg_lw + A.sg_lh);
                     pix_i = ((tile % A.tiles_x) << A.sg_lw) + px;
                     pix_j = ((tile / A.tiles_x) << A.sg_lh) + py;
-                    sample = A.sample_begin + (int32_t)(sg * (64u >> (A.sg_lw + A.sg_lh)) + ds);
+                    // the offset in the shard decides: begin + offset may pass INT32_MAX in the last group's padding, and wraps
+                    const uint32_t s_off = sg * (64u >> (A.sg_lw + A.sg_lh)) + ds;
+                    sample = (int32_t)((uint32_t)A.sample_begin + s_off);
                     uint32_t row = pix_j;   // BATCH: pix_j counts the rows of a whole batch; the frame's own row decides
                     if constexpr (BATCH) row -= batch_frame(A, pix_j) * (A.tiles_y << A.sg_lh);
-                    if (pix_i < (uint32_t)cam.W && row < (uint32_t)cam.H && sample < A.sample_end) state = ST_NEED_SAMPLE;
+                    if (pix_i < (uint32_t)cam.W && row < (uint32_t)cam.H && s_off < (uint32_t)(A.sample_end - A.sample_begin)) state = ST_NEED_SAMPLE;
                     // else: padding of an edge tile or of the last sample group, ask again next round
                 }
             }

@@ -23,6 +23,9 @@ namespace cr {
 
 constexpr uint32_t QK_SLOTS = 1024;
 constexpr uint32_t QK_LOG = 10;
+// what a slot's packed words hold (s_pix: i | j << 16; s_depth: depth_left | stack_n << 16, a non-negative int32): larger
+// renders go to the plain megakernel (render_queue)
+constexpr int32_t kQueueMaxExtent = 65535, kQueueMaxDepth = 32767;
 constexpr uint32_t QK_SPIN_LIMIT = 1u << 24;   // idle polls (~60 ns each) before a wave gives up: ~1 s, far beyond any legitimate wait
 enum : int { QC_RQ_HEAD = 0, QC_RQ_TAIL = 1, QC_HQ_HEAD = 2, QC_HQ_TAIL = 3, QC_DONE = 4, QC_ABORT = 5, QC_WORDS = 16 };
 

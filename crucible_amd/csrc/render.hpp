@@ -75,7 +75,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
                 }
             }
         } else {
-            auto batch_bytes = [&](int32_t b) { return (size_t)tiles * ((size_t)(b + (int32_t)ns - 1) / ns) * 64u * 3u * sizeof(real); };
+            auto batch_bytes = [&](int32_t b) { return (size_t)tiles * (((size_t)b + ns - 1) / ns) * 64u * 3u * sizeof(real); };
             while (batch > (int32_t)ns && batch_bytes(batch) > std::max(h->sample_buf_limit, batch_bytes((int32_t)ns))) batch -= (int32_t)ns;
             if (batch > 0 && h->sample_buf.ensure(batch_bytes(batch)) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
             if (batch > 0 && batch < s_end - s_begin && h->sg_acc.ensure(per_sample) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
@@ -84,7 +84,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     }
     args.sg_on = batch > 0 ? 1u : 0u;
     const uint32_t ns = args.sg_on ? (64u >> (args.sg_lw + args.sg_lh)) : 1u;
-    auto groups_of = [&](int32_t n) { return (uint32_t)((n + (int32_t)ns - 1) / (int32_t)ns); };
+    auto groups_of = [&](int32_t n) { return (uint32_t)(((int64_t)n + ns - 1) / ns); };
     uint64_t total_work = args.sg_on ? (uint64_t)args.tiles_x * args.tiles_y * fpl * groups_of(std::min(batch, s_end - s_begin)) * 64u
                                      : (uint64_t)args.tiles_x * args.tiles_y * 64u;
     uint32_t grid = (uint32_t)(h->n_cus * per_cu);
@@ -121,10 +121,10 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
                 args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
                 args.fx_acc = fx_frame0 + (size_t)f0 * npix * 3;
             }
-            for (int32_t b0 = s_begin; b0 < s_end; b0 += batch) {
-                const int32_t b1 = std::min(s_end, b0 + batch);
-                args.sample_begin = b0; args.sample_end = b1;
-                args.sg_groups = groups_of(b1 - b0);
+            for (int64_t b0 = s_begin; b0 < s_end; b0 += batch) {   // (64 bits: b0 + batch may pass INT32_MAX)
+                const int32_t b1 = (int32_t)std::min<int64_t>(s_end, b0 + batch);
+                args.sample_begin = (int32_t)b0; args.sample_end = b1;
+                args.sg_groups = groups_of(b1 - (int32_t)b0);
                 args.sg_total = (uint32_t)((uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn * args.sg_groups * 64u);
                 {   // 1024 items per atomic keeps the counter quiet on long launches; a short launch (a small frame, or one
                     // GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most
@@ -139,7 +139,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
                 if constexpr (!RELAX) {   // (relaxed: the sums stay in fx_acc until the last batch)
                     const size_t fin_threads = ((size_t)args.tiles_x * args.tiles_y) << (args.sg_lw + args.sg_lh);
                     hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((fin_threads + 255) / 256)), dim3(256), 0, h->stream, args,
-                                       (real*)h->sg_acc.p, b1 - b0, b0 == s_begin ? 1 : 0, b1 == s_end ? 1 : 0);
+                                       (real*)h->sg_acc.p, b1 - (int32_t)b0, b0 == s_begin ? 1 : 0, b1 == s_end ? 1 : 0);
                     HIP_TRY(h, hipGetLastError());
                 }
             }

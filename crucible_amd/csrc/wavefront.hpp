@@ -36,7 +36,7 @@ template <typename real> struct WfArgs {
     uint32_t* job;               // [n_slots] job id or WF_IDLE
     uint64_t* rng;               // [n_slots]
     real* ray;                   // [7][n_slots]: ox oy oz dx dy dz time
-    int32_t* depth;              // [n_slots] depth_left | stack_n << 16
+    int32_t* depth;              // [2][n_slots]: depth_left, stack_n (a word each: both count up to max_depth)
     real* hit_t;                 // [n_slots]
     int32_t* hit_prim;           // [n_slots]
     uint32_t* job_chunk;         // [n_slots/64][2] each logic wave's private job range {next, end}
@@ -73,8 +73,7 @@ __global__ void __launch_bounds__(256) wf_logic_kernel(const WfArgs<real> W) {
         rd = mk<real>(W.ray[3 * (size_t)N + slot], W.ray[4 * (size_t)N + slot], W.ray[5 * (size_t)N + slot]);
         if (ANIM) rtime = W.ray[6 * (size_t)N + slot];
         rng = W.rng[slot];
-        int32_t dp = W.depth[slot];
-        depth_left = dp & 0xFFFF; stack_n = dp >> 16;
+        depth_left = W.depth[slot]; stack_n = W.depth[(size_t)N + slot];
         V3<real> col = mk<real>(0, 0, 0);
         bool finished = shade<real, ANIM>(A, A.prims, A.mats, A.texs, ro, rd, rtime, rng, depth_left, stack_n, W.hit_t[slot], W.hit_prim[slot],
                                           N, slot, c_tex, col);
@@ -134,7 +133,7 @@ __global__ void __launch_bounds__(256) wf_logic_kernel(const WfArgs<real> W) {
         W.ray[3 * (size_t)N + slot] = rd.x; W.ray[4 * (size_t)N + slot] = rd.y; W.ray[5 * (size_t)N + slot] = rd.z;
         if (ANIM) W.ray[6 * (size_t)N + slot] = rtime;
         W.rng[slot] = rng;
-        W.depth[slot] = depth_left | (stack_n << 16);
+        W.depth[slot] = depth_left; W.depth[(size_t)N + slot] = stack_n;
         W.hit_prim[slot] = WF_PENDING;
         c_seg = 1;
     }

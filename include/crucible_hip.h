@@ -361,7 +361,12 @@ CR_API int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* scene);
  * resident lane, ~150 MB at depth 50) and a per-sample colour buffer of image_width*image_height*3 reals per
  * sample index, up to 40 GiB (CRUCIBLE_SAMPLE_BUF_MB; a render that needs more runs as consecutive sample
  * batches, CRUCIBLE_SAMPLE_GRANULAR=0 avoids the buffer at a large cost in speed).  The buffers are
- * grown on demand, reused by later renders and freed by cr_destroy. */
+ * grown on demand, reused by later renders and freed by cr_destroy.
+ * Limits: image_width * image_height <= 2^26; 0 <= sample_begin, sample_begin + sample_count <= samples <= INT32_MAX
+ * (the sum is formed in 64 bits); any max_depth >= 0 the attenuation stack has memory for; at most 512 camera
+ * keyframes (from + at), more: CR_ERR_UNSUPPORTED.  CRUCIBLE_PIPELINE=queue: the LDS-queue kernel takes renders of
+ * image_width <= 65535, image_height <= 65535 and max_depth <= 32767 (what its packed slot words hold); larger ones run on
+ * the plain megakernel, as scenes do that leave its slots no LDS.  CRUCIBLE_PIPELINE=wavefront has no limit of its own. */
 CR_API int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
                          void* d_out_rgb, CrStats* stats);
 

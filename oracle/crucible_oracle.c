@@ -1444,13 +1444,23 @@ EXPORT int32_t oracle_render(const Scene* sc, const CrCameraDesc* cd, const CrRe
     g_mat_rc = sc->mat_rc;
     Job* jobs = (Job*)calloc((size_t)n_threads, sizeof(Job));
     pthread_t* th = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)n_threads);
+    /* ray_color recurses once per bounce (352 bytes a level in the f64 build): the render threads -- a single one too --
+     * get a stack that holds max_depth levels, 512 bytes each, on top of the usual 8 MiB.  (ray_color_relaxed loops.) */
+    pthread_attr_t attr;
+    pthread_attr_init(&attr);
+    size_t stack = (size_t)8 << 20;
+    if (p->sum_order != CR_SUM_RELAXED) stack += (size_t)512 * (size_t)(p->max_depth < (1 << 22) ? (p->max_depth < 0 ? 0 : p->max_depth) : (1 << 22));
+    pthread_attr_setstacksize(&attr, stack);
+    int started = 0;
     for (int t = 0; t < n_threads; t++) {
         jobs[t].sc = sc; jobs[t].cam = &cam; jobs[t].p = p; jobs[t].out = out;
         jobs[t].pix_begin = pix_begin; jobs[t].pix_end = pix_end; jobs[t].next = &next; jobs[t].fx_s = fx_s;
-        if (n_threads > 1) pthread_create(&th[t], NULL, worker, &jobs[t]);
     }
-    if (n_threads == 1) worker(&jobs[0]);
-    else for (int t = 0; t < n_threads; t++) pthread_join(th[t], NULL);
+    for (; started < n_threads; started++)
+        if (pthread_create(&th[started], &attr, worker, &jobs[started]) != 0) break;
+    pthread_attr_destroy(&attr);
+    for (int t = 0; t < started; t++) pthread_join(th[t], NULL);
+    if (started == 0) { free(jobs); free(th); free(cam.key_store); return CR_ERR_UNSUPPORTED; }   /* (fewer threads than asked for still render every pixel) */
     if (stats) {
         memset(stats, 0, sizeof *stats);
         for (int t = 0; t < n_threads; t++) {

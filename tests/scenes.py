@@ -424,3 +424,83 @@ def _real_orders():
 
 
 REAL_ORDERS, REAL_ORDER_IDS = _real_orders()
+
+
+def mirror_box_scene(size=80.0, gap=1e-4, samples=2, depth=70000, albedo=0.99999):
+    """Paths of tens of thousands of bounces: the camera inside a closed box of 12 mirror triangles (Metal, fuzz 0,
+    albedo just below 1), `size` units wide.  One of the two triangles of the top face is drawn short by `gap` of its
+    edge, which leaves a small triangle of the face out: the way to the sky.  (A path also leaves where it meets a wall
+    within 0.001 of an edge -- the hit interval starts there -- which is why the box is large.)  The corners are moved off
+    the axis-aligned box by up to 1 % of its size: a triangle flat along an axis has a box without thickness and never hits
+    when it is alone in its leaf (bvh.rs:126), and walls that are not quite parallel spread the bounce counts.
+    4 x 4 pixels: every path has a lane of one workgroup, so a reference-order attenuation stack of max_depth records
+    stays below 1 GB."""
+    sc = Scene.new_image(1.0, 4, 24, 180.0, 1)
+    cam = sc.scene_cam
+    cam.set_samples(samples)
+    cam.set_max_depth(depth)
+    cam.look_from((0.07 * size, -0.03 * size, 0.05 * size))
+    cam.look_at((0.4 * size, 0.31 * size, -0.5 * size))
+    cam.set_vfov(80.0)
+    h = 0.5 * size
+    rs = np.random.RandomState(7)
+    c = {(i, j, k): (h * i + 0.01 * size * rs.uniform(-1, 1), h * j + 0.01 * size * rs.uniform(-1, 1), h * k + 0.01 * size * rs.uniform(-1, 1))
+         for i in (-1, 1) for j in (-1, 1) for k in (-1, 1)}
+    mirror = Metal.new((albedo, albedo, albedo), 0.0)
+    faces = []
+    for axis in range(3):
+        for side in (-1, 1):
+            q = []
+            for a, b in ((-1, -1), (1, -1), (1, 1), (-1, 1)):
+                key = [a, b]
+                key.insert(axis, side)
+                q.append(c[tuple(key)])
+            faces.append(q)
+    n = 0
+    for f, q in enumerate(faces):
+        sc.add_element(Triangle.new(q[0], q[1], q[2], mirror), f"w{n}")
+        last = q[3]
+        if f == 3:   # the top face (y = +size / 2): its second triangle stops short of the corner
+            last = tuple(q[3][k] + gap * (q[0][k] - q[3][k]) for k in range(3))
+        sc.add_element(Triangle.new(q[0], q[2], last, mirror), f"w{n + 1}")
+        n += 2
+    return sc
+
+
+def extent_scene(width, height, samples, keyed=False):
+    """A row of five spheres seen as a width x height image whose long side spans about 8 units at the focus distance,
+    however thin the other side is (65537 x 1: a strip one pixel high across the row), so that the far ends of the long
+    side still meet spheres, the ground and the sky.  keyed: the camera moves between frames (a frame batch's frames differ)."""
+    sc = few_spheres(5, samples=samples)
+    sc.add_element(Sphere.new((0.0, -100.0, 0.0), 100.0, Lambertian.new_from_color((0.5, 0.6, 0.4), 1.0)), "ground")
+    cam = sc.scene_cam
+    cam.image_width, cam.image_height = int(width), int(height)
+    cam.set_max_depth(4)
+    cam.look_at((0.0, 0.45, 0.0))
+    import math
+    vh = 8.0 * min(1.0, height / width)   # the viewport's height at the focus distance (10): its width is vh * width / height
+    cam.set_vfov(math.degrees(2.0 * math.atan(vh / 20.0)))
+    if keyed:
+        sc.cam_translate_point((0.4, 1.3, 6.2), 0.03, LERP, WORLD, "from")
+        sc.cam_translate_point((0.1, 0.5, 0.0), 0.06, NERP, WORLD, "at")
+    return sc
+
+
+def keyed_camera_scene(n_from=300, n_at=212, amp=0.3, width=8):
+    """n_from + n_at camera keyframes (CrHandle::kMaxCamKeys is 512): translations of look_from and look_at, LERP and NERP
+    in turn, every one with its own end time (a LERP key starts where the previous key of its axis ended, so 151 start times are
+    distinct among the 300 look_from keys and the rest tie with a NERP key), spread over [0, 0.09] -- frame 1 at 24 fps with a 180 degree shutter draws
+    ray times in [1/24, 1/16], so keys lie before, inside and after the exposure.  amp scales every displacement (another
+    amp: another key set of the same shape)."""
+    sc = few_spheres(4, width=width, samples=3)
+    cam = sc.scene_cam
+    cam.image_width, cam.image_height = width, width
+    cam.frame = 1
+    rs = np.random.RandomState(99)
+    for tl, base, n, dt in ((cam.look_from_tl, (0.0, 1.0, 6.0), n_from, 0.0009), (cam.look_at_tl, (0.0, 0.5, 0.0), n_at, 0.0012)):
+        for k in range(n):
+            axis, step = k % 3, k // 3
+            t = dt * (step + 1) + 0.0001 * axis
+            value = base[axis] + amp * rs.uniform(-1.0, 1.0)
+            (tl.translate_x, tl.translate_y, tl.translate_z)[axis](value, t, LERP if (step + axis) % 2 == 0 else NERP, WORLD)
+    return sc
