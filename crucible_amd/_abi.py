@@ -11,6 +11,7 @@ CR_MAT_LAMBERTIAN, CR_MAT_METAL, CR_MAT_DIELECTRIC = 0, 1, 2
 CR_TEX_SOLID, CR_TEX_CHECKER, CR_TEX_IMAGE = 0, 1, 2
 CR_SKY_DEFAULT, CR_SKY_SPHERICAL = 0, 1
 CR_BVH_REFERENCE, CR_BVH_SAH, CR_BVH_SAH_ORDERED, CR_BVH_LBVH = 0, 1, 2, 3
+CR_BVH_BUILD_DEVICE = 0x100   # OR-ed into bvh_mode: the SAH modes build on the device
 CR_KEY_TX, CR_KEY_TY, CR_KEY_TZ, CR_KEY_RADIUS, CR_KEY_SCALE_X, CR_KEY_SCALE_Y, CR_KEY_SCALE_Z = 0, 1, 2, 3, 4, 5, 6
 CR_MAX_CHECKER_DEPTH = 32
 CR_KEY_NERP, CR_KEY_LERP = 0, 1
@@ -77,6 +78,15 @@ class CrStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CrBuildInfo(C.Structure):
+    _fields_ = [("bvh_mode", C.c_int32), ("built_on_device", C.c_int32), ("n_wrappers", C.c_int32),
+                ("device_rounds", C.c_int32), ("large_nodes", C.c_int32), ("small_subtrees", C.c_int32),
+                ("small_threshold", C.c_int32), ("_pad", C.c_int32), ("tree_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "_pad"}
+
+
 class CrGroupStats(C.Structure):
     _fields_ = [("render", CrStats), ("reduce_ms", C.c_double), ("members", C.c_int32), ("used_rccl", C.c_int32)]
 
@@ -103,6 +113,7 @@ SYMBOLS = {
                                        C.POINTER(CrStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
+    "cr_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),
     "cr_update_primitives": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]),
     "cr_last_kernel_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "cr_synchronize": (C.c_int32, [C.c_void_p]),

@@ -1,8 +1,10 @@
 // build.hip -- from the handle's host copy of the scene to a precision's device copy (build_dev_scene): filters hidden
 // primitives, builds the BVH in the reference's topology (or the opt-in SAH / LBVH trees), lays tree and primitives out
-// for the device and uploads them; cr_export_bvh hands the tree back.  The only unit that includes hipcub.
+// for the device and uploads them; cr_export_bvh hands the tree back, cr_build_info what the build did.  Includes hipcub
+// (as sah_device.hip does, the driver of the device-side SAH build this unit calls under CR_BVH_BUILD_DEVICE).
 #include "handle.hpp"
 #include "lbvh.hpp"
+#include "sah_device.hpp"
 #include "pack.hpp"
 #include <hipcub/hipcub.hpp>
 
@@ -463,14 +465,31 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     bool spliced = false;
     ds.ordered = h->bvh_mode == CR_BVH_SAH_ORDERED;
     lap("primitive records and boxes");
+    const auto t_tree = std::chrono::steady_clock::now();
     const bool lbvh = h->bvh_mode == CR_BVH_LBVH;
+    const bool sah_device = h->bvh_device && (h->bvh_mode == CR_BVH_SAH || h->bvh_mode == CR_BVH_SAH_ORDERED);
+    bool device_boxes = lbvh;   // the wrapper boxes are filled in on the device after the upload
+    SahDeviceStats dev_stats;
     if (lbvh) {
         int32_t rc = build_lbvh<real>(h, src, b.bmin, b.bmax, b.order, b.entries, ds.level_begin);
         if (rc != CR_OK) return rc;
     } else if (n > 0 && h->bvh_mode != CR_BVH_REFERENCE) {
         SahBuilder<real> sb;
         sb.bmin = b.bmin; sb.bmax = b.bmax; sb.order = &b.order;
-        sb.build_root(n);
+        if (sah_device && n >= 3) {   // the node graph and the order from the device (sah_device.hpp); never the host builder
+            std::vector<double> box6((size_t)n * 6);
+            for (int32_t i = 0; i < n; i++) for (int a = 0; a < 3; a++) { box6[(size_t)i * 6 + a] = (double)b.bmin[a][i]; box6[(size_t)i * 6 + 3 + a] = (double)b.bmax[a][i]; }
+            std::vector<SahNodeRec> graph;
+            int32_t rc = build_sah_device(h, box6.data(), n, graph, b.order, dev_stats);
+            if (rc != CR_OK) return rc;
+            sb.nodes.assign(graph.size(), typename SahBuilder<real>::Node());
+            for (size_t i = 0; i < graph.size(); i++) {
+                typename SahBuilder<real>::Node& nd = sb.nodes[i];
+                nd.left = graph[i].left < 0 ? -1 : graph[i].left; nd.right = graph[i].left < 0 ? -1 : graph[i].left + 1;
+                nd.start = graph[i].start; nd.end = graph[i].end; nd.axis = graph[i].axis;
+            }
+            device_boxes = true;
+        } else sb.build_root(n);
         sb.linearise(b.entries, axis);
         relayout_bfs(b.entries, ds.level_begin, &axis);
     } else if (n > 0) {
@@ -544,6 +563,7 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     }
     else ds.level_begin.assign(1, 0);
     lap("tree");
+    const double tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tree).count();
     // Primitive records in leaf order; a list contributes its visible objects in the list's order (a hidden object
     // returns no hit before anything is computed: sphere.rs:62, triangle.rs:87).
     std::vector<Prim<real>> leaf_prims;
@@ -644,11 +664,18 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     ds.lds_bytes = r16(b.entries.size() * ds.entry_bytes) + r16(leaf_prims.size() * sizeof(Prim<real>)) +
                    r16(mats.size() * sizeof(Mat<real>)) + r16(texs.size() * sizeof(Tex<real>));
     ds.animated = any_keys;
-    if (lbvh && ds.n_entries > 0) {   // boxes: construction-time primitive boxes, bottom-up, on the device
+    if (device_boxes && ds.n_entries > 0) {   // boxes: construction-time primitive boxes, bottom-up, on the device
         int32_t rc = run_box_kernels<real>(h, ds, ds.entries.p, real(0), real(0), false);
         if (rc != CR_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(b.entries.data(), ds.entries.p, b.entries.size() * sizeof(Entry<real>), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (!ds.ordered) {
+            HIP_TRY(h, hipMemcpyAsync(b.entries.data(), ds.entries.p, b.entries.size() * sizeof(Entry<real>), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        } else {   // EntryO records: only their boxes go into the host's Entry records
+            std::vector<EntryO<real>> eo(b.entries.size());
+            HIP_TRY(h, hipMemcpyAsync(eo.data(), ds.entries.p, eo.size() * sizeof(EntryO<real>), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            for (size_t i = 0; i < eo.size(); i++) for (int k = 0; k < 6; k++) b.entries[i].b[k] = eo[i].b[k];
+        }
     }
     if (ds.n_entries > 0) {   // the f32 screening records of an f64 scene / the link-layout records of an f32 scene (pathtrace.hpp walk_round)
         int32_t rc = make_screen(h, ds, ds.entries.p, ds.screen, &ds.screen_usable);
@@ -662,6 +689,14 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     for (int32_t i = 0; i < n; i++) ds.leaf_desc[i] = objs[b.order[i]].desc;
     ds.has_bvh_elements = spliced;
     ds.built = true;
+    ds.info = CrBuildInfo();
+    ds.info.bvh_mode = h->bvh_mode;
+    ds.info.built_on_device = (lbvh || (sah_device && n >= 3)) ? 1 : 0;   // fewer than 3 primitives are one leaf, written on the host
+    ds.info.n_wrappers = ds.n_entries;
+    ds.info.device_rounds = dev_stats.rounds; ds.info.large_nodes = dev_stats.large_nodes;
+    ds.info.small_subtrees = dev_stats.small_subtrees; ds.info.small_threshold = dev_stats.small_threshold;
+    ds.info.tree_ms = tree_ms;
+    ds.info.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     h->upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return CR_OK;
 }
@@ -716,6 +751,18 @@ template int32_t build_dev_scene<double>(CrHandle*);
 }   // namespace cr
 
 using namespace cr;
+
+extern "C" int32_t cr_build_info(CrHandle* h, int32_t real_type, CrBuildInfo* out) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!out) return fail(h, CR_ERR_INVALID_ARG, "cr_build_info: null out");
+    if (real_type != CR_REAL_F32 && real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_build_info before cr_upload_scene");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int32_t rc = real_type == CR_REAL_F64 ? build_dev_scene<double>(h) : build_dev_scene<float>(h);
+    if (rc != CR_OK) return rc;
+    *out = real_type == CR_REAL_F64 ? h->s64.info : h->s32.info;
+    return CR_OK;
+}
 
 extern "C" int32_t cr_export_bvh(CrHandle* h, int32_t real_type, double* boxes, int32_t* children, int32_t* split_axis, int32_t capacity,
                       int32_t* n_wrappers) {

@@ -2,7 +2,8 @@
 // include/crucible_hip.h, a precision's device copy of the scene, and the internal functions one unit calls in another.
 // Those are hidden-visibility functions of cr:: (exports.map keeps the dynamic table to the ABI); each is defined in
 // the unit its declaration names.  A kernel instantiation is emitted by exactly one unit:
-//   build.hip          host BVH builders, the LBVH driver (lbvh.hpp, hipcub), build_dev_scene, cr_export_bvh
+//   build.hip          host BVH builders, the LBVH driver (lbvh.hpp, hipcub), build_dev_scene, cr_export_bvh, cr_build_info
+//   sah_device.hip     the device-side SAH builder of CR_BVH_BUILD_DEVICE (sah_device.hpp, hipcub)
 //   scene.hip          cr_upload_scene, refit.hpp's box kernels, the screening records, cr_update_primitives (update.hpp)
 //   render.hip         render_typed: a render's kernel arguments up to the choice of ladder; the stats epilogue
 //   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder)
@@ -70,6 +71,7 @@ template <typename real> struct DevScene {
     DevBuf desc_pos;                         // the inverse, on the device: index in the caller's primitive list -> position of its record in
                                              // `prims`, -1 where it has none (hidden); scenes without list elements only (cr_update_primitives)
     bool desc_pos_valid = false;
+    CrBuildInfo info = {};                   // what the last build of this precision did (cr_build_info)
     bool side_tables = false;                // mats / texs / keys hold the uploaded scene's (a rebuild after cr_update_primitives keeps them)
     void release() { desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
 };
@@ -78,6 +80,13 @@ template <typename real> struct DevScene {
 
 using cr::DevBuf;
 using cr::DevScene;
+
+// The device-side SAH build's working set (sah_device.hip).  Grow-only and kept on the handle, so that a rebuild of the
+// same scene allocates nothing; an upload without CR_BVH_BUILD_DEVICE and cr_destroy release it.
+struct SahDeviceWork {
+    DevBuf box, order[2], seg[2], pbins, flags, scan, tmp, slots[2], nodes, small, ctr;
+    void release() { for (DevBuf* b : {&box, &order[0], &order[1], &seg[0], &seg[1], &pbins, &flags, &scan, &tmp, &slots[0], &slots[1], &nodes, &small, &ctr}) b->release(); }
+};
 
 struct CrHandle {
     int device = 0;
@@ -91,9 +100,11 @@ struct CrHandle {
     std::vector<CrMaterial> materials;
     std::vector<CrTexture> textures;
     std::vector<CrKeyframe> keys;
-    int32_t sky_kind = 0, sky_image = -1, bvh_mode = 0;
+    int32_t sky_kind = 0, sky_image = -1, bvh_mode = 0;   // bvh_mode: the base mode, CrSceneDesc.bvh_mode's low byte
+    bool bvh_device = false;          // CR_BVH_BUILD_DEVICE: the SAH modes build on the device (sah_device.hpp)
     bool has_list_elements = false;   // some CR_PRIM_LIST / CR_PRIM_BVH record: cr_update_primitives does not apply
     DevBuf update_stage;              // cr_update_primitives: the call's rows (9 doubles each), then its indices
+    SahDeviceWork sah_work;           // build_sah_device's buffers, kept from build to build: CR_UPDATE_REBUILD sits in an edit loop
     // images are precision independent
     DevBuf images, texels;
     int32_t n_images = 0;
@@ -215,6 +226,10 @@ struct WalkChoice {
 
 // build.hip
 template <typename real> int32_t build_dev_scene(CrHandle* h);
+// sah_device.hip: the node graph and the primitive order of the SAH tree over n >= 1 boxes (6 doubles each: lo xyz, hi xyz)
+struct SahNodeRec;
+struct SahDeviceStats;
+int32_t build_sah_device(CrHandle* h, const double* boxes, int32_t n, std::vector<SahNodeRec>& nodes, std::vector<int32_t>& order, SahDeviceStats& st);
 // scene.hip
 template <typename real> int32_t run_box_kernels(CrHandle* h, DevScene<real>& ds, void* entries, real ta, real tb, bool use_keys);
 int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevBuf& out, bool* usable);

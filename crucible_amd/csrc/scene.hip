@@ -235,7 +235,10 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
         if (p.kind == CR_PRIM_SPHERE && !(p.v[3] >= 0.0)) return fail(h, CR_ERR_INVALID_ARG, "Cannot make a sphere with negative radius");   // sphere.rs:26
     }
     if (s->sky_kind != CR_SKY_DEFAULT && s->sky_kind != CR_SKY_SPHERICAL) return fail(h, CR_ERR_INVALID_ARG, "unknown sky kind");
-    if (s->bvh_mode < CR_BVH_REFERENCE || s->bvh_mode > CR_BVH_LBVH) return fail(h, CR_ERR_INVALID_ARG, "unknown bvh_mode");
+    const int32_t bvh_base = s->bvh_mode & 0xFF, bvh_flags = s->bvh_mode & ~0xFF;
+    if (s->bvh_mode < 0 || bvh_base > CR_BVH_LBVH || (bvh_flags & ~CR_BVH_BUILD_DEVICE)) return fail(h, CR_ERR_INVALID_ARG, "unknown bvh_mode");
+    if ((bvh_flags & CR_BVH_BUILD_DEVICE) && bvh_base == CR_BVH_REFERENCE)
+        return fail(h, CR_ERR_UNSUPPORTED, "CR_BVH_BUILD_DEVICE: the reference tree's stable sort has no device form (use it with CR_BVH_SAH, CR_BVH_SAH_ORDERED or CR_BVH_LBVH)");
     if (s->sky_kind == CR_SKY_SPHERICAL && (s->sky_image < 0 || s->sky_image >= s->n_images)) return fail(h, CR_ERR_INVALID_ARG, "sky image index out of range");
     for (int i = 0; i < s->n_images; i++)
         if (s->images[i].width < 1 || s->images[i].height < 1 || !s->images[i].rgb8) return fail(h, CR_ERR_INVALID_ARG, "bad image");
@@ -247,7 +250,8 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
     h->materials.assign(s->materials, s->materials + s->n_materials);
     h->textures.assign(s->textures, s->textures + s->n_textures);
     h->keys.assign(s->keys, s->keys + s->n_keys);
-    h->sky_kind = s->sky_kind; h->sky_image = s->sky_image; h->bvh_mode = s->bvh_mode;
+    h->sky_kind = s->sky_kind; h->sky_image = s->sky_image; h->bvh_mode = bvh_base; h->bvh_device = (bvh_flags & CR_BVH_BUILD_DEVICE) != 0;
+    if (!h->bvh_device) h->sah_work.release();
     h->s32.built = false; h->s64.built = false;
     h->s32.side_tables = false; h->s64.side_tables = false;
     h->has_list_elements = false;

@@ -4,7 +4,7 @@
 // Extras (not in the reference): --width, --samples, --seed, --scene-seed, --real f32|f64, --device,
 // --format ppm|p6|png (frame files: the reference's ASCII P3, binary PPM, PNG),
 // --sky FILE.hdr (Radiance map as the spherical skybox; world 5 = demo_images::garden_skybox needs it),
-// --bvh reference|sah|ordered|lbvh (the tree cr_upload_scene builds; reference = the parity mode, default), --refit (re-derive
+// --bvh reference|sah|ordered|lbvh|sah-device|ordered-device (the tree cr_upload_scene builds; reference = the parity mode, default), --refit (re-derive
 // the wrapper boxes per frame so keyframed primitives are not clipped; the reference does not),
 // --dump-desc FILE (write the flattened scene description and exit; used by the tests to check
 // this mirror against the Python one), --sum-order reference|relaxed (CrRenderParams.sum_order; default: the library's),
@@ -113,8 +113,11 @@ int main(int argc, char** argv) {
         if (!sky.empty() && world != 5) scene.load_spherical_skybox(RTWImage::load_hdr(sky));
         scene.seed = seed; scene.device = device;
         scene.real_type = real == "f64" ? CR_REAL_F64 : CR_REAL_F32;
-        if (bvh != "reference" && bvh != "sah" && bvh != "ordered" && bvh != "lbvh") { fprintf(stderr, "--bvh takes reference, sah, ordered or lbvh\n"); return 2; }
+        const bool bvh_device = bvh == "sah-device" || bvh == "ordered-device";   // CR_BVH_BUILD_DEVICE: the same tree, built on the device
+        if (bvh_device) bvh = bvh.substr(0, bvh.size() - 7);
+        if (bvh != "reference" && bvh != "sah" && bvh != "ordered" && bvh != "lbvh") { fprintf(stderr, "--bvh takes reference, sah, ordered, lbvh, sah-device or ordered-device\n"); return 2; }
         scene.bvh_mode = bvh == "sah" ? CR_BVH_SAH : (bvh == "ordered" ? CR_BVH_SAH_ORDERED : (bvh == "lbvh" ? CR_BVH_LBVH : CR_BVH_REFERENCE));
+        if (bvh_device) scene.bvh_mode |= CR_BVH_BUILD_DEVICE;
         scene.refit_boxes = refit;
         scene.gpus = std::max(1, gpus); scene.use_group = use_group;
         if (frames_per_launch < 1) { fprintf(stderr, "--frames-per-launch takes a positive count\n"); return 2; }

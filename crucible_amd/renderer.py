@@ -203,6 +203,14 @@ class Renderer:
                                            C.byref(n)))
         return boxes[:n.value], kids[:n.value], axis[:n.value]
 
+    def build_info(self, real_type=A.CR_REAL_F32):
+        """cr_build_info: which builder made the tree of `real_type` and what it went through, as a dict (bvh_mode,
+        built_on_device, n_wrappers, device_rounds, large_nodes, small_subtrees, small_threshold, tree_ms, total_ms).
+        Builds the tree if it is not built yet."""
+        info = A.CrBuildInfo()
+        self._check(self.lib.cr_build_info(self.h, real_type, C.byref(info)))
+        return info.as_dict()
+
     def last_kernel_ms(self):
         ms = C.c_double()
         self._check(self.lib.cr_last_kernel_ms(self.h, C.byref(ms)))

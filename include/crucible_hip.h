@@ -199,8 +199,23 @@ typedef struct CrKeyframe {
  *                     primitive-box centroids, radix sort, Karras' topology; one primitive per leaf) in a few
  *                     milliseconds instead of the host builders' 0.3-0.4 s per million primitives.  Walked in
  *                     BVHWrapper::hit's order like CR_BVH_SAH; a lower-quality tree than SAH.
+ *
+ * CR_BVH_BUILD_DEVICE is a flag OR-ed into bvh_mode (the low byte keeps the mode):
+ *   with CR_BVH_SAH / CR_BVH_SAH_ORDERED  the same tree -- children, split_axis, boxes and primitive order, wrapper for
+ *                     wrapper -- built on the device instead of on the host: level-synchronous rounds over the large
+ *                     ranges, one wave per small subtree.  Meant for large scenes that are edited or
+ *                     animated with CR_UPDATE_REBUILD.  Its build time has NOT been measured against the host
+ *                     builder's yet: expect it to lose on small scenes, where the host needs 0.2 ms
+ *                     for book1 and a round of kernel launches costs more.  A caller's choice, never switched on by the
+ *                     library; never a silent fallback either:
+ *                     a device failure is CR_ERR_HIP.  CRUCIBLE_SAH_SMALL=<n> (read at every build) sets the span up to
+ *                     which one wave finishes a subtree.
+ *   with CR_BVH_LBVH  accepted, changes nothing (that tree is device-built already);
+ *   with CR_BVH_REFERENCE  CR_ERR_UNSUPPORTED: the median split's stable sort has no device form.
+ * Any other bit is CR_ERR_INVALID_ARG.
  */
 enum { CR_BVH_REFERENCE = 0, CR_BVH_SAH = 1, CR_BVH_SAH_ORDERED = 2, CR_BVH_LBVH = 3 };
+enum { CR_BVH_BUILD_DEVICE = 0x100 };
 
 typedef struct CrSceneDesc {
     int32_t n_prims;
@@ -210,7 +225,7 @@ typedef struct CrSceneDesc {
     int32_t n_keys;
     int32_t sky_kind;
     int32_t sky_image;
-    int32_t bvh_mode;       /* CR_BVH_REFERENCE (0) | CR_BVH_SAH | CR_BVH_SAH_ORDERED | CR_BVH_LBVH */
+    int32_t bvh_mode;       /* CR_BVH_REFERENCE (0) | CR_BVH_SAH | CR_BVH_SAH_ORDERED | CR_BVH_LBVH, optionally | CR_BVH_BUILD_DEVICE */
     const CrPrimitive* prims;
     const CrMaterial* materials;
     const CrTexture* textures;
@@ -455,6 +470,27 @@ CR_API int32_t cr_export_bvh(CrHandle* h, int32_t real_type, double* boxes, int3
                              int32_t capacity, int32_t* n_wrappers);
 
 /*
+ * What the build of the uploaded scene's tree did, for one real type: which builder ran and the phases it went through
+ * (the laps CRUCIBLE_BUILD_TIMING prints).  Builds the tree if it is not built yet, as cr_export_bvh does.
+ * CR_ERR_INVALID_ARG for a null handle, a null `out` or an unknown real_type; CR_ERR_NO_SCENE before an upload.
+ */
+typedef struct CrBuildInfo {
+    int32_t bvh_mode;          /* base mode (without CR_BVH_BUILD_DEVICE) */
+    int32_t built_on_device;   /* 1: CR_BVH_LBVH, or a SAH mode with CR_BVH_BUILD_DEVICE over at least 3 primitives (fewer are one leaf,
+                                  which the host writes: 0, with small_threshold 0) */
+    int32_t n_wrappers;
+    int32_t device_rounds;     /* device SAH build: level-synchronous rounds run */
+    int32_t large_nodes;       /* ... nodes split in those rounds */
+    int32_t small_subtrees;    /* ... subtrees finished by one wave each */
+    int32_t small_threshold;   /* ... the span limit in effect (0 when that builder did not run) */
+    int32_t _pad;
+    double tree_ms;            /* the tree phase alone: topology and primitive order (the device builders fill the
+                                  wrapper boxes after the upload: that is in total_ms) */
+    double total_ms;           /* the whole build, uploads included */
+} CrBuildInfo;
+CR_API int32_t cr_build_info(CrHandle* h, int32_t real_type, CrBuildInfo* out);
+
+/*
  * Edit primitives of the uploaded scene in place: new coordinates for n spheres / triangles, without another
  * cr_upload_scene.  prim_index[k] is an index into the CrSceneDesc.prims of the last upload (NULL: 0..n-1) and
  * v + 9k its new CrPrimitive.v: a sphere reads v[0..3] (what it stores beyond them is kept), a triangle all nine.
@@ -472,7 +508,7 @@ CR_API int32_t cr_export_bvh(CrHandle* h, int32_t real_type, double* boxes, int3
  *                      travel far leave large, overlapping boxes (correct, slower to walk).  A precision not built yet
  *                      builds at first use from the edited description; a hidden primitive changes in the host copy
  *                      only.  refit_boxes and the stale-box default behave as after an upload of the edited description.
- *   CR_UPDATE_REBUILD  the same edit, after which the trees are rebuilt by the scene's bvh_mode builder at next use: the
+ *   CR_UPDATE_REBUILD  the same edit, after which the trees are rebuilt by the scene's bvh_mode builder (on the device under CR_BVH_BUILD_DEVICE) at next use: the
  *                      handle is then what a cr_upload_scene of the edited description leaves, without re-uploading
  *                      images, materials, textures and keys.
  *
