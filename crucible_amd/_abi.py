@@ -17,6 +17,18 @@ CR_MAX_CHECKER_DEPTH = 32
 CR_KEY_NERP, CR_KEY_LERP = 0, 1
 CR_SUM_DEFAULT, CR_SUM_REFERENCE_ORDER, CR_SUM_RELAXED = 0, 1, 2
 CR_UPDATE_REFIT, CR_UPDATE_REBUILD = 0, 1   # cr_update_primitives flags
+CR_REFIT_OFF, CR_REFIT_BOXES, CR_REFIT_REBUILD = 0, 1, 2   # CrRenderParams.refit_boxes
+
+
+def refit_code(value):
+    """CrRenderParams.refit_boxes from what the mirrors accept: False / True / "rebuild" (or one of the codes)."""
+    if isinstance(value, str):
+        if value != "rebuild":
+            raise ValueError(f"refit_boxes: {value!r} is not False, True or 'rebuild'")
+        return CR_REFIT_REBUILD
+    if value is True or value is False or value is None:
+        return CR_REFIT_BOXES if value else CR_REFIT_OFF
+    return int(value)
 CR_AOV_ALBEDO, CR_AOV_NORMAL, CR_AOV_DEPTH, CR_AOV_COVERAGE = 1, 2, 4, 8   # cr_render_aov_* layers
 CR_AOV_ALL = 15
 # the planes of a guide-layer buffer in their order (ascending bit): name, bit, channels
@@ -114,6 +126,9 @@ SYMBOLS = {
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
     "cr_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),
+    "cr_export_render_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.POINTER(C.c_int32)]),
+    "cr_frame_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),
     "cr_update_primitives": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]),
     "cr_last_kernel_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "cr_synchronize": (C.c_int32, [C.c_void_p]),

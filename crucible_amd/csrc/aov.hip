@@ -44,10 +44,11 @@ __global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long l
 
 template <typename real>
 int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats) {
-    int32_t rc = build_dev_scene<real>(h);
+    DevScene<real>* walk = nullptr;
+    bool refit = false;
+    int32_t rc = select_tree<real>(h, p, false, &walk, &refit);   // as a render decides it
     if (rc != CR_OK) return rc;
-    DevScene<real>& ds = dev_scene<real>(h);
-    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;   // as a render decides it
+    DevScene<real>& ds = *walk;
     const size_t npix = (size_t)cd->image_width * (size_t)cd->image_height;
     hipError_t e = h->aov_acc.ensure(npix * kAovWords * sizeof(unsigned long long));
     if (e == hipSuccess) e = h->aov_flags.ensure(npix * sizeof(uint32_t));
@@ -62,6 +63,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         // the walk is the megakernel's under every pipeline setting: the cross-check pipelines have no guide pass of their own
         rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, nullptr, 1, times, a.k, w, fb);
         if (rc != CR_OK) return rc;
+        dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
         a.k.tiles_x = ((uint32_t)cd->image_width + 3u) >> 2; a.k.tiles_y = ((uint32_t)cd->image_height + 3u) >> 2;
         a.k.fx_scale = fx_scale_for(p->samples);   // of the whole frame, so that the words of shards add up
         a.acc = (unsigned long long*)h->aov_acc.p; a.flags = (uint32_t*)h->aov_flags.p;

@@ -206,7 +206,7 @@ void cr_destroy(CrHandle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->s32.release(); h->s64.release(); h->update_stage.release(); h->sah_work.release();
+    h->s32.release(); h->s64.release(); h->f32.release(); h->f64.release(); h->update_stage.release(); h->sah_work.release();
     h->images.release(); h->texels.release(); h->work_counter.release(); h->counters.release();
     h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release(); h->aov_acc.release(); h->aov_flags.release();
     h->wf_job.release(); h->wf_rng.release(); h->wf_ray.release(); h->wf_depth.release(); h->wf_hit_t.release(); h->wf_hit_prim.release();

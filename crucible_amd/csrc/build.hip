@@ -1,11 +1,13 @@
 // build.hip -- from the handle's host copy of the scene to a precision's device copy (build_dev_scene): filters hidden
 // primitives, builds the BVH in the reference's topology (or the opt-in SAH / LBVH trees), lays tree and primitives out
-// for the device and uploads them; cr_export_bvh hands the tree back, cr_build_info what the build did.  Includes hipcub
+// for the device and uploads them; cr_export_bvh hands the tree back, cr_build_info what the build did.  Also the second
+// tree of refit_boxes = CR_REFIT_REBUILD (build_frame_scene, select_tree; cr_export_render_bvh, cr_frame_build_info).  Includes hipcub
 // (as sah_device.hip does, the driver of the device-side SAH build this unit calls under CR_BVH_BUILD_DEVICE).
 #include "handle.hpp"
 #include "lbvh.hpp"
 #include "sah_device.hpp"
 #include "pack.hpp"
+#include "refit.hpp"
 #include <hipcub/hipcub.hpp>
 
 #include <atomic>
@@ -356,6 +358,103 @@ int32_t build_lbvh(CrHandle* h, const std::vector<Prim<real>>& src, const std::v
     return CR_OK;
 }
 
+// The CR_BVH_SAH / CR_BVH_SAH_ORDERED tree over n >= 1 primitive boxes: the pre-order wrappers re-laid
+// level by level, the split axes and the primitive order.  on_device: the node graph and the order come from the device
+// builder (sah_device.hpp), never the host's -- from bmin / bmax, or, resident, from the boxes h->sah_work.box already
+// holds (bmin / bmax are then not read); the wrapper boxes are left for run_box_kernels.  Otherwise the host SahBuilder.
+template <typename real>
+int32_t sah_tree(CrHandle* h, const std::vector<real>* bmin, const std::vector<real>* bmax, int32_t n, bool on_device, bool resident,
+                 std::vector<int32_t>& order, std::vector<Entry<real>>& entries, std::vector<int8_t>& axis, std::vector<int32_t>& level_begin,
+                 SahDeviceStats& dev_stats) {
+    SahBuilder<real> sb;
+    sb.bmin = bmin; sb.bmax = bmax; sb.order = &order;
+    if (on_device) {
+        std::vector<SahNodeRec> graph;
+        int32_t rc;
+        if (resident) rc = build_sah_device_resident(h, n, graph, order, dev_stats);
+        else {
+            std::vector<double> box6((size_t)n * 6);
+            for (int32_t i = 0; i < n; i++) for (int a = 0; a < 3; a++) { box6[(size_t)i * 6 + a] = (double)bmin[a][i]; box6[(size_t)i * 6 + 3 + a] = (double)bmax[a][i]; }
+            rc = build_sah_device(h, box6.data(), n, graph, order, dev_stats);
+        }
+        if (rc != CR_OK) return rc;
+        sb.nodes.assign(graph.size(), typename SahBuilder<real>::Node());
+        for (size_t i = 0; i < graph.size(); i++) {
+            typename SahBuilder<real>::Node& nd = sb.nodes[i];
+            nd.left = graph[i].left < 0 ? -1 : graph[i].left; nd.right = graph[i].left < 0 ? -1 : graph[i].left + 1;
+            nd.start = graph[i].start; nd.end = graph[i].end; nd.axis = graph[i].axis;
+        }
+    } else sb.build_root(n);
+    sb.linearise(entries, axis);
+    relayout_bfs(entries, level_begin, &axis);
+    return CR_OK;
+}
+
+static hipError_t upload(DevBuf& d, const void* src_p, size_t bytes, size_t front_pad = 0) {
+    hipError_t e = d.ensure(bytes ? bytes : 16, front_pad);
+    if (e != hipSuccess) return e;
+    if (bytes) return hipMemcpy(d.p, src_p, bytes, hipMemcpyHostToDevice);
+    return hipSuccess;
+}
+
+// The wrapper array onto the device in the layout of the mode: `entries` with the links of `dev_entries` (the same records,
+// or those that name primitive runs), or under CR_BVH_SAH_ORDERED the EntryO records with their per-octant links.
+template <typename real>
+int32_t upload_entries(CrHandle* h, DevScene<real>& ds, const std::vector<Entry<real>>& entries, const std::vector<Entry<real>>& dev_entries,
+                       const std::vector<int8_t>& axis) {
+    ds.entry_bytes = ds.ordered ? sizeof(EntryO<real>) : sizeof(Entry<real>);
+    if (ds.ordered) {   // per-octant skip links, parents before children (level order)
+        const int32_t ne = (int32_t)entries.size();
+        std::vector<EntryO<real>> eo((size_t)ne);
+        for (int32_t i = 0; i < ne; i++) {
+            for (int k = 0; k < 6; k++) eo[i].b[k] = entries[i].b[k];
+            eo[i].unused = 0;
+            const int32_t leaf = entries[i].leaf;
+            eo[i].leaf = leaf < 0 ? -((-leaf) * 4 + axis[i]) : leaf;
+        }
+        if (ne > 0) for (int o = 0; o < 8; o++) eo[0].skip[o] = ne;
+        for (int32_t i = 0; i < ne; i++) {
+            const int32_t leaf = entries[i].leaf;
+            if (leaf >= 0) continue;
+            const int32_t left = -leaf;
+            for (int o = 0; o < 8; o++) {
+                const int32_t nearc = left + ((o >> axis[i]) & 1), farc = left + 1 - ((o >> axis[i]) & 1);
+                eo[nearc].skip[o] = farc;
+                eo[farc].skip[o] = eo[i].skip[o];
+            }
+        }
+        HIP_TRY(h, upload(ds.entries, eo.data(), eo.size() * sizeof(EntryO<real>), entry_pad<EntryO<real>>()));
+    } else
+    HIP_TRY(h, upload(ds.entries, dev_entries.data(), dev_entries.size() * sizeof(Entry<real>), entry_pad<Entry<real>>()));
+    return CR_OK;
+}
+
+// After the uploads: where the builder left the wrapper boxes to the device (device_boxes), run_box_kernels fills them --
+// the construction-time boxes, or with use_keys the boxes over the ray times [ta, tb] -- and the host's records take them
+// back; then the f32 screening records of an f64 scene / the link-layout records of an f32 scene (pathtrace.hpp walk_round).
+template <typename real>
+int32_t finish_boxes(CrHandle* h, DevScene<real>& ds, std::vector<Entry<real>>& entries, bool device_boxes, real ta, real tb, bool use_keys) {
+    if (device_boxes && ds.n_entries > 0) {
+        int32_t rc = run_box_kernels<real>(h, ds, ds.entries.p, ta, tb, use_keys);
+        if (rc != CR_OK) return rc;
+        if (!ds.ordered) {
+            HIP_TRY(h, hipMemcpyAsync(entries.data(), ds.entries.p, entries.size() * sizeof(Entry<real>), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        } else {   // EntryO records: only their boxes go into the host's Entry records
+            std::vector<EntryO<real>> eo(entries.size());
+            HIP_TRY(h, hipMemcpyAsync(eo.data(), ds.entries.p, eo.size() * sizeof(EntryO<real>), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            for (size_t i = 0; i < eo.size(); i++) for (int k = 0; k < 6; k++) entries[i].b[k] = eo[i].b[k];
+        }
+    }
+    if (ds.n_entries > 0) {
+        int32_t rc = make_screen(h, ds, ds.entries.p, ds.screen, &ds.screen_usable);
+        if (rc != CR_OK) return rc;
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    } else ds.screen.release();
+    return CR_OK;
+}
+
 template <typename real> int32_t build_dev_scene(CrHandle* h) {
     DevScene<real>& ds = dev_scene<real>(h);
     if (ds.built) return CR_OK;
@@ -474,24 +573,9 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
         int32_t rc = build_lbvh<real>(h, src, b.bmin, b.bmax, b.order, b.entries, ds.level_begin);
         if (rc != CR_OK) return rc;
     } else if (n > 0 && h->bvh_mode != CR_BVH_REFERENCE) {
-        SahBuilder<real> sb;
-        sb.bmin = b.bmin; sb.bmax = b.bmax; sb.order = &b.order;
-        if (sah_device && n >= 3) {   // the node graph and the order from the device (sah_device.hpp); never the host builder
-            std::vector<double> box6((size_t)n * 6);
-            for (int32_t i = 0; i < n; i++) for (int a = 0; a < 3; a++) { box6[(size_t)i * 6 + a] = (double)b.bmin[a][i]; box6[(size_t)i * 6 + 3 + a] = (double)b.bmax[a][i]; }
-            std::vector<SahNodeRec> graph;
-            int32_t rc = build_sah_device(h, box6.data(), n, graph, b.order, dev_stats);
-            if (rc != CR_OK) return rc;
-            sb.nodes.assign(graph.size(), typename SahBuilder<real>::Node());
-            for (size_t i = 0; i < graph.size(); i++) {
-                typename SahBuilder<real>::Node& nd = sb.nodes[i];
-                nd.left = graph[i].left < 0 ? -1 : graph[i].left; nd.right = graph[i].left < 0 ? -1 : graph[i].left + 1;
-                nd.start = graph[i].start; nd.end = graph[i].end; nd.axis = graph[i].axis;
-            }
-            device_boxes = true;
-        } else sb.build_root(n);
-        sb.linearise(b.entries, axis);
-        relayout_bfs(b.entries, ds.level_begin, &axis);
+        int32_t rc = sah_tree<real>(h, b.bmin, b.bmax, n, sah_device && n >= 3, false, b.order, b.entries, axis, ds.level_begin, dev_stats);
+        if (rc != CR_OK) return rc;
+        device_boxes = sah_device && n >= 3;
     } else if (n > 0) {
         b.build_root(n);
         if (!inners.empty()) {
@@ -613,80 +697,41 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
     if (!keys.empty()) memset(keys.data(), 0, keys.size() * sizeof(Key<real>));
     for (size_t i = 0; i < h->keys.size(); i++) key_to_real(h->keys[i], keys[i]);
 
-    auto up = [&](DevBuf& d, const void* src_p, size_t bytes, size_t front_pad = 0) -> hipError_t {
-        hipError_t e = d.ensure(bytes ? bytes : 16, front_pad);
-        if (e != hipSuccess) return e;
-        if (bytes) return hipMemcpy(d.p, src_p, bytes, hipMemcpyHostToDevice);
-        return hipSuccess;
-    };
-    ds.entry_bytes = ds.ordered ? sizeof(EntryO<real>) : sizeof(Entry<real>);
-    if (ds.ordered) {   // per-octant skip links, parents before children (level order)
-        const int32_t ne = (int32_t)b.entries.size();
-        std::vector<EntryO<real>> eo((size_t)ne);
-        for (int32_t i = 0; i < ne; i++) {
-            for (int k = 0; k < 6; k++) eo[i].b[k] = b.entries[i].b[k];
-            eo[i].unused = 0;
-            const int32_t leaf = b.entries[i].leaf;
-            eo[i].leaf = leaf < 0 ? -((-leaf) * 4 + axis[i]) : leaf;
-        }
-        if (ne > 0) for (int o = 0; o < 8; o++) eo[0].skip[o] = ne;
-        for (int32_t i = 0; i < ne; i++) {
-            const int32_t leaf = b.entries[i].leaf;
-            if (leaf >= 0) continue;
-            const int32_t left = -leaf;
-            for (int o = 0; o < 8; o++) {
-                const int32_t nearc = left + ((o >> axis[i]) & 1), farc = left + 1 - ((o >> axis[i]) & 1);
-                eo[nearc].skip[o] = farc;
-                eo[farc].skip[o] = eo[i].skip[o];
-            }
-        }
-        HIP_TRY(h, up(ds.entries, eo.data(), eo.size() * sizeof(EntryO<real>), entry_pad<EntryO<real>>()));
-    } else
-    HIP_TRY(h, up(ds.entries, up_entries.data(), up_entries.size() * sizeof(Entry<real>), entry_pad<Entry<real>>()));
-    HIP_TRY(h, up(ds.leaf_runs, leaf_runs.data(), leaf_runs.size() * sizeof(int32_t)));
+    { int32_t rc = upload_entries<real>(h, ds, b.entries, up_entries, axis); if (rc != CR_OK) return rc; }
+    HIP_TRY(h, upload(ds.leaf_runs, leaf_runs.data(), leaf_runs.size() * sizeof(int32_t)));
     ds.has_leaf_runs = !leaf_runs.empty();
     ds.has_lists = any_lists;
-    HIP_TRY(h, up(ds.prims, leaf_prims.data(), leaf_prims.size() * sizeof(Prim<real>)));
+    HIP_TRY(h, upload(ds.prims, leaf_prims.data(), leaf_prims.size() * sizeof(Prim<real>)));
     if (!ds.side_tables) {   // a rebuild after cr_update_primitives: these still hold the uploaded scene's
-        HIP_TRY(h, up(ds.mats, mats.data(), mats.size() * sizeof(Mat<real>)));
-        HIP_TRY(h, up(ds.texs, texs.data(), texs.size() * sizeof(Tex<real>)));
-        HIP_TRY(h, up(ds.keys, keys.data(), keys.size() * sizeof(Key<real>)));
+        HIP_TRY(h, upload(ds.mats, mats.data(), mats.size() * sizeof(Mat<real>)));
+        HIP_TRY(h, upload(ds.texs, texs.data(), texs.size() * sizeof(Tex<real>)));
+        HIP_TRY(h, upload(ds.keys, keys.data(), keys.size() * sizeof(Key<real>)));
         ds.side_tables = true;
     }
     ds.desc_pos_valid = !any_lists && !spliced && !h->has_list_elements;
     if (ds.desc_pos_valid) {   // every object is one primitive: record i of leaf_prims is objs[b.order[i]]
         std::vector<int32_t> pos(h->prims.size(), -1);
         for (int32_t i = 0; i < n; i++) pos[(size_t)objs[b.order[i]].desc] = i;
-        HIP_TRY(h, up(ds.desc_pos, pos.data(), pos.size() * sizeof(int32_t)));
+        HIP_TRY(h, upload(ds.desc_pos, pos.data(), pos.size() * sizeof(int32_t)));
     }
     ds.n_entries = (int32_t)b.entries.size(); ds.n_prims = (int32_t)leaf_prims.size(); ds.n_mats = (int32_t)mats.size(); ds.n_texs = (int32_t)texs.size();
     ds.n_scene_keys = (int32_t)h->keys.size();
     ds.lds_bytes = r16(b.entries.size() * ds.entry_bytes) + r16(leaf_prims.size() * sizeof(Prim<real>)) +
                    r16(mats.size() * sizeof(Mat<real>)) + r16(texs.size() * sizeof(Tex<real>));
     ds.animated = any_keys;
-    if (device_boxes && ds.n_entries > 0) {   // boxes: construction-time primitive boxes, bottom-up, on the device
-        int32_t rc = run_box_kernels<real>(h, ds, ds.entries.p, real(0), real(0), false);
-        if (rc != CR_OK) return rc;
-        if (!ds.ordered) {
-            HIP_TRY(h, hipMemcpyAsync(b.entries.data(), ds.entries.p, b.entries.size() * sizeof(Entry<real>), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-        } else {   // EntryO records: only their boxes go into the host's Entry records
-            std::vector<EntryO<real>> eo(b.entries.size());
-            HIP_TRY(h, hipMemcpyAsync(eo.data(), ds.entries.p, eo.size() * sizeof(EntryO<real>), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            for (size_t i = 0; i < eo.size(); i++) for (int k = 0; k < 6; k++) b.entries[i].b[k] = eo[i].b[k];
-        }
-    }
-    if (ds.n_entries > 0) {   // the f32 screening records of an f64 scene / the link-layout records of an f32 scene (pathtrace.hpp walk_round)
-        int32_t rc = make_screen(h, ds, ds.entries.p, ds.screen, &ds.screen_usable);
-        if (rc != CR_OK) return rc;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    } else ds.screen.release();
+    // device builders: the construction-time primitive boxes, bottom-up, on the device; then the screening records
+    { int32_t rc = finish_boxes<real>(h, ds, b.entries, device_boxes, real(0), real(0), false); if (rc != CR_OK) return rc; }
     lap("uploads and boxes");
     ds.host_entries = b.entries;
     ds.host_axis = axis;
     ds.leaf_desc.resize(n);
     for (int32_t i = 0; i < n; i++) ds.leaf_desc[i] = objs[b.order[i]].desc;
+    ds.in_desc.resize(n);
+    for (int32_t i = 0; i < n; i++) ds.in_desc[i] = objs[i].desc;
+    ds.base_order = b.order;
+    frame_scene<real>(h).frame_valid = false;   // built from the tree this one replaces
+    frame_scene<real>(h).info = CrBuildInfo();
+    ds.last_walk = kWalkNone;
     ds.has_bvh_elements = spliced;
     ds.built = true;
     ds.info = CrBuildInfo();
@@ -705,14 +750,11 @@ template <typename real> int32_t build_dev_scene(CrHandle* h) {
 // wrapper = box + left/right child) in walk order.  A leaf wrapper of one primitive holds it twice, as the
 // reference's span-1 wrappers do (bvhwrapper.rs:58-60).
 template <typename real>
-int32_t export_bvh(CrHandle* h, double* boxes, int32_t* children, int32_t* split_axis, int32_t capacity, int32_t* n_out) {
-    int32_t rc = build_dev_scene<real>(h);
-    if (rc != CR_OK) return rc;
-    const DevScene<real>& ds = dev_scene<real>(h);
-    if (ds.has_bvh_elements) return fail(h, CR_ERR_UNSUPPORTED, "cr_export_bvh: the scene holds a BVHWrapper element (CR_BVH_REFERENCE): its records are not two-children wrappers");
-    const std::vector<Entry<real>>& E = ds.host_entries;
+int32_t export_tree(CrHandle* h, const DevScene<real>& ds, const std::vector<Entry<real>>& E, const char* what, double* boxes, int32_t* children,
+                    int32_t* split_axis, int32_t capacity, int32_t* n_out) {
+    if (ds.has_bvh_elements) return fail(h, CR_ERR_UNSUPPORTED, std::string(what) + ": the scene holds a BVHWrapper element (CR_BVH_REFERENCE): its records are not two-children wrappers");
     *n_out = (int32_t)E.size();
-    if (!boxes || !children || capacity < (int32_t)E.size()) return E.empty() || (!boxes && !children) ? CR_OK : fail(h, CR_ERR_INVALID_ARG, "cr_export_bvh: capacity too small");
+    if (!boxes || !children || capacity < (int32_t)E.size()) return E.empty() || (!boxes && !children) ? CR_OK : fail(h, CR_ERR_INVALID_ARG, std::string(what) + ": capacity too small");
     if (E.empty()) return CR_OK;
     struct Frame { int32_t entry, out, state; };
     std::vector<Frame> fr{{0, -1, 0}};
@@ -745,8 +787,151 @@ int32_t export_bvh(CrHandle* h, double* boxes, int32_t* children, int32_t* split
     return CR_OK;
 }
 
+template <typename real>
+int32_t export_bvh(CrHandle* h, double* boxes, int32_t* children, int32_t* split_axis, int32_t capacity, int32_t* n_out) {
+    int32_t rc = build_dev_scene<real>(h);
+    if (rc != CR_OK) return rc;
+    const DevScene<real>& ds = dev_scene<real>(h);
+    return export_tree<real>(h, ds, ds.host_entries, "cr_export_bvh", boxes, children, split_axis, capacity, n_out);
+}
+
+// ---------------------------------------------------------------- CR_REFIT_REBUILD: the tree of one frame
+// A second tree beside the base tree of a SAH mode: section 6.1's binned SAH over the visible primitives' motion boxes
+// for the ray times [ta, tb] (prim_box_over, the box a refit gives a one-primitive leaf), with the wrapper boxes a refit
+// derives for that topology.  The primitives, their order and the builders are build_dev_scene's; the records are gathered
+// on the device from the base tree's, and materials, textures and keys are the base tree's own buffers.  Kept on the handle
+// and reused while the interval stays the same.
+template <typename real> int32_t build_frame_scene(CrHandle* h, real ta, real tb) {
+    DevScene<real>& base = dev_scene<real>(h);
+    DevScene<real>& fs = frame_scene<real>(h);
+    if (fs.frame_valid && fs.frame_ta == ta && fs.frame_tb == tb) return CR_OK;
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int32_t n = base.n_prims;
+    if (base.has_lists || base.has_bvh_elements || base.in_desc.size() != (size_t)n || base.base_order.size() != (size_t)n || n < 1)
+        return fail(h, CR_ERR_UNSUPPORTED, "CR_REFIT_REBUILD: the base tree is not a SAH tree over single primitives");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier render may still walk the frame tree this build overwrites
+    fs.frame_valid = false; fs.built = false;
+    fs.info = CrBuildInfo();
+    // the side tables are the base tree's (not owned: a DevBuf without an allocation of its own releases nothing)
+    for (auto pr : {std::make_pair(&fs.mats, &base.mats), std::make_pair(&fs.texs, &base.texs), std::make_pair(&fs.keys, &base.keys)}) {
+        pr.first->p = pr.second->p; pr.first->raw = nullptr; pr.first->bytes = pr.second->bytes; pr.first->pad = pr.second->pad;
+    }
+    fs.ordered = base.ordered; fs.animated = base.animated; fs.has_triangles = base.has_triangles; fs.has_spheres = base.has_spheres;
+    fs.has_leaf_runs = false; fs.has_lists = false; fs.has_bvh_elements = false; fs.desc_pos_valid = false;
+    fs.n_mats = base.n_mats; fs.n_texs = base.n_texs; fs.n_scene_keys = base.n_scene_keys;
+    const bool on_device = h->bvh_device && n >= 3;   // fewer are one leaf, written on the host (as in build_dev_scene)
+    const dim3 block(256), grid((unsigned)((n + 255) / 256));
+    HIP_TRY(h, fs.frame_map.ensure((size_t)n * 2 * sizeof(int32_t)));
+    int32_t* d_input_of = (int32_t*)fs.frame_map.p;
+    int32_t* d_src = d_input_of + n;
+    std::vector<real> bmin[3], bmax[3];
+    const auto t_tree = std::chrono::steady_clock::now();
+    if (on_device) {   // the motion boxes straight into the builder's input: no host pass over the primitives
+        HIP_TRY(h, h->sah_work.box.ensure((size_t)n * 48));
+        HIP_TRY(h, hipMemcpyAsync(d_input_of, base.base_order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL((motion_boxes_kernel<real>), grid, block, 0, h->stream, (const Prim<real>*)base.prims.p, (const int32_t*)d_input_of, n,
+                           (const Key<real>*)base.keys.p, ta, tb, (double*)h->sah_work.box.p);
+        HIP_TRY(h, hipGetLastError());
+    } else {           // the same rule on the host (CR_HD), from the handle's copy of the scene
+        std::vector<Key<real>> keys(h->keys.size() + 1);
+        memset(keys.data(), 0, keys.size() * sizeof(Key<real>));
+        for (size_t i = 0; i < h->keys.size(); i++) key_to_real(h->keys[i], keys[i]);
+        for (int a = 0; a < 3; a++) { bmin[a].resize(n); bmax[a].resize(n); }
+        for (int32_t j = 0; j < n; j++) {
+            const Prim<real> q = pack_prim<real>(h->prims[(size_t)base.in_desc[j]]);
+            real lo[3], hi[3];
+            for (int a = 0; a < 3; a++) { lo[a] = r_inf(real(0)); hi[a] = -r_inf(real(0)); }
+            prim_box_over(q, keys.data(), ta, tb, lo, hi, true);
+            for (int a = 0; a < 3; a++) { bmin[a][j] = lo[a]; bmax[a][j] = hi[a]; }
+        }
+    }
+    std::vector<int32_t> order((size_t)n);
+    for (int32_t i = 0; i < n; i++) order[i] = i;
+    std::vector<Entry<real>> entries;
+    std::vector<int8_t> axis;
+    SahDeviceStats dev_stats;
+    int32_t rc = sah_tree<real>(h, bmin, bmax, n, on_device, true, order, entries, axis, fs.level_begin, dev_stats);
+    if (rc != CR_OK) return rc;
+    const double tree_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tree).count();
+    // the records in the frame tree's leaf order: position i holds builder input order[i], which the base tree keeps at inv[order[i]]
+    std::vector<int32_t> inv((size_t)n), src((size_t)n);
+    for (int32_t i = 0; i < n; i++) inv[(size_t)base.base_order[i]] = i;
+    for (int32_t i = 0; i < n; i++) src[i] = inv[(size_t)order[i]];
+    HIP_TRY(h, hipMemcpyAsync(d_src, src.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, fs.prims.ensure((size_t)n * sizeof(Prim<real>)));
+    hipLaunchKernelGGL((gather_prims_kernel<real>), grid, block, 0, h->stream, (const Prim<real>*)base.prims.p, (const int32_t*)d_src, n, (Prim<real>*)fs.prims.p);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // `src` and the base order were read from host vectors
+    rc = upload_entries<real>(h, fs, entries, entries, axis);
+    if (rc != CR_OK) return rc;
+    fs.n_entries = (int32_t)entries.size(); fs.n_prims = n;
+    fs.lds_bytes = r16(entries.size() * fs.entry_bytes) + r16((size_t)n * sizeof(Prim<real>)) + r16((size_t)fs.n_mats * sizeof(Mat<real>)) + r16((size_t)fs.n_texs * sizeof(Tex<real>));
+    // the boxes a refit gives this topology for [ta, tb], on the device for either builder; then the screening records
+    rc = finish_boxes<real>(h, fs, entries, true, ta, tb, true);
+    if (rc != CR_OK) return rc;
+    fs.host_entries.swap(entries);
+    fs.host_axis.swap(axis);
+    fs.leaf_desc.resize(n);
+    for (int32_t i = 0; i < n; i++) fs.leaf_desc[i] = base.in_desc[(size_t)order[i]];
+    fs.built = true;
+    fs.frame_valid = true; fs.frame_ta = ta; fs.frame_tb = tb;
+    fs.info.bvh_mode = h->bvh_mode;
+    fs.info.built_on_device = on_device ? 1 : 0;
+    fs.info.n_wrappers = fs.n_entries;
+    fs.info.device_rounds = dev_stats.rounds; fs.info.large_nodes = dev_stats.large_nodes;
+    fs.info.small_subtrees = dev_stats.small_subtrees; fs.info.small_threshold = dev_stats.small_threshold;
+    fs.info.tree_ms = tree_ms;
+    fs.info.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return CR_OK;
+}
+
+template <typename real> int32_t select_tree(CrHandle* h, const CrRenderParams* p, bool batch, DevScene<real>** walk, bool* refit) {
+    const bool rebuild = p->refit_boxes == CR_REFIT_REBUILD;
+    if (rebuild && h->bvh_mode != CR_BVH_SAH && h->bvh_mode != CR_BVH_SAH_ORDERED)
+        return fail(h, CR_ERR_UNSUPPORTED, "CR_REFIT_REBUILD builds the binned-SAH tree of the frame: it needs a scene uploaded with CR_BVH_SAH or CR_BVH_SAH_ORDERED");
+    int32_t rc = build_dev_scene<real>(h);
+    if (rc != CR_OK) return rc;
+    DevScene<real>& ds = dev_scene<real>(h);
+    *walk = &ds;
+    // without primitive keys the boxes would not change -- unless a HitList element's box is not its objects' union
+    *refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;
+    if (!rebuild || !*refit || batch) return CR_OK;   // (a batch with a refit of either kind is refused by its caller)
+    real ta, shutter;
+    frame_times(p, ta, shutter);
+    rc = build_frame_scene<real>(h, ta, ta + shutter);
+    if (rc != CR_OK) return rc;
+    *walk = &frame_scene<real>(h);
+    *refit = false;   // its boxes are this frame's already
+    return CR_OK;
+}
+
+// cr_export_render_bvh: the tree the last render or guide pass of this precision walked, with the boxes it walked
+template <typename real>
+int32_t export_render_bvh(CrHandle* h, double* boxes, int32_t* children, int32_t* split_axis, int32_t capacity, int32_t* n_out) {
+    DevScene<real>& ds = dev_scene<real>(h);
+    const char* what = "cr_export_render_bvh";
+    if (!ds.built || ds.last_walk == kWalkNone) return fail(h, CR_ERR_NO_SCENE, "cr_export_render_bvh before a render of this precision");
+    if (ds.last_walk == kWalkFrame) {
+        const DevScene<real>& fs = frame_scene<real>(h);
+        if (!fs.frame_valid) return fail(h, CR_ERR_NO_SCENE, "cr_export_render_bvh before a render of this precision");
+        return export_tree<real>(h, fs, fs.host_entries, what, boxes, children, split_axis, capacity, n_out);
+    }
+    if (ds.last_walk == kWalkBase || !boxes || !children || capacity < ds.n_entries || ds.host_entries.size() != (size_t)ds.n_entries)
+        return export_tree<real>(h, ds, ds.host_entries, what, boxes, children, split_axis, capacity, n_out);
+    // the base topology with the refitted boxes, which live on the device (entries_refit) until the next refit overwrites them
+    std::vector<Entry<real>> E = ds.host_entries;
+    const size_t rec = ds.entry_bytes;
+    std::vector<char> raw((size_t)ds.n_entries * rec);
+    HIP_TRY(h, hipMemcpyAsync(raw.data(), ds.entries_refit.p, raw.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < E.size(); i++) memcpy(E[i].b, raw.data() + i * rec, 6 * sizeof(real));   // Entry and EntryO both begin with the box
+    return export_tree<real>(h, ds, E, what, boxes, children, split_axis, capacity, n_out);
+}
+
 template int32_t build_dev_scene<float>(CrHandle*);
 template int32_t build_dev_scene<double>(CrHandle*);
+template int32_t select_tree<float>(CrHandle*, const CrRenderParams*, bool, DevScene<float>**, bool*);
+template int32_t select_tree<double>(CrHandle*, const CrRenderParams*, bool, DevScene<double>**, bool*);
 
 }   // namespace cr
 
@@ -762,6 +947,26 @@ extern "C" int32_t cr_build_info(CrHandle* h, int32_t real_type, CrBuildInfo* ou
     if (rc != CR_OK) return rc;
     *out = real_type == CR_REAL_F64 ? h->s64.info : h->s32.info;
     return CR_OK;
+}
+
+extern "C" int32_t cr_frame_build_info(CrHandle* h, int32_t real_type, CrBuildInfo* out) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!out) return fail(h, CR_ERR_INVALID_ARG, "cr_frame_build_info: null out");
+    if (real_type != CR_REAL_F32 && real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_frame_build_info before cr_upload_scene");
+    *out = real_type == CR_REAL_F64 ? h->f64.info : h->f32.info;   // all zero while no frame tree exists
+    return CR_OK;
+}
+
+extern "C" int32_t cr_export_render_bvh(CrHandle* h, int32_t real_type, double* boxes, int32_t* children, int32_t* split_axis, int32_t capacity,
+                             int32_t* n_wrappers) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!n_wrappers) return fail(h, CR_ERR_INVALID_ARG, "cr_export_render_bvh: null n_wrappers");
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_export_render_bvh before cr_upload_scene");
+    if (real_type != CR_REAL_F32 && real_type != CR_REAL_F64) return fail(h, CR_ERR_INVALID_ARG, "unknown real_type");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return real_type == CR_REAL_F64 ? export_render_bvh<double>(h, boxes, children, split_axis, capacity, n_wrappers)
+                                    : export_render_bvh<float>(h, boxes, children, split_axis, capacity, n_wrappers);
 }
 
 extern "C" int32_t cr_export_bvh(CrHandle* h, int32_t real_type, double* boxes, int32_t* children, int32_t* split_axis, int32_t capacity,

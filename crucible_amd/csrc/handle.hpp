@@ -2,7 +2,8 @@
 // include/crucible_hip.h, a precision's device copy of the scene, and the internal functions one unit calls in another.
 // Those are hidden-visibility functions of cr:: (exports.map keeps the dynamic table to the ABI); each is defined in
 // the unit its declaration names.  A kernel instantiation is emitted by exactly one unit:
-//   build.hip          host BVH builders, the LBVH driver (lbvh.hpp, hipcub), build_dev_scene, cr_export_bvh, cr_build_info
+//   build.hip          host BVH builders, the LBVH driver (lbvh.hpp, hipcub), build_dev_scene, cr_export_bvh, cr_build_info;
+//                      the per-frame tree of CR_REFIT_REBUILD (build_frame_scene), cr_export_render_bvh, cr_frame_build_info
 //   sah_device.hip     the device-side SAH builder of CR_BVH_BUILD_DEVICE (sah_device.hpp, hipcub)
 //   scene.hip          cr_upload_scene, refit.hpp's box kernels, the screening records, cr_update_primitives (update.hpp)
 //   render.hip         render_typed: a render's kernel arguments up to the choice of ladder; the stats epilogue
@@ -45,6 +46,8 @@ struct DevBuf {
 // wrapper then share a cache line (f64: exactly one 128-byte line), so the walk's left-then-right visits touch it once.
 template <typename E> constexpr size_t entry_pad() { return (sizeof(E) & (sizeof(E) - 1)) == 0 ? sizeof(E) : 0; }
 
+enum { kWalkNone = 0, kWalkBase = 1, kWalkRefit = 2, kWalkFrame = 3 };
+
 template <typename real> struct DevScene {
     bool built = false;
     DevBuf entries, prims, mats, texs, keys;
@@ -73,7 +76,15 @@ template <typename real> struct DevScene {
     bool desc_pos_valid = false;
     CrBuildInfo info = {};                   // what the last build of this precision did (cr_build_info)
     bool side_tables = false;                // mats / texs / keys hold the uploaded scene's (a rebuild after cr_update_primitives keeps them)
-    void release() { desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
+    // CR_REFIT_REBUILD (build.hip build_frame_scene).  On the base tree of a SAH mode: what a frame build starts from.
+    std::vector<int32_t> in_desc;            // builder input position -> index in the caller's primitive list (the order the SAH builders see)
+    std::vector<int32_t> base_order;         // leaf-order position -> builder input position (leaf_desc[i] = in_desc[base_order[i]])
+    int32_t last_walk = kWalkNone;           // which tree the last render or guide pass of this precision walked (cr_export_render_bvh)
+    // On the frame tree (CrHandle::f32 / f64): the ray-time interval it was built for; mats / texs / keys alias the base tree's
+    bool frame_valid = false;
+    real frame_ta = real(0), frame_tb = real(0);
+    DevBuf frame_map;                        // a frame build's index tables on the device (input positions, then gather sources)
+    void release() { frame_map.release(); frame_valid = false; last_walk = kWalkNone; desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
 };
 
 }   // namespace cr
@@ -110,6 +121,8 @@ struct CrHandle {
     int32_t n_images = 0;
     DevScene<float> s32;
     DevScene<double> s64;
+    DevScene<float> f32;              // CR_REFIT_REBUILD: the frame tree of each precision, beside the base tree
+    DevScene<double> f64;
     DevBuf work_counter, counters, att_stack, out_buf;
     // Camera keyframes of a render travel in a ring of per-launch slots: a pinned host slot is filled, copied to its
     // device slot on the handle's stream and kept until that copy's event has fired, so back-to-back asynchronous
@@ -192,6 +205,16 @@ template <typename real> DevScene<real>& dev_scene(CrHandle* h);
 template <> inline DevScene<float>& dev_scene<float>(CrHandle* h) { return h->s32; }
 template <> inline DevScene<double>& dev_scene<double>(CrHandle* h) { return h->s64; }
 
+template <typename real> DevScene<real>& frame_scene(CrHandle* h);
+template <> inline DevScene<float>& frame_scene<float>(CrHandle* h) { return h->f32; }
+template <> inline DevScene<double>& frame_scene<double>(CrHandle* h) { return h->f64; }
+// The frame trees go with the scene they were built from: cr_upload_scene, cr_update_primitives (the buffers stay for the next build)
+inline void drop_frame_trees(CrHandle* h) {
+    h->f32.frame_valid = false; h->f64.frame_valid = false;
+    h->f32.info = CrBuildInfo(); h->f64.info = CrBuildInfo();
+    h->s32.last_walk = kWalkNone; h->s64.last_walk = kWalkNone;
+}
+
 inline size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline size_t real_size(int32_t real_type) { return real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float); }
 
@@ -226,10 +249,16 @@ struct WalkChoice {
 
 // build.hip
 template <typename real> int32_t build_dev_scene(CrHandle* h);
+// What a render or guide pass walks: builds the base tree, settles CrRenderParams.refit_boxes -- *refit: the
+// base tree with this frame's boxes (CR_REFIT_BOXES) -- and under CR_REFIT_REBUILD builds or reuses the frame tree and
+// returns that one in *walk.  batch: a cr_render_frames_* call.
+template <typename real> int32_t select_tree(CrHandle* h, const CrRenderParams* p, bool batch, DevScene<real>** walk, bool* refit);
 // sah_device.hip: the node graph and the primitive order of the SAH tree over n >= 1 boxes (6 doubles each: lo xyz, hi xyz)
 struct SahNodeRec;
 struct SahDeviceStats;
 int32_t build_sah_device(CrHandle* h, const double* boxes, int32_t n, std::vector<SahNodeRec>& nodes, std::vector<int32_t>& order, SahDeviceStats& st);
+// ... the same over boxes that are on the device already: h->sah_work.box holds them (n * 6 doubles, written on h->stream)
+int32_t build_sah_device_resident(CrHandle* h, int32_t n, std::vector<SahNodeRec>& nodes, std::vector<int32_t>& order, SahDeviceStats& st);
 // scene.hip
 template <typename real> int32_t run_box_kernels(CrHandle* h, DevScene<real>& ds, void* entries, real ta, real tb, bool use_keys);
 int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevBuf& out, bool* usable);

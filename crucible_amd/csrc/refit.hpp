@@ -27,8 +27,12 @@
 // timeline_pad, a bound on twice that error.  And the value at a sample time is its right limit: a zero-length LERP key
 // evaluated at its own instant gives 0/0, but just after it the key is complete.  Conservative (a superset), never too small.
 //
-// On a scene without primitive keys this reproduces the construction-time boxes exactly.  The topology is never
-// changed.  (The test suite's CPU checker applies the same rule to its own tree.)
+// On a scene without primitive keys this reproduces the construction-time boxes exactly.  A refit never changes the
+// topology.  (The test suite's CPU checker applies the same rule to its own tree.)
+//
+// refit_boxes = CR_REFIT_REBUILD builds another tree for the frame instead, over the primitives' boxes of
+// this rule (prim_box_over; motion_boxes_kernel below computes them for the device builder), and fills its wrapper boxes
+// with the same kernels: build.hip, build_frame_scene.
 #pragma once
 #include "pathtrace.hpp"
 
@@ -226,6 +230,35 @@ __global__ void refit_level_kernel(typename EntryOf<real, ORD>::type* entries, i
     }
     real* b = entries[i].b;
     b[0] = lo[0]; b[1] = hi[0]; b[2] = lo[1]; b[3] = hi[1]; b[4] = lo[2]; b[5] = hi[2];
+}
+
+// CR_REFIT_REBUILD: the input of the device SAH builder for one frame.  One thread per record of the base
+// tree's `prims` (leaf order, read coalesced); its box over the ray times [ta, tb] -- prim_box_over in `real`, the bits a
+// refit gives a one-primitive leaf -- goes, widened to f64 (exact), to the position the builders see that primitive at:
+// input_of[i], six doubles lo xyz, hi xyz as build_sah_device takes them.  The keyed loop's trip count is per primitive (a
+// scaled triangle: quadratic in its keys), so a wave runs as long as its longest timeline; records are not regrouped by key
+// count -- the pass runs once per frame build and unkeyed primitives leave after one box.
+template <typename real>
+__global__ void motion_boxes_kernel(const Prim<real>* prims, const int32_t* input_of, int32_t n, const Key<real>* keys, real ta, real tb, double* box6) {
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const int32_t j = input_of[i];
+    if (j < 0 || j >= n) return;   // (a permutation of 0 .. n-1: never taken)
+    real lo[3], hi[3];
+    for (int a = 0; a < 3; a++) { lo[a] = r_inf(real(0)); hi[a] = -r_inf(real(0)); }
+    prim_box_over(prims[i], keys, ta, tb, lo, hi, true);
+    double* o = box6 + (size_t)j * 6;
+    for (int a = 0; a < 3; a++) { o[a] = (double)lo[a]; o[3 + a] = (double)hi[a]; }
+}
+
+// The frame tree's primitive records in its own leaf order, gathered from the base tree's: out[i] = base[src[i]].
+template <typename real>
+__global__ void gather_prims_kernel(const Prim<real>* base, const int32_t* src, int32_t n, Prim<real>* out) {
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const int32_t s = src[i];
+    if (s < 0 || s >= n) return;
+    out[i] = base[s];
 }
 #endif
 

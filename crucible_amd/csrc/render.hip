@@ -173,15 +173,15 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
 // One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*).
 template <typename real>
 int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames) {
-    int32_t rc = build_dev_scene<real>(h);
+    DevScene<real>* walk = nullptr;
+    bool refit = false;
+    int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // the base tree, or the frame's own (CR_REFIT_REBUILD)
     if (rc != CR_OK) return rc;
-    DevScene<real>& ds = dev_scene<real>(h);
+    DevScene<real>& ds = *walk;
     const int sum_order = resolve_sum_order(h, p);
     const bool fixed = p->output_sum == CR_OUTPUT_FIXED_SUM;
     if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
         return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
-    // without primitive keys the boxes would not change -- unless a HitList element's box is not its objects' union
-    const bool refit = p->refit_boxes && (ds.animated || ds.has_lists) && ds.n_entries > 0;
     if (frames) {
         if (sum_order != CR_SUM_RELAXED || h->pipeline != 0)
             return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
@@ -205,6 +205,7 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     std::vector<real> times;
     rc = prepare_args<real>(h, cd, p, ds, refit, h->pipeline == 0, d_out, frames, n_frames, times, a, w, fb);
     if (rc != CR_OK) return rc;
+    dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
     // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
     if (sum_order == CR_SUM_RELAXED && h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_SUM_RELAXED is implemented by the megakernel pipeline only");
     const bool relax = sum_order == CR_SUM_RELAXED;

@@ -14,7 +14,18 @@ int32_t sah_small_threshold() {
     return t;
 }
 
+#define SAH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(h, CR_ERR_HIP, std::string("device SAH build: ") + hipGetErrorString(e_)); } while (0)
+
 int32_t build_sah_device(CrHandle* h, const double* boxes, int32_t n, std::vector<SahNodeRec>& nodes, std::vector<int32_t>& order, SahDeviceStats& st) {
+    st = SahDeviceStats();
+    nodes.clear();
+    if (n < 1) return CR_OK;
+    SAH_TRY(h->sah_work.box.ensure((size_t)n * 48));
+    SAH_TRY(hipMemcpyAsync(h->sah_work.box.p, boxes, (size_t)n * 48, hipMemcpyHostToDevice, h->stream));
+    return build_sah_device_resident(h, n, nodes, order, st);
+}
+
+int32_t build_sah_device_resident(CrHandle* h, int32_t n, std::vector<SahNodeRec>& nodes, std::vector<int32_t>& order, SahDeviceStats& st) {
     st = SahDeviceStats();
     const int32_t T = st.small_threshold = sah_small_threshold();
     nodes.clear();
@@ -24,10 +35,8 @@ int32_t build_sah_device(CrHandle* h, const double* boxes, int32_t n, std::vecto
     SahDeviceWork& w = h->sah_work;
     DevBuf &d_box = w.box, *d_order = w.order, *d_seg = w.seg, &d_pbins = w.pbins, &d_flags = w.flags, &d_scan = w.scan, &d_tmp = w.tmp, *d_slots = w.slots,
            &d_nodes = w.nodes, &d_small = w.small, &d_ctr = w.ctr;
-#define SAH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(h, CR_ERR_HIP, std::string("device SAH build: ") + hipGetErrorString(e_)); } while (0)
     const bool large = n > T;
-    SAH_TRY(d_box.ensure((size_t)n * 48));
-    SAH_TRY(hipMemcpyAsync(d_box.p, boxes, (size_t)n * 48, hipMemcpyHostToDevice, h->stream));
+    if (d_box.bytes < (size_t)n * 48) return fail(h, CR_ERR_HIP, "device SAH build: the primitive boxes are not on the device");
     order.resize(n);
     for (int32_t i = 0; i < n; i++) order[i] = i;
     SAH_TRY(d_order[0].ensure((size_t)n * 4));

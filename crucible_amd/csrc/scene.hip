@@ -121,6 +121,7 @@ static int32_t refit_updated(CrHandle* h, const int32_t* d_index, const double* 
 int32_t apply_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags) {
     if (n == 0) return CR_OK;
     HIP_TRY(h, hipSetDevice(h->device));
+    drop_frame_trees(h);   // CR_REFIT_REBUILD's trees were built over the primitives as they were
     const bool refit = flags == CR_UPDATE_REFIT && (h->s32.built || h->s64.built);
     if (refit) {   // one staged buffer: the rows, then the indices; the stream orders the copy after earlier renders
         const size_t row_bytes = (size_t)n * 9 * sizeof(double), idx_bytes = prim_index ? (size_t)n * sizeof(int32_t) : 0;
@@ -254,6 +255,7 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
     if (!h->bvh_device) h->sah_work.release();
     h->s32.built = false; h->s64.built = false;
     h->s32.side_tables = false; h->s64.side_tables = false;
+    drop_frame_trees(h);
     h->has_list_elements = false;
     for (const CrPrimitive& p : h->prims) h->has_list_elements |= p.kind == CR_PRIM_LIST || p.kind == CR_PRIM_BVH;
     // images: RGB8 -> RGBA8 words, one flat texel array (pack.hpp)

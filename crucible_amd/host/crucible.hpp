@@ -400,6 +400,17 @@ public:
 };
 
 // ---------------------------------------------------------------- scene
+// CrRenderParams.refit_boxes as Scene::refit_boxes takes it: false / true (as before), "rebuild" (CR_REFIT_REBUILD), or a CR_REFIT_* code
+struct RefitMode {
+    int32_t code = CR_REFIT_OFF;
+    RefitMode() = default;
+    RefitMode(bool on) : code(on ? CR_REFIT_BOXES : CR_REFIT_OFF) {}
+    RefitMode(int32_t c) : code(c) {}
+    RefitMode(const char* name) : code(CR_REFIT_REBUILD) { if (std::string(name) != "rebuild") throw std::invalid_argument("refit_boxes takes false, true or \"rebuild\""); }
+    RefitMode(const std::string& name) : RefitMode(name.c_str()) {}
+    operator int32_t() const { return code; }
+};
+
 class Scene {
     std::map<std::string, std::pair<size_t, std::string>> aliases_{{"cam", {0, "Camera"}}};   // id_vendor.rs
     size_t next_id_ = 1;
@@ -425,7 +436,7 @@ public:
     uint64_t seed = 0xC0FFEE;
     int real_type = CR_REAL_F32;
     int bvh_mode = CR_BVH_REFERENCE;   // CR_BVH_SAH: the quality builder (include/crucible_hip.h)
-    bool refit_boxes = false;          // CrRenderParams.refit_boxes: wrapper boxes follow keyframed primitives
+    RefitMode refit_boxes = false;     // CrRenderParams.refit_boxes: true = wrapper boxes follow keyframed primitives, "rebuild" = the SAH tree is built per frame
     std::string frame_format = "ppm";  // "ppm" (ASCII P3, the reference's) | "p6" | "png"
     int device = 0;
     int gpus = 1;            // > 1 (or use_group): still images split their samples over devices 0..gpus-1 through cr_group_*;
@@ -581,7 +592,7 @@ public:
     CrRenderParams render_params(size_t frame) const {
         const Camera& c = scene_cam;
         CrRenderParams p{(int32_t)c.samples, 0, (int32_t)c.samples, (int32_t)c.max_depth, seed, (int32_t)frame, real_type,
-                         c.frame_rate, c.shutter_angle, 0, refit_boxes ? 1 : 0, sum_order, 0};
+                         c.frame_rate, c.shutter_angle, 0, refit_boxes.code, sum_order, 0};
         return p;
     }
     // The render proper: W*H*3 reals of `real_type` into `buf` (sized for either scalar type), at the camera's frame

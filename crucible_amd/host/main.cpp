@@ -5,7 +5,8 @@
 // --format ppm|p6|png (frame files: the reference's ASCII P3, binary PPM, PNG),
 // --sky FILE.hdr (Radiance map as the spherical skybox; world 5 = demo_images::garden_skybox needs it),
 // --bvh reference|sah|ordered|lbvh|sah-device|ordered-device (the tree cr_upload_scene builds; reference = the parity mode, default), --refit (re-derive
-// the wrapper boxes per frame so keyframed primitives are not clipped; the reference does not),
+// the wrapper boxes per frame so keyframed primitives are not clipped; the reference does not; --refit rebuild: build the SAH tree
+// itself for every frame, CR_REFIT_REBUILD -- with --bvh sah, ordered, sah-device or ordered-device),
 // --dump-desc FILE (write the flattened scene description and exit; used by the tests to check
 // this mirror against the Python one), --sum-order reference|relaxed (CrRenderParams.sum_order; default: the library's),
 // --frames-per-launch N (movies: N frames per library call through cr_render_frames_host, relaxed sums; default 1),
@@ -46,7 +47,8 @@ int main(int argc, char** argv) {
     uint64_t seed = 0xC0FFEE, scene_seed = 1;
     int device = 0;
     std::string bvh = "reference", sky, format = "ppm";
-    bool refit = false, use_group = false, timing = false;
+    bool use_group = false, timing = false;
+    RefitMode refit = false;
     int gpus = 1, repeat = 1;
     long frames_per_launch = 1;
     std::string sum_order = "default", aov;
@@ -68,7 +70,10 @@ int main(int argc, char** argv) {
         else if (a == "--bvh") bvh = next();
         else if (a == "--sky") sky = next();
         else if (a == "--format") format = next();
-        else if (a == "--refit") refit = true;
+        else if (a == "--refit") {   // plain, or followed by the word rebuild
+            refit = true;
+            if (i + 1 < argc && std::string(argv[i + 1]) == "rebuild") { refit = "rebuild"; i++; }
+        }
         else if (a == "--gpus") gpus = (int)strtol(next(), nullptr, 10);
         else if (a == "--group") use_group = true;
         else if (a == "--timing") timing = true;

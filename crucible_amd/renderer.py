@@ -193,15 +193,30 @@ class Renderer:
     def export_bvh(self, real_type=A.CR_REAL_F32):
         """The wrapper tree the device walks: (boxes (n, 6) f64, children (n, 2) i32, split_axis (n,) i32), see
         cr_export_bvh."""
+        return self._export(self.lib.cr_export_bvh, real_type)
+
+    def _export(self, fn, real_type):
         n = C.c_int32()
-        self._check(self.lib.cr_export_bvh(self.h, real_type, None, None, None, 0, C.byref(n)))
+        self._check(fn(self.h, real_type, None, None, None, 0, C.byref(n)))
         boxes = np.zeros((max(1, n.value), 6), dtype=np.float64)
         kids = np.zeros((max(1, n.value), 2), dtype=np.int32)
         axis = np.full(max(1, n.value), -1, dtype=np.int32)
-        self._check(self.lib.cr_export_bvh(self.h, real_type, boxes.ctypes.data_as(C.c_void_p),
-                                           kids.ctypes.data_as(C.c_void_p), axis.ctypes.data_as(C.c_void_p), n.value,
-                                           C.byref(n)))
+        self._check(fn(self.h, real_type, boxes.ctypes.data_as(C.c_void_p), kids.ctypes.data_as(C.c_void_p),
+                       axis.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
         return boxes[:n.value], kids[:n.value], axis[:n.value]
+
+    def export_render_bvh(self, real_type=A.CR_REAL_F32):
+        """cr_export_render_bvh: the tree the last render or guide pass of `real_type` walked, with the boxes it walked,
+        in export_bvh's layout -- the frame tree after a refit_boxes="rebuild" render, the refitted boxes after
+        refit_boxes=True."""
+        return self._export(self.lib.cr_export_render_bvh, real_type)
+
+    def frame_build_info(self, real_type=A.CR_REAL_F32):
+        """cr_frame_build_info: build_info's dict for the last frame-tree build (refit_boxes="rebuild"); n_wrappers is
+        0 while there is no frame tree.  Builds nothing."""
+        info = A.CrBuildInfo()
+        self._check(self.lib.cr_frame_build_info(self.h, real_type, C.byref(info)))
+        return info.as_dict()
 
     def build_info(self, real_type=A.CR_REAL_F32):
         """cr_build_info: which builder made the tree of `real_type` and what it went through, as a dict (bvh_mode,

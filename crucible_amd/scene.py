@@ -390,7 +390,9 @@ class Camera:
         self.samples, self.max_depth = 10, 10
         self.thread_count = thread_count
         self.frame_rate, self.frame, self.shutter_angle = float(frame_rate), 0, float(shutter_angle)
-        self.refit_boxes = False   # True: CrRenderParams.refit_boxes (wrapper boxes follow keyframed primitives)
+        # CrRenderParams.refit_boxes.  True: wrapper boxes follow keyframed primitives; "rebuild": the SAH tree itself
+        # is built for each frame (CR_REFIT_REBUILD; needs bvh_mode CR_BVH_SAH or CR_BVH_SAH_ORDERED)
+        self.refit_boxes = False
 
     def next_frame(self):
         self.frame += 1
@@ -442,7 +444,7 @@ class Camera:
     def params(self, seed, real_type, sample_begin=0, sample_count=None, output_sum=False, sum_order=A.CR_SUM_DEFAULT):
         n = self.samples if sample_count is None else sample_count
         return A.CrRenderParams(self.samples, sample_begin, n, self.max_depth, seed, self.frame, real_type,
-                                self.frame_rate, self.shutter_angle, int(output_sum), 1 if self.refit_boxes else 0,
+                                self.frame_rate, self.shutter_angle, int(output_sum), A.refit_code(self.refit_boxes),
                                 sum_order, 0)
 
 

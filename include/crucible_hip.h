@@ -327,10 +327,28 @@ typedef struct CrRenderParams {
                                (bvhwrapper.rs:47-50) -- keyframed primitives are clipped where they leave them;
                                1: SURVEY 8(f) rows 1-2: boxes are re-derived on the device for this frame's
                                ray-time interval before the render (crucible_amd/csrc/refit.hpp), so moving
-                               primitives are intersected wherever they are.  No effect without primitive keys. */
+                               primitives are intersected wherever they are.  No effect without primitive keys;
+                               CR_REFIT_REBUILD (2): the tree itself is built for this frame, see below.  Any other
+                               value acts as 1. */
     int32_t sum_order;      /* CR_SUM_DEFAULT (0) | CR_SUM_REFERENCE_ORDER | CR_SUM_RELAXED */
     int32_t _reserved;
 } CrRenderParams;
+
+/*
+ * CrRenderParams.refit_boxes.  CR_REFIT_REBUILD: before the render the binned-SAH tree is
+ * built over the visible primitives' boxes for this frame's ray times [current_time, current_time + shutter_length] --
+ * the box a refit gives a one-primitive leaf --, with the wrapper boxes refit_boxes = 1 derives for that topology; the
+ * render walks that tree.  It needs bvh_mode CR_BVH_SAH or CR_BVH_SAH_ORDERED (with CR_BVH_BUILD_DEVICE the device builder
+ * builds it, from boxes computed on the device; without, the host builder): CR_ERR_UNSUPPORTED under CR_BVH_REFERENCE and
+ * CR_BVH_LBVH, whatever the scene.  Where refit_boxes = 1 would change nothing (no primitive keys) the call is exactly
+ * refit_boxes = 0 and nothing is built.  cr_render_frames_* refuse it as they refuse 1.
+ * Not sticky: the frame tree is a second tree on the handle, per real type, beside the tree of the upload; renders with
+ * refit_boxes 0 or 1 walk that one as before, and cr_export_bvh / cr_build_info keep describing it.  The frame tree is
+ * kept until the next cr_upload_scene, cr_update_primitives or cr_destroy, and a render or guide pass with the same ray
+ * times reuses it without building (sample batches, a frame and its guide pass).  The build is deterministic, so every
+ * member of a group builds the same tree.
+ */
+enum { CR_REFIT_OFF = 0, CR_REFIT_BOXES = 1, CR_REFIT_REBUILD = 2 };
 
 /*
  * Work counters of the last render (the algorithmic-bytes model of DESIGN.md):
@@ -489,6 +507,22 @@ typedef struct CrBuildInfo {
     double total_ms;           /* the whole build, uploads included */
 } CrBuildInfo;
 CR_API int32_t cr_build_info(CrHandle* h, int32_t real_type, CrBuildInfo* out);
+
+/*
+ * The tree that the last render or guide pass of `real_type` on this handle walked, with the boxes it walked, in
+ * cr_export_bvh's layout: after refit_boxes = CR_REFIT_REBUILD the frame tree, after refit_boxes = 1 the uploaded scene's
+ * topology with that frame's boxes, after refit_boxes = 0 what cr_export_bvh returns.  CR_ERR_NO_SCENE before any render
+ * of that real type since the last cr_upload_scene or cr_update_primitives.  May synchronise the handle's stream.
+ */
+CR_API int32_t cr_export_render_bvh(CrHandle* h, int32_t real_type, double* boxes, int32_t* children, int32_t* split_axis,
+                                    int32_t capacity, int32_t* n_wrappers);
+
+/*
+ * What the last frame-tree build (CR_REFIT_REBUILD) of `real_type` did: builder, rounds, tree_ms (boxes of the frame,
+ * topology and order), total_ms (the whole build).  All zero -- n_wrappers = 0 -- while no frame tree exists.  Builds nothing.
+ * CR_ERR_INVALID_ARG for a null handle, a null `out` or an unknown real_type; CR_ERR_NO_SCENE before an upload.
+ */
+CR_API int32_t cr_frame_build_info(CrHandle* h, int32_t real_type, CrBuildInfo* out);
 
 /*
  * Edit primitives of the uploaded scene in place: new coordinates for n spheres / triangles, without another
