@@ -2,7 +2,8 @@
 // include/crucible_hip.h, a precision's device copy of the scene, and the internal functions one unit calls in another.
 // Those are hidden-visibility functions of cr:: (exports.map keeps the dynamic table to the ABI); each is defined in
 // the unit its declaration names.  A kernel instantiation is emitted by exactly one unit:
-//   build.hip          host BVH builders, the LBVH driver (lbvh.hpp, hipcub), build_dev_scene, cr_export_bvh, cr_build_info;
+//   build.hip          build_dev_scene as stages over the host tree code of tree.hpp (a header free of the HIP runtime: the builders,
+//                      the splice, the leaf layout, the export walk), the LBVH driver (lbvh.hpp, hipcub), cr_export_bvh, cr_build_info;
 //                      the per-frame tree of CR_REFIT_REBUILD (build_frame_scene), cr_export_render_bvh, cr_frame_build_info
 //   sah_device.hip     the device-side SAH builder of CR_BVH_BUILD_DEVICE (sah_device.hpp, hipcub)
 //   scene.hip          cr_upload_scene, refit.hpp's box kernels, the screening records, cr_update_primitives (update.hpp)

@@ -34,6 +34,7 @@
 // this rule (prim_box_over; motion_boxes_kernel below computes them for the device builder), and fills its wrapper boxes
 // with the same kernels: build.hip, build_frame_scene.
 #pragma once
+#include "pack.hpp"
 #include "pathtrace.hpp"
 
 namespace cr {
@@ -189,6 +190,25 @@ CR_HD void prim_box_over(const Prim<real>& p, const Key<real>* keys, real ta, re
             prim_box_at(p, keys, k.t0, true, lo, hi, true, pad);
         }
         if (ta < k.t1 && k.t1 < tb) prim_box_at(p, keys, k.t1, false, lo, hi, true, pad);
+    }
+}
+
+// The same rule on the host, from the caller's description of the scene: the boxes of n primitives over [ta, tb] -- desc[j]
+// names the j-th in `prims`, desc = nullptr takes the first n in order -- as the SAH builders read them (bmin / bmax: [3]).
+// What build_frame_scene hands the host builder; motion_boxes_kernel below writes the same bits for the device builder.
+template <typename real>
+void motion_boxes(const std::vector<CrPrimitive>& prims, const int32_t* desc, int32_t n, const std::vector<CrKeyframe>& scene_keys, real ta, real tb,
+                  std::vector<real>* bmin, std::vector<real>* bmax) {
+    std::vector<Key<real>> keys(scene_keys.size() + 1);
+    memset(keys.data(), 0, keys.size() * sizeof(Key<real>));
+    for (size_t i = 0; i < scene_keys.size(); i++) key_to_real(scene_keys[i], keys[i]);
+    for (int a = 0; a < 3; a++) { bmin[a].resize(n); bmax[a].resize(n); }
+    for (int32_t j = 0; j < n; j++) {
+        const Prim<real> q = pack_prim<real>(prims[(size_t)(desc ? desc[j] : j)]);
+        real lo[3], hi[3];
+        for (int a = 0; a < 3; a++) { lo[a] = r_inf(real(0)); hi[a] = -r_inf(real(0)); }
+        prim_box_over(q, keys.data(), ta, tb, lo, hi, true);
+        for (int a = 0; a < 3; a++) { bmin[a][j] = lo[a]; bmax[a][j] = hi[a]; }
     }
 }
 

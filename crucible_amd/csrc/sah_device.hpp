@@ -1,5 +1,5 @@
 // CR_BVH_BUILD_DEVICE -- the CR_BVH_SAH / CR_BVH_SAH_ORDERED tree, built on the device.
-// The same tree as SahBuilder's (build.hip), decision for decision: the device produces the node graph (left, right =
+// The same tree as SahBuilder's (tree.hpp), decision for decision: the device produces the node graph (left, right =
 // left + 1, start, end, axis per node) and the final primitive order; SahBuilder::linearise and relayout_bfs run on the
 // host on what comes back, and the wrapper boxes are filled bottom-up by run_box_kernels as for the LBVH.
 //

@@ -1,7 +1,7 @@
 // The motion-box rule of CR_REFIT_REBUILD on the CPU: compiles the CR_HD functions of crucible_amd/csrc/refit.hpp
-// (prim_box_over and what it calls) with a plain C++ compiler, packs its inputs with the library's own pack.hpp and prints
-// the box of every primitive over a frame's ray times -- what build_frame_scene hands the host builder and what
-// motion_boxes_kernel writes for the device builder.  tests/test_motion_boxes_host.py holds the output to the oracle.
+// (motion_boxes: prim_box_over and what it calls, on inputs packed by the library's own pack.hpp) with a plain C++ compiler and
+// prints the box of every primitive over a frame's ray times -- the very function build_frame_scene hands the host builder's
+// input from, and what motion_boxes_kernel writes for the device builder.  tests/test_motion_boxes_host.py holds the output to the oracle.
 //   motion_boxes_check FILE: FILE holds int32 is_f64, n_prims, n_keys, frame; double frame_rate, shutter_angle; then
 //   n_prims CrPrimitive and n_keys CrKeyframe records.  Output: one line per primitive, xmin xmax ymin ymax zmin zmax as
 //   hexadecimal floats (the values of the real type, widened exactly).
@@ -13,19 +13,12 @@
 
 template <typename real>
 static void run(const std::vector<CrPrimitive>& prims, const std::vector<CrKeyframe>& keys, const CrRenderParams& p) {
-    std::vector<cr::Key<real>> k(keys.size() + 1);
-    memset(k.data(), 0, k.size() * sizeof(cr::Key<real>));
-    for (size_t i = 0; i < keys.size(); i++) cr::key_to_real(keys[i], k[i]);
     real ta, shutter;
     cr::frame_times(&p, ta, shutter);
-    const real tb = ta + shutter;
-    for (const CrPrimitive& d : prims) {
-        const cr::Prim<real> q = cr::pack_prim<real>(d);
-        real lo[3], hi[3];
-        for (int a = 0; a < 3; a++) { lo[a] = cr::r_inf(real(0)); hi[a] = -cr::r_inf(real(0)); }
-        cr::prim_box_over(q, k.data(), ta, tb, lo, hi, true);
-        printf("%a %a %a %a %a %a\n", (double)lo[0], (double)hi[0], (double)lo[1], (double)hi[1], (double)lo[2], (double)hi[2]);
-    }
+    std::vector<real> lo[3], hi[3];
+    cr::motion_boxes<real>(prims, nullptr, (int32_t)prims.size(), keys, ta, ta + shutter, lo, hi);
+    for (size_t i = 0; i < prims.size(); i++)
+        printf("%a %a %a %a %a %a\n", (double)lo[0][i], (double)hi[0][i], (double)lo[1][i], (double)hi[1][i], (double)lo[2][i], (double)hi[2][i]);
 }
 
 int main(int argc, char** argv) {

@@ -1,7 +1,8 @@
 """tests/sah_model.py, the plain model the binned-SAH trees are held to (tests/test_gpu_sah_build.py), pinned on the CPU
-before any GPU sees it.  The library's builder does not compile for the host, so the model is pinned from the other
-side: trees worked out by hand, and a brute-force recomputation of every decision of every inner wrapper -- all 45
-candidate costs with plain Python floats and loops over sets -- on random primitive sets.  Every comparison is exact."""
+before any GPU sees it.  The library's own builder is held to the model elsewhere (tests/test_tree_host.py on the
+CPU, tests/test_gpu_sah_build.py on the device); here the model is pinned from the other side: trees worked out by
+hand, and a brute-force recomputation of every decision of every inner wrapper -- all 45 candidate costs with plain
+Python floats and loops over sets -- on random primitive sets.  Every comparison is exact."""
 import math
 
 import numpy as np
