@@ -123,6 +123,10 @@ SYMBOLS = {
                                          C.POINTER(CrStats)]),
     "cr_render_aov_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32, C.c_void_p,
                                        C.POINTER(CrStats)]),
+    "cr_render_aov_frames_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                                C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_frames_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                              C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
     "cr_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),

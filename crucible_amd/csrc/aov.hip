@@ -1,4 +1,4 @@
-// aov.hip -- the guide pass behind cr_render_aov_*: first-hit albedo, normal, depth and coverage per pixel (aov.hpp has the
+// aov.hip -- the guide pass behind cr_render_aov_* and cr_render_aov_frames_*: first-hit albedo, normal, depth and coverage per pixel (aov.hpp has the
 // accumulator layout, include/crucible_hip.h the definition of every layer).  aov_typed sets a launch up through the
 // render's own prepare_args (camera-key slot, ray times, refitted boxes, screening records: render.hip), runs the first-hit
 // kernel of the scene's residency (aov_f32.hip / aov_f64.hip) and turns the accumulators into the requested planes.
@@ -10,11 +10,15 @@ namespace cr {
 // fx_finalize_kernel turns a relaxed sum into one -- the word's magnitude in two exact halves, one rounding in their add,
 // times 2^-S, divided by the frame's sample count unless the shard's sum is asked for -- with the word's sign put back;
 // a flagged channel is NaN.  Depth: the complement of the largest word, +inf where no sample hit.
+// blockIdx.y: the frame of a batch, whose planes begin frame_reals reals after the previous frame's.
 template <typename real>
 __global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long long* acc, const uint32_t* flags, real* out, size_t npix, int32_t layers,
-                                                           double inv_scale, double count, int32_t output_sum) {
+                                                           double inv_scale, double count, int32_t output_sum, size_t frame_reals) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npix) return;
+    acc += (size_t)blockIdx.y * npix * kAovWords;
+    flags += (size_t)blockIdx.y * npix;
+    out += (size_t)blockIdx.y * frame_reals;
     const unsigned long long* w = acc + i * kAovWords;
     const uint32_t bad = flags[i];
     auto value = [&](uint32_t c) -> real {
@@ -42,14 +46,21 @@ __global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long l
     if (layers & CR_AOV_COVERAGE) o[i] = value(kAovCoverage);
 }
 
+// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_aov_frames_*):
+// the batch's frames lie one behind the other in the accumulators, in the flags and in the output.
 template <typename real>
-int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats) {
+int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats, const int32_t* frames,
+                  int32_t n_frames) {
     DevScene<real>* walk = nullptr;
     bool refit = false;
-    int32_t rc = select_tree<real>(h, p, false, &walk, &refit);   // as a render decides it
+    int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // as a render decides it
     if (rc != CR_OK) return rc;
+    if (frames && refit)
+        return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
+                                           "(render such frames one at a time)");
     DevScene<real>& ds = *walk;
-    const size_t npix = (size_t)cd->image_width * (size_t)cd->image_height;
+    const size_t frame_pix = (size_t)cd->image_width * (size_t)cd->image_height;
+    const size_t npix = frame_pix * (size_t)n_frames;   // (at most 2^26 * 2^31: the byte counts below fit in 64 bits)
     hipError_t e = h->aov_acc.ensure(npix * kAovWords * sizeof(unsigned long long));
     if (e == hipSuccess) e = h->aov_flags.ensure(npix * sizeof(uint32_t));
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("guide accumulators: ") + hipGetErrorString(e)); }
@@ -61,7 +72,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         FrameBatch<real> fb;
         std::vector<real> times;
         // the walk is the megakernel's under every pipeline setting: the cross-check pipelines have no guide pass of their own
-        rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, nullptr, 1, times, a.k, w, fb);
+        rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, frames, n_frames, times, a.k, w, fb);
         if (rc != CR_OK) return rc;
         dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
         a.k.tiles_x = ((uint32_t)cd->image_width + 3u) >> 2; a.k.tiles_y = ((uint32_t)cd->image_height + 3u) >> 2;
@@ -69,6 +80,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         a.acc = (unsigned long long*)h->aov_acc.p; a.flags = (uint32_t*)h->aov_flags.p;
         a.layers = layers;
         a.groups = ((uint32_t)p->sample_count + 3u) >> 2;
+        if (frames) { a.n_frames = (uint32_t)n_frames; a.frame_times = fb.d_times; }
         const size_t need = aov_lds_bytes(MaxBlock<real>::value);   // the waves' slots share the LDS
         w.screen_lds = w.screen && h->screen_lds && w.lds_all_screen + need <= h->lds_limit;
         w.plain_lds = ds.lds_bytes + need <= h->lds_limit;
@@ -81,14 +93,20 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         rc = aov_ladder<real>(h, a, ds, w, &res);
         if (rc != CR_OK) return rc;
     }
-    hipLaunchKernelGGL((aov_finalize_kernel<real>), dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, h->stream, (const unsigned long long*)h->aov_acc.p,
-                       (const uint32_t*)h->aov_flags.p, (real*)d_out, npix, layers, 1.0 / fx_scale_for(p->samples), (double)p->samples, p->output_sum);
-    HIP_TRY(h, hipGetLastError());
+    const size_t frame_reals = frame_pix * (size_t)((layers & CR_AOV_ALBEDO ? 3 : 0) + (layers & CR_AOV_NORMAL ? 3 : 0) + (layers & CR_AOV_DEPTH ? 1 : 0) +
+                                                    (layers & CR_AOV_COVERAGE ? 1 : 0));
+    for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += 65535) {   // (a grid has at most 65535 rows)
+        const size_t fn = std::min<size_t>(65535, (size_t)n_frames - f0);
+        hipLaunchKernelGGL((aov_finalize_kernel<real>), dim3((unsigned)((frame_pix + 255) / 256), (unsigned)fn), dim3(256), 0, h->stream,
+                           (const unsigned long long*)h->aov_acc.p + f0 * frame_pix * kAovWords, (const uint32_t*)h->aov_flags.p + f0 * frame_pix,
+                           (real*)d_out + f0 * frame_reals, frame_pix, layers, 1.0 / fx_scale_for(p->samples), (double)p->samples, p->output_sum, frame_reals);
+        HIP_TRY(h, hipGetLastError());
+    }
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     return stats ? finish_stats(h, stats, (uint64_t)npix * (uint64_t)p->sample_count, ds.n_entries, res) : CR_OK;
 }
 
-template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*);
-template int32_t aov_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*);
+template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t);
+template int32_t aov_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t);
 
 }   // namespace cr

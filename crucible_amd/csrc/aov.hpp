@@ -30,6 +30,12 @@ template <typename real> struct AovArgs {
     uint32_t unit_chunks;           // units per tile
     uint32_t n_units;
     uint32_t acc_lds_off;           // byte offset of the waves' slots in LDS (behind the staged scene)
+    // A batch of frames (cr_render_aov_frames_*, the BATCH kernels): the units of n_frames frames one after the other,
+    // frame_tiles tiles each.  Frame f's ray times start at frame_times[f]; its accumulators are acc + f * W * H *
+    // kAovWords, its flags are flags + f * W * H.  n_frames = 0: a single frame (cr_render_aov_*), none of this is read.
+    uint32_t n_frames;
+    uint32_t frame_tiles;
+    const real* frame_times;
 };
 
 // aov_f32.hip, aov_f64.hip: the residency ladder of the guide kernels (the render's own choices, render.hpp walk_ladder:

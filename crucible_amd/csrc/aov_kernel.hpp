@@ -20,7 +20,10 @@ CR_D bool aov_word(double x, double scale, long long& v) {
     return true;
 }
 
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+// BATCH: the kernels of cr_render_aov_frames_* -- the units of G.n_frames frames in one launch, frame after frame.  A unit
+// lies in one frame, so all that depends on the frame (its first ray time, its accumulators and flags) is wave-uniform;
+// pixels, tiles and the RNG key stay the frame's own.  The single-frame kernels do not carry the arithmetic.
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH>
 CR_D void aov_body(const AovArgs<real>& G) {
     using EntryT = typename EntryOf<real, ORD>::type;
     const KernelArgs<real>& A = G.k;
@@ -92,7 +95,12 @@ CR_D void aov_body(const AovArgs<real>& G) {
         if (lane == 0) wu = atomicAdd(A.work_counter, 1u);
         wu = (uint32_t)__builtin_amdgcn_readfirstlane((int)wu);
         if (wu >= G.n_units) break;
-        const uint32_t tile = wu / G.unit_chunks, chunk = wu - tile * G.unit_chunks;
+        const uint32_t unit_tile = wu / G.unit_chunks, chunk = wu - unit_tile * G.unit_chunks;
+        // BATCH: the unit's frame and what goes with it, from wu alone (scalar registers); `tile` is the frame's own
+        const uint32_t frame = BATCH ? unit_tile / G.frame_tiles : 0u;
+        const uint32_t tile = BATCH ? unit_tile - frame * G.frame_tiles : unit_tile;
+        const size_t frame_pix = BATCH ? (size_t)frame * ((size_t)cam.W * (size_t)cam.H) : 0;   // the frame's first pixel in the batch's planes
+        const real frame_time = BATCH ? G.frame_times[frame] : real(0);
         const uint32_t g0 = chunk * G.unit_groups, g1 = g0 + G.unit_groups < G.groups ? g0 + G.unit_groups : G.groups;
         const uint32_t px = lane & 15u;
         const uint32_t pix_i = ((tile % A.tiles_x) << 2) + (px & 3u), pix_j = ((tile / A.tiles_x) << 2) + (px >> 2);
@@ -108,7 +116,8 @@ CR_D void aov_body(const AovArgs<real>& G) {
             ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.best_t = 0; ws.best = -1; ws.idx = n_entries; ws.exact_box = false; ws.oct = 0; ws.pending = -1;
             bool walking = false;
             if (active) {   // cast_ray's primary ray (the keyed camera is a per-launch, wave-uniform branch of camera_ray)
-                camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
+                if constexpr (BATCH) camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime, frame_time);
+                else camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
                 c_seg++;
                 walk_begin(ws, rd);
                 walking = n_entries > 0;
@@ -192,7 +201,7 @@ CR_D void aov_body(const AovArgs<real>& G) {
                 if (!aov_word((double)vals[c], fxs, v)) bad |= 1u << c;
                 else if (v) (void)__hip_atomic_fetch_add(slot_word(px * kAovWords + c), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
-            if (bad) atomicOr(G.flags + ((size_t)pix_j * (size_t)cam.W + pix_i), bad);
+            if (bad) atomicOr(G.flags + (BATCH ? frame_pix : 0) + ((size_t)pix_j * (size_t)cam.W + pix_i), bad);
             if (want_depth && hit) {
                 unsigned long long bits, inf_bits;
                 if constexpr (std::is_same<real, double>::value) { bits = __builtin_bit_cast(unsigned long long, depth); inf_bits = 0x7ff0000000000000ull; }
@@ -210,7 +219,7 @@ CR_D void aov_body(const AovArgs<real>& G) {
                 slot[k] = 0ull;
                 const uint32_t q = k / kAovWords, ch = k - q * kAovWords;
                 const uint32_t pi = ((tile % A.tiles_x) << 2) + (q & 3u), pj = ((tile / A.tiles_x) << 2) + (q >> 2);
-                auto g = (__attribute__((address_space(1))) unsigned long long*)(G.acc + ((size_t)pj * (size_t)cam.W + pi) * kAovWords + ch);
+                auto g = (__attribute__((address_space(1))) unsigned long long*)(G.acc + (BATCH ? frame_pix * kAovWords : 0) + ((size_t)pj * (size_t)cam.W + pi) * kAovWords + ch);
                 if (ch == kAovDepth) (void)__hip_atomic_fetch_max(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 else (void)__hip_atomic_fetch_add(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -234,18 +243,21 @@ CR_D void aov_body(const AovArgs<real>& G) {
 }
 
 // (the arguments are read through the kernarg segment where they are used, as pathtrace_kernel reads its own)
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH = false>
 __global__ void __launch_bounds__(MaxBlock<real>::value) aov_kernel(const AovArgs<real> G) {
-    aov_body<real, RES, ANIM, ORD, SCREEN>(*(const AovArgs<real>*)(const __attribute__((address_space(4))) AovArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr());
+    aov_body<real, RES, ANIM, ORD, SCREEN, BATCH>(*(const AovArgs<real>*)(const __attribute__((address_space(4))) AovArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
 #endif   // __HIPCC__
 
 // One launch: persistent workgroups (one LDS copy of the scene each), the waves' slots behind the scene, units handed
 // out by the work counter -- about eight per resident wave, so that the tail is short and a unit still flushes rarely.
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+// A batch (a.n_frames frames, the BATCH kernels) is sized as one piece of work: the eight units per wave count the units
+// of all its frames, which share one ramp-up and one tail.  Its units are capped by the handle's work_counter_max; a
+// batch with more runs as consecutive launches of whole frames, each on its own part of the accumulators.
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH>
 int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* res) {
-    void (*kern)(const AovArgs<real>) = aov_kernel<real, RES, ANIM, ORD, SCREEN>;
+    void (*kern)(const AovArgs<real>) = aov_kernel<real, RES, ANIM, ORD, SCREEN, BATCH>;
     const int max_block = MaxBlock<real>::value;
     const size_t off = RES != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
     a.acc_lds_off = (uint32_t)off;
@@ -253,29 +265,50 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
     int block = 256, per_cu = 1;
     { int32_t rc = pick_block(h, (const void*)kern, max_block, true, off, aov_lds_bytes(64), "guide kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
     const uint64_t tiles = (uint64_t)a.k.tiles_x * a.k.tiles_y;
+    const uint64_t n_frames = BATCH ? a.n_frames : 1;
     const uint64_t resident = (uint64_t)h->n_cus * per_cu * (block / 64);
-    uint64_t ug = std::min<uint64_t>(a.groups, std::max<uint64_t>(1, tiles * a.groups / (8 * resident)));
-    const uint64_t max_units = 0xF0000000ull;   // the 32-bit work counter
+    uint64_t ug = std::min<uint64_t>(a.groups, std::max<uint64_t>(1, n_frames * tiles * a.groups / (8 * resident)));
+    // the 32-bit work counter (a frame has at most 2^22 tiles; a limit below one frame's tiles, which only a test sets, is raised to them)
+    const uint64_t max_units = BATCH ? std::max<uint64_t>(h->work_counter_max, tiles) : 0xF0000000ull;
     if (tiles * ((a.groups + ug - 1) / ug) > max_units) ug = (a.groups + max_units / tiles - 1) / (max_units / tiles);
     a.unit_groups = (uint32_t)ug;
     a.unit_chunks = (uint32_t)((a.groups + ug - 1) / ug);
-    a.n_units = (uint32_t)(tiles * a.unit_chunks);
-    uint32_t grid = (uint32_t)(h->n_cus * per_cu);
-    const uint64_t need_blocks = ((uint64_t)a.n_units + (block / 64) - 1) / (block / 64);
-    if ((uint64_t)grid > need_blocks) grid = (uint32_t)need_blocks;
-    if (grid < 1) grid = 1;
-    HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), off + aov_lds_bytes(block), h->stream, a);
-    HIP_TRY(h, hipGetLastError());
-    h->last_block = block; h->last_grid = (int)grid;
+    a.frame_tiles = (uint32_t)tiles;
+    const uint64_t frame_units = tiles * a.unit_chunks;
+    const uint64_t per_launch = std::min<uint64_t>(n_frames, max_units / frame_units);   // frames
+    const size_t npix = (size_t)a.k.cam.W * (size_t)a.k.cam.H;
+    unsigned long long* const acc = a.acc;
+    uint32_t* const flags = a.flags;
+    const real* const times = a.frame_times;
+    for (uint64_t f0 = 0; f0 < n_frames; f0 += per_launch) {
+        const uint64_t fn = std::min<uint64_t>(per_launch, n_frames - f0);
+        if constexpr (BATCH) {
+            a.n_frames = (uint32_t)fn;
+            a.frame_times = times + f0;
+            a.acc = acc + f0 * npix * kAovWords;
+            a.flags = flags + f0 * npix;
+        }
+        a.n_units = (uint32_t)(fn * frame_units);
+        uint32_t grid = (uint32_t)(h->n_cus * per_cu);
+        const uint64_t need_blocks = ((uint64_t)a.n_units + (block / 64) - 1) / (block / 64);
+        if ((uint64_t)grid > need_blocks) grid = (uint32_t)need_blocks;
+        if (grid < 1) grid = 1;
+        HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), off + aov_lds_bytes(block), h->stream, a);
+        HIP_TRY(h, hipGetLastError());
+        h->last_block = block; h->last_grid = (int)grid;
+    }
     *res = RES;
     return CR_OK;
 }
 
 // keyed primitives and leaves that hold a list walk with the ANIM decode (render.hip); a keyed camera needs no kernel of its own here
+// a.n_frames != 0: a batch (cr_render_aov_frames_*), on the BATCH kernels whatever its length
 template <typename real, int RES, bool ORD, bool SCREEN>
 int32_t aov_variant(CrHandle* h, AovArgs<real>& a, size_t lds_bytes, const WalkChoice& w, int* res) {
-    return w.anim ? aov_launch<real, RES, true, ORD, SCREEN>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN>(h, a, lds_bytes, res);
+    if (a.n_frames)
+        return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, true>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, true>(h, a, lds_bytes, res);
+    return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, false>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, false>(h, a, lds_bytes, res);
 }
 
 // walk_ladder's choices (render.hpp) for the guide kernels; the 6-waves-per-SIMD entry point has no counterpart here

@@ -50,7 +50,8 @@ static int32_t render_device(CrHandle* h, const CrCameraDesc* cam, const CrRende
     HIP_TRY(h, hipSetDevice(h->device));
     h->cam_pending_slot = -1;
     int32_t rc;
-    if (layers) rc = p->real_type == CR_REAL_F64 ? aov_typed<double>(h, cam, p, layers, d_out, stats) : aov_typed<float>(h, cam, p, layers, d_out, stats);
+    if (layers) rc = p->real_type == CR_REAL_F64 ? aov_typed<double>(h, cam, p, layers, d_out, stats, frames, n_frames)
+                                                     : aov_typed<float>(h, cam, p, layers, d_out, stats, frames, n_frames);
     else rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames)
                                           : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames);
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
@@ -117,21 +118,25 @@ static int32_t render_entry(CrHandle* h, const CrCameraDesc* cam, const CrRender
     return host ? render_host(h, cam, p, out, stats, frames, n_frames) : render_device(h, cam, p, out, stats, frames, n_frames);
 }
 
-// cr_render_aov_*: a render's argument checks, then the pass's own; the host form goes through the handle's output buffer
-static int32_t aov_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, bool host, void* out, CrStats* stats) {
+// cr_render_aov_*, cr_render_aov_frames_* (batch: `frames` is checked too): a render's argument checks, then the pass's
+// own; the host form goes through the handle's output buffer
+static int32_t aov_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, bool batch, const int32_t* frames, int32_t n_frames,
+                         bool host, void* out, CrStats* stats) {
     int32_t rc = validate_render(h, cam, p);
     if (rc != CR_OK) return rc;
+    if (batch && !frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
+    if (batch && n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
     const int32_t all = CR_AOV_ALBEDO | CR_AOV_NORMAL | CR_AOV_DEPTH | CR_AOV_COVERAGE;
     if (layers == 0 || (layers & ~all)) return fail(h, CR_ERR_INVALID_ARG, "layers must be a non-empty mask of CR_AOV_*");
     if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
     if (p->output_sum == CR_OUTPUT_FIXED_SUM) return fail(h, CR_ERR_UNSUPPORTED, "guide layers come as reals (output_sum 0 or 1), not as fixed-point words");
-    if (!host) return render_device(h, cam, p, out, stats, nullptr, 1, layers);
+    if (!host) return render_device(h, cam, p, out, stats, frames, n_frames, layers);
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t channels = (layers & CR_AOV_ALBEDO ? 3 : 0) + (layers & CR_AOV_NORMAL ? 3 : 0) + (layers & CR_AOV_DEPTH ? 1 : 0) + (layers & CR_AOV_COVERAGE ? 1 : 0);
-    const size_t bytes = (size_t)cam->image_width * cam->image_height * channels * real_size(p->real_type);
+    const size_t bytes = (size_t)n_frames * (size_t)cam->image_width * cam->image_height * channels * real_size(p->real_type);
     const hipError_t e = h->out_buf.ensure(bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
-    rc = render_device(h, cam, p, h->out_buf.p, stats, nullptr, 1, layers);
+    rc = render_device(h, cam, p, h->out_buf.p, stats, frames, n_frames, layers);
     if (rc != CR_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -245,11 +250,21 @@ int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRend
 }
 
 int32_t cr_render_aov_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, false, d_out, stats);
+    return aov_entry(h, cam, p, layers, false, nullptr, 1, false, d_out, stats);
 }
 
 int32_t cr_render_aov_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, void* h_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, true, h_out, stats);
+    return aov_entry(h, cam, p, layers, false, nullptr, 1, true, h_out, stats);
+}
+
+int32_t cr_render_aov_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames, int32_t n_frames,
+                                    void* d_out, CrStats* stats) {
+    return aov_entry(h, cam, p, layers, true, frames, n_frames, false, d_out, stats);
+}
+
+int32_t cr_render_aov_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames, int32_t n_frames,
+                                  void* h_out, CrStats* stats) {
+    return aov_entry(h, cam, p, layers, true, frames, n_frames, true, h_out, stats);
 }
 
 int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples, int32_t real_type,

@@ -284,9 +284,10 @@ int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size
 template <typename real> int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>& ds, bool anim, CrStats* stats);
 template <typename real> int32_t render_queue(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, bool anim, CrStats* stats, bool* launched);
 int32_t check_queue_abort(CrHandle* h);
-// aov.hip: the guide pass (cr_render_aov_*) after its argument checks; aov_f32.hip, aov_f64.hip: its kernels (aov.hpp)
+// aov.hip: the guide pass (cr_render_aov_*, cr_render_aov_frames_*) after its argument checks; aov_f32.hip, aov_f64.hip: its kernels (aov.hpp)
 template <typename real>
-int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats);
+int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats, const int32_t* frames,
+                  int32_t n_frames);
 // api.hip
 int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p);
 int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n, int32_t samples, bool f64, void* out);

@@ -576,7 +576,7 @@ public:
     // ---- Camera::render over the library (scene/mod.rs:283-347)
     // Wall-clock phases of the last render_scene call (a measurement aid: the reference's one benchmark times the whole
     // of render_scene -- BVH build, render, file -- benches/renderer_benchmark.rs:16-42).
-    struct Timing { double create_ms = 0, flatten_ms = 0, upload_ms = 0, bvh_build_ms = 0, render_ms = 0, write_ms = 0, total_ms = 0, kernel_ms = 0; size_t frames = 0; };
+    struct Timing { double create_ms = 0, flatten_ms = 0, upload_ms = 0, bvh_build_ms = 0, render_ms = 0, write_ms = 0, total_ms = 0, kernel_ms = 0; size_t frames = 0, guide_calls = 0; };   // guide_calls: cr_render_aov_* calls of a movie
     Timing timing;
     int sum_order = CR_SUM_DEFAULT;    // CrRenderParams.sum_order
     static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -623,6 +623,13 @@ public:
         CrCameraDesc cd = camera_desc(fk, ak);
         CrRenderParams p = render_params(frame < 0 ? (size_t)scene_cam.frame : (size_t)frame);
         return cr_render_aov_host(h, &cd, &p, aov_layers, planes, stats);
+    }
+    // The guide layers of the frames `frs` in one call (cr_render_aov_frames_host): frame k at k * aov_reals() reals in `planes`.
+    int32_t render_aov_frames(CrHandle* h, void* planes, const std::vector<int32_t>& frs, CrStats* stats = nullptr) const {
+        std::vector<CrKeyframe> fk, ak;
+        CrCameraDesc cd = camera_desc(fk, ak);
+        CrRenderParams p = render_params(0);   // the frame indices come from frs
+        return cr_render_aov_frames_host(h, &cd, &p, aov_layers, frs.data(), (int32_t)frs.size(), planes, stats);
     }
     // <fname>.albedo.pfm, .normal.pfm, .depth.pfm, .coverage.pfm: the requested planes of one frame
     int32_t write_aov(const std::string& fname, const void* planes) const {
@@ -681,7 +688,8 @@ public:
     }
     // render_movie (scene/mod.rs:295-322) for the frames first, first + step, ... on one handle, frames_per_launch of
     // them per call (cr_render_frames_host; a library that refuses the batch -- reference order, refit boxes -- gets one
-    // frame per call, the same files).  Batch b is encoded and written by a helper thread while batch b+1 renders (two
+    // frame per call, the same files; the batch's guide layers come from one cr_render_aov_frames_host call either way,
+    // unless the library refuses that one too -- refit boxes -- and gets one cr_render_aov_host call per frame).  Batch b is encoded and written by a helper thread while batch b+1 renders (two
     // buffers; SURVEY 8(f) row 3 -- the reference formats and writes each frame before starting the next).  render_ms:
     // time this thread spent inside renders; write_ms: time the helper threads spent encoding and writing (overlapped,
     // so it is not part of the wall clock unless it is the longer one).
@@ -692,25 +700,48 @@ public:
         int32_t write_rc[2] = {CR_OK, CR_OK};
         double write_ms[2] = {0, 0};
         int32_t rc = CR_OK;
-        bool batched = frames_per_launch > 1;
+        bool batched = frames_per_launch > 1, guides_batched = frames_per_launch > 1;
+        const size_t rs = real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float);
         size_t k = 0;
         for (size_t fr = first; rc == CR_OK && fr < frames; k++) {
             const int slot = (int)(k & 1);
             if (writers[slot].joinable()) { writers[slot].join(); if (write_rc[slot] != CR_OK) { rc = write_rc[slot]; break; } }
             std::vector<int32_t> batch;   // fr, fr + step, ...
-            for (size_t f = fr; f < frames && batch.size() < (batched ? frames_per_launch : 1); f += step) batch.push_back((int32_t)f);
+            for (size_t f = fr; f < frames && batch.size() < ((batched || (aov_layers && guides_batched)) ? frames_per_launch : 1); f += step) batch.push_back((int32_t)f);
             CrStats st;
+            memset(&st, 0, sizeof st);
             const double t0 = now_ms();
+            double kernel_ms = 0;
             if (batched) {
                 rc = render_frames(h, bufs[slot], batch, &st);
-                if (rc == CR_ERR_UNSUPPORTED) { batched = false; batch.resize(1); }
+                kernel_ms = st.kernel_ms;
+                if (rc == CR_ERR_UNSUPPORTED) batched = false;
             }
-            if (!batched) rc = render_frame(h, bufs[slot], &st, (int64_t)batch[0]);
-            if (tm) { tm->render_ms += now_ms() - t0; tm->kernel_ms += st.kernel_ms; tm->frames += batch.size(); }
+            if (!batched) {   // one frame per call into the batch's buffer (a batch of several: its guide layers still share a call)
+                std::vector<double> one;
+                bufs[slot].resize((frame_bytes() * batch.size() + sizeof(double) - 1) / sizeof(double));
+                rc = CR_OK;
+                for (size_t i = 0; i < batch.size() && rc == CR_OK; i++) {
+                    rc = render_frame(h, one, &st, (int64_t)batch[i]);
+                    if (rc == CR_OK) { memcpy((char*)bufs[slot].data() + i * frame_bytes(), one.data(), frame_bytes()); kernel_ms += st.kernel_ms; }
+                }
+            }
+            if (tm) { tm->render_ms += now_ms() - t0; tm->kernel_ms += kernel_ms; tm->frames += batch.size(); }
             if (stats) *stats = st;
             if (rc == CR_OK && aov_layers) {
-                guides[slot].resize(aov_reals() * batch.size());
-                for (size_t i = 0; i < batch.size() && rc == CR_OK; i++) rc = render_aov(h, (void*)((char*)guides[slot].data() + i * aov_reals() * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float))), nullptr, (int64_t)batch[i]);
+                guides[slot].resize((aov_reals() * rs * batch.size() + sizeof(double) - 1) / sizeof(double));
+                if (guides_batched) {
+                    rc = render_aov_frames(h, guides[slot].data(), batch);
+                    if (rc == CR_ERR_UNSUPPORTED) guides_batched = false;
+                    else if (tm) tm->guide_calls++;
+                }
+                if (!guides_batched) {
+                    rc = CR_OK;
+                    for (size_t i = 0; i < batch.size() && rc == CR_OK; i++) {
+                        rc = render_aov(h, (void*)((char*)guides[slot].data() + i * aov_reals() * rs), nullptr, (int64_t)batch[i]);
+                        if (tm) tm->guide_calls++;
+                    }
+                }
             }
             if (rc != CR_OK) break;
             std::vector<std::string> stems;
@@ -778,7 +809,7 @@ public:
         int32_t rc = CR_OK;
         for (int m = 0; m < n; m++) {
             timing.render_ms = std::max(timing.render_ms, member_tm[(size_t)m].render_ms); timing.write_ms = std::max(timing.write_ms, member_tm[(size_t)m].write_ms);
-            timing.kernel_ms += member_tm[(size_t)m].kernel_ms; timing.frames += member_tm[(size_t)m].frames;
+            timing.kernel_ms += member_tm[(size_t)m].kernel_ms; timing.frames += member_tm[(size_t)m].frames; timing.guide_calls += member_tm[(size_t)m].guide_calls;
             if (member_rc[(size_t)m] != CR_OK) { fprintf(stderr, "Render failed on device %d. %s\n", device + m, member_err[(size_t)m].c_str()); if (rc == CR_OK) rc = member_rc[(size_t)m]; }
         }
         if (rc == CR_OK) print_mp4_command(fname, digits);

@@ -153,9 +153,9 @@ int main(int argc, char** argv) {
                 const double samples = (double)scene.scene_cam.image_width * scene.scene_cam.image_height * scene.scene_cam.samples * (movie ? (double)t.frames : 1.0);
                 printf("{\"run\": %d, \"width\": %u, \"height\": %u, \"samples\": %u, \"frames\": %zu, \"format\": \"%s\", \"real\": \"%s\", \"create_ms\": %.3f, \"flatten_ms\": %.3f, "
                        "\"upload_ms\": %.3f, \"bvh_build_ms\": %.3f, \"render_ms\": %.3f, \"kernel_ms\": %.3f, \"write_ms\": %.3f, \"total_ms\": %.3f, \"msamples_per_s_end_to_end\": %.1f, "
-                       "\"msamples_per_s_kernel\": %.1f}\n",
+                       "\"msamples_per_s_kernel\": %.1f, \"guide_calls\": %zu}\n",
                        rep, scene.scene_cam.image_width, scene.scene_cam.image_height, scene.scene_cam.samples, movie ? t.frames : (size_t)1, format.c_str(), real.c_str(), t.create_ms,
-                       t.flatten_ms, t.upload_ms, t.bvh_build_ms, t.render_ms, t.kernel_ms, t.write_ms, t.total_ms, samples / t.total_ms / 1e3, t.kernel_ms > 0 ? samples / t.kernel_ms / 1e3 : 0.0);
+                       t.flatten_ms, t.upload_ms, t.bvh_build_ms, t.render_ms, t.kernel_ms, t.write_ms, t.total_ms, samples / t.total_ms / 1e3, t.kernel_ms > 0 ? samples / t.kernel_ms / 1e3 : 0.0, t.guide_calls);
                 fflush(stdout);
             }
         }

@@ -183,6 +183,43 @@ class Renderer:
                                                   C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    def render_aov_frames(self, cam, frames, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
+                          sample_count=None, output_sum=False, want_stats=True):
+        """cr_render_aov_frames_host: the guide layers `layers` of the frames `frames` (frame indices; cam.frame is not
+        used) in one launch.  Returns (list of per-frame dicts shaped like render_aov's, stats dict of the whole call);
+        frame k equals render_aov() at frame frames[k] bit for bit."""
+        layers = aov_mask(layers)
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        fr, fr_ptr = frame_list(frames)
+        H, W = cam.image_height, cam.image_width
+        planes = [(n, c) for n, bit, c in A.AOV_LAYERS if layers & bit]
+        stride = W * H * sum(c for _, c in planes)
+        buf = np.empty(max(1, stride * fr.size), dtype=np_real(real_type))
+        st = A.CrStats()
+        self._check(self.lib.cr_render_aov_frames_host(self.h, C.byref(cd), C.byref(p), layers, fr_ptr, fr.size,
+                                                       buf.ctypes.data_as(C.c_void_p), C.byref(st) if want_stats else None))
+        out = []
+        for k in range(fr.size):
+            frame, o = {}, k * stride
+            for n, c in planes:
+                frame[n] = buf[o:o + W * H * c].reshape((H, W, 3) if c == 3 else (H, W))
+                o += W * H * c
+            out.append(frame)
+        return out, st.as_dict()
+
+    def render_aov_frames_device(self, cam, frames, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32,
+                                 sample_begin=0, sample_count=None, output_sum=False, want_stats=False):
+        """cr_render_aov_frames_device: frame after frame into device memory at `d_ptr`, each frame's requested planes
+        one after the other in ascending bit order.  Asynchronous unless want_stats."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        fr, fr_ptr = frame_list(frames)
+        st = A.CrStats()
+        self._check(self.lib.cr_render_aov_frames_device(self.h, C.byref(cd), C.byref(p), aov_mask(layers), fr_ptr, fr.size,
+                                                         C.c_void_p(d_ptr), C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
         """cr_fixed_sums_to_rgb: summed CR_OUTPUT_FIXED_SUM words of a whole frame (device pointer, W*H*3 uint64) ->
         its per-pixel means at device pointer `d_out` (W*H*3 reals), exactly the relaxed frame.  Asynchronous on the
@@ -252,6 +289,14 @@ class Renderer:
         rc = fn(path.encode(), img.ctypes.data_as(C.c_void_p), rt, img.shape[1], img.shape[0])
         if rc != A.CR_OK:
             raise CrucibleError(rc, "cannot write " + path)
+
+
+def frame_list(frames):
+    """(int32 array, pointer to it) of a batch's frame indices; None stays a null pointer (the library refuses it)."""
+    if frames is None:
+        return np.zeros(0, dtype=np.int32), None
+    fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+    return fr, fr.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def aov_mask(layers):

@@ -478,6 +478,7 @@ class Scene:
         self.device = 0
         self.bvh_mode = A.CR_BVH_REFERENCE   # A.CR_BVH_SAH: the quality builder (include/crucible_hip.h)
         self.frames_per_launch = 1   # render_movie: N > 1 renders N frames per call through Renderer.render_frames
+        self.aov_layers = 0          # CR_AOV_* mask or layer names: writes <frame>.<layer>.pfm next to every frame file
 
     @classmethod
     def new_image(cls, aspect_ratio, image_width, frame_rate, shutter_angle, thread_count):
@@ -658,8 +659,15 @@ class Scene:
             return self.render_movie(fname)
         return self.render_image(fname)
 
+    @staticmethod
+    def _write_aov(stem, planes):
+        """<stem>.albedo.pfm, .normal.pfm, .depth.pfm, .coverage.pfm: the planes of one frame"""
+        from .renderer import write_pfm
+        for name, plane in planes.items():
+            write_pfm(f"{stem}.{name}.pfm", plane)
+
     def render_image(self, fname, renderer=None):
-        from .renderer import Renderer
+        from .renderer import Renderer, aov_mask
         own = renderer is None
         r = renderer or Renderer(self.device)
         try:
@@ -667,6 +675,9 @@ class Scene:
             img, stats = r.render(self.scene_cam, seed=self.seed, real_type=self.real_type)
             r.write_ppm(fname + ".ppm", img)
             print(f"Successful render! Image stored at: {fname}.ppm")
+            if aov_mask(self.aov_layers):
+                planes, _ = r.render_aov(self.scene_cam, self.aov_layers, seed=self.seed, real_type=self.real_type)
+                self._write_aov(fname, planes)
             return stats
         finally:
             if own:
@@ -680,34 +691,50 @@ class Scene:
                 f"{fname}/movie.mp4"]
 
     def render_movie(self, fname):
-        from .renderer import CrucibleError, Renderer
+        from .renderer import CrucibleError, Renderer, aov_mask
         os.mkdir(fname)   # scene/mod.rs:296: fails if it exists
         os.mkdir(os.path.join(fname, "artifacts"))
         frames = self.compute_frame_count()
         digits = len(str(frames))
+        layers = aov_mask(self.aov_layers)
         r = Renderer(self.device)
         try:
             r.upload_scene(self.flatten())
             n = max(1, int(self.frames_per_launch))
-            batched = n > 1
+            # the frames and the guide layers of a batch each come from one call, until the library refuses that call
+            # (frames: reference order or refit boxes; guide layers: refit boxes): then one call per frame, the same files
+            batched = guides_batched = n > 1
+            cam = self.scene_cam
             frame = 0
             while frame < frames:
+                # the camera's frame counter for each file, as the one-frame loop advances it
+                first = cam.frame
+                batch = [first + k for k in range(min(n, frames - frame) if batched or (layers and guides_batched) else 1)]
+                imgs = None
                 if batched:
-                    # the camera's frame counter for each file, as the one-frame loop advances it
-                    batch = [self.scene_cam.frame + k for k in range(min(n, frames - frame))]
                     try:
-                        imgs, _ = r.render_frames(self.scene_cam, batch, seed=self.seed, real_type=self.real_type)
+                        imgs, _ = r.render_frames(cam, batch, seed=self.seed, real_type=self.real_type)
                     except CrucibleError as e:
                         if e.code != A.CR_ERR_UNSUPPORTED:
                             raise
-                        batched = False   # reference order or refit boxes: one frame per call, the same files
-                        continue
-                else:
-                    img, _ = r.render(self.scene_cam, seed=self.seed, real_type=self.real_type)
-                    imgs = img[None]
-                for img in imgs:
-                    r.write_ppm(os.path.join(fname, "artifacts", f"image{frame:0{digits}d}.ppm"), img)
-                    self.scene_cam.next_frame()
+                        batched = False
+                guides = None
+                if layers and guides_batched:
+                    try:
+                        guides, _ = r.render_aov_frames(cam, batch, layers, seed=self.seed, real_type=self.real_type)
+                    except CrucibleError as e:
+                        if e.code != A.CR_ERR_UNSUPPORTED:
+                            raise
+                        guides_batched = False
+                for k, f in enumerate(batch):
+                    cam.frame = f
+                    img = imgs[k] if imgs is not None else r.render(cam, seed=self.seed, real_type=self.real_type)[0]
+                    stem = os.path.join(fname, "artifacts", f"image{frame:0{digits}d}")
+                    r.write_ppm(stem + ".ppm", img)
+                    if layers:
+                        self._write_aov(stem, guides[k] if guides is not None else
+                                        r.render_aov(cam, layers, seed=self.seed, real_type=self.real_type)[0])
                     frame += 1
+                cam.frame = first + len(batch)
         finally:
             r.close()

@@ -476,6 +476,44 @@ CR_API int32_t cr_render_aov_device(CrHandle* h, const CrCameraDesc* cam, const 
 CR_API int32_t cr_render_aov_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
                                   void* h_out, CrStats* stats);
 
+/*
+ * The guide layers of a batch of movie frames in one launch: what cr_render_frames_* is to cr_render_device, for
+ * cr_render_aov_device.  frames[k] is the frame index params->frame would carry for frame k (params->frame itself is
+ * ignored); any list works -- consecutive, strided, descending or repeated.  The output holds n_frames consecutive
+ * frames, frame k at k * R reals, R the reals of the requested planes (3*W*H per three-channel layer, W*H per
+ * one-channel layer), each laid out as cr_render_aov_device lays out one frame: planes in ascending bit order, layers
+ * that were not requested take no space.
+ *
+ * Frame k is bit for bit what cr_render_aov_device writes for the same camera, params and `layers` with
+ * frame = frames[k]: in f32 and f64, for output_sum 0 and 1, every sample_begin / sample_count, every bvh_mode, every
+ * residency of the scene and every CRUCIBLE_PIPELINE and CRUCIBLE_SUM_ORDER setting -- the frames differ only in their
+ * ray times (computed on the host as for a single call), the RNG streams are keyed by the frame's own pixel index, and
+ * the accumulators are integer sums and minima.  Unlike cr_render_frames_* it does not need CR_SUM_RELAXED: sum_order
+ * and max_depth are validated and otherwise not read.  The frames' work is handed out as one launch (one ramp-up and
+ * one tail for all of them); a batch with more work units than the 32-bit work counter holds runs as several launches
+ * of whole frames.
+ *
+ * `stats` covers the whole call: `samples` and the counters summed over the frames (segments == samples), one
+ * kernel_ms, bvh_entries and scene_in_lds as for one frame.
+ *
+ * A null `frames` or n_frames < 1: CR_ERR_INVALID_ARG.  layers == 0 or an unknown bit: CR_ERR_INVALID_ARG.  Everything
+ * cr_render_aov_device rejects is rejected alike (CR_OUTPUT_FIXED_SUM: CR_ERR_UNSUPPORTED).  A call that would refit
+ * or rebuild boxes (refit_boxes with keyed primitives or HitList elements, CR_REFIT_REBUILD where it would build) is
+ * CR_ERR_UNSUPPORTED as for cr_render_frames_* -- boxes are per frame, a batch shares one set -- and the caller makes
+ * one cr_render_aov_* call per frame; refit_boxes on a scene where a refit changes nothing is accepted.  A refused
+ * call leaves the handle as it was.
+ * The handle keeps 64 bytes of accumulators and 4 of flags per pixel PER FRAME of the batch, grown on demand, freed
+ * by cr_destroy; a batch too large for device memory fails with CR_ERR_HIP.  An empty shard (sample_count == 0)
+ * launches no first-hit kernel and writes, for every frame, what the single call writes.
+ * Asynchronous unless `stats` is non-NULL.
+ */
+CR_API int32_t cr_render_aov_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                           const int32_t* frames, int32_t n_frames, void* d_out, CrStats* stats);
+
+/* Same, into a HOST buffer of n_frames frames (synchronous). */
+CR_API int32_t cr_render_aov_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                         const int32_t* frames, int32_t n_frames, void* h_out, CrStats* stats);
+
 /* The wrapper tree the device walks for `real_type`, as BVHWrapper's shape (src/objects/bvhwrapper.rs:7-11):
  * wrapper k has boxes[6k..6k+5] = xmin,xmax,ymin,ymax,zmin,zmax (exact values of `real_type`) and
  * children[2k], children[2k+1] = left, right: >= 0 another wrapper's index, < 0 the bitwise complement of a
