@@ -37,8 +37,9 @@ def fx_log2(samples):   # fx_scale_for
     return min(52, 62 - lg)
 
 
-def model_words(oracle, scene_h, flat, cam, seed, sample_begin=0, sample_count=None):
-    """Per pixel: the 7 integer sums (albedo, encoded normal, coverage), the flagged channels and the minimum depth."""
+def model_words(oracle, scene_h, flat, cam, seed, sample_begin=0, sample_count=None, tmin=0.001):
+    """Per pixel: the 7 integer sums (albedo, encoded normal, coverage), the flagged channels and the minimum depth.
+    tmin: where the hit interval starts -- the pass's 0.001, or another value for a test that shows a scene depends on it."""
     R = oracle.np_real
     L = oracle.lib
     cd = cam.desc()
@@ -59,7 +60,7 @@ def model_words(oracle, scene_h, flat, cam, seed, sample_begin=0, sample_count=N
                 L.oracle_camera_ray(C.byref(cd), C.byref(p), i, j, s, ptr(ray))
                 orig[:] = ray[0:3]
                 dirn[:] = ray[3:6]
-                hit = L.oracle_world_hit(scene_h, ptr(orig), ptr(dirn), oracle.real(ray[6]), oracle.real(0.001),
+                hit = L.oracle_world_hit(scene_h, ptr(orig), ptr(dirn), oracle.real(ray[6]), oracle.real(tmin),
                                          oracle.real(np.inf), ptr(rec), C.byref(mat))
                 if hit:
                     m = flat.materials[mat.value]
@@ -114,17 +115,20 @@ def finalize(words, cam, R, output_sum):
             "depth": depth.reshape(H, W), "coverage": np.ascontiguousarray(out[:, 6]).reshape(H, W)}
 
 
-def model(oracle, scene, seed, tree=None, sample_begin=0, sample_count=None, output_sum=0):
+def model(oracle, scene, seed, tree=None, sample_begin=0, sample_count=None, output_sum=0, linear_list=False, tmin=0.001):
+    """linear_list: the probes walk no tree at all (Oracle.render_image's switch), for an exported tree without wrappers."""
     flat = scene.flatten()
     cam = scene.scene_cam
     h = oracle.scene_create(flat)
     try:
         if tree is not None:
             oracle.set_tree(h, *tree)
+        if linear_list:
+            oracle.lib.oracle_use_list(h)
         # oracle_render leaves the boxes of its frame in the scene it rendered (scene_prepare_boxes: the refitted ones
         # with refit_boxes, else the construction-time ones): a one-pixel render primes the scene for the probes
         oracle.render(h, cam, seed=seed, pix_begin=0, pix_end=1, n_threads=1)
-        words = model_words(oracle, h, flat, cam, seed, sample_begin, sample_count)
+        words = model_words(oracle, h, flat, cam, seed, sample_begin, sample_count, tmin)
     finally:
         oracle.scene_destroy(h)
     return finalize(words, cam, oracle.np_real, output_sum), words
