@@ -131,8 +131,9 @@ CR_HD uint64_t rng_key(uint64_t seed_mixed, uint32_t pixel, uint32_t sample) {
     const uint64_t k = mix64(seed_mixed ^ (((uint64_t)pixel << 32) | (uint64_t)sample));
     return k ? k : RNG_GAMMA;   // xorshift state must not be zero
 }
+CR_HD void rng_step(uint64_t& s) { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; }   // the state alone: a draw whose value nobody reads
 CR_HD uint64_t rng_next(uint64_t& s) {
-    s ^= s >> 12; s ^= s << 25; s ^= s >> 27;
+    rng_step(s);
     return s * 0x2545F4914F6CDD1DULL;
 }
 // The conversions go through 32-bit words (exact: 24 resp. 21+32 significant bits), which is much
@@ -399,7 +400,8 @@ template <typename real> CR_HD CamFrame<real> camera_frame(const CamConst<real>&
 #ifdef CR_DIAG
 enum { DG_BOX_WAVE = 0, DG_BOX_LANE, DG_PRIM_WAVE, DG_PRIM_LANE, DG_ROUND_WAVE, DG_ROUND_LANE, DG_LEAFPH_WAVE, DG_LEAFPH_LANE,
        DG_SHADE_WAVE, DG_SHADE_LANE, DG_LAMB_LANE, DG_METAL_LANE, DG_DIEL_LANE, DG_SKY_LANE, DG_RUV_WAVE, DG_RUV_LANE,
-       DG_REGEN_WAVE, DG_REGEN_LANE, DG_OUTER_WAVE, DG_UNWIND_WAVE, DG_UNWIND_LANE, DG_HITSH_WAVE, DG_HITSH_LANE, DG_BAND_WAVE, DG_BAND_LANE, DG_N };
+       DG_REGEN_WAVE, DG_REGEN_LANE, DG_OUTER_WAVE, DG_UNWIND_WAVE, DG_UNWIND_LANE, DG_HITSH_WAVE, DG_HITSH_LANE, DG_BAND_WAVE, DG_BAND_LANE,
+       DG_ROOT2_WAVE, DG_ROOT2_LANE, DG_N };
 struct Diag { uint32_t v[DG_N]; };
 #define CR_DIAG_LEADER() ((threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)__ballot(1)) - 1))
 #define CR_DIAG_HIT(dg, wave_i, lane_i) do { if (dg) { (dg)->v[lane_i]++; if (CR_DIAG_LEADER()) (dg)->v[wave_i]++; } } while (0)
@@ -471,8 +473,46 @@ CR_D bool box_miss_fast(const real* b, Pair<real> ox, Pair<real> oy, Pair<real> 
 }
 
 // Sphere::hit root search (sphere.rs:72-95): returns t or a negative number for a miss.
-template <typename real>
-CR_D bool sphere_t(real cx, real cy, real cz, real radius, V3<real> o, V3<real> d, real a /* |d|^2 */, real tmin, real tmax, real& t_out) {
+// The reference divides twice, root1 = (h - sqrtd) / a and, when that one is out of range, root2 = (h + sqrtd) / a.  An
+// IEEE division is ~16 VALU instructions and a wave runs the second one as soon as ONE lane asks for it -- and every
+// scattered ray starts on the sphere it left, reaches that sphere's leaf and finds both roots near zero there.  So the
+// outcome of the second test is decided without dividing wherever that is provable; a lane that still divides computes
+// what the reference computes.  With n1 = fl(h - sqrtd), n2 = fl(h + sqrtd), a = |d|^2 (+0 or above, or NaN: a sum of
+// squares) and root1 outside (tmin, tmax):
+//   Rule A: !(root1 <= tmin) -> miss.  Then root1 > tmin or root1 is NaN.
+//     root1 > tmin: the first test failed at its upper end, !(root1 < tmax), so tmax is NaN (every `< tmax` fails) or
+//       root1 >= tmax.  sqrtd >= 0 (or -0) gives h - sqrtd <= h + sqrtd exactly, rounding to nearest is monotone, so
+//       n2 >= n1, and for a > 0 the rounded quotients keep that order: root2 >= root1 >= tmax.  a subnormal: the quotients
+//       may overflow to +inf, which keeps the order.  a = 0: root1 = +inf here, so n2 >= n1 > 0 and root2 = +inf as well.
+//       (sqrtd = +inf with a finite h, or h = -inf, give n1 = -inf: root1 <= tmin, not this rule.)
+//     root1 NaN: then root2 is NaN or +inf, and neither is below any tmax.  Case by case: a NaN -> root2 NaN.  n1 NaN: h or
+//       sqrtd is NaN (a NaN disc passes `disc < 0`) -> n2 NaN; or h = sqrtd = +inf -> n2 = +inf, root2 = +inf (NaN for
+//       a = +inf).  n1 = +-0 over a = 0: n2 >= 0, root2 = NaN or +inf.  n1 = +-inf over a = +inf: n2 is +inf or NaN, root2 NaN.
+//   Rule B: hi(n2) < hi(a) - 11 * 2^M as signed integers (hi: the word holding sign and exponent, M: the exponent's bit
+//     position in it) -> miss, valid for tmin >= 2^-10; tmin is 0.001 in every walk.  a is not NaN here (rule A took it).
+//     hi(n2) < 0: n2 is negative, -0 or a negative NaN, and n2 / a is negative, -0, -inf or NaN for every a >= +0.
+//     hi(n2) >= 0: then hi(a) > hi(n2) + 11 * 2^M, so a >= 2^11 * the smallest normal and n2 is finite and not NaN.  Let v
+//       be n2 with 11 added to its exponent field: v = 2^11 n2 for a normal n2 and v >= 2^11 n2 for a subnormal or zero
+//       one ((1 + m) 2^e >= 2 m 2^e for a fraction m < 1).  hi(v) < hi(a), both non-negative, gives v < a, so exactly
+//       n2 / a < 2^-11, the rounded quotient is <= 2^-11 < tmin, and `tmin < root2` fails (a = +inf: root2 = 0).
+//     No product is formed, so nothing underflows.  (`n2 > 0` alone is provable in a line but is not enough: on the sphere
+//     a ray leaves, n2 is rounding noise of either sign, and one lane that asks is enough to run the division for the wave.)
+// tests/sphere_roots_check.hip compares this with the two divisions written out, on the device.
+CR_D bool root2_below_tmin(double n2, double a, double tmin) {
+    if (!(tmin >= 0x1.0p-10)) return false;
+    const int32_t hn = (int32_t)((uint64_t)__double_as_longlong(n2) >> 32), ha = (int32_t)((uint64_t)__double_as_longlong(a) >> 32);
+    return hn < ha - (11 << 20);
+}
+CR_D bool root2_below_tmin(float n2, float a, float tmin) {
+    if (!(tmin >= 0x1.0p-10f)) return false;
+    return __float_as_int(n2) < __float_as_int(a) - (11 << 23);
+}
+// RULE_B = false keeps rule A alone: the extra exit costs the f64 kernels that read their tree from global memory (RES_GLOBAL,
+// RES_TOP) two VGPR spills in the shading code, and the frames that run them and test few or no spheres lost 0.6-1.1 %
+// (teapot, the orbit movie; profiles/experiments/decided_early_ab.txt), so walk_round asks for rule B in the RES_LDS kernels only.
+template <bool RULE_B = true, typename real>
+CR_D bool sphere_t(real cx, real cy, real cz, real radius, V3<real> o, V3<real> d, real a /* |d|^2 */, real tmin, real tmax, real& t_out,
+                   Diag* dg = nullptr) {
     V3<real> oc = sub(mk<real>(cx, cy, cz), o);
     real h = dot(d, oc);
     real c = len2(oc) - radius * radius;
@@ -481,7 +521,11 @@ CR_D bool sphere_t(real cx, real cy, real cz, real radius, V3<real> o, V3<real> 
     real sqrtd = r_sqrt(disc);
     real root = (h - sqrtd) / a;
     if (!(tmin < root && root < tmax)) {
-        root = (h + sqrtd) / a;
+        if (!(root <= tmin)) return false;                 // rule A
+        const real n2 = h + sqrtd;
+        if (RULE_B && root2_below_tmin(n2, a, tmin)) return false;   // rule B
+        CR_DIAG_HIT(dg, DG_ROOT2_WAVE, DG_ROOT2_LANE);
+        root = n2 / a;
         if (!(tmin < root && root < tmax)) return false;
     }
     t_out = root;
@@ -870,7 +914,13 @@ CR_D bool shade(const KernelArgs<real>& A, const Prim<real>* prims, const Mat<re
             }
             att = c_scale(m.aux, (m.param < real(0)) ? c_neg(tc) : tc);   // tc / scatter_prob
             ndir = dir;
-            some = rng_uniform<real>(rng) <= m.param;
+            // Lambertian scatters when a uniform draw u <= scatter_prob (lambertian.rs:55).  u = k * 2^-53 (2^-24 in f32)
+            // with k below 2^53 (2^24), so u <= 1 - 2^-53 < 1 and the test holds whatever the draw once scatter_prob >= 1:
+            // every Lambertian of the book scenes.  When all Lambertian lanes of the wave are of that kind (one ballot, a
+            // scalar branch) the stream advances by its state step alone -- the output multiply (64-bit, quarter rate) and
+            // the conversion are never formed.  A smaller or NaN probability in any lane: the reference's test, whole wave.
+            if (__ballot(!(m.param >= real(1))) == 0ull) { rng_step(rng); some = true; }
+            else some = rng_uniform<real>(rng) <= m.param;
         } else if (m.kind == 1) {                           // metal.rs:29-42
             V3<real> refl = reflect(rd, n);
             refl = add(unit(refl), scale(m.param, ruv));
@@ -1340,7 +1390,7 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             const int32_t kind = A.uniform_kind >= 0 ? A.uniform_kind : p.kind();   // a scalar test; one load fewer per primitive when it holds
             if (kind == 0) {
                 if (ANIM && p.key_count) timeline_eval(A.keys + p.key_first, p.key_count, rtime, g0, g1, g2, g3);
-                h = sphere_t(g0, g1, g2, g3, ro, rd, w.dd, tmin, w.best_t, t);
+                h = sphere_t<RES == RES_LDS>(g0, g1, g2, g3, ro, rd, w.dd, tmin, w.best_t, t, dg);
             } else {
                 V3<real> a = mk<real>(g0, g1, g2), b = mk<real>(g3, p.g[4], p.g[5]), c = mk<real>(p.g[6], p.g[7], p.g[8]);
                 if (ANIM && p.key_count) {
