@@ -75,7 +75,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, frames, n_frames, times, a.k, w, fb);
         if (rc != CR_OK) return rc;
         dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
-        a.k.tiles_x = ((uint32_t)cd->image_width + 3u) >> 2; a.k.tiles_y = ((uint32_t)cd->image_height + 3u) >> 2;
+        set_tiles(a.k, ((uint32_t)cd->image_width + 3u) >> 2, ((uint32_t)cd->image_height + 3u) >> 2);
         a.k.fx_scale = fx_scale_for(p->samples);   // of the whole frame, so that the words of shards add up
         a.acc = (unsigned long long*)h->aov_acc.p; a.flags = (uint32_t*)h->aov_flags.p;
         a.layers = layers;

@@ -103,7 +103,9 @@ CR_D void aov_body(const AovArgs<real>& G) {
         const real frame_time = BATCH ? G.frame_times[frame] : real(0);
         const uint32_t g0 = chunk * G.unit_groups, g1 = g0 + G.unit_groups < G.groups ? g0 + G.unit_groups : G.groups;
         const uint32_t px = lane & 15u;
-        const uint32_t pix_i = ((tile % A.tiles_x) << 2) + (px & 3u), pix_j = ((tile / A.tiles_x) << 2) + (px >> 2);
+        uint32_t tile_x, tile_y;   // (scalars, like the tile)
+        tile_xy(A, tile, tile_x, tile_y);
+        const uint32_t pix_i = (tile_x << 2) + (px & 3u), pix_j = (tile_y << 2) + (px >> 2);
         const bool in_image = pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H;
         for (uint32_t g = g0; g < g1; g++) {
             const uint32_t s_off = g * 4u + (lane >> 4);   // begin + offset may pass INT32_MAX in the last group's padding: the offset decides
@@ -218,7 +220,7 @@ CR_D void aov_body(const AovArgs<real>& G) {
             if (v) {   // (only pixels inside the image ever add)
                 slot[k] = 0ull;
                 const uint32_t q = k / kAovWords, ch = k - q * kAovWords;
-                const uint32_t pi = ((tile % A.tiles_x) << 2) + (q & 3u), pj = ((tile / A.tiles_x) << 2) + (q >> 2);
+                const uint32_t pi = (tile_x << 2) + (q & 3u), pj = (tile_y << 2) + (q >> 2);
                 auto g = (__attribute__((address_space(1))) unsigned long long*)(G.acc + (BATCH ? frame_pix * kAovWords : 0) + ((size_t)pj * (size_t)cam.W + pi) * kAovWords + ch);
                 if (ch == kAovDepth) (void)__hip_atomic_fetch_max(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 else (void)__hip_atomic_fetch_add(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

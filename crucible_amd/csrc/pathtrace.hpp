@@ -18,10 +18,11 @@
 #include <stdint.h>
 #include <type_traits>
 
-namespace cr {
-
 #define CR_HD __host__ __device__ __forceinline__
 #define CR_D __device__ __forceinline__
+#include "fastdiv.hpp"
+
+namespace cr {
 
 // ------------------------------------------------------------------ scalar traits
 template <typename real> struct RealTraits;
@@ -318,10 +319,25 @@ template <typename real> struct KernelArgs {
     // render, whose times start at current_time (frame_times is not read).
     uint32_t n_frames;
     const real* frame_times;
+    // Work items are decoded without a division (fastdiv.hpp): the records of sg_groups, tiles_x and tiles_y, filled
+    // wherever those are (set_tiles, set_groups).
+    FastDiv fd_groups, fd_tiles_x, fd_tiles_y;
 };
+template <typename real> inline void set_tiles(KernelArgs<real>& a, uint32_t tiles_x, uint32_t tiles_y) {
+    a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+    a.fd_tiles_x = fastdiv_make(tiles_x); a.fd_tiles_y = fastdiv_make(tiles_y);
+}
+template <typename real> inline void set_groups(KernelArgs<real>& a, uint32_t groups) {
+    a.sg_groups = groups; a.fd_groups = fastdiv_make(groups);
+}
+// a tile's column and row among the launch's tiles
+template <typename real> CR_HD void tile_xy(const KernelArgs<real>& A, uint32_t tile, uint32_t& tx, uint32_t& ty) {
+    ty = fastdiv(tile, A.fd_tiles_x);
+    tx = tile - ty * A.tiles_x;
+}
 // the frame of the batch that a batch-wide pixel row belongs to (0 in a single render)
 template <typename real> CR_HD uint32_t batch_frame(const KernelArgs<real>& A, uint32_t pix_j) {
-    return A.n_frames > 1u ? (pix_j >> A.sg_lh) / A.tiles_y : 0u;
+    return A.n_frames > 1u ? fastdiv(pix_j >> A.sg_lh, A.fd_tiles_y) : 0u;
 }
 constexpr unsigned long long kFxNaN = 0x8000000000000000ull;
 constexpr size_t fx_lds_bytes(int block, uint32_t tile_log2) { return (size_t)(block / 64) * 2 * ((size_t)3 << tile_log2) * sizeof(unsigned long long); }
@@ -509,7 +525,9 @@ CR_D bool root2_below_tmin(float n2, float a, float tmin) {
 }
 // RULE_B = false keeps rule A alone: the extra exit costs the f64 kernels that read their tree from global memory (RES_GLOBAL,
 // RES_TOP) two VGPR spills in the shading code, and the frames that run them and test few or no spheres lost 0.6-1.1 %
-// (teapot, the orbit movie; profiles/experiments/decided_early_ab.txt), so walk_round asks for rule B in the RES_LDS kernels only.
+// (teapot, the orbit movie; profiles/experiments/decided_early_ab.txt), so walk_round asked for rule B in the RES_LDS kernels only.
+// Since the f64 kernels without keyed primitives stopped spilling (profiles/experiments/uniform_and_decode_ab.txt) they take
+// rule B under every residency; in the f32 kernels below the LDS window it would cost a wave per SIMD, in the keyed f64 ones spills.
 template <bool RULE_B = true, typename real>
 CR_D bool sphere_t(real cx, real cy, real cz, real radius, V3<real> o, V3<real> d, real a /* |d|^2 */, real tmin, real tmax, real& t_out,
                    Diag* dg = nullptr) {
@@ -693,9 +711,17 @@ template <typename real> CR_HD real soft_acos(real x) {
     const real s = r_sqrt(t);
     return real(2) * (s + s * (t * K::S(t)));
 }
-template <typename real> CR_D real r_atan2(real y, real x) { return soft_atan2(y, x); }
-template <typename real> CR_D real r_asin(real x) { return soft_asin(x); }
-template <typename real> CR_D real r_acos(real x) { return soft_acos(x); }
+// What the kernels call (the spherical sky map and Sphere's uv on an image texture: once per missed sample, or never).
+// f64: real calls.  Inlined, the ~25 registers of coefficients were hoisted out of the kernels' outer loop and held, or
+// spilled, for the whole launch, in frames that never evaluate them too; as callees they load them where they are used.
+// The same expressions, so the same bits.  f32: inlined as before (profiles/experiments/uniform_and_decode_ab.txt).
+CR_D float r_atan2(float y, float x) { return soft_atan2(y, x); }
+CR_D float r_asin(float x) { return soft_asin(x); }
+CR_D float r_acos(float x) { return soft_acos(x); }
+#define CR_D_CALL static __device__ __attribute__((noinline))
+CR_D_CALL double r_atan2(double y, double x) { return soft_atan2(y, x); }
+CR_D_CALL double r_asin(double x) { return soft_asin(x); }
+CR_D_CALL double r_acos(double x) { return soft_acos(x); }
 
 // random_unit_vector (utils.rs:127-136) and random_in_unit_disk (utils.rs:110-124) for the f64 kernel, with the
 // rejection test SCREENED in f32.  A wave leaves a rejection loop only when its slowest lane does (six rounds for a
@@ -1390,7 +1416,7 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             const int32_t kind = A.uniform_kind >= 0 ? A.uniform_kind : p.kind();   // a scalar test; one load fewer per primitive when it holds
             if (kind == 0) {
                 if (ANIM && p.key_count) timeline_eval(A.keys + p.key_first, p.key_count, rtime, g0, g1, g2, g3);
-                h = sphere_t<RES == RES_LDS>(g0, g1, g2, g3, ro, rd, w.dd, tmin, w.best_t, t, dg);
+                h = sphere_t<RES == RES_LDS || (std::is_same<real, double>::value && !ANIM)>(g0, g1, g2, g3, ro, rd, w.dd, tmin, w.best_t, t, dg);
             } else {
                 V3<real> a = mk<real>(g0, g1, g2), b = mk<real>(g3, p.g[4], p.g[5]), c = mk<real>(p.g[6], p.g[7], p.g[8]);
                 if (ANIM && p.key_count) {
@@ -1443,6 +1469,11 @@ enum : int { ST_NEED_PIXEL = 0, ST_NEED_SAMPLE = 1, ST_TRACE = 2, ST_DONE = 3, S
 // spilled to scratch (profiles/r03_kernel_resources.json) -- in round 1 the f64 kernel at 4 waves/SIMD with its spills
 // measured 7 % faster than at 2 waves/SIMD without, and 5 waves/SIMD (<= 96 VGPRs, 78 spills) loses 32 %.
 template <typename real> struct MaxBlock { static constexpr int value = 1024; };
+
+// How many lanes below this one are set in a ballot: v_mbcnt on the ballot's scalar halves, no per-lane mask
+CR_D uint32_t wave_rank(uint64_t ballot) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
 
 // The persistent kernel body.  A work item is one (pixel, sample) handed out in chunks from one global counter (sample-granular
 // mode, the default); the reference-order variants keep per-sample colours for the ordered sum, the RELAX variants add into
@@ -1531,8 +1562,9 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         if constexpr (RELAX) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             if (tile != kFxNoTile) {
-                const uint32_t ti = (tile % A.tiles_x) << A.sg_lw;
-                uint32_t tj = (tile / A.tiles_x) << A.sg_lh;
+                uint32_t ti, tj;
+                tile_xy(A, tile, ti, tj);
+                ti <<= A.sg_lw; tj <<= A.sg_lh;
                 // BATCH: the tile's first row in fx_acc, where a batch's frames are H rows apart (tiles_y << sg_lh in pix_j)
                 if constexpr (BATCH) tj -= batch_frame(A, tj) * ((A.tiles_y << A.sg_lh) - (uint32_t)A.cam.H);
                 for (uint32_t k = lane; k < fx_words; k += 64) {   // 48 words for the usual 4 x 4 tile: one pass
@@ -1588,24 +1620,28 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
             // the counter sees one atomic per 1024 samples.
             const uint32_t cnt = (uint32_t)__popcll(need), avail = wv_end - wv_next;
             uint32_t fresh = 0;
+            uint32_t my_tile = kFxNoTile;   // the tile of the item this lane takes in this round
             if (cnt > avail) {
                 const int leader = __ffsll((unsigned long long)need) - 1;
                 if ((int)lane == leader) fresh = atomicAdd(A.work_counter, SG_CHUNK);
-                fresh = __shfl(fresh, leader);
+                fresh = (uint32_t)__builtin_amdgcn_readlane((int)fresh, leader);   // a scalar: the cursor stays in scalar registers
             }
             if (state == ST_NEED_PIXEL) {
-                const uint32_t rank = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
+                const uint32_t rank = wave_rank(need);
                 // past the end of the counter's range (also when it wrapped): nothing left
                 const uint32_t w = rank < avail ? wv_next + rank : fresh + (rank - avail);
                 if (w >= total_work) state = ST_DONE;
                 else {
                     item = w;
                     const uint32_t group = w >> 6, in = w & 63u;
-                    const uint32_t tile = group / A.sg_groups, sg = group - tile * A.sg_groups;
+                    const uint32_t tile = fastdiv(group, A.fd_groups), sg = group - tile * A.sg_groups;
+                    uint32_t tx, ty;
+                    tile_xy(A, tile, tx, ty);
+                    my_tile = tile;
                     const uint32_t px = in & ((1u << A.sg_lw) - 1u), py = (in >> A.sg_lw) & ((1u << A.sg_lh) - 1u);
                     const uint32_t ds = in >> (A.sg_lw + A.sg_lh);
-                    pix_i = ((tile % A.tiles_x) << A.sg_lw) + px;
-                    pix_j = ((tile / A.tiles_x) << A.sg_lh) + py;
+                    pix_i = (tx << A.sg_lw) + px;
+                    pix_j = (ty << A.sg_lh) + py;
                     // the offset in the shard decides: begin + offset may pass INT32_MAX in the last group's padding, and wraps
                     const uint32_t s_off = sg * (64u >> (A.sg_lw + A.sg_lh)) + ds;
                     sample = (int32_t)((uint32_t)A.sample_begin + s_off);
@@ -1619,7 +1655,6 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
             else wv_next += cnt;
             if constexpr (RELAX) {
                 // make room for the tiles this round's new items belong to (consecutive items: one or two tiles)
-                const uint32_t my_tile = (pix_j >> A.sg_lh) * A.tiles_x + (pix_i >> A.sg_lw);
                 uint64_t fresh_items = __ballot(state == ST_NEED_SAMPLE) & need;
                 while (fresh_items) {
                     const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)my_tile, __ffsll((unsigned long long)fresh_items) - 1);
@@ -1627,23 +1662,24 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                     if (t == fx_tile0) fx_mru = 0;
                     else if (t == fx_tile1) fx_mru = 1;
                     else if (fx_mru == 0) { fx_flush(1, fx_tile1); fx_tile1 = t; fx_mru = 1; }
-                    else { fx_flush(0, fx_tile0); fx_tile0 = t; fx_mru = 0; }
-                }
+                    else { fx_flush(0, fx_tile0); fx_tile0 = t; fx_mru = 0; }                }
             }
         } else if (need) {
             uint32_t cnt = (uint32_t)__popcll(need);
             uint32_t base = 0;
             int leader = __ffsll((unsigned long long)need) - 1;
             if ((int)lane == leader) base = atomicAdd(A.work_counter, cnt);
-            base = __shfl(base, leader);
+            base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
             if (state == ST_NEED_PIXEL) {
-                uint32_t rank = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
+                uint32_t rank = wave_rank(need);
                 uint32_t w = base + rank;
                 if (w >= total_work) state = ST_DONE;
                 else {
                     uint32_t tile = w >> 6, in = w & 63u;
-                    pix_i = (tile % A.tiles_x) * 8u + (in & 7u);
-                    pix_j = (tile / A.tiles_x) * 8u + (in >> 3);
+                    uint32_t tx, ty;
+                    tile_xy(A, tile, tx, ty);
+                    pix_i = tx * 8u + (in & 7u);
+                    pix_j = ty * 8u + (in >> 3);
                     if (pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H) {
                         state = ST_NEED_SAMPLE; sample = A.sample_begin; acc_r = acc_g = acc_b = 0;
                     }   // else: padding of an edge tile, ask again next round
@@ -1854,8 +1890,10 @@ __global__ void __launch_bounds__(256) sg_finalize_kernel(const KernelArgs<real>
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t tile = (uint32_t)(t >> (A.sg_lw + A.sg_lh)), in_px = (uint32_t)t & (tile_px - 1u);
     if (tile >= A.tiles_x * A.tiles_y) return;
-    const uint32_t pi = ((tile % A.tiles_x) << A.sg_lw) + (in_px & ((1u << A.sg_lw) - 1u));
-    const uint32_t pj = ((tile / A.tiles_x) << A.sg_lh) + (in_px >> A.sg_lw);
+    uint32_t tx, ty;
+    tile_xy(A, tile, tx, ty);
+    const uint32_t pi = (tx << A.sg_lw) + (in_px & ((1u << A.sg_lw) - 1u));
+    const uint32_t pj = (ty << A.sg_lh) + (in_px >> A.sg_lw);
     if (pi >= (uint32_t)A.cam.W || pj >= (uint32_t)A.cam.H) return;
     const size_t p = (size_t)pj * (size_t)A.cam.W + pi;
     const uint32_t ns = 64u >> (A.sg_lw + A.sg_lh);

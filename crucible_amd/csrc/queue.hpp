@@ -188,8 +188,10 @@ __global__ void __launch_bounds__(1024) queue_kernel(const KernelArgs<real> A) {
                     if (w >= total_work) { need_pixel = false; retired = true; }
                     else {
                         const uint32_t tile = w >> 6, in = w & 63u;
-                        pix_i = (tile % A.tiles_x) * 8u + (in & 7u);
-                        pix_j = (tile / A.tiles_x) * 8u + (in >> 3);
+                        uint32_t tx, ty;
+                        tile_xy(A, tile, tx, ty);
+                        pix_i = tx * 8u + (in & 7u);
+                        pix_j = ty * 8u + (in >> 3);
                         if (pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H) {
                             need_pixel = false; need_sample = true; sample = A.sample_begin; acc_r = acc_g = acc_b = 0;
                         }   // else: padding of an edge tile, ask again

@@ -152,7 +152,7 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     const size_t screen_rec = ds.ordered ? sizeof(ScreenEntryO) : sizeof(ScreenEntry);
     w.screen = screen;
     w.lds_all_screen = ds.lds_bytes - r16((size_t)ds.n_entries * ds.entry_bytes) + r16((size_t)ds.n_entries * screen_rec);
-    a.tiles_x = (uint32_t)(c.W + 7) / 8u; a.tiles_y = (uint32_t)(c.H + 7) / 8u;
+    set_tiles(a, (uint32_t)(c.W + 7) / 8u, (uint32_t)(c.H + 7) / 8u);
     a.work_counter = (uint32_t*)h->work_counter.p;
     a.counters = (uint64_t*)h->counters.p;
     a.out = (real*)d_out;
@@ -160,7 +160,7 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.walk_exit_lanes = (uint32_t)(h->walk_exit_lanes >= 0 ? h->walk_exit_lanes : (ds.has_triangles ? 40 : 56));
     a.walk_round_steps = (uint32_t)(h->walk_round_steps >= 0 ? h->walk_round_steps : (ds.has_triangles ? 8 : 10));
     a.walk_leaf_min = mega ? (uint32_t)(h->walk_leaf_min >= 0 ? h->walk_leaf_min : 8) : 0u;   // the other pipelines test a leaf in the round that found it
-    a.sg_on = 0; a.sg_lw = a.sg_lh = 3; a.sg_groups = 0; a.sg_total = 0; a.sample_buf = nullptr;   // set by launch()
+    a.sg_on = 0; a.sg_lw = a.sg_lh = 3; set_groups(a, 0); a.sg_total = 0; a.sample_buf = nullptr;   // set by launch()
 
     // the ANIM kernels also carry the decode of leaves that hold a HitList element (pathtrace.hpp walk_round)
     w.anim = ds.animated || ds.has_leaf_runs;   // keyed primitives (the ANIM kernels also follow a keyed camera)

@@ -55,8 +55,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         if (!RELAX && h->sg_lw < 0) { const int ns = batch >= 4 ? 4 : (batch >= 2 ? 2 : 1); lw = ns == 4 ? 2 : 3; lh = ns == 1 ? 3 : 2; }   // by the batch, which the buffer may have cut
         const uint32_t ns = 64u >> (lw + lh);
         args.sg_lw = (uint32_t)lw; args.sg_lh = (uint32_t)lh;
-        args.tiles_x = ((uint32_t)args.cam.W + (1u << lw) - 1) >> lw;
-        args.tiles_y = ((uint32_t)args.cam.H + (1u << lh) - 1) >> lh;
+        set_tiles(args, ((uint32_t)args.cam.W + (1u << lw) - 1) >> lw, ((uint32_t)args.cam.H + (1u << lh) - 1) >> lh);
         const uint64_t tiles = (uint64_t)args.tiles_x * args.tiles_y;
         // the 32-bit work counter must hold tiles * groups * 64 plus one chunk per wave
         const uint64_t max_groups = h->work_counter_max / (tiles * 64);
@@ -79,7 +78,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
             while (batch > (int32_t)ns && batch_bytes(batch) > std::max(h->sample_buf_limit, batch_bytes((int32_t)ns))) batch -= (int32_t)ns;
             if (batch > 0 && h->sample_buf.ensure(batch_bytes(batch)) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
             if (batch > 0 && batch < s_end - s_begin && h->sg_acc.ensure(per_sample) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
-            if (batch == 0) { args.tiles_x = args_in.tiles_x; args.tiles_y = args_in.tiles_y; }   // fall back: a lane owns a pixel
+            if (batch == 0) set_tiles(args, args_in.tiles_x, args_in.tiles_y);   // fall back: a lane owns a pixel
         }
     }
     args.sg_on = batch > 0 ? 1u : 0u;
@@ -124,7 +123,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
             for (int64_t b0 = s_begin; b0 < s_end; b0 += batch) {   // (64 bits: b0 + batch may pass INT32_MAX)
                 const int32_t b1 = (int32_t)std::min<int64_t>(s_end, b0 + batch);
                 args.sample_begin = (int32_t)b0; args.sample_end = b1;
-                args.sg_groups = groups_of(b1 - (int32_t)b0);
+                set_groups(args, groups_of(b1 - (int32_t)b0));
                 args.sg_total = (uint32_t)((uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn * args.sg_groups * 64u);
                 {   // 1024 items per atomic keeps the counter quiet on long launches; a short launch (a small frame, or one
                     // GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most

@@ -80,8 +80,9 @@ __global__ void __launch_bounds__(256) wf_logic_kernel(const WfArgs<real> W) {
         if (!finished && depth_left == 0) { finished = true; col = mk<real>(0, 0, 0); }   // the next ray_color call returns black: product is 0
         if (finished) {
             uint32_t s_local = jb / W.total_work, w = jb % W.total_work;
-            uint32_t tile = w >> 6, in = w & 63u;
-            uint32_t pi = (tile % A.tiles_x) * 8u + (in & 7u), pj = (tile / A.tiles_x) * 8u + (in >> 3);
+            uint32_t tile = w >> 6, in = w & 63u, tx, ty;
+            tile_xy(A, tile, tx, ty);
+            uint32_t pi = tx * 8u + (in & 7u), pj = ty * 8u + (in >> 3);
             size_t o = ((size_t)s_local * ((size_t)A.cam.W * A.cam.H) + ((size_t)pj * A.cam.W + pi)) * 3;
             W.sample_rgb[o] = col.x; W.sample_rgb[o + 1] = col.y; W.sample_rgb[o + 2] = col.z;
             need_job = true;
@@ -110,8 +111,9 @@ __global__ void __launch_bounds__(256) wf_logic_kernel(const WfArgs<real> W) {
         if (need_job && rank < avail) {
             uint32_t j = cn + rank;
             uint32_t s_local = j / W.total_work, w = j % W.total_work;
-            uint32_t tile = w >> 6, in = w & 63u;
-            uint32_t pi = (tile % A.tiles_x) * 8u + (in & 7u), pj = (tile / A.tiles_x) * 8u + (in >> 3);
+            uint32_t tile = w >> 6, in = w & 63u, tx, ty;
+            tile_xy(A, tile, tx, ty);
+            uint32_t pi = tx * 8u + (in & 7u), pj = ty * 8u + (in >> 3);
             if (pi < (uint32_t)A.cam.W && pj < (uint32_t)A.cam.H) {
                 if (A.max_depth == 0) {   // ray_color(depth 0) is black without tracing
                     size_t o = ((size_t)s_local * ((size_t)A.cam.W * A.cam.H) + ((size_t)pj * A.cam.W + pi)) * 3;
