@@ -90,6 +90,10 @@ class CrStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CrRegion(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class CrBuildInfo(C.Structure):
     _fields_ = [("bvh_mode", C.c_int32), ("built_on_device", C.c_int32), ("n_wrappers", C.c_int32),
                 ("device_rounds", C.c_int32), ("large_nodes", C.c_int32), ("small_subtrees", C.c_int32),
@@ -127,6 +131,14 @@ SYMBOLS = {
                                                 C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_aov_frames_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
                                               C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_region_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.POINTER(CrRegion),
+                                            C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_region_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.POINTER(CrRegion),
+                                          C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_region_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                                C.POINTER(CrRegion), C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_region_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                              C.POINTER(CrRegion), C.c_void_p, C.POINTER(CrStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
     "cr_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),

@@ -47,10 +47,12 @@ __global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long l
 }
 
 // One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_aov_frames_*):
-// the batch's frames lie one behind the other in the accumulators, in the flags and in the output.
+// the batch's frames lie one behind the other in the accumulators, in the flags and in the output.  region: the pixels
+// of the one frame that the pass covers (cr_render_aov_region_*) -- accumulators, flags and planes are then the region's
+// size, and the pass runs as a batch of one frame on the BATCH kernels, which carry the region's offsets.
 template <typename real>
 int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats, const int32_t* frames,
-                  int32_t n_frames) {
+                  int32_t n_frames, const CrRegion* region) {
     DevScene<real>* walk = nullptr;
     bool refit = false;
     int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // as a render decides it
@@ -59,7 +61,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
                                            "(render such frames one at a time)");
     DevScene<real>& ds = *walk;
-    const size_t frame_pix = (size_t)cd->image_width * (size_t)cd->image_height;
+    const size_t frame_pix = region ? (size_t)region->width * (size_t)region->height : (size_t)cd->image_width * (size_t)cd->image_height;
     const size_t npix = frame_pix * (size_t)n_frames;   // (at most 2^26 * 2^31: the byte counts below fit in 64 bits)
     hipError_t e = h->aov_acc.ensure(npix * kAovWords * sizeof(unsigned long long));
     if (e == hipSuccess) e = h->aov_flags.ensure(npix * sizeof(uint32_t));
@@ -72,15 +74,20 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         FrameBatch<real> fb;
         std::vector<real> times;
         // the walk is the megakernel's under every pipeline setting: the cross-check pipelines have no guide pass of their own
-        rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, frames, n_frames, times, a.k, w, fb);
+        rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, frames, n_frames, times, a.k, w, fb, region);
         if (rc != CR_OK) return rc;
+        if (region) {   // the BATCH kernels read a frame's first ray time from the device's table
+            rc = stage_frame_times(h, &a.k.current_time, sizeof(real));
+            if (rc != CR_OK) return rc;
+        }
         dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
-        set_tiles(a.k, ((uint32_t)cd->image_width + 3u) >> 2, ((uint32_t)cd->image_height + 3u) >> 2);
+        set_tiles(a.k, (a.k.reg_w + 3u) >> 2, (a.k.reg_h + 3u) >> 2);
         a.k.fx_scale = fx_scale_for(p->samples);   // of the whole frame, so that the words of shards add up
         a.acc = (unsigned long long*)h->aov_acc.p; a.flags = (uint32_t*)h->aov_flags.p;
         a.layers = layers;
         a.groups = ((uint32_t)p->sample_count + 3u) >> 2;
         if (frames) { a.n_frames = (uint32_t)n_frames; a.frame_times = fb.d_times; }
+        else if (region) { a.n_frames = 1u; a.frame_times = (const real*)h->times_dev.p; }
         const size_t need = aov_lds_bytes(MaxBlock<real>::value);   // the waves' slots share the LDS
         w.screen_lds = w.screen && h->screen_lds && w.lds_all_screen + need <= h->lds_limit;
         w.plain_lds = ds.lds_bytes + need <= h->lds_limit;
@@ -106,7 +113,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
     return stats ? finish_stats(h, stats, (uint64_t)npix * (uint64_t)p->sample_count, ds.n_entries, res) : CR_OK;
 }
 
-template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t);
-template int32_t aov_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t);
+template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
+template int32_t aov_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
 
 }   // namespace cr

@@ -23,6 +23,9 @@ CR_D bool aov_word(double x, double scale, long long& v) {
 // BATCH: the kernels of cr_render_aov_frames_* -- the units of G.n_frames frames in one launch, frame after frame.  A unit
 // lies in one frame, so all that depends on the frame (its first ray time, its accumulators and flags) is wave-uniform;
 // pixels, tiles and the RNG key stay the frame's own.  The single-frame kernels do not carry the arithmetic.
+// The BATCH kernels also render a region (cr_render_aov_region_*, as a batch of one frame): their tiles are anchored at
+// (k.reg_x0, k.reg_y0), the accumulators and flags hold k.reg_w x k.reg_h pixels per frame, and camera_ray alone sees the
+// frame's own pixel.  A whole frame is the region (0, 0, W, H).
 template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH>
 CR_D void aov_body(const AovArgs<real>& G) {
     using EntryT = typename EntryOf<real, ORD>::type;
@@ -99,14 +102,16 @@ CR_D void aov_body(const AovArgs<real>& G) {
         // BATCH: the unit's frame and what goes with it, from wu alone (scalar registers); `tile` is the frame's own
         const uint32_t frame = BATCH ? unit_tile / G.frame_tiles : 0u;
         const uint32_t tile = BATCH ? unit_tile - frame * G.frame_tiles : unit_tile;
-        const size_t frame_pix = BATCH ? (size_t)frame * ((size_t)cam.W * (size_t)cam.H) : 0;   // the frame's first pixel in the batch's planes
+        const size_t frame_pix = BATCH ? (size_t)frame * ((size_t)A.reg_w * (size_t)A.reg_h) : 0;   // the frame's first pixel in the batch's planes
         const real frame_time = BATCH ? G.frame_times[frame] : real(0);
         const uint32_t g0 = chunk * G.unit_groups, g1 = g0 + G.unit_groups < G.groups ? g0 + G.unit_groups : G.groups;
         const uint32_t px = lane & 15u;
         uint32_t tile_x, tile_y;   // (scalars, like the tile)
         tile_xy(A, tile, tile_x, tile_y);
         const uint32_t pix_i = (tile_x << 2) + (px & 3u), pix_j = (tile_y << 2) + (px >> 2);
-        const bool in_image = pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H;
+        // BATCH: inside the region, and the frame's own pixel for camera_ray (one integer each)
+        const bool in_image = BATCH ? pix_i < A.reg_w && pix_j < A.reg_h : pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H;
+        const uint32_t cam_i = BATCH ? A.reg_x0 + pix_i : pix_i, cam_j = BATCH ? A.reg_y0 + pix_j : pix_j;
         for (uint32_t g = g0; g < g1; g++) {
             const uint32_t s_off = g * 4u + (lane >> 4);   // begin + offset may pass INT32_MAX in the last group's padding: the offset decides
             const int32_t sample = (int32_t)((uint32_t)A.sample_begin + s_off);
@@ -118,7 +123,7 @@ CR_D void aov_body(const AovArgs<real>& G) {
             ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.best_t = 0; ws.best = -1; ws.idx = n_entries; ws.exact_box = false; ws.oct = 0; ws.pending = -1;
             bool walking = false;
             if (active) {   // cast_ray's primary ray (the keyed camera is a per-launch, wave-uniform branch of camera_ray)
-                if constexpr (BATCH) camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime, frame_time);
+                if constexpr (BATCH) camera_ray<real, true>(A, cam_i, cam_j, sample, rng, ro, rd, rtime, frame_time);
                 else camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
                 c_seg++;
                 walk_begin(ws, rd);
@@ -203,7 +208,7 @@ CR_D void aov_body(const AovArgs<real>& G) {
                 if (!aov_word((double)vals[c], fxs, v)) bad |= 1u << c;
                 else if (v) (void)__hip_atomic_fetch_add(slot_word(px * kAovWords + c), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
-            if (bad) atomicOr(G.flags + (BATCH ? frame_pix : 0) + ((size_t)pix_j * (size_t)cam.W + pix_i), bad);
+            if (bad) atomicOr(G.flags + (BATCH ? frame_pix + ((size_t)pix_j * (size_t)A.reg_w + pix_i) : ((size_t)pix_j * (size_t)cam.W + pix_i)), bad);
             if (want_depth && hit) {
                 unsigned long long bits, inf_bits;
                 if constexpr (std::is_same<real, double>::value) { bits = __builtin_bit_cast(unsigned long long, depth); inf_bits = 0x7ff0000000000000ull; }
@@ -221,7 +226,8 @@ CR_D void aov_body(const AovArgs<real>& G) {
                 slot[k] = 0ull;
                 const uint32_t q = k / kAovWords, ch = k - q * kAovWords;
                 const uint32_t pi = (tile_x << 2) + (q & 3u), pj = (tile_y << 2) + (q >> 2);
-                auto g = (__attribute__((address_space(1))) unsigned long long*)(G.acc + (BATCH ? frame_pix * kAovWords : 0) + ((size_t)pj * (size_t)cam.W + pi) * kAovWords + ch);
+                const size_t row_w = BATCH ? (size_t)A.reg_w : (size_t)cam.W;   // the accumulators' rows: the region's
+                auto g = (__attribute__((address_space(1))) unsigned long long*)(G.acc + (BATCH ? frame_pix * kAovWords : 0) + ((size_t)pj * row_w + pi) * kAovWords + ch);
                 if (ch == kAovDepth) (void)__hip_atomic_fetch_max(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 else (void)__hip_atomic_fetch_add(g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -278,7 +284,7 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
     a.frame_tiles = (uint32_t)tiles;
     const uint64_t frame_units = tiles * a.unit_chunks;
     const uint64_t per_launch = std::min<uint64_t>(n_frames, max_units / frame_units);   // frames
-    const size_t npix = (size_t)a.k.cam.W * (size_t)a.k.cam.H;
+    const size_t npix = (size_t)a.k.reg_w * (size_t)a.k.reg_h;
     unsigned long long* const acc = a.acc;
     uint32_t* const flags = a.flags;
     const real* const times = a.frame_times;

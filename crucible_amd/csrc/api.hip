@@ -19,12 +19,24 @@ int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n,
     return f64 ? fx_finalize<double>(h, sums, (double*)out, n, inv_scale, (double)samples, 0) : fx_finalize<float>(h, sums, (float*)out, n, inv_scale, (double)samples, 0);
 }
 
-int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p) {
+// region_call: a cr_render_region_* / cr_render_aov_region_* call -- `region` is checked too, and the frame may have up to
+// 2^31 - 1 pixels (the RNG key's pixel index has 32 bits) where a whole-frame call stops at 2^26
+int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, bool region_call) {
     if (!h) return CR_ERR_INVALID_ARG;
     if (!cam || !p) return fail(h, CR_ERR_INVALID_ARG, "null camera or params");
+    if (region_call && !region) return fail(h, CR_ERR_INVALID_ARG, "region is null");
     if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_render before cr_upload_scene");
     if (cam->image_width < 1 || cam->image_height < 1) return fail(h, CR_ERR_INVALID_ARG, "image size must be positive");
-    if ((int64_t)cam->image_width * cam->image_height > (int64_t)1 << 26) return fail(h, CR_ERR_INVALID_ARG, "image too large");
+    if (!region_call && (int64_t)cam->image_width * cam->image_height > (int64_t)1 << 26) return fail(h, CR_ERR_INVALID_ARG, "image too large");
+    if (region_call) {
+        if ((int64_t)cam->image_width * cam->image_height > (int64_t)INT32_MAX)
+            return fail(h, CR_ERR_INVALID_ARG, "frame too large: a region's frame has at most 2^31 - 1 pixels");
+        if (region->width < 1 || region->height < 1) return fail(h, CR_ERR_INVALID_ARG, "region size must be positive");
+        if (region->x0 < 0 || region->y0 < 0) return fail(h, CR_ERR_INVALID_ARG, "region origin must not be negative");
+        if ((int64_t)region->x0 + region->width > cam->image_width || (int64_t)region->y0 + region->height > cam->image_height)
+            return fail(h, CR_ERR_INVALID_ARG, "region reaches outside the frame");
+        if ((int64_t)region->width * region->height > (int64_t)1 << 26) return fail(h, CR_ERR_INVALID_ARG, "region too large (more than 2^26 pixels)");
+    }
     if (p->samples < 1) return fail(h, CR_ERR_INVALID_ARG, "The camera must have a positive number of samples.");   // camera/mod.rs:235-238
     if (p->sample_begin < 0 || p->sample_count < 0 || (int64_t)p->sample_begin + p->sample_count > p->samples)   // (in 64 bits: the sum of two int32 may pass 2^31)
         return fail(h, CR_ERR_INVALID_ARG, "sample range outside [0, samples)");
@@ -45,15 +57,16 @@ int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
 
 // cr_render_device / cr_render_frames_device after their own argument checks (frames == nullptr: params->frame)
 // layers != 0: the guide pass of cr_render_aov_* instead of the render
+// region != nullptr: those pixels of the one frame (cr_render_region_*, cr_render_aov_region_*)
 static int32_t render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats,
-                      const int32_t* frames, int32_t n_frames, int32_t layers = 0) {
+                      const int32_t* frames, int32_t n_frames, int32_t layers = 0, const CrRegion* region = nullptr) {
     HIP_TRY(h, hipSetDevice(h->device));
     h->cam_pending_slot = -1;
     int32_t rc;
-    if (layers) rc = p->real_type == CR_REAL_F64 ? aov_typed<double>(h, cam, p, layers, d_out, stats, frames, n_frames)
-                                                     : aov_typed<float>(h, cam, p, layers, d_out, stats, frames, n_frames);
-    else rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames)
-                                          : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames);
+    if (layers) rc = p->real_type == CR_REAL_F64 ? aov_typed<double>(h, cam, p, layers, d_out, stats, frames, n_frames, region)
+                                                     : aov_typed<float>(h, cam, p, layers, d_out, stats, frames, n_frames, region);
+    else rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames, region)
+                                          : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames, region);
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
         hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
         h->cam_pending_slot = -1;
@@ -78,15 +91,15 @@ uint64_t bad_pixels(const void* rgb, int32_t real_type, size_t n_pix) {
 
 // cr_render_host / cr_render_frames_host: render into the handle's buffer, copy back, check the means frame by frame
 static int32_t render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* h_out, CrStats* stats,
-                    const int32_t* frames, int32_t n_frames) {
+                    const int32_t* frames, int32_t n_frames, const CrRegion* region = nullptr) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)cam->image_width * cam->image_height * 3;   // reals (or words) per frame
+    const size_t n = (region ? (size_t)region->width * region->height : (size_t)cam->image_width * cam->image_height) * 3;   // reals (or words) per frame
     const size_t frame_bytes = n * (p->output_sum == CR_OUTPUT_FIXED_SUM ? sizeof(uint64_t) : real_size(p->real_type));
     const size_t bytes = frame_bytes * (size_t)n_frames;
     const hipError_t e = h->out_buf.ensure(bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
     CrStats local;
-    int32_t rc = render_device(h, cam, p, h->out_buf.p, stats ? stats : &local, frames, n_frames);
+    int32_t rc = render_device(h, cam, p, h->out_buf.p, stats ? stats : &local, frames, n_frames, 0, region);
     if (rc != CR_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -108,21 +121,25 @@ static int32_t render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderP
 }
 
 // The four cr_render_* entry points: their argument checks in one order, then the render (batch: `frames` is checked too)
+// region_call: cr_render_region_* (`region` is checked too, and what a region render needs of the handle and the params)
 static int32_t render_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, bool batch, const int32_t* frames, int32_t n_frames,
-                            bool host, void* out, CrStats* stats) {
-    int32_t rc = validate_render(h, cam, p);
+                            bool host, void* out, CrStats* stats, const CrRegion* region = nullptr, bool region_call = false) {
+    int32_t rc = validate_render(h, cam, p, region, region_call);
     if (rc != CR_OK) return rc;
     if (batch && !frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
     if (batch && n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
     if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
-    return host ? render_host(h, cam, p, out, stats, frames, n_frames) : render_device(h, cam, p, out, stats, frames, n_frames);
+    if (region_call && (resolve_sum_order(h, p) != CR_SUM_RELAXED || h->pipeline != 0))
+        return fail(h, CR_ERR_UNSUPPORTED, "cr_render_region needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
+                                           "sequential over samples; the region's offsets live in the relaxed kernels)");
+    return host ? render_host(h, cam, p, out, stats, frames, n_frames, region) : render_device(h, cam, p, out, stats, frames, n_frames, 0, region);
 }
 
 // cr_render_aov_*, cr_render_aov_frames_* (batch: `frames` is checked too): a render's argument checks, then the pass's
 // own; the host form goes through the handle's output buffer
 static int32_t aov_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, bool batch, const int32_t* frames, int32_t n_frames,
-                         bool host, void* out, CrStats* stats) {
-    int32_t rc = validate_render(h, cam, p);
+                         bool host, void* out, CrStats* stats, const CrRegion* region = nullptr, bool region_call = false) {
+    int32_t rc = validate_render(h, cam, p, region, region_call);
     if (rc != CR_OK) return rc;
     if (batch && !frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
     if (batch && n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
@@ -130,13 +147,14 @@ static int32_t aov_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderPar
     if (layers == 0 || (layers & ~all)) return fail(h, CR_ERR_INVALID_ARG, "layers must be a non-empty mask of CR_AOV_*");
     if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
     if (p->output_sum == CR_OUTPUT_FIXED_SUM) return fail(h, CR_ERR_UNSUPPORTED, "guide layers come as reals (output_sum 0 or 1), not as fixed-point words");
-    if (!host) return render_device(h, cam, p, out, stats, frames, n_frames, layers);
+    if (!host) return render_device(h, cam, p, out, stats, frames, n_frames, layers, region);
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t channels = (layers & CR_AOV_ALBEDO ? 3 : 0) + (layers & CR_AOV_NORMAL ? 3 : 0) + (layers & CR_AOV_DEPTH ? 1 : 0) + (layers & CR_AOV_COVERAGE ? 1 : 0);
-    const size_t bytes = (size_t)n_frames * (size_t)cam->image_width * cam->image_height * channels * real_size(p->real_type);
+    const size_t frame_pix = region ? (size_t)region->width * region->height : (size_t)cam->image_width * cam->image_height;
+    const size_t bytes = (size_t)n_frames * frame_pix * channels * real_size(p->real_type);
     const hipError_t e = h->out_buf.ensure(bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
-    rc = render_device(h, cam, p, h->out_buf.p, stats, frames, n_frames, layers);
+    rc = render_device(h, cam, p, h->out_buf.p, stats, frames, n_frames, layers, region);
     if (rc != CR_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -265,6 +283,24 @@ int32_t cr_render_aov_frames_device(CrHandle* h, const CrCameraDesc* cam, const 
 int32_t cr_render_aov_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames, int32_t n_frames,
                                   void* h_out, CrStats* stats) {
     return aov_entry(h, cam, p, layers, true, frames, n_frames, true, h_out, stats);
+}
+
+int32_t cr_render_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, void* d_out, CrStats* stats) {
+    return render_entry(h, cam, p, false, nullptr, 1, false, d_out, stats, region, true);
+}
+
+int32_t cr_render_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, void* h_out, CrStats* stats) {
+    return render_entry(h, cam, p, false, nullptr, 1, true, h_out, stats, region, true);
+}
+
+int32_t cr_render_aov_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,
+                                    void* d_out, CrStats* stats) {
+    return aov_entry(h, cam, p, layers, false, nullptr, 1, false, d_out, stats, region, true);
+}
+
+int32_t cr_render_aov_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,
+                                  void* h_out, CrStats* stats) {
+    return aov_entry(h, cam, p, layers, false, nullptr, 1, true, h_out, stats, region, true);
 }
 
 int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples, int32_t real_type,

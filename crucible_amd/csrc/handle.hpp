@@ -270,11 +270,14 @@ int32_t apply_update(CrHandle* h, const int32_t* prim_index, const double* v, in
 int32_t finish_stats(CrHandle* h, CrStats* stats, uint64_t samples, int32_t bvh_entries, int32_t scene_in_lds);
 int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_large_override, size_t lds_base, size_t lds_per_wave,
                    const char* what, int& block, int& per_cu);
+int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes);   // ray times into the handle's device table (times_dev), in stream order
 template <typename real>
-int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames);
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames,
+                     const CrRegion* region = nullptr);
 template <typename real>
 int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, DevScene<real>& ds, bool refit, bool mega, void* d_out,
-                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb);
+                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb,
+                     const CrRegion* region = nullptr);
 // render_f32_reference.hip, render_f32_relaxed.hip, render_f64_reference.hip, render_f64_relaxed.hip (render.hpp)
 template <typename real, bool ORD, bool RELAX>
 int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb);
@@ -287,9 +290,9 @@ int32_t check_queue_abort(CrHandle* h);
 // aov.hip: the guide pass (cr_render_aov_*, cr_render_aov_frames_*) after its argument checks; aov_f32.hip, aov_f64.hip: its kernels (aov.hpp)
 template <typename real>
 int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats, const int32_t* frames,
-                  int32_t n_frames);
+                  int32_t n_frames, const CrRegion* region = nullptr);
 // api.hip
-int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p);
+int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region = nullptr, bool region_call = false);
 int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n, int32_t samples, bool f64, void* out);
 uint64_t bad_pixels(const void* rgb, int32_t real_type, size_t n_pix);   // pixels of a host frame with a mean outside [0,1] or NaN
 

@@ -15,6 +15,7 @@
 // -ffp-contract=off so no FMA is formed, and IEEE div/sqrt.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -284,6 +285,7 @@ template <typename real> struct KernelArgs {
     real current_time, shutter_length;
     int32_t output_sum;
     uint32_t tiles_x, tiles_y;
+    uint32_t reg_x0;          // a region's origin in the frame (see n_frames below)
     uint32_t* work_counter;   // zeroed before launch
     // Sample-granular scheduling (megakernel; speed only).  sg_on = 0: a lane owns a pixel and sums its samples
     // in a register.  sg_on = 1: a work item is one (pixel, sample); 64 consecutive items are a tile of
@@ -298,6 +300,7 @@ template <typename real> struct KernelArgs {
     uint64_t* counters;       // [0] segments [1] node tests [2] prim tests [3] texel fetches
     real* att_stack;          // max_depth * n_threads records of 3 reals, level-major
     uint32_t n_threads;
+    uint32_t reg_y0;
     real* out;
     uint32_t walk_exit_lanes;   // megakernel: leave the walk once this many lanes are done walking (speed only)
     uint32_t walk_round_steps;  // wrappers a lane may step through before the wave intersects the parked leaves (speed only)
@@ -305,6 +308,7 @@ template <typename real> struct KernelArgs {
     int32_t uniform_kind;       // 0 / 1: every primitive is a sphere / a triangle (the test need not load the record's kind word); -1: mixed
     uint32_t queue_walk_waves;  // queue_kernel: how many of the workgroup's 16 waves walk (the rest shade)
     uint32_t queue_min_batch, queue_patience;   // queue_kernel: shaders wait for this many hits, at most this many polls
+    uint32_t reg_w;             // a region's size
     // CR_SUM_RELAXED (the RELAX kernels): per-pixel fixed-point sums instead of per-sample colours.  A finished sample adds
     // round(colour * fx_scale) to three 64-bit integers of its pixel -- integer adds commute, so the image does not
     // depend on which wave finished which sample when.  Bit 63 of a sum is the NaN flag (a colour that is not a number).
@@ -315,14 +319,26 @@ template <typename real> struct KernelArgs {
     // A batch of frames in one launch (cr_render_frames_*: the RELAX kernels with keys, see pathtrace_body).  The tile rows of the n_frames frames
     // follow each other -- frame f owns the tile rows [f * tiles_y, (f + 1) * tiles_y) -- so a work item's pix_j counts
     // the rows of the whole batch (tiles_y << sg_lh per frame, edge padding included) and no tile straddles two frames.
-    // Frame f's ray times start at frame_times[f] and its sums sit at fx_acc + f * W * H * 3.  n_frames = 1: a single
+    // Frame f's ray times start at frame_times[f] and its sums sit at fx_acc + f * reg_w * reg_h * 3.  n_frames = 1: a single
     // render, whose times start at current_time (frame_times is not read).
     uint32_t n_frames;
     const real* frame_times;
+    // A region of the frame (cr_render_region_*, on the same kernels): the launch's tiles are anchored at pixel (reg_x0, reg_y0)
+    // of the frame and cover reg_w x reg_h pixels, so pix_i / pix_j count within the region, fx_acc holds reg_w * reg_h pixels
+    // (per frame of a batch) and only camera_ray sees the frame's own pixel (reg_x0 + pix_i, reg_y0 + pix_j): cam.W and cam.H
+    // stay the whole frame's (the viewport, the pixel deltas, the RNG's pixel index).  A whole frame is the region
+    // (0, 0, cam.W, cam.H), which prepare_args sets for every launch; the kernels without the frame arithmetic read cam.W / cam.H.
+    // The four words reg_x0, reg_y0, reg_w, reg_h each sit where the record had four bytes of alignment padding (behind
+    // tiles_y, n_threads, queue_patience and fd_tiles_y), so no other argument moved and the kernels that do not read them
+    // compile to what they were (the static_asserts below hold the layout).
     // Work items are decoded without a division (fastdiv.hpp): the records of sg_groups, tiles_x and tiles_y, filled
     // wherever those are (set_tiles, set_groups).
     FastDiv fd_groups, fd_tiles_x, fd_tiles_y;
+    uint32_t reg_h;
 };
+static_assert(sizeof(KernelArgs<float>) == 480 && sizeof(KernelArgs<double>) == 600, "the region's words fill padding: the record keeps its size");
+static_assert(offsetof(KernelArgs<float>, work_counter) == 304 && offsetof(KernelArgs<float>, out) == 368 && offsetof(KernelArgs<float>, fx_acc) == 408 &&
+              offsetof(KernelArgs<float>, fd_tiles_y) == 464, "the region's words fill padding: no argument moved");
 template <typename real> inline void set_tiles(KernelArgs<real>& a, uint32_t tiles_x, uint32_t tiles_y) {
     a.tiles_x = tiles_x; a.tiles_y = tiles_y;
     a.fd_tiles_x = fastdiv_make(tiles_x); a.fd_tiles_y = fastdiv_make(tiles_y);
@@ -1487,10 +1503,24 @@ CR_D uint32_t wave_rank(uint64_t ballot) {
 // BATCH: the kernels that render a batch of frames (KernelArgs::n_frames) -- the RELAX kernels movies run on, with a keyed
 // camera (CAMK) or keyed primitives (ANIM); a batch of a scene without keys runs on the CAMK kernel.  The static kernels
 // (the stills, the headline among them) do not carry the frame arithmetic: in them it moved the register allocation.
-template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
+// The ~70 launch parameters are read where they are used, through the kernarg segment's own address (constant address
+// space: s_load, served by the scalar cache).  As a by-value parameter they were all loaded at kernel entry and stayed
+// live for the whole launch: the f64 kernel spilled 97 of them to VGPR lanes (230 v_readlane / v_writelane, 20 VGPRs
+// pushed to scratch); read this way it spills 6 (19, and 6).
+template <typename real> CR_D const KernelArgs<real>& kernel_args() {
+    return *(const KernelArgs<real>*)(const __attribute__((address_space(4))) KernelArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+// REG: the body carries a region's offsets where it carries the frame arithmetic (BATCH).  The 6-waves-per-SIMD entry point
+// passes false: at its 80 VGPRs the offsets cost spills, so region renders stay on pathtrace_kernel (render.hpp walk_ladder)
+// and the latency kernels compile to what they were.  A parameter of the body, not of a kernel: the kernels stay the same set.
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true>
 CR_D void pathtrace_body(const KernelArgs<real>& A) {
     using EntryT = typename EntryOf<real, ORD>::type;
     constexpr bool BATCH = RELAX && (ANIM || CAMK);
+    constexpr bool REGION = BATCH && REG;
+    // REGION: the region's words (reg_x0 .. reg_h) are read through the kernarg segment where they are used, also in the
+    // kernels that keep the by-value parameter: there they would be four more scalars alive for the whole launch
+    const KernelArgs<real>& RG = kernel_args<real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #ifdef CR_HOLD_VCC
     unsigned long long vcc_hold;
@@ -1566,7 +1596,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                 tile_xy(A, tile, ti, tj);
                 ti <<= A.sg_lw; tj <<= A.sg_lh;
                 // BATCH: the tile's first row in fx_acc, where a batch's frames are H rows apart (tiles_y << sg_lh in pix_j)
-                if constexpr (BATCH) tj -= batch_frame(A, tj) * ((A.tiles_y << A.sg_lh) - (uint32_t)A.cam.H);
+                if constexpr (BATCH) tj -= batch_frame(A, tj) * ((A.tiles_y << A.sg_lh) - (REGION ? RG.reg_h : (uint32_t)A.cam.H));
                 for (uint32_t k = lane; k < fx_words; k += 64) {   // 48 words for the usual 4 x 4 tile: one pass
                     unsigned long long* w = fx_slots + slot * fx_words + k;
                     const unsigned long long v = *w;
@@ -1574,7 +1604,9 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                         *w = 0ull;
                         const uint32_t px = k / 3u, ch = k - px * 3u;
                         const uint32_t pi = ti + (px & ((1u << A.sg_lw) - 1u)), pj = tj + (px >> A.sg_lw);
-                        unsigned long long* g = A.fx_acc + ((size_t)pj * (size_t)A.cam.W + pi) * 3 + ch;
+                        unsigned long long* g;   // (REGION: fx_acc's rows are the region's)
+                        if constexpr (REGION) g = A.fx_acc + ((size_t)pj * (size_t)RG.reg_w + pi) * 3 + ch;
+                        else g = A.fx_acc + ((size_t)pj * (size_t)A.cam.W + pi) * 3 + ch;
                         if (v & ~kFxNaN) atomicAdd(g, v & ~kFxNaN);
                         if (v & kFxNaN) atomicOr(g, kFxNaN);
                     }
@@ -1647,8 +1679,15 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                     sample = (int32_t)((uint32_t)A.sample_begin + s_off);
                     uint32_t row = pix_j;   // BATCH: pix_j counts the rows of a whole batch; the frame's own row decides
                     if constexpr (BATCH) row -= batch_frame(A, pix_j) * (A.tiles_y << A.sg_lh);
-                    if (pix_i < (uint32_t)cam.W && row < (uint32_t)cam.H && s_off < (uint32_t)(A.sample_end - A.sample_begin)) state = ST_NEED_SAMPLE;
+                    bool inside;   // (REGION: inside the region, which is the whole frame unless a region was asked for)
+                    if constexpr (REGION) inside = pix_i < RG.reg_w && row < RG.reg_h;
+                    else inside = pix_i < (uint32_t)cam.W && row < (uint32_t)cam.H;
+                    if (inside && s_off < (uint32_t)(A.sample_end - A.sample_begin)) state = ST_NEED_SAMPLE;
                     // else: padding of an edge tile or of the last sample group, ask again next round
+                    // REGION: from here on the lane keeps the pixel at the frame's origin (the region's offset added once,
+                    // to integers): camera_ray reads it as it is, the sums' addresses take the offset off again -- kept
+                    // the other way round, the sums of the offsets were two more registers alive through camera_ray
+                    if constexpr (REGION) { pix_i += RG.reg_x0; pix_j += RG.reg_y0; }
                 }
             }
             if (cnt > avail) { wv_next = fresh + (cnt - avail); wv_end = fresh + SG_CHUNK; }
@@ -1691,8 +1730,8 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         // ---------------- regeneration: camera rays (cast_ray, ray_casting.rs:82-105)
         if (state == ST_NEED_SAMPLE) {
             CR_DIAG_HIT(dgp, DG_REGEN_WAVE, DG_REGEN_LANE);
-            if constexpr (BATCH) {   // a frame of a batch: its own row and its own ray times
-                const uint32_t f = batch_frame(A, pix_j);
+            if constexpr (BATCH) {   // a frame of a batch: its own row and its own ray times; a region: the frame's own pixel, as one integer
+                const uint32_t f = batch_frame(A, REGION ? pix_j - RG.reg_y0 : pix_j);
                 camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j - f * (A.tiles_y << A.sg_lh), sample, rng, ro, rd, rtime,
                                              A.n_frames > 1u ? A.frame_times[f] : A.current_time);
             } else camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
@@ -1743,8 +1782,10 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                 // the bit patterns.  A colour that is not a number sets the pixel's NaN flag instead.
                 const bool black = col.x == real(0) && col.y == real(0) && col.z == real(0);   // adds nothing (depth ran out, scatter None)
                 if (!black) {
-                    const uint32_t tile = (pix_j >> A.sg_lh) * A.tiles_x + (pix_i >> A.sg_lw);
-                    const uint32_t px = ((pix_j & ((1u << A.sg_lh) - 1u)) << A.sg_lw) | (pix_i & ((1u << A.sg_lw) - 1u));
+                    uint32_t ri = pix_i, rj = pix_j;   // the pixel among the launch's tiles (REGION: without the region's offset)
+                    if constexpr (REGION) { ri -= RG.reg_x0; rj -= RG.reg_y0; }
+                    const uint32_t tile = (rj >> A.sg_lh) * A.tiles_x + (ri >> A.sg_lw);
+                    const uint32_t px = ((rj & ((1u << A.sg_lh) - 1u)) << A.sg_lw) | (ri & ((1u << A.sg_lw) - 1u));
                     const real cc[3] = {col.x, col.y, col.z};
                     unsigned long long v[3];
 #pragma unroll
@@ -1758,9 +1799,11 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                     if (tile == fx_tile0) dst = fx_slots + px * 3u;
                     else if (tile == fx_tile1) dst = fx_slots + fx_words + px * 3u;
                     else {
-                        uint32_t row = pix_j;   // fx_acc's row
-                        if constexpr (BATCH) row -= batch_frame(A, pix_j) * ((A.tiles_y << A.sg_lh) - (uint32_t)cam.H);
-                        dst = A.fx_acc + ((size_t)row * (size_t)cam.W + pix_i) * 3; in_lds = false;
+                        uint32_t row = rj;   // fx_acc's row
+                        if constexpr (BATCH) row -= batch_frame(A, rj) * ((A.tiles_y << A.sg_lh) - (REGION ? RG.reg_h : (uint32_t)cam.H));
+                        if constexpr (REGION) dst = A.fx_acc + ((size_t)row * (size_t)RG.reg_w + ri) * 3;
+                        else dst = A.fx_acc + ((size_t)row * (size_t)cam.W + ri) * 3;
+                        in_lds = false;
                     }
                     if (!nan) {
                         if (in_lds) {
@@ -1827,13 +1870,6 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
 
     }
 }
-// The ~70 launch parameters are read where they are used, through the kernarg segment's own address (constant address
-// space: s_load, served by the scalar cache).  As a by-value parameter they were all loaded at kernel entry and stayed
-// live for the whole launch: the f64 kernel spilled 97 of them to VGPR lanes (230 v_readlane / v_writelane, 20 VGPRs
-// pushed to scratch); read this way it spills 6 (19, and 6).
-template <typename real> CR_D const KernelArgs<real>& kernel_args() {
-    return *(const KernelArgs<real>*)(const __attribute__((address_space(4))) KernelArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr();
-}
 template <typename real, int RES, bool ANIM, bool ORD = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
 __global__ void __launch_bounds__(MaxBlock<real>::value) pathtrace_kernel(const KernelArgs<real> A) {
     // the LDS-resident f32 kernels have registers to spare and lose 1 % to the reloads: they keep the by-value parameter
@@ -1849,7 +1885,7 @@ constexpr int LatencyBlock = 512;
 template <typename real, bool ANIM, bool ORD = false, bool CAMK = false, bool RELAX = false>
 __global__ void __attribute__((amdgpu_flat_work_group_size(64, LatencyBlock), amdgpu_waves_per_eu(6, 6)))
 pathtrace_kernel_latency(const KernelArgs<real> A) {
-    pathtrace_body<real, RES_TOP, ANIM, ORD, CAMK, RELAX>(A);
+    pathtrace_body<real, RES_TOP, ANIM, ORD, CAMK, RELAX, false, false>(A);
 }
 
 // One plane of a screening record (screen.hpp's kernels make the records): the f64 plane rounded to the nearest f32 (the

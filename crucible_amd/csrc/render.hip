@@ -47,7 +47,7 @@ int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_lar
 }
 
 // cr_render_frames_*: the batch's ray times through the handle's pinned staging buffer into its device table
-static int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
+int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
     if (h->times_ev) HIP_TRY(h, hipEventSynchronize(h->times_ev));   // the previous batch's copy has read the staging buffer
     else HIP_TRY(h, hipEventCreateWithFlags(&h->times_ev, hipEventDisableTiming));
     if (bytes > h->times_cap) {
@@ -68,10 +68,12 @@ static int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
 // What a render settles before its kernels are chosen, shared with the guide pass (aov.hip): the kernel arguments (scene
 // tables, camera and its key slot, sample range, ray times -- of a batch's frames too --, this frame's refitted boxes and
 // screening records, the walk's scheduling knobs) and the kernel kind.  mega: the walk runs in a megakernel-style kernel
-// (screening records, parked leaves); the cross-check pipelines walk without either.
+// (screening records, parked leaves); the cross-check pipelines walk without either.  region: the pixels of the frame that
+// the launch covers (cr_render_region_*, cr_render_aov_region_*); nullptr: all of them.
 template <typename real>
 int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, DevScene<real>& ds, bool refit, bool mega, void* d_out,
-                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb) {
+                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb,
+                     const CrRegion* region) {
     memset(&a, 0, sizeof a);
     a.entries = (const Entry<real>*)ds.entries.p; a.prims = (const Prim<real>*)ds.prims.p; a.leaf_runs = ds.has_leaf_runs ? (const int32_t*)ds.leaf_runs.p : nullptr;
     a.mats = (const Mat<real>*)ds.mats.p; a.texs = (const Tex<real>*)ds.texs.p;
@@ -112,6 +114,8 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
         h->cam_pending_slot = slot;
     }
     pack_camera_frame(c);   // static camera: the per-sample vectors
+    a.reg_x0 = region ? (uint32_t)region->x0 : 0u; a.reg_y0 = region ? (uint32_t)region->y0 : 0u;
+    a.reg_w = (uint32_t)(region ? region->width : c.W); a.reg_h = (uint32_t)(region ? region->height : c.H);
 
     a.sample_begin = p->sample_begin; a.sample_end = p->sample_begin + p->sample_count;
     a.samples_total = p->samples; a.max_depth = p->max_depth;
@@ -165,14 +169,17 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     // the ANIM kernels also carry the decode of leaves that hold a HitList element (pathtrace.hpp walk_round)
     w.anim = ds.animated || ds.has_leaf_runs;   // keyed primitives (the ANIM kernels also follow a keyed camera)
     // camera keys alone: the static kernels' CAMK variant, which also renders the batches of scenes without keys (the
-    // static kernels do not carry a batch's frame arithmetic; with an unkeyed camera CAMK computes what they compute)
-    w.cam_keys = c.animated || frames != nullptr;
+    // static kernels do not carry a batch's frame arithmetic; with an unkeyed camera CAMK computes what they compute),
+    // and for the same reason the regions of such scenes
+    w.cam_keys = c.animated || frames != nullptr || region != nullptr;
     return CR_OK;
 }
 
-// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*).
+// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*), or the
+// pixels `region` of one frame (cr_render_region_*, whose entry has checked the sum order and the pipeline).
 template <typename real>
-int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames) {
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames,
+                     const CrRegion* region) {
     DevScene<real>* walk = nullptr;
     bool refit = false;
     int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // the base tree, or the frame's own (CR_REFIT_REBUILD)
@@ -193,7 +200,8 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     if (p->sample_count == 0) {
         // An empty shard (more ranks than samples): the sum of no samples, and 0 / samples for the mean, are both
         // zero -- cast_ray's loop body never runs (ray_casting.rs:82).  No kernel is launched.
-        const size_t bytes = (size_t)n_frames * (size_t)cd->image_width * (size_t)cd->image_height * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
+        const size_t frame_pix = region ? (size_t)region->width * (size_t)region->height : (size_t)cd->image_width * (size_t)cd->image_height;
+        const size_t bytes = (size_t)n_frames * frame_pix * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
         HIP_TRY(h, hipMemsetAsync(d_out, 0, bytes, h->stream));
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -203,7 +211,7 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     WalkChoice w;
     FrameBatch<real> fb;
     std::vector<real> times;
-    rc = prepare_args<real>(h, cd, p, ds, refit, h->pipeline == 0, d_out, frames, n_frames, times, a, w, fb);
+    rc = prepare_args<real>(h, cd, p, ds, refit, h->pipeline == 0, d_out, frames, n_frames, times, a, w, fb, region);
     if (rc != CR_OK) return rc;
     dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
     // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
@@ -225,9 +233,9 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     return relax ? walk_ladder<real, false, true>(h, a, ds, w, stats, fb) : walk_ladder<real, false, false>(h, a, ds, w, stats, fb);
 }
 
-template int32_t prepare_args<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<float>&, bool, bool, void*, const int32_t*, int32_t, std::vector<float>&, KernelArgs<float>&, WalkChoice&, FrameBatch<float>&);
-template int32_t prepare_args<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<double>&, bool, bool, void*, const int32_t*, int32_t, std::vector<double>&, KernelArgs<double>&, WalkChoice&, FrameBatch<double>&);
-template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t);
-template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t);
+template int32_t prepare_args<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<float>&, bool, bool, void*, const int32_t*, int32_t, std::vector<float>&, KernelArgs<float>&, WalkChoice&, FrameBatch<float>&, const CrRegion*);
+template int32_t prepare_args<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<double>&, bool, bool, void*, const int32_t*, int32_t, std::vector<double>&, KernelArgs<double>&, WalkChoice&, FrameBatch<double>&, const CrRegion*);
+template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
+template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
 
 }   // namespace cr

@@ -42,12 +42,15 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     const size_t lds_bytes = lds_for(block);
     // Sample-granular mode: batches of samples whose colours fit the buffer; each batch is one launch of the
     // path tracer followed by the ordered sum (sg_finalize_kernel).
-    const size_t npix = (size_t)args.cam.W * (size_t)args.cam.H;
+    // the launch's pixels: the region's (prepare_args: the whole frame unless cr_render_region_* named one; RELAX kernels with keys only)
+    const size_t npix = (size_t)args.reg_w * (size_t)args.reg_h;
     const int32_t s_begin = args.sample_begin, s_end = args.sample_end;
     int32_t batch = 0;
     int32_t fpl = 1;   // frames per launch (a batch of frames: as many whole frames as the work counter holds)
     args.n_frames = 1; args.frame_times = nullptr;
     if (fb.n > 1 && !(RELAX && (ANIM || CAMK))) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
+    if ((args.reg_x0 || args.reg_y0 || args.reg_w != (uint32_t)args.cam.W || args.reg_h != (uint32_t)args.cam.H) && (LATENCY || !(RELAX && (ANIM || CAMK))))
+        return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders whole frames");
     if ((h->sample_granular || RELAX) && s_end > s_begin) {
         const size_t per_sample = npix * 3 * sizeof(real);
         batch = (int32_t)std::min<size_t>((size_t)(s_end - s_begin), RELAX ? (size_t)INT32_MAX : std::max<size_t>(1, h->sample_buf_limit / per_sample));
@@ -55,7 +58,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         if (!RELAX && h->sg_lw < 0) { const int ns = batch >= 4 ? 4 : (batch >= 2 ? 2 : 1); lw = ns == 4 ? 2 : 3; lh = ns == 1 ? 3 : 2; }   // by the batch, which the buffer may have cut
         const uint32_t ns = 64u >> (lw + lh);
         args.sg_lw = (uint32_t)lw; args.sg_lh = (uint32_t)lh;
-        set_tiles(args, ((uint32_t)args.cam.W + (1u << lw) - 1) >> lw, ((uint32_t)args.cam.H + (1u << lh) - 1) >> lh);
+        set_tiles(args, (args.reg_w + (1u << lw) - 1) >> lw, (args.reg_h + (1u << lh) - 1) >> lh);
         const uint64_t tiles = (uint64_t)args.tiles_x * args.tiles_y;
         // the 32-bit work counter must hold tiles * groups * 64 plus one chunk per wave
         const uint64_t max_groups = h->work_counter_max / (tiles * 64);
@@ -152,7 +155,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     h->last_block = block; h->last_grid = (int)grid;
     if (stats) {
-        int32_t rc = finish_stats(h, stats, (uint64_t)args.cam.W * (uint64_t)args.cam.H * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, RES);
+        int32_t rc = finish_stats(h, stats, (uint64_t)npix * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, RES);
         if (rc != CR_OK) return rc;
 #ifdef CR_DIAG
         {
@@ -196,7 +199,9 @@ int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, 
         a.screen = nullptr;
         return launch_variant<real, RES_LDS, ORD, false, RELAX>(h, a, ds.lds_bytes, stats, w, fb);
     }
-    const bool latency = f32 && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
+    // (the 6-waves-per-SIMD kernels render whole frames: a region of such a tree runs on the regular kernel, the same bytes)
+    const bool whole = !a.reg_x0 && !a.reg_y0 && a.reg_w == (uint32_t)a.cam.W && a.reg_h == (uint32_t)a.cam.H;
+    const bool latency = f32 && whole && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
     // a window of screening records holds twice the wrappers
     const size_t window_rec = w.screen ? sizeof(std::conditional_t<ORD, ScreenEntryO, ScreenEntry>) : sizeof(typename EntryOf<real, ORD>::type);
     const int32_t top = (int32_t)std::min<size_t>((size_t)ds.n_entries, (latency ? h->latency_top_bytes : h->lds_top_bytes) / window_rec);

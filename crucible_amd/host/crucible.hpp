@@ -442,6 +442,15 @@ public:
     int gpus = 1;            // > 1 (or use_group): still images split their samples over devices 0..gpus-1 through cr_group_*;
     bool use_group = false;  // movies give frame f to device f % gpus (scene/mod.rs:307-316: frames are independent)
     size_t frames_per_launch = 1;   // movies: > 1 renders that many frames per cr_render_frames_host call (relaxed sums)
+    // A region of the frame (cr_render_region_host, cr_render_aov_region_host): render_frame / render_aov fill, and the
+    // files hold, only the pixels `region` of the frame the camera describes; a movie applies it to every frame, one call
+    // per frame (the batch calls take whole frames).  Needs relaxed sums, like the batch calls.
+    bool has_region = false;
+    CrRegion region = {0, 0, 0, 0};
+    void set_region(int32_t x0, int32_t y0, int32_t w, int32_t h) { has_region = true; region = CrRegion{x0, y0, w, h}; }
+    // what a render writes: the region's size, or the frame's
+    size_t out_width() const { return has_region ? (size_t)std::max(region.width, 0) : (size_t)scene_cam.image_width; }
+    size_t out_height() const { return has_region ? (size_t)std::max(region.height, 0) : (size_t)scene_cam.image_height; }
 
     Scene(double aspect, uint32_t width, size_t rate, double shutter, size_t threads)
         : scene_cam(aspect, width, (double)rate, shutter, threads), frame_rate(rate) {}
@@ -596,12 +605,13 @@ public:
         return p;
     }
     // The render proper: W*H*3 reals of `real_type` into `buf` (sized for either scalar type), at the camera's frame
-    // counter or at `frame`.
+    // counter or at `frame`; with a region, its w*h*3 reals.
     int32_t render_frame(CrHandle* h, std::vector<double>& buf, CrStats* stats = nullptr, int64_t frame = -1) const {
         std::vector<CrKeyframe> fk, ak;
         CrCameraDesc cd = camera_desc(fk, ak);
         CrRenderParams p = render_params(frame < 0 ? (size_t)scene_cam.frame : (size_t)frame);
-        buf.resize((size_t)scene_cam.image_width * scene_cam.image_height * 3);
+        buf.resize(std::max<size_t>(1, out_width() * out_height() * 3));
+        if (has_region) return cr_render_region_host(h, &cd, &p, &region, buf.data(), stats);
         return cr_render_host(h, &cd, &p, buf.data(), stats);
     }
     // The frames `frs` in one call: frame k at k * W*H*3 reals of `real_type` in `buf`.
@@ -616,12 +626,13 @@ public:
     int32_t aov_layers = 0;   // CR_AOV_* mask: > 0 writes <frame>.<layer>.pfm next to every frame file
     size_t aov_reals() const {
         const size_t ch = (aov_layers & CR_AOV_ALBEDO ? 3 : 0) + (aov_layers & CR_AOV_NORMAL ? 3 : 0) + (aov_layers & CR_AOV_DEPTH ? 1 : 0) + (aov_layers & CR_AOV_COVERAGE ? 1 : 0);
-        return (size_t)scene_cam.image_width * scene_cam.image_height * ch;
+        return out_width() * out_height() * ch;
     }
     int32_t render_aov(CrHandle* h, void* planes, CrStats* stats = nullptr, int64_t frame = -1) const {
         std::vector<CrKeyframe> fk, ak;
         CrCameraDesc cd = camera_desc(fk, ak);
         CrRenderParams p = render_params(frame < 0 ? (size_t)scene_cam.frame : (size_t)frame);
+        if (has_region) return cr_render_aov_region_host(h, &cd, &p, aov_layers, &region, planes, stats);
         return cr_render_aov_host(h, &cd, &p, aov_layers, planes, stats);
     }
     // The guide layers of the frames `frs` in one call (cr_render_aov_frames_host): frame k at k * aov_reals() reals in `planes`.
@@ -635,26 +646,25 @@ public:
     int32_t write_aov(const std::string& fname, const void* planes) const {
         static const struct { int32_t bit; const char* name; int32_t ch; } layer[4] = {
             {CR_AOV_ALBEDO, "albedo", 3}, {CR_AOV_NORMAL, "normal", 3}, {CR_AOV_DEPTH, "depth", 1}, {CR_AOV_COVERAGE, "coverage", 1}};
-        const Camera& c = scene_cam;
         const size_t rs = real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float);
         const char* at = (const char*)planes;
         for (const auto& l : layer) {
             if (!(aov_layers & l.bit)) continue;
-            const int32_t rc = cr_write_pfm((fname + "." + l.name + ".pfm").c_str(), at, real_type, c.image_width, c.image_height, l.ch);
+            const int32_t rc = cr_write_pfm((fname + "." + l.name + ".pfm").c_str(), at, real_type, (int32_t)out_width(), (int32_t)out_height(), l.ch);
             if (rc != CR_OK) return rc;
-            at += (size_t)c.image_width * c.image_height * (size_t)l.ch * rs;
+            at += out_width() * out_height() * (size_t)l.ch * rs;
         }
         return CR_OK;
     }
-    size_t frame_bytes() const { return (size_t)scene_cam.image_width * scene_cam.image_height * 3 * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float)); }
+    size_t frame_bytes() const { return out_width() * out_height() * 3 * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float)); }
     // The file: "ppm" = the reference's ASCII P3 (camera/mod.rs:286,306-311); "p6" / "png" = SURVEY 8(f) row 3,
     // the same per-channel bytes in binary PPM / PNG.
     int32_t write_frame(const std::string& fname, const void* rgb) const {
-        const Camera& c = scene_cam;
+        const int32_t w = (int32_t)out_width(), hgt = (int32_t)out_height();   // the region's size when there is one
         const std::string path = fname + (frame_format == "png" ? ".png" : ".ppm");
-        int32_t rc = frame_format == "png" ? cr_write_png(path.c_str(), rgb, real_type, c.image_width, c.image_height)
-                   : frame_format == "p6" ? cr_write_ppm_binary(path.c_str(), rgb, real_type, c.image_width, c.image_height)
-                                          : cr_write_ppm(path.c_str(), rgb, real_type, c.image_width, c.image_height);
+        int32_t rc = frame_format == "png" ? cr_write_png(path.c_str(), rgb, real_type, w, hgt)
+                   : frame_format == "p6" ? cr_write_ppm_binary(path.c_str(), rgb, real_type, w, hgt)
+                                          : cr_write_ppm(path.c_str(), rgb, real_type, w, hgt);
         if (rc == CR_OK && !quiet) fprintf(stderr, "Successful render! Image stored at: %s\n", path.c_str());
         return rc;
     }
@@ -700,7 +710,8 @@ public:
         int32_t write_rc[2] = {CR_OK, CR_OK};
         double write_ms[2] = {0, 0};
         int32_t rc = CR_OK;
-        bool batched = frames_per_launch > 1, guides_batched = frames_per_launch > 1;
+        // (a region: one region call per frame, the batch calls take whole frames)
+        bool batched = frames_per_launch > 1 && !has_region, guides_batched = frames_per_launch > 1 && !has_region;
         const size_t rs = real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float);
         size_t k = 0;
         for (size_t fr = first; rc == CR_OK && fr < frames; k++) {
@@ -774,6 +785,10 @@ public:
     // frames m, m + n, ... -- no communicator, no RCCL.
     int32_t render_scene_group(const std::string& fname, CrStats* stats) {
         const int n = std::max(1, gpus);
+        if (has_region && !is_movie) {   // a group splits a frame by samples and renders whole frames (cr_group_render_host)
+            fprintf(stderr, "Render failed. a region renders on one device: cr_group_* takes whole frames\n");
+            return CR_ERR_UNSUPPORTED;
+        }
         FlatScene f = flatten();
         if (!is_movie) {
             std::vector<int32_t> ids;

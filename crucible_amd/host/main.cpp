@@ -11,6 +11,8 @@
 // this mirror against the Python one), --sum-order reference|relaxed (CrRenderParams.sum_order; default: the library's),
 // --frames-per-launch N (movies: N frames per library call through cr_render_frames_host, relaxed sums; default 1),
 // --aov albedo,normal,depth,coverage (guide layers through cr_render_aov_host: <frame>.<layer>.pfm next to every frame file),
+// --region x0,y0,w,h (render those pixels of the frame through cr_render_region_host and write them as a w x h file; with --aov the
+// region's planes; a movie applies it to every frame, one call per frame; needs relaxed sums; --timing names the region),
 // --repeat N --timing (measurement: render_scene N times in this process, one JSON line of wall-clock phases each --
 // the shape of the reference's criterion benchmark, benches/renderer_benchmark.rs:16-42 -- the first is the cold one).
 #include "crucible.hpp"
@@ -51,7 +53,7 @@ int main(int argc, char** argv) {
     RefitMode refit = false;
     int gpus = 1, repeat = 1;
     long frames_per_launch = 1;
-    std::string sum_order = "default", aov;
+    std::string sum_order = "default", aov, region;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -81,6 +83,7 @@ int main(int argc, char** argv) {
         else if (a == "--frames-per-launch") frames_per_launch = atol(next());
         else if (a == "--sum-order") sum_order = next();
         else if (a == "--aov") aov = next();
+        else if (a == "--region") region = next();
         else if (a == "--dump-desc") dump = next();
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -139,6 +142,13 @@ int main(int argc, char** argv) {
             scene.aov_layers |= bit;
             at = end + 1;
         }
+        if (!region.empty()) {
+            int x0 = 0, y0 = 0, rw = 0, rh = 0;
+            char tail = 0;
+            if (sscanf(region.c_str(), "%d,%d,%d,%d%c", &x0, &y0, &rw, &rh, &tail) != 4) { fprintf(stderr, "--region takes x0,y0,w,h\n"); return 2; }
+            if (!movie && (gpus > 1 || use_group)) { fprintf(stderr, "--region renders on one device (a group splits a frame by samples)\n"); return 2; }
+            scene.set_region(x0, y0, rw, rh);   // the library checks it against the frame
+        }
         if (!dump.empty()) { dump_desc(scene.flatten(), dump.c_str()); return 0; }
         int32_t rc = CR_OK;
         for (int rep = 0; rep < repeat && rc == CR_OK; rep++) {
@@ -150,12 +160,13 @@ int main(int argc, char** argv) {
             if (rc == CR_OK && !timing) fprintf(stderr, "kernel %.3f ms, %.1f Msamples/s\n", st.kernel_ms, st.kernel_ms > 0 ? st.samples / st.kernel_ms / 1e3 : 0.0);
             if (rc == CR_OK && timing) {
                 const Scene::Timing& t = scene.timing;
-                const double samples = (double)scene.scene_cam.image_width * scene.scene_cam.image_height * scene.scene_cam.samples * (movie ? (double)t.frames : 1.0);
+                const double samples = (double)scene.out_width() * (double)scene.out_height() * scene.scene_cam.samples * (movie ? (double)t.frames : 1.0);
+                const std::string region_field = scene.has_region ? ", \"region\": \"" + region + "\"" : "";
                 printf("{\"run\": %d, \"width\": %u, \"height\": %u, \"samples\": %u, \"frames\": %zu, \"format\": \"%s\", \"real\": \"%s\", \"create_ms\": %.3f, \"flatten_ms\": %.3f, "
                        "\"upload_ms\": %.3f, \"bvh_build_ms\": %.3f, \"render_ms\": %.3f, \"kernel_ms\": %.3f, \"write_ms\": %.3f, \"total_ms\": %.3f, \"msamples_per_s_end_to_end\": %.1f, "
-                       "\"msamples_per_s_kernel\": %.1f, \"guide_calls\": %zu}\n",
+                       "\"msamples_per_s_kernel\": %.1f, \"guide_calls\": %zu%s}\n",
                        rep, scene.scene_cam.image_width, scene.scene_cam.image_height, scene.scene_cam.samples, movie ? t.frames : (size_t)1, format.c_str(), real.c_str(), t.create_ms,
-                       t.flatten_ms, t.upload_ms, t.bvh_build_ms, t.render_ms, t.kernel_ms, t.write_ms, t.total_ms, samples / t.total_ms / 1e3, t.kernel_ms > 0 ? samples / t.kernel_ms / 1e3 : 0.0, t.guide_calls);
+                       t.flatten_ms, t.upload_ms, t.bvh_build_ms, t.render_ms, t.kernel_ms, t.write_ms, t.total_ms, samples / t.total_ms / 1e3, t.kernel_ms > 0 ? samples / t.kernel_ms / 1e3 : 0.0, t.guide_calls, region_field.c_str());
                 fflush(stdout);
             }
         }

@@ -220,6 +220,94 @@ class Renderer:
                                                          C.c_void_p(d_ptr), C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    def render_region(self, cam, region, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
+                      want_stats=True, sum_order=None):
+        """cr_render_region_host: the pixels `region` = (x0, y0, w, h) of the frame `cam` describes, as an (h, w, 3) host
+        array of f32/f64 -- of uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM.  Pixel (i, j) equals pixel
+        (x0 + i, y0 + j) of render() bit for bit; region=None passes a null pointer (the library refuses it).  Needs
+        CR_SUM_RELAXED.  Returns (image, stats dict of the region's samples)."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
+        reg, (w, h) = region_arg(region)
+        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
+        out = np.empty((max(1, h), max(1, w), 3), dtype=dtype)
+        st = A.CrStats()
+        self._check(self.lib.cr_render_region_host(self.h, C.byref(cd), C.byref(p), reg, out.ctypes.data_as(C.c_void_p),
+                                                   C.byref(st) if want_stats else None))
+        return out, st.as_dict()
+
+    def render_region_device(self, cam, region, d_ptr, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                             output_sum=False, want_stats=False, sum_order=None):
+        """cr_render_region_device: the region into device memory at `d_ptr` (w*h*3 reals, or uint64 words with
+        output_sum=A.CR_OUTPUT_FIXED_SUM).  Asynchronous unless want_stats."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
+        reg, _ = region_arg(region)
+        st = A.CrStats()
+        self._check(self.lib.cr_render_region_device(self.h, C.byref(cd), C.byref(p), reg, C.c_void_p(d_ptr),
+                                                     C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def render_aov_region(self, cam, region, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
+                          sample_count=None, output_sum=False, want_stats=True, sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_region_host: render_aov's planes over the pixels `region` = (x0, y0, w, h): a dict of (h, w, 3) /
+        (h, w) host arrays, each the crop of render_aov's plane bit for bit, and the stats dict of the region's samples."""
+        layers = aov_mask(layers)
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        reg, (w, h) = region_arg(region)
+        w, h = max(1, w), max(1, h)
+        planes = [(n, c) for n, bit, c in A.AOV_LAYERS if layers & bit]
+        buf = np.empty(max(1, w * h * sum(c for _, c in planes)), dtype=np_real(real_type))
+        st = A.CrStats()
+        self._check(self.lib.cr_render_aov_region_host(self.h, C.byref(cd), C.byref(p), layers, reg, buf.ctypes.data_as(C.c_void_p),
+                                                       C.byref(st) if want_stats else None))
+        out, o = {}, 0
+        for n, c in planes:
+            out[n] = buf[o:o + w * h * c].reshape((h, w, 3) if c == 3 else (h, w))
+            o += w * h * c
+        return out, st.as_dict()
+
+    def render_aov_region_device(self, cam, region, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
+                                 sample_count=None, output_sum=False, want_stats=False, sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_region_device: the region's requested planes, one after the other in ascending bit order, into
+        device memory at `d_ptr`.  Asynchronous unless want_stats."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        reg, _ = region_arg(region)
+        st = A.CrStats()
+        self._check(self.lib.cr_render_aov_region_device(self.h, C.byref(cd), C.byref(p), aov_mask(layers), reg, C.c_void_p(d_ptr),
+                                                         C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def render_tiled(self, cam, tile=(1024, 1024), *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                     output_sum=False, sum_order=None):
+        """A whole frame assembled from render_region() calls over tiles of `tile` = (tw, th) pixels (edge tiles are
+        smaller): render()'s frame bit for bit, and the way to a frame of more than 2^26 pixels (up to 2^31 - 1).  Returns
+        (image (H, W, 3), stats dict: the regions' counters, samples, nan_pixels and kernel_ms summed; the rest from the
+        last region)."""
+        tw, th = int(tile[0]), int(tile[1])
+        if tw < 1 or th < 1:
+            raise ValueError("render_tiled: tile sizes must be positive")
+        H, W = cam.image_height, cam.image_width
+        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
+        out = np.empty((H, W, 3), dtype=dtype)
+        total = None
+        for y0 in range(0, H, th):
+            for x0 in range(0, W, tw):
+                w, h = min(tw, W - x0), min(th, H - y0)
+                img, st = self.render_region(cam, (x0, y0, w, h), seed=seed, real_type=real_type, sample_begin=sample_begin,
+                                             sample_count=sample_count, output_sum=output_sum, sum_order=sum_order)
+                out[y0:y0 + h, x0:x0 + w] = img
+                if total is None:
+                    total = dict(st)
+                else:
+                    for k in ("samples", "segments", "node_tests", "prim_tests", "texel_fetches", "nan_pixels", "kernel_ms"):
+                        total[k] += st[k]
+                    for k in ("upload_ms", "bvh_entries", "scene_in_lds"):
+                        total[k] = st[k]
+        return out, total
+
     def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
         """cr_fixed_sums_to_rgb: summed CR_OUTPUT_FIXED_SUM words of a whole frame (device pointer, W*H*3 uint64) ->
         its per-pixel means at device pointer `d_out` (W*H*3 reals), exactly the relaxed frame.  Asynchronous on the
@@ -297,6 +385,15 @@ def frame_list(frames):
         return np.zeros(0, dtype=np.int32), None
     fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
     return fr, fr.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def region_arg(region):
+    """(pointer to a CrRegion or None, (w, h)) from (x0, y0, w, h); None stays a null pointer (the library refuses it)."""
+    if region is None:
+        return None, (1, 1)
+    x0, y0, w, h = (int(v) for v in region)
+    reg = A.CrRegion(x0, y0, w, h)
+    return C.pointer(reg), (w, h)
 
 
 def aov_mask(layers):

@@ -514,6 +514,57 @@ CR_API int32_t cr_render_aov_frames_device(CrHandle* h, const CrCameraDesc* cam,
 CR_API int32_t cr_render_aov_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
                                          const int32_t* frames, int32_t n_frames, void* h_out, CrStats* stats);
 
+/*
+ * A region of a frame: the pixels [x0, x0 + width) x [y0, y0 + height) of the frame that `cam` describes.
+ * cam->image_width / image_height stay the WHOLE frame's: they define the viewport, the pixel deltas and the RNG's
+ * pixel index (y0 + j) * image_width + (x0 + i).  The output holds the region only: width*height*3 reals, row-major
+ * (uint64_t words at the whole frame's scale under CR_OUTPUT_FIXED_SUM, so shards of a region add up exactly and
+ * cr_fixed_sums_to_rgb with the region's width and height finalises them).
+ *
+ * Output pixel (i, j) is bit for bit pixel (x0 + i, y0 + j) of what cr_render_device writes for the same cam and
+ * params: in f32 and f64, for every output_sum, every sample_begin / sample_count, every bvh_mode, every residency of
+ * the scene and refit_boxes 0, 1 and CR_REFIT_REBUILD (a region call renders one frame, so boxes may be refitted).
+ * The RNG streams are keyed by the frame's pixel index, the camera vectors are those of the whole frame and relaxed
+ * sums are integer sums.  A region that is the whole frame gives cr_render_device's bytes and counters.
+ * stats: samples = width * height * sample_count; segments, node_tests, prim_tests and texel_fetches count the
+ * region's samples only, so the counters of regions that partition a frame add up to the frame's.
+ *
+ * Limits: width * height <= 2^26; the frame itself may have up to 2^31 - 1 pixels here (the RNG key's pixel index has
+ * 32 bits) -- a frame beyond cr_render_device's limit is rendered region by region.  Regions split a frame by pixels
+ * across handles (devices, processes, nodes) as sample_begin / sample_count split it by samples.
+ *
+ * CR_ERR_INVALID_ARG: a null `region`, width < 1, height < 1, a negative origin, x0 + width > image_width or
+ * y0 + height > image_height (sums formed in 64 bits), more than 2^26 pixels in the region, and whatever
+ * cr_render_device rejects.  CR_ERR_UNSUPPORTED: a sum order other than CR_SUM_RELAXED (after CR_SUM_DEFAULT /
+ * CRUCIBLE_SUM_ORDER are resolved) or a pipeline other than the megakernel, as for cr_render_frames_*.  Everything is
+ * checked before anything changes: a refused call leaves the handle as it was.  An empty shard (sample_count == 0)
+ * zero-fills a buffer of the region's size.  Asynchronous unless `stats` is non-NULL, like cr_render_device;
+ * cr_export_render_bvh, cr_last_kernel_ms and cr_frame_build_info behave as after a whole-frame call.
+ */
+typedef struct CrRegion { int32_t x0, y0, width, height; } CrRegion;   /* pixels of the frame cam describes */
+CR_API int32_t cr_render_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, const CrRegion* region,
+                                       void* d_out, CrStats* stats);
+
+/* Same, into a HOST buffer of the region's size (synchronous); the Color::new check of cr_render_host applies to the
+ * region's pixels. */
+CR_API int32_t cr_render_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, const CrRegion* region,
+                                     void* h_out, CrStats* stats);
+
+/*
+ * The guide layers of a region: what cr_render_region_* is to cr_render_device, for cr_render_aov_device.  The output
+ * holds the requested planes at the region's size (albedo width*height*3 reals, normal width*height*3, depth
+ * width*height, coverage width*height) in cr_render_aov_device's order, and value (i, j) of a plane is bit for bit
+ * value (x0 + i, y0 + j) of the whole frame's plane.  Works under every sum order and pipeline, as cr_render_aov_*
+ * do.  Refusals: those of cr_render_aov_device (layers; CR_OUTPUT_FIXED_SUM) and the region ones above.  An empty
+ * shard writes what the single guide call writes.  stats as for cr_render_aov_device, over the region's samples.
+ */
+CR_API int32_t cr_render_aov_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                           const CrRegion* region, void* d_out, CrStats* stats);
+
+/* Same, into a HOST buffer (synchronous). */
+CR_API int32_t cr_render_aov_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                         const CrRegion* region, void* h_out, CrStats* stats);
+
 /* The wrapper tree the device walks for `real_type`, as BVHWrapper's shape (src/objects/bvhwrapper.rs:7-11):
  * wrapper k has boxes[6k..6k+5] = xmin,xmax,ymin,ymax,zmin,zmax (exact values of `real_type`) and
  * children[2k], children[2k+1] = left, right: >= 0 another wrapper's index, < 0 the bitwise complement of a
