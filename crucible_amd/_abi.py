@@ -94,6 +94,21 @@ class CrRegion(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class CrAdaptiveParams(C.Structure):
+    _fields_ = [("min_samples", C.c_int32), ("pass_samples", C.c_int32), ("block_log2", C.c_int32), ("_reserved", C.c_int32),
+                ("tolerance", C.c_double)]
+
+
+class CrAdaptiveStats(C.Structure):
+    _fields_ = [("render", CrStats), ("judge_ms", C.c_double), ("passes", C.c_int32), ("blocks", C.c_int32),
+                ("blocks_stopped", C.c_int32), ("_pad", C.c_int32)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("render", "_pad")}
+        d["render"] = self.render.as_dict()
+        return d
+
+
 class CrBuildInfo(C.Structure):
     _fields_ = [("bvh_mode", C.c_int32), ("built_on_device", C.c_int32), ("n_wrappers", C.c_int32),
                 ("device_rounds", C.c_int32), ("large_nodes", C.c_int32), ("small_subtrees", C.c_int32),
@@ -139,6 +154,10 @@ SYMBOLS = {
                                                 C.POINTER(CrRegion), C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_aov_region_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
                                               C.POINTER(CrRegion), C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_adaptive_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
+                                              C.POINTER(CrAdaptiveParams), C.c_void_p, C.c_void_p, C.POINTER(CrAdaptiveStats)]),
+    "cr_render_adaptive_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
+                                            C.POINTER(CrAdaptiveParams), C.c_void_p, C.c_void_p, C.POINTER(CrAdaptiveStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
     "cr_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),

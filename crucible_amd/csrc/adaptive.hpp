@@ -1,0 +1,45 @@
+// adaptive.hpp -- the arithmetic of cr_render_adaptive_* (include/crucible_hip.h) that the judge kernel and
+// the host share: a block's geometry, one term of its difference sum D_b and its threshold T_b.  Free of the HIP runtime,
+// so that a plain C++ compiler can check it (tests/adaptive_check.cpp), as it checks fastdiv.hpp and tree.hpp.
+#pragma once
+#include <stdint.h>
+
+#if !defined(CR_HD)          // a plain C++ compiler; the library defines it in pathtrace.hpp
+#define CR_HD inline
+#endif
+
+namespace cr {
+
+constexpr uint64_t kAdaptiveFlag = 0x8000000000000000ull;   // bit 63 of a relaxed sum: the NaN flag, not part of the magnitude
+
+// d(x, c) = |mag(E) - mag(O)| >> 12 of one channel's two half-frame sums
+CR_HD uint64_t adaptive_term(uint64_t e, uint64_t o) {
+    const uint64_t a = e & ~kAdaptiveFlag, b = o & ~kAdaptiveFlag;
+    return (a > b ? a - b : b - a) >> 12;
+}
+
+// T_b = (uint64) min(floor(tolerance * (2^(S-12) * qP * 3 N_b)), 2^63): scale12 = 2^(S-12), qp = q * P (the samples in each
+// half), n_b = the block's pixels inside the frame.  The weight is an integer below 2^53 times a power of two, exact in
+// f64; then one multiply and one floor.  tolerance >= 0 and finite (the entry checks it); a product at or beyond 2^63,
+// infinity included, gives 2^63, which no D_b reaches.
+CR_HD uint64_t adaptive_threshold(double tolerance, double scale12, uint32_t qp, uint32_t n_b) {
+    const double weight = scale12 * (double)((uint64_t)qp * 3u * (uint64_t)n_b);
+    const double t = __builtin_floor(tolerance * weight);
+    return t < 0x1.0p63 ? (uint64_t)t : (uint64_t)1 << 63;
+}
+
+// Blocks of 2^block_log2 pixels square, anchored at pixel (0, 0), numbered row by row; edge blocks are partial.
+CR_HD uint32_t adaptive_blocks_x(int32_t W, uint32_t block_log2) { return ((uint32_t)W + (1u << block_log2) - 1u) >> block_log2; }
+CR_HD uint32_t adaptive_blocks_y(int32_t H, uint32_t block_log2) { return ((uint32_t)H + (1u << block_log2) - 1u) >> block_log2; }
+// block b's pixels inside the frame: bw columns from x0, bh rows from y0 (N_b = bw * bh)
+CR_HD void adaptive_block_rect(int32_t W, int32_t H, uint32_t block_log2, uint32_t b, uint32_t& x0, uint32_t& y0, uint32_t& bw, uint32_t& bh) {
+    const uint32_t bx_n = adaptive_blocks_x(W, block_log2), B = 1u << block_log2;
+    const uint32_t by = b / bx_n, bx = b - by * bx_n;
+    x0 = bx << block_log2; y0 = by << block_log2;
+    bw = (uint32_t)W - x0 < B ? (uint32_t)W - x0 : B;
+    bh = (uint32_t)H - y0 < B ? (uint32_t)H - y0 : B;
+}
+// does a block with difference sum d stop?
+CR_HD bool adaptive_stops(uint64_t d, uint64_t t) { return d <= t; }
+
+}   // namespace cr

@@ -239,6 +239,9 @@ void cr_destroy(CrHandle* h) {
         h->cam_dev[i].release();
         if (h->cam_ev[i]) (void)hipEventDestroy(h->cam_ev[i]);
     }
+    h->ad_acc.release(); h->ad_lists.release(); h->ad_block_n.release(); h->ad_ctrl.release(); h->ad_counts.release();
+    if (h->ad_ev0) (void)hipEventDestroy(h->ad_ev0);
+    if (h->ad_ev1) (void)hipEventDestroy(h->ad_ev1);
     if (h->times_host) (void)hipHostFree(h->times_host);
     h->times_dev.release();
     if (h->times_ev) (void)hipEventDestroy(h->times_ev);

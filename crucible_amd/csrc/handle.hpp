@@ -12,6 +12,7 @@
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
 //   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
+//   adaptive.hip       cr_render_adaptive_*: the pass loop, the judge and finalize kernels (adaptive.hpp)
 //   api.hip            cr_create / cr_destroy, cr_render_*, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
 #pragma once
 #include "../../include/crucible_hip.h"
@@ -22,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -137,6 +139,10 @@ struct CrHandle {
     DevBuf sample_buf, sg_acc;   // sample-granular megakernel: per-sample colours of a batch, running sums between batches
     DevBuf aov_acc, aov_flags;   // cr_render_aov_*: per pixel 8 x u64 (albedo, normal, coverage sums; depth) and the channels' NaN bits
     DevBuf fx_acc;               // CR_SUM_RELAXED: per-pixel fixed-point sums (3 x u64 per pixel; per frame of a batch)
+    // cr_render_adaptive_* (adaptive.hip): the two half-frame accumulators E and O (relaxed sums, apart from fx_acc), the two
+    // tile lists, each block's final sample count, the judge's cursor, the count plane of the host form; the judge's events
+    DevBuf ad_acc, ad_lists, ad_block_n, ad_ctrl, ad_counts;
+    hipEvent_t ad_ev0 = nullptr, ad_ev1 = nullptr;
     // cr_render_frames_*: a batch's per-frame ray times travel through one pinned host buffer, refilled only after the
     // previous batch's copy has run (times_ev); the device table is reused in stream order
     void* times_host = nullptr;
@@ -234,11 +240,33 @@ inline int resolve_sum_order(const CrHandle* h, const CrRenderParams* p) {
 
 // The frames of one render: n frames whose ray times start at times[k] (host) and d_times[k] (the device's copy).  A
 // single render is a batch of one without a table (its times start at KernelArgs::current_time).  RELAX kernels only.
+struct AdaptiveRun;
 template <typename real> struct FrameBatch {
     int32_t n = 1;
     const real* times = nullptr;
     const real* d_times = nullptr;
+    const AdaptiveRun* ad = nullptr;   // cr_render_adaptive_*: launch() hands its kernel to adaptive_passes instead of launching it
 };
+
+// cr_render_adaptive_* (adaptive.hip).  What the entry point settled ...
+struct AdaptiveRun {
+    int32_t min_samples, pass_samples, block_log2;
+    double tolerance;
+    int32_t* d_counts;          // may be null
+    CrAdaptiveStats* stats;     // may be null
+};
+// ... and what launch() settled: the frame, the render kernel's tile shape and tile counts, the scale of the sums
+struct AdaptiveFrame {
+    int32_t W, H, samples;
+    uint32_t lw, lh, tiles_x, tiles_y;
+    double fx_scale;
+    void* out;
+    bool f64;
+    int32_t n_entries, scene_in_lds;
+};
+// one launch of the render kernel: samples [s0, s1) of the n_tiles tiles `tile_list` names (nullptr: all, in order) into `acc`
+using AdaptivePass = std::function<int32_t(const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc)>;
+int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame& fr, const AdaptivePass& pass);
 
 // What render_typed settled before the residency ladder (render.hpp)
 struct WalkChoice {
@@ -273,7 +301,7 @@ int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_lar
 int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes);   // ray times into the handle's device table (times_dev), in stream order
 template <typename real>
 int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames,
-                     const CrRegion* region = nullptr);
+                     const CrRegion* region = nullptr, const AdaptiveRun* adaptive = nullptr);
 template <typename real>
 int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, DevScene<real>& ds, bool refit, bool mega, void* d_out,
                      const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb,

@@ -335,8 +335,15 @@ template <typename real> struct KernelArgs {
     // wherever those are (set_tiles, set_groups).
     FastDiv fd_groups, fd_tiles_x, fd_tiles_y;
     uint32_t reg_h;
+    // The launch's tiles by name (cr_render_adaptive_*, pathtrace_kernel_listed): work item w belongs
+    // to tile tile_list[w / (sg_groups * 64)] of the frame instead of tile w / (sg_groups * 64), and sg_total counts the listed
+    // tiles only.  Read by pathtrace_kernel_listed alone.  Everything behind the decode sees the frame's own tile number and pixel: the RNG key, the LDS slots, the
+    // addresses in fx_acc (a whole frame's).  nullptr, as prepare_args leaves it: every tile of the launch, in order.  The word
+    // follows the record's last one, so no other argument moved.
+    const int32_t* tile_list;
 };
-static_assert(sizeof(KernelArgs<float>) == 480 && sizeof(KernelArgs<double>) == 600, "the region's words fill padding: the record keeps its size");
+static_assert(sizeof(KernelArgs<float>) == 488 && sizeof(KernelArgs<double>) == 608 && offsetof(KernelArgs<float>, tile_list) == 480 &&
+              offsetof(KernelArgs<double>, tile_list) == 600, "the region's words fill padding, the tile list follows the record: 8 bytes more");
 static_assert(offsetof(KernelArgs<float>, work_counter) == 304 && offsetof(KernelArgs<float>, out) == 368 && offsetof(KernelArgs<float>, fx_acc) == 408 &&
               offsetof(KernelArgs<float>, fd_tiles_y) == 464, "the region's words fill padding: no argument moved");
 template <typename real> inline void set_tiles(KernelArgs<real>& a, uint32_t tiles_x, uint32_t tiles_y) {
@@ -1513,7 +1520,10 @@ template <typename real> CR_D const KernelArgs<real>& kernel_args() {
 // REG: the body carries a region's offsets where it carries the frame arithmetic (BATCH).  The 6-waves-per-SIMD entry point
 // passes false: at its 80 VGPRs the offsets cost spills, so region renders stay on pathtrace_kernel (render.hpp walk_ladder)
 // and the latency kernels compile to what they were.  A parameter of the body, not of a kernel: the kernels stay the same set.
-template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true>
+// LIST: the work decode names its tiles through KernelArgs::tile_list (cr_render_adaptive_*).  Only pathtrace_kernel_listed
+// passes true: read in the kernels that movies and regions run on, the list cost them 0.3 - 0.8 % at unchanged registers
+// (profiles/experiments/adaptive_sampling.txt), so it has kernels of its own and every other kernel compiles to what it was.
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true, bool LIST = false>
 CR_D void pathtrace_body(const KernelArgs<real>& A) {
     using EntryT = typename EntryOf<real, ORD>::type;
     constexpr bool BATCH = RELAX && (ANIM || CAMK);
@@ -1666,7 +1676,10 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
                 else {
                     item = w;
                     const uint32_t group = w >> 6, in = w & 63u;
-                    const uint32_t tile = fastdiv(group, A.fd_groups), sg = group - tile * A.sg_groups;
+                    uint32_t tile = fastdiv(group, A.fd_groups);
+                    const uint32_t sg = group - tile * A.sg_groups;
+                    // LIST: a launch that names its tiles (KernelArgs::tile_list) -- the frame's own tile number from here on
+                    if constexpr (REGION && LIST) { const int32_t* const listed = RG.tile_list; if (listed) tile = (uint32_t)listed[tile]; }
                     uint32_t tx, ty;
                     tile_xy(A, tile, tx, ty);
                     my_tile = tile;
@@ -1875,6 +1888,15 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) pathtrace_kernel(const 
     // the LDS-resident f32 kernels have registers to spare and lose 1 % to the reloads: they keep the by-value parameter
     if constexpr (std::is_same<real, double>::value || RES != RES_LDS) pathtrace_body<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>(kernel_args<real>());
     else pathtrace_body<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>(A);
+}
+
+// The relaxed kernels with keys once more, with the active-tile list in their work decode: the passes of cr_render_adaptive_*
+// (adaptive.hip).  Kernels of their own, so that the ones movies and regions run on do not pay for the list.
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK, bool SCREEN>
+__global__ void __launch_bounds__(MaxBlock<real>::value) pathtrace_kernel_listed(const KernelArgs<real> A) {
+    static_assert(ANIM != CAMK, "keyed primitives or camera keys alone, as for pathtrace_kernel");
+    if constexpr (std::is_same<real, double>::value || RES != RES_LDS) pathtrace_body<real, RES, ANIM, ORD, CAMK, true, SCREEN, true, true>(kernel_args<real>());
+    else pathtrace_body<real, RES, ANIM, ORD, CAMK, true, SCREEN, true, true>(A);
 }
 
 // The same kernel compiled for 6 waves per SIMD (<= 80 VGPRs, 512-thread groups), for trees far larger than the

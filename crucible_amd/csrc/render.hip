@@ -176,10 +176,11 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
 }
 
 // One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*), or the
-// pixels `region` of one frame (cr_render_region_*, whose entry has checked the sum order and the pipeline).
+// pixels `region` of one frame (cr_render_region_*, whose entry has checked the sum order and the pipeline), or one frame to
+// a noise target (cr_render_adaptive_*, whose entry has checked the same: `adaptive`, adaptive.hip).
 template <typename real>
 int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames,
-                     const CrRegion* region) {
+                     const CrRegion* region, const AdaptiveRun* adaptive) {
     DevScene<real>* walk = nullptr;
     bool refit = false;
     int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // the base tree, or the frame's own (CR_REFIT_REBUILD)
@@ -213,6 +214,7 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     std::vector<real> times;
     rc = prepare_args<real>(h, cd, p, ds, refit, h->pipeline == 0, d_out, frames, n_frames, times, a, w, fb, region);
     if (rc != CR_OK) return rc;
+    if (adaptive) { fb.ad = adaptive; w.cam_keys = true; }   // the active-tile list lives where the region's offsets do: a scene without keys runs on CAMK
     dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
     // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
     if (sum_order == CR_SUM_RELAXED && h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_SUM_RELAXED is implemented by the megakernel pipeline only");
@@ -235,7 +237,7 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
 
 template int32_t prepare_args<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<float>&, bool, bool, void*, const int32_t*, int32_t, std::vector<float>&, KernelArgs<float>&, WalkChoice&, FrameBatch<float>&, const CrRegion*);
 template int32_t prepare_args<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<double>&, bool, bool, void*, const int32_t*, int32_t, std::vector<double>&, KernelArgs<double>&, WalkChoice&, FrameBatch<double>&, const CrRegion*);
-template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
-template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
+template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*, const AdaptiveRun*);
+template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*, const AdaptiveRun*);
 
 }   // namespace cr

@@ -16,18 +16,23 @@ int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size
     return CR_OK;
 }
 
-template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
+// LIST: the passes of cr_render_adaptive_* -- pathtrace_kernel_listed, handed to adaptive_passes (adaptive.hip)
+template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool LIST = false>
 int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats, const FrameBatch<real>& fb) {
     constexpr bool LDS = RES != RES_GLOBAL || RELAX;
     static_assert(!LATENCY || RES == RES_TOP, "the 6-waves-per-SIMD entry point exists for RES_TOP only");
     KernelArgs<real> args = args_in;
     void (*kern)(const KernelArgs<real>) = pathtrace_kernel<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>;
     if constexpr (LATENCY) kern = pathtrace_kernel_latency<real, ANIM, ORD, CAMK, RELAX>;
+    if constexpr (LIST) kern = pathtrace_kernel_listed<real, RES, ANIM, ORD, CAMK, SCREEN>;
+    static_assert(!LIST || (RELAX && ANIM != CAMK && !LATENCY), "the listed kernels are relaxed kernels with keys");
     const int max_block = LATENCY ? LatencyBlock : MaxBlock<real>::value;
     // The work tile (sample-granular hand-out): 2^lw x 2^lh pixels times 64 >> (lw + lh) consecutive samples; by default
     // 4 x 4 x 4, wider tiles of fewer samples when fewer than 4 samples are rendered.
-    const int32_t n_samples = args.sample_end - args.sample_begin;
+    // (cr_render_adaptive_*: a launch renders one pass of pass_samples samples, and the tile's sides divide the block's)
+    const int32_t n_samples = fb.ad ? fb.ad->pass_samples : args.sample_end - args.sample_begin;
     int tile_lw = h->sg_lw, tile_lh = h->sg_lh;
+    if (fb.ad && (tile_lw > fb.ad->block_log2 || tile_lh > fb.ad->block_log2)) tile_lw = tile_lh = -1;
     if (tile_lw < 0) { const int ns = n_samples >= 4 ? 4 : (n_samples >= 2 ? 2 : 1); tile_lw = ns == 4 ? 2 : 3; tile_lh = ns == 1 ? 3 : 2; }
     // RELAX: the waves' accumulator slots follow the scene in LDS (2 x 384 B per wave for a 16-pixel tile); a tile too
     // large for what the scene leaves free falls back to 16 pixels (the surplus sample slots of its groups stay empty)
@@ -44,13 +49,14 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     // path tracer followed by the ordered sum (sg_finalize_kernel).
     // the launch's pixels: the region's (prepare_args: the whole frame unless cr_render_region_* named one; RELAX kernels with keys only)
     const size_t npix = (size_t)args.reg_w * (size_t)args.reg_h;
-    const int32_t s_begin = args.sample_begin, s_end = args.sample_end;
+    const int32_t s_begin = args.sample_begin, s_end = fb.ad ? s_begin + n_samples : args.sample_end;
     int32_t batch = 0;
     int32_t fpl = 1;   // frames per launch (a batch of frames: as many whole frames as the work counter holds)
     args.n_frames = 1; args.frame_times = nullptr;
     if (fb.n > 1 && !(RELAX && (ANIM || CAMK))) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
     if ((args.reg_x0 || args.reg_y0 || args.reg_w != (uint32_t)args.cam.W || args.reg_h != (uint32_t)args.cam.H) && (LATENCY || !(RELAX && (ANIM || CAMK))))
         return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders whole frames");
+    if (LIST != (fb.ad != nullptr)) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
     if ((h->sample_granular || RELAX) && s_end > s_begin) {
         const size_t per_sample = npix * 3 * sizeof(real);
         batch = (int32_t)std::min<size_t>((size_t)(s_end - s_begin), RELAX ? (size_t)INT32_MAX : std::max<size_t>(1, h->sample_buf_limit / per_sample));
@@ -69,7 +75,8 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
             if (batch <= 0) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
             // a frame that needs sample batches on its own renders frame by frame
             if (batch == s_end - s_begin) fpl = (int32_t)std::min<uint64_t>((uint64_t)fb.n, max_groups / (((uint64_t)batch + ns - 1) / ns));
-            if (args.output_sum != CR_OUTPUT_FIXED_SUM) {
+            if (fb.ad && batch < s_end - s_begin) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter at this pass_samples");
+            if (args.output_sum != CR_OUTPUT_FIXED_SUM && !fb.ad) {   // (adaptive_passes keeps its own two accumulators)
                 const hipError_t e = h->fx_acc.ensure((size_t)fb.n * npix * 3 * sizeof(unsigned long long));
                 if (e != hipSuccess) {
                     (void)hipGetLastError();
@@ -102,11 +109,34 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         // the scale of the n samples a pixel receives in this render; CR_OUTPUT_FIXED_SUM: of the whole frame, so the words
         // of any shards of it add up to the frame's, and they go straight into the caller's buffer
         const bool fixed = args.output_sum == CR_OUTPUT_FIXED_SUM;
-        args.fx_scale = fx_scale_for(fixed ? args.samples_total : s_end - s_begin);
+        args.fx_scale = fx_scale_for(fixed || fb.ad ? args.samples_total : s_end - s_begin);
         args.fx_acc = fixed ? (unsigned long long*)args.out : (unsigned long long*)h->fx_acc.p;
-        HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, (size_t)fb.n * npix * 3 * sizeof(unsigned long long), h->stream));
+        if (!fb.ad) HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, (size_t)fb.n * npix * 3 * sizeof(unsigned long long), h->stream));
     }
     HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
+    if constexpr (LIST) {
+        // cr_render_adaptive_*: the passes are adaptive_passes' (adaptive.hip), each one a launch of this kernel over the tiles
+        // it names, into the accumulator it names; the counters add up over the passes
+        if (!args.sg_on) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
+        h->last_block = block; h->last_grid = (int)grid;
+        const AdaptivePass pass = [&](const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc) -> int32_t {
+            args.tile_list = tile_list; args.sample_begin = s0; args.sample_end = s1; args.fx_acc = acc;
+            args.n_frames = 1; args.frame_times = nullptr;
+            set_groups(args, groups_of(s1 - s0));
+            args.sg_total = (uint32_t)((uint64_t)n_tiles * args.sg_groups * 64u);
+            const uint32_t pass_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block));
+            const uint64_t per_wave = (uint64_t)args.sg_total / std::max<uint64_t>(1, (uint64_t)pass_grid * block / 64);   // the chunk: as below
+            const uint64_t c = h->sg_chunk_override > 0 ? (uint64_t)h->sg_chunk_override : std::min<uint64_t>(1024, std::max<uint64_t>(64, per_wave / 128));
+            args.sg_chunk = (uint32_t)((c + 63) / 64 * 64);
+            HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
+            hipLaunchKernelGGL(kern, dim3(pass_grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
+            HIP_TRY(h, hipGetLastError());
+            return CR_OK;
+        };
+        const AdaptiveFrame fr = {args.cam.W, args.cam.H, args.samples_total, args.sg_lw, args.sg_lh, args.tiles_x, args.tiles_y, args.fx_scale,
+                                  (void*)args.out, std::is_same<real, double>::value, args.n_entries, RES};
+        return adaptive_passes(h, *fb.ad, fr, pass);
+    }
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     if (!args.sg_on) {
         HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
@@ -180,6 +210,12 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
 // camera themselves, so ANIM with CAMK is never instantiated.
 template <typename real, int RES, bool ORD, bool LATENCY, bool RELAX, bool SCREEN = false>
 int32_t launch_variant(CrHandle* h, const KernelArgs<real>& a, size_t lds_bytes, CrStats* stats, const WalkChoice& w, const FrameBatch<real>& fb) {
+    if (fb.ad) {   // cr_render_adaptive_*: the listed kernels (a scene without keys on the camera-key one)
+        if constexpr (RELAX && !LATENCY) {
+            if (w.anim) return launch<real, RES, true, ORD, false, false, true, SCREEN, true>(h, a, lds_bytes, stats, fb);
+            return launch<real, RES, false, ORD, false, true, true, SCREEN, true>(h, a, lds_bytes, stats, fb);
+        } else return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
+    }
     if (w.anim) return launch<real, RES, true, ORD, LATENCY, false, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
     if (w.cam_keys) return launch<real, RES, false, ORD, LATENCY, true, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
     return launch<real, RES, false, ORD, LATENCY, false, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
@@ -201,7 +237,7 @@ int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, 
     }
     // (the 6-waves-per-SIMD kernels render whole frames: a region of such a tree runs on the regular kernel, the same bytes)
     const bool whole = !a.reg_x0 && !a.reg_y0 && a.reg_w == (uint32_t)a.cam.W && a.reg_h == (uint32_t)a.cam.H;
-    const bool latency = f32 && whole && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
+    const bool latency = f32 && whole && !fb.ad && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
     // a window of screening records holds twice the wrappers
     const size_t window_rec = w.screen ? sizeof(std::conditional_t<ORD, ScreenEntryO, ScreenEntry>) : sizeof(typename EntryOf<real, ORD>::type);
     const int32_t top = (int32_t)std::min<size_t>((size_t)ds.n_entries, (latency ? h->latency_top_bytes : h->lds_top_bytes) / window_rec);

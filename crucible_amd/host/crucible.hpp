@@ -448,6 +448,20 @@ public:
     bool has_region = false;
     CrRegion region = {0, 0, 0, 0};
     void set_region(int32_t x0, int32_t y0, int32_t w, int32_t h) { has_region = true; region = CrRegion{x0, y0, w, h}; }
+    // A frame to a noise target (cr_render_adaptive_host): scene_cam.samples is the maximum per pixel, blocks of `block`
+    // pixels square stop once their two half-frame means differ by at most `tolerance` on average (include/crucible_hip.h has
+    // the exact rule).  render_frame then keeps the samples each pixel took and the call's stats; sample_map = true has
+    // render_image write the counts as <frame>.samples.pfm.  Whole frames on one device, one call per frame of a movie; needs
+    // relaxed sums.
+    bool has_adaptive = false, sample_map = false;
+    CrAdaptiveParams adaptive = {0, 0, 0, 0, 0.0};
+    mutable std::vector<int32_t> adaptive_counts;
+    mutable CrAdaptiveStats adaptive_stats = {};
+    void set_adaptive(double tolerance, int32_t min_samples, int32_t pass_samples, int32_t block = 16) {
+        has_adaptive = true;
+        const int32_t log2 = block == 0 ? 0 : block == 8 ? 3 : block == 16 ? 4 : block == 32 ? 5 : -1;   // (-1: the library refuses it)
+        adaptive = CrAdaptiveParams{min_samples, pass_samples, log2, 0, tolerance};
+    }
     // what a render writes: the region's size, or the frame's
     size_t out_width() const { return has_region ? (size_t)std::max(region.width, 0) : (size_t)scene_cam.image_width; }
     size_t out_height() const { return has_region ? (size_t)std::max(region.height, 0) : (size_t)scene_cam.image_height; }
@@ -612,6 +626,12 @@ public:
         CrRenderParams p = render_params(frame < 0 ? (size_t)scene_cam.frame : (size_t)frame);
         buf.resize(std::max<size_t>(1, out_width() * out_height() * 3));
         if (has_region) return cr_render_region_host(h, &cd, &p, &region, buf.data(), stats);
+        if (has_adaptive) {
+            adaptive_counts.resize((size_t)scene_cam.image_width * scene_cam.image_height);
+            const int32_t rc = cr_render_adaptive_host(h, &cd, &p, &adaptive, buf.data(), adaptive_counts.data(), &adaptive_stats);
+            if (stats) *stats = adaptive_stats.render;
+            return rc;
+        }
         return cr_render_host(h, &cd, &p, buf.data(), stats);
     }
     // The frames `frs` in one call: frame k at k * W*H*3 reals of `real_type` in `buf`.
@@ -677,6 +697,10 @@ public:
         double t1 = now_ms();
         timing.render_ms += t1 - t0;
         if (rc == CR_OK) { rc = write_frame(fname, buf); timing.write_ms += now_ms() - t1; timing.frames++; }
+        if (rc == CR_OK && has_adaptive && sample_map) {   // the samples each pixel took, one f32 channel
+            const std::vector<float> map(adaptive_counts.begin(), adaptive_counts.end());
+            rc = cr_write_pfm((fname + ".samples.pfm").c_str(), map.data(), CR_REAL_F32, (int32_t)scene_cam.image_width, (int32_t)scene_cam.image_height, 1);
+        }
         if (rc == CR_OK && aov_layers) {
             std::vector<double> planes(aov_reals());
             rc = render_aov(h, planes.data());
@@ -711,7 +735,7 @@ public:
         double write_ms[2] = {0, 0};
         int32_t rc = CR_OK;
         // (a region: one region call per frame, the batch calls take whole frames)
-        bool batched = frames_per_launch > 1 && !has_region, guides_batched = frames_per_launch > 1 && !has_region;
+        bool batched = frames_per_launch > 1 && !has_region && !has_adaptive, guides_batched = frames_per_launch > 1 && !has_region;
         const size_t rs = real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float);
         size_t k = 0;
         for (size_t fr = first; rc == CR_OK && fr < frames; k++) {
@@ -785,6 +809,10 @@ public:
     // frames m, m + n, ... -- no communicator, no RCCL.
     int32_t render_scene_group(const std::string& fname, CrStats* stats) {
         const int n = std::max(1, gpus);
+        if (has_adaptive && !is_movie) {
+            fprintf(stderr, "Render failed. an adaptive render runs on one device: cr_group_* splits a frame by samples\n");
+            return CR_ERR_UNSUPPORTED;
+        }
         if (has_region && !is_movie) {   // a group splits a frame by samples and renders whole frames (cr_group_render_host)
             fprintf(stderr, "Render failed. a region renders on one device: cr_group_* takes whole frames\n");
             return CR_ERR_UNSUPPORTED;

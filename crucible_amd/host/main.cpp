@@ -13,6 +13,11 @@
 // --aov albedo,normal,depth,coverage (guide layers through cr_render_aov_host: <frame>.<layer>.pfm next to every frame file),
 // --region x0,y0,w,h (render those pixels of the frame through cr_render_region_host and write them as a w x h file; with --aov the
 // region's planes; a movie applies it to every frame, one call per frame; needs relaxed sums; --timing names the region),
+// --adaptive tol[,min[,pass[,block]]] (render to a noise target through cr_render_adaptive_host: --samples is the maximum per pixel,
+// blocks of `block` pixels square (8, 16, 32; default 16) stop once their two half-frame means differ by at most tol on average,
+// judged every 2 * pass samples (default 8) from min samples on (default 4 * pass); needs relaxed sums and whole frames on one
+// device; a movie renders frame by frame; --sample-map also writes <frame>.samples.pfm, the samples each pixel took; --timing
+// adds the passes, the blocks stopped and the samples taken),
 // --repeat N --timing (measurement: render_scene N times in this process, one JSON line of wall-clock phases each --
 // the shape of the reference's criterion benchmark, benches/renderer_benchmark.rs:16-42 -- the first is the cold one).
 #include "crucible.hpp"
@@ -53,7 +58,8 @@ int main(int argc, char** argv) {
     RefitMode refit = false;
     int gpus = 1, repeat = 1;
     long frames_per_launch = 1;
-    std::string sum_order = "default", aov, region;
+    std::string sum_order = "default", aov, region, adaptive;
+    bool sample_map = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(2); } return argv[++i]; };
@@ -84,6 +90,8 @@ int main(int argc, char** argv) {
         else if (a == "--sum-order") sum_order = next();
         else if (a == "--aov") aov = next();
         else if (a == "--region") region = next();
+        else if (a == "--adaptive") adaptive = next();
+        else if (a == "--sample-map") sample_map = true;
         else if (a == "--dump-desc") dump = next();
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -149,6 +157,18 @@ int main(int argc, char** argv) {
             if (!movie && (gpus > 1 || use_group)) { fprintf(stderr, "--region renders on one device (a group splits a frame by samples)\n"); return 2; }
             scene.set_region(x0, y0, rw, rh);   // the library checks it against the frame
         }
+        if (!adaptive.empty()) {
+            double tol = 0;
+            int pass = 8, min_samples = -1, block = 16;
+            char tail = 0;
+            const int got = sscanf(adaptive.c_str(), "%lf,%d,%d,%d%c", &tol, &min_samples, &pass, &block, &tail);
+            if (got < 1 || got > 4) { fprintf(stderr, "--adaptive takes tol[,min[,pass[,block]]]\n"); return 2; }
+            if (got < 2) min_samples = 4 * pass;
+            if (!region.empty() || !aov.empty()) { fprintf(stderr, "--adaptive renders whole beauty frames (no --region, no --aov)\n"); return 2; }
+            if (!movie && (gpus > 1 || use_group)) { fprintf(stderr, "--adaptive renders on one device (a group splits a frame by samples)\n"); return 2; }
+            scene.set_adaptive(tol, min_samples, pass, block);   // the library checks the rest
+            scene.sample_map = sample_map;
+        } else if (sample_map) { fprintf(stderr, "--sample-map goes with --adaptive\n"); return 2; }
         if (!dump.empty()) { dump_desc(scene.flatten(), dump.c_str()); return 0; }
         int32_t rc = CR_OK;
         for (int rep = 0; rep < repeat && rc == CR_OK; rep++) {
@@ -161,12 +181,17 @@ int main(int argc, char** argv) {
             if (rc == CR_OK && timing) {
                 const Scene::Timing& t = scene.timing;
                 const double samples = (double)scene.out_width() * (double)scene.out_height() * scene.scene_cam.samples * (movie ? (double)t.frames : 1.0);
-                const std::string region_field = scene.has_region ? ", \"region\": \"" + region + "\"" : "";
+                std::string extra_fields = scene.has_region ? ", \"region\": \"" + region + "\"" : "";
+                if (scene.has_adaptive) {   // (a movie: the last frame's)
+                    const CrAdaptiveStats& as = scene.adaptive_stats;
+                    extra_fields += ", \"adaptive\": \"" + adaptive + "\", \"passes\": " + std::to_string(as.passes) + ", \"blocks\": " + std::to_string(as.blocks) +
+                                    ", \"blocks_stopped\": " + std::to_string(as.blocks_stopped) + ", \"samples_taken\": " + std::to_string(as.render.samples);
+                }
                 printf("{\"run\": %d, \"width\": %u, \"height\": %u, \"samples\": %u, \"frames\": %zu, \"format\": \"%s\", \"real\": \"%s\", \"create_ms\": %.3f, \"flatten_ms\": %.3f, "
                        "\"upload_ms\": %.3f, \"bvh_build_ms\": %.3f, \"render_ms\": %.3f, \"kernel_ms\": %.3f, \"write_ms\": %.3f, \"total_ms\": %.3f, \"msamples_per_s_end_to_end\": %.1f, "
                        "\"msamples_per_s_kernel\": %.1f, \"guide_calls\": %zu%s}\n",
                        rep, scene.scene_cam.image_width, scene.scene_cam.image_height, scene.scene_cam.samples, movie ? t.frames : (size_t)1, format.c_str(), real.c_str(), t.create_ms,
-                       t.flatten_ms, t.upload_ms, t.bvh_build_ms, t.render_ms, t.kernel_ms, t.write_ms, t.total_ms, samples / t.total_ms / 1e3, t.kernel_ms > 0 ? samples / t.kernel_ms / 1e3 : 0.0, t.guide_calls, region_field.c_str());
+                       t.flatten_ms, t.upload_ms, t.bvh_build_ms, t.render_ms, t.kernel_ms, t.write_ms, t.total_ms, samples / t.total_ms / 1e3, t.kernel_ms > 0 ? samples / t.kernel_ms / 1e3 : 0.0, t.guide_calls, extra_fields.c_str());
                 fflush(stdout);
             }
         }

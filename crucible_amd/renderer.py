@@ -308,6 +308,37 @@ class Renderer:
                         total[k] = st[k]
         return out, total
 
+    def render_adaptive(self, cam, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples, pass_samples, block=16,
+                        want_counts=True, want_stats=True, sum_order=None):
+        """cr_render_adaptive_host: the frame to a noise target -- cam.samples is the maximum per pixel, blocks of `block`
+        (8, 16 or 32) pixels square stop once the mean absolute difference of their two half-frame means is at most
+        `tolerance` (the exact rule: include/crucible_hip.h).  Needs CR_SUM_RELAXED.  Returns (image (H, W, 3), counts
+        (H, W) int32 or None, stats dict: passes, blocks, blocks_stopped, judge_ms, and the render's CrStats under
+        "render")."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
+        ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
+        out = np.empty((cam.image_height, cam.image_width, 3), dtype=np_real(real_type))
+        counts = np.empty((cam.image_height, cam.image_width), dtype=np.int32) if want_counts else None
+        st = A.CrAdaptiveStats()
+        self._check(self.lib.cr_render_adaptive_host(self.h, C.byref(cd), C.byref(p), C.byref(ap), out.ctypes.data_as(C.c_void_p),
+                                                     counts.ctypes.data_as(C.c_void_p) if want_counts else None,
+                                                     C.byref(st) if want_stats else None))
+        return out, counts, st.as_dict()
+
+    def render_adaptive_device(self, cam, d_ptr, d_counts=None, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples,
+                               pass_samples, block=16, want_stats=True, sum_order=None):
+        """cr_render_adaptive_device: the frame into device memory at `d_ptr` (W*H*3 reals) and, if given, the counts at
+        `d_counts` (W*H int32).  Synchronous.  Returns the stats dict of render_adaptive."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
+        ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
+        st = A.CrAdaptiveStats()
+        self._check(self.lib.cr_render_adaptive_device(self.h, C.byref(cd), C.byref(p), C.byref(ap), C.c_void_p(d_ptr),
+                                                       C.c_void_p(d_counts) if d_counts else None,
+                                                       C.byref(st) if want_stats else None))
+        return st.as_dict()
+
     def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
         """cr_fixed_sums_to_rgb: summed CR_OUTPUT_FIXED_SUM words of a whole frame (device pointer, W*H*3 uint64) ->
         its per-pixel means at device pointer `d_out` (W*H*3 reals), exactly the relaxed frame.  Asynchronous on the
@@ -394,6 +425,14 @@ def region_arg(region):
     x0, y0, w, h = (int(v) for v in region)
     reg = A.CrRegion(x0, y0, w, h)
     return C.pointer(reg), (w, h)
+
+
+def adaptive_arg(tolerance, min_samples, pass_samples, block=16):
+    """A CrAdaptiveParams from the mirrors' arguments: `block` is the block's side in pixels (8, 16, 32; 0 or None: the
+    library's default); any other side goes through as a block_log2 the library refuses."""
+    block = int(block or 0)
+    log2 = {0: 0, 8: 3, 16: 4, 32: 5}.get(block, -1)
+    return A.CrAdaptiveParams(int(min_samples), int(pass_samples), log2, 0, float(tolerance))
 
 
 def aov_mask(layers):

@@ -479,6 +479,10 @@ class Scene:
         self.bvh_mode = A.CR_BVH_REFERENCE   # A.CR_BVH_SAH: the quality builder (include/crucible_hip.h)
         self.frames_per_launch = 1   # render_movie: N > 1 renders N frames per call through Renderer.render_frames
         self.aov_layers = 0          # CR_AOV_* mask or layer names: writes <frame>.<layer>.pfm next to every frame file
+        # set_adaptive: frames to a noise target through Renderer.render_adaptive (scene_cam.samples is the maximum per
+        # pixel; needs relaxed sums; a movie renders frame by frame); sample_map also writes <frame>.samples.pfm
+        self.adaptive = None
+        self.sample_map = False
 
     @classmethod
     def new_image(cls, aspect_ratio, image_width, frame_rate, shutter_angle, thread_count):
@@ -576,6 +580,20 @@ class Scene:
         tl = self.scene_cam.look_from_tl if which == "from" else self.scene_cam.look_at_tl
         tl.translate_point(p, keyframe, it, space)
 
+    def set_adaptive(self, tolerance, min_samples, pass_samples, block=16):
+        self.adaptive = dict(tolerance=float(tolerance), min_samples=int(min_samples), pass_samples=int(pass_samples), block=int(block))
+
+    def _render_frame(self, r, stem=None):
+        """The frame at the camera's counter: (image, stats); an adaptive frame's sample map goes to <stem>.samples.pfm."""
+        if self.adaptive is None:
+            return r.render(self.scene_cam, seed=self.seed, real_type=self.real_type)
+        from .renderer import write_pfm
+        img, counts, stats = r.render_adaptive(self.scene_cam, seed=self.seed, real_type=self.real_type, want_counts=self.sample_map,
+                                               **self.adaptive)
+        if self.sample_map and stem is not None:
+            write_pfm(stem + ".samples.pfm", counts.astype("float32"))
+        return img, stats
+
     # ---- flatten to the C ABI
     def flatten(self):
         materials, textures, images, keys, prims = [], [], [], [], []
@@ -672,7 +690,7 @@ class Scene:
         r = renderer or Renderer(self.device)
         try:
             r.upload_scene(self.flatten())
-            img, stats = r.render(self.scene_cam, seed=self.seed, real_type=self.real_type)
+            img, stats = self._render_frame(r, fname)
             r.write_ppm(fname + ".ppm", img)
             print(f"Successful render! Image stored at: {fname}.ppm")
             if aov_mask(self.aov_layers):
@@ -704,6 +722,8 @@ class Scene:
             # the frames and the guide layers of a batch each come from one call, until the library refuses that call
             # (frames: reference order or refit boxes; guide layers: refit boxes): then one call per frame, the same files
             batched = guides_batched = n > 1
+            if self.adaptive is not None:
+                batched = False   # an adaptive frame is one call
             cam = self.scene_cam
             frame = 0
             while frame < frames:
@@ -728,8 +748,8 @@ class Scene:
                         guides_batched = False
                 for k, f in enumerate(batch):
                     cam.frame = f
-                    img = imgs[k] if imgs is not None else r.render(cam, seed=self.seed, real_type=self.real_type)[0]
                     stem = os.path.join(fname, "artifacts", f"image{frame:0{digits}d}")
+                    img = imgs[k] if imgs is not None else self._render_frame(r, stem)[0]
                     r.write_ppm(stem + ".ppm", img)
                     if layers:
                         self._write_aov(stem, guides[k] if guides is not None else

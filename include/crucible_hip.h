@@ -565,6 +565,72 @@ CR_API int32_t cr_render_aov_region_device(CrHandle* h, const CrCameraDesc* cam,
 CR_API int32_t cr_render_aov_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
                                          const CrRegion* region, void* h_out, CrStats* stats);
 
+/*
+ * A frame to a noise target: blocks of pixels stop taking samples once their two half-frame means agree.
+ * params->samples is the MAXIMUM per pixel.  The output is image_width*image_height*3 reals, each pixel's mean over the
+ * samples that pixel took; `counts` (may be NULL) receives image_width*image_height int32_t, the samples each pixel took.
+ *
+ * The rule, in exact integer arithmetic.  Let P = pass_samples and S = the exponent of the fixed-point scale 2^S of
+ * params->samples (as CR_OUTPUT_FIXED_SUM defines it: the largest S <= 52 with samples * 2^S < 2^63; 52 up to 2047 samples).
+ *   - Pass p = 0, 1, ... renders the sample indices [pP, (p+1)P) of every pixel of every still-active block.
+ *   - Even passes add into accumulator E, odd passes into accumulator O: two sets of relaxed sums, 24 bytes per pixel
+ *     each, bit 63 of a word the NaN flag.
+ *   - After each pair of passes (q = 1, 2, ...: n = 2qP samples taken) every active block b with n >= min_samples is judged:
+ *       d(x, c) = |mag(E[x,c]) - mag(O[x,c])| >> 12, mag = bits 0..62 of the word;
+ *       D_b = the sum of d over the block's pixels inside the frame and the three channels, an exact 64-bit integer
+ *             (fewer than 2^12 terms, each below 2^51);
+ *       T_b = (uint64) min(floor(tolerance * (2^(S-12) * qP * 3 N_b)), 2^63), N_b = the block's pixels inside the frame;
+ *             the bracket is exact in f64, then there is one f64 multiply and one floor;
+ *       the block stops iff D_b <= T_b, else it stays active.
+ *     In words: a block stops when the mean absolute difference between its two half-frame means is at most
+ *     `tolerance` (linear colour).
+ *   - A block that stops at n is final.  Blocks still active at n = params->samples end there (they are not judged there).
+ *   - The blocks are 2^block_log2 pixels square and anchored at pixel (0, 0); edge blocks are partial.
+ *   - The output is ((mag(E) + mag(O)) * 2^-S) / n_b in the arithmetic that finalizes every relaxed frame, n_b the
+ *     block's sample count; NaN where either word's flag is set.
+ * Consequences: the frame and the counts are deterministic and independent of scheduling (integer sums; the order of the
+ * active-tile list never reaches the output).  With params->samples <= 2047 (S = 52) every pixel is BIT FOR BIT the pixel
+ * of cr_render_device with samples = counts[pixel] under CR_SUM_RELAXED (beyond that a shorter render uses a finer scale).
+ * min_samples == params->samples is exactly the plain relaxed render, counters included.
+ *
+ * CR_ERR_INVALID_ARG: a null `adaptive`; block_log2 outside {0, 3, 4, 5}; _reserved != 0; pass_samples < 1;
+ * params->samples or min_samples not a positive multiple of 2 * pass_samples; min_samples > params->samples; a negative
+ * or non-finite tolerance; a null output; and whatever cr_render_device rejects.  CR_ERR_UNSUPPORTED: a sum order other
+ * than CR_SUM_RELAXED (after CR_SUM_DEFAULT / CRUCIBLE_SUM_ORDER are resolved) or a pipeline other than the megakernel,
+ * as for cr_render_region_*; sample_begin != 0 or sample_count != samples (the judgement needs all samples of a pixel);
+ * output_sum != 0.  Everything is checked before anything changes: a refused call leaves the handle as it was.
+ * refit_boxes 0, 1 and CR_REFIT_REBUILD work: the boxes or the tree are prepared once and the passes reuse them.
+ *
+ * The call is synchronous: the host reads the number of active tiles back (4 bytes) after every judged pair of passes.
+ * The handle keeps 48 bytes per pixel for E and O, apart from the other calls' buffers, freed by cr_destroy.
+ * Afterwards cr_export_render_bvh behaves as after a render.  cr_last_kernel_ms reports only the passes since the last
+ * judgement (the handle's event pair is recorded anew for every such run); the call's whole render time is
+ * stats->render.kernel_ms, the sum over all passes.
+ */
+typedef struct CrAdaptiveParams {
+    int32_t min_samples;    /* no block is judged before it has this many samples per pixel            */
+    int32_t pass_samples;   /* P: samples per pixel per launch                                          */
+    int32_t block_log2;     /* 3, 4 or 5: blocks of 8, 16 or 32 pixels square; 0 = the default, 4       */
+    int32_t _reserved;      /* 0 */
+    double  tolerance;      /* >= 0, finite: see the rule above                                         */
+} CrAdaptiveParams;
+
+typedef struct CrAdaptiveStats {
+    CrStats render;         /* counters and samples summed over all passes, kernel_ms their sum         */
+    double  judge_ms;       /* HIP-event time of the judge and finalize kernels                         */
+    int32_t passes;         /* launches of the render kernel                                            */
+    int32_t blocks;         /* blocks of the frame                                                      */
+    int32_t blocks_stopped; /* blocks that stopped before params->samples                               */
+    int32_t _pad;
+} CrAdaptiveStats;
+
+CR_API int32_t cr_render_adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                         const CrAdaptiveParams* adaptive, void* d_out_rgb, int32_t* d_counts, CrAdaptiveStats* stats);
+
+/* Same, into HOST buffers; the Color::new check of cr_render_host applies (stats->render.nan_pixels, CR_ERR_NAN). */
+CR_API int32_t cr_render_adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                       const CrAdaptiveParams* adaptive, void* h_out_rgb, int32_t* h_counts, CrAdaptiveStats* stats);
+
 /* The wrapper tree the device walks for `real_type`, as BVHWrapper's shape (src/objects/bvhwrapper.rs:7-11):
  * wrapper k has boxes[6k..6k+5] = xmin,xmax,ymin,ymax,zmin,zmax (exact values of `real_type`) and
  * children[2k], children[2k+1] = left, right: >= 0 another wrapper's index, < 0 the bitwise complement of a
