@@ -61,6 +61,17 @@ CR_HD double r_sqrt(double x) {
 #endif
     return __builtin_sqrt(x);
 }
+// The operand range of Sphere::hit's short quotient (sphere_quot below, where the argument stands): 2^-400 <= |x| < 2^400, read
+// from the word that holds sign and exponent.  kQuotLo: that word for 2^-400; kQuotSpan: 800 binades of exponent field.
+// tests/quot_range_check.cpp holds quot_in_range to frexp on the host.
+constexpr uint32_t kQuotLo = 0x26f00000u, kQuotSpan = 800u << 20;
+CR_HD bool quot_in_range(double x) {
+    const uint32_t hi = (uint32_t)((unsigned long long)__builtin_bit_cast(long long, x) >> 32);
+    return ((hi << 1) - (kQuotLo << 1)) < (kQuotSpan << 1);
+}
+// the reciprocal that means "divide": every quotient by it takes `/` (a NaN; the f32 kernels keep `/` and never read theirs)
+template <typename real> CR_HD real quot_divide() { return real(0); }
+template <> CR_HD double quot_divide<double>() { return __builtin_bit_cast(double, 0x7ff8000000000000ll); }
 CR_HD float r_abs(float x) { return __builtin_fabsf(x); }
 CR_HD double r_abs(double x) { return __builtin_fabs(x); }
 CR_HD float r_floor(float x) { return __builtin_floorf(x); }
@@ -440,7 +451,7 @@ template <typename real> CR_HD CamFrame<real> camera_frame(const CamConst<real>&
 enum { DG_BOX_WAVE = 0, DG_BOX_LANE, DG_PRIM_WAVE, DG_PRIM_LANE, DG_ROUND_WAVE, DG_ROUND_LANE, DG_LEAFPH_WAVE, DG_LEAFPH_LANE,
        DG_SHADE_WAVE, DG_SHADE_LANE, DG_LAMB_LANE, DG_METAL_LANE, DG_DIEL_LANE, DG_SKY_LANE, DG_RUV_WAVE, DG_RUV_LANE,
        DG_REGEN_WAVE, DG_REGEN_LANE, DG_OUTER_WAVE, DG_UNWIND_WAVE, DG_UNWIND_LANE, DG_HITSH_WAVE, DG_HITSH_LANE, DG_BAND_WAVE, DG_BAND_LANE,
-       DG_ROOT2_WAVE, DG_ROOT2_LANE, DG_N };
+       DG_ROOT2_WAVE, DG_ROOT2_LANE, DG_QUOT_WAVE, DG_QUOT_LANE, DG_QUOTDIV_WAVE, DG_QUOTDIV_LANE, DG_N };
 struct Diag { uint32_t v[DG_N]; };
 #define CR_DIAG_LEADER() ((threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)__ballot(1)) - 1))
 #define CR_DIAG_HIT(dg, wave_i, lane_i) do { if (dg) { (dg)->v[lane_i]++; if (CR_DIAG_LEADER()) (dg)->v[wave_i]++; } } while (0)
@@ -546,27 +557,95 @@ CR_D bool root2_below_tmin(float n2, float a, float tmin) {
     if (!(tmin >= 0x1.0p-10f)) return false;
     return __float_as_int(n2) < __float_as_int(a) - (11 << 23);
 }
+// Sphere::hit's quotients with one reciprocal per path segment (f64 kernels; SHARED below).  Both roots divide by a = |d|^2,
+// the same number for every sphere a segment tests, and the compiler's IEEE division refines 1/a again each time:
+//     s0 = div_scale(a, a, n)   s1 = div_scale(n, a, n)               (the operands, scaled by 2^+-128 near the range's ends)
+//     r0 = rcp(s0)   e0 = fma(-s0, r0, 1)   r1 = fma(r0, e0, r0)   e1 = fma(-s0, r1, 1)   r = fma(r1, e1, r1)
+//     q  = s1 * r    m  = fma(-s0, q, s1)   div_fmas(m, r, q)  [= fma(m, r, q), rescaled when s1 was]   div_fixup(., a, n)
+// For 2^-400 <= a < 2^400 and 2^-400 <= |n| < 2^400 neither div_scale scales (they do so for a subnormal operand, an exponent
+// of n at most 2^-970, one of a beyond 2^+-1021 or a difference of the two beyond 768 or towards a subnormal quotient -- all at
+// least 200 binades away), so s0 = a, s1 = n; div_fmas is the plain FMA; and div_fixup, which replaces the value for NaN, zero
+// and infinite operands and for an exponent difference beyond the format, only puts sign(n) ^ sign(a) on |value| -- the sign it
+// has: 2^-800 < |n / a| < 2^800 is an ordinary number and so is every intermediate.  Then r depends on a alone,
+//     shared_rcp(a) = r,       n / a = fma(fma(-a, q, n), r, q)  with  q = n * r,
+// the same operations on the same operands in the same order, hence the same bits: three instructions for twelve
+// (tests/quotient_check.hip compares the two on the device, 2^22 pairs and the edges of the range; the first comparison, over
+// 2^24 pairs, is in profiles/experiments/r03_small_experiments.txt).
+//   operand                         short form would give          n / a gives            so the wave
+//   |n| or a in [2^-400, 2^400)     the bits of n / a              --                     takes the short form
+//   n = +0                          +0 (0 r = 0, m = +0, +0)       +0                     divides: the guard reads the word
+//   n = -0                          +0 (m = fma(-a, -0, -0) = +0)  -0                       with sign and exponent only, where
+//   n subnormal                     not proven (s1 is scaled)      the quotient             +-0 and a subnormal are one value
+//   n = +-inf, NaN                  NaN (inf - inf in m)           +-inf, NaN             divides
+//   |n| outside the range           not proven                     the quotient           divides
+//   a = 0, subnormal, +inf, NaN,    r is the sentinel              NaN, +-inf, +-0 or     divides
+//     or outside the range                                           the quotient
+// A zero numerator is not rare enough to ignore and not worth a third instruction: n1 = h - sqrtd is rounding noise around zero
+// on the sphere a refracted ray enters from (section 3.8 of DESIGN.md), exactly 0 there now and then; only its sign would differ
+// (-0 for +0 -- invisible to `tmin < root`, `root <= tmin` and `root < tmax`, and t_out is never a zero), but the helper promises the
+// bits of n / a, so a zero divides.  The -DCR_DIAG build counts the wave-level quotients and those that divided
+// (profiles/experiments/shared_reciprocal_ab.txt has the share).
+// The guard is wave-uniform like r_sqrt's: one active lane outside the range sends the wave to `/`, which is right for every
+// operand.  Per lane it is two integer instructions and a compare: u = (hi(n) << 1) - (0x26f00000 << 1) drops n's sign and is
+// below 800 << 21 exactly for an exponent field in [1023 - 400, 1023 + 400); max(u, hi(r)) folds the sentinel in, because a
+// valid r lies in (2^-400, 2^400] -- hi(r) <= 0x58f00000 < 800 << 21 = 0x64000000 -- and the sentinel, a NaN, has hi = 0x7ff80000.
+// (kQuotLo, kQuotSpan, quot_in_range and quot_divide stand with r_sqrt at the top of the file: the host can compile them)
+CR_D double shared_rcp(double a) {
+    double r = __builtin_amdgcn_rcp(a);
+    r = __builtin_fma(r, __builtin_fma(-a, r, 1.0), r);
+    r = __builtin_fma(r, __builtin_fma(-a, r, 1.0), r);
+    return quot_in_range(a) ? r : quot_divide<double>();
+}
+CR_D float shared_rcp(float) { return quot_divide<float>(); }
+// n / a, bit for bit; r = shared_rcp(a) or quot_divide().  SHARED = false is the division alone.
+template <bool SHARED>
+CR_D double sphere_quot(double n, double a, double r, Diag* dg = nullptr) {
+    if constexpr (SHARED) {
+        CR_DIAG_HIT(dg, DG_QUOT_WAVE, DG_QUOT_LANE);
+        typedef uint32_t Words __attribute__((ext_vector_type(2)));   // (the high word as a register of its own, not a 64-bit shift)
+        const uint32_t hn = __builtin_bit_cast(Words, n).y, hr = __builtin_bit_cast(Words, r).y;
+        const uint32_t u = (hn << 1) - (kQuotLo << 1);
+        const bool ok = (u > hr ? u : hr) < (kQuotSpan << 1);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) == 0ull, 1)) {
+            const double q = n * r;
+            return __builtin_fma(__builtin_fma(-a, q, n), r, q);
+        }
+        CR_DIAG_HIT(dg, DG_QUOTDIV_WAVE, DG_QUOTDIV_LANE);
+        // (two empty statements the compiler cannot move, around this division: without them it computes both forms in every
+        // test and selects one)
+        asm volatile("" : "+v"(n));
+        double q = n / a;
+        asm volatile("" : "+v"(q));
+        return q;
+    }
+    return n / a;
+}
+template <bool SHARED>
+CR_D float sphere_quot(float n, float a, float, Diag* = nullptr) { return n / a; }
+
 // RULE_B = false keeps rule A alone: the extra exit costs the f64 kernels that read their tree from global memory (RES_GLOBAL,
 // RES_TOP) two VGPR spills in the shading code, and the frames that run them and test few or no spheres lost 0.6-1.1 %
 // (teapot, the orbit movie; profiles/experiments/decided_early_ab.txt), so walk_round asked for rule B in the RES_LDS kernels only.
 // Since the f64 kernels without keyed primitives stopped spilling (profiles/experiments/uniform_and_decode_ab.txt) they take
 // rule B under every residency; in the f32 kernels below the LDS window it would cost a wave per SIMD, in the keyed f64 ones spills.
-template <bool RULE_B = true, typename real>
+// SHARED: the two quotients go through sphere_quot with ra = shared_rcp(a) (WalkState::rda); without it, or with the default
+// ra, they are the divisions.
+template <bool RULE_B = true, bool SHARED = false, typename real>
 CR_D bool sphere_t(real cx, real cy, real cz, real radius, V3<real> o, V3<real> d, real a /* |d|^2 */, real tmin, real tmax, real& t_out,
-                   Diag* dg = nullptr) {
+                   Diag* dg = nullptr, real ra = quot_divide<real>()) {
     V3<real> oc = sub(mk<real>(cx, cy, cz), o);
     real h = dot(d, oc);
     real c = len2(oc) - radius * radius;
     real disc = h * h - a * c;
     if (disc < real(0)) return false;
     real sqrtd = r_sqrt(disc);
-    real root = (h - sqrtd) / a;
+    real root = sphere_quot<SHARED>(h - sqrtd, a, ra, dg);
     if (!(tmin < root && root < tmax)) {
         if (!(root <= tmin)) return false;                 // rule A
         const real n2 = h + sqrtd;
         if (RULE_B && root2_below_tmin(n2, a, tmin)) return false;   // rule B
         CR_DIAG_HIT(dg, DG_ROOT2_WAVE, DG_ROOT2_LANE);
-        root = n2 / a;
+        root = sphere_quot<SHARED>(n2, a, ra, dg);
         if (!(tmin < root && root < tmax)) return false;
     }
     t_out = root;
@@ -1169,6 +1248,7 @@ CR_D ScreenStepO fetch_screen_ordered(const ScreenEntryO* lds, const ScreenEntry
 template <typename real> struct WalkState {
     V3<real> inv;        // 1 / direction
     real dd;             // |direction|^2: Sphere::hit's `a`, the same for every sphere of the segment
+    real rda;            // shared_rcp(dd) in the kernels that share it (quot_form() == 1), quot_divide() in the others
     real best_t;         // closest hit so far = the interval's max handed to the next wrapper
     int32_t best;        // leaf-order index of that primitive, -1 = none
     int32_t idx;         // next wrapper to visit; n_entries = walk finished
@@ -1177,12 +1257,13 @@ template <typename real> struct WalkState {
     int32_t pending;     // a leaf wrapper whose box was hit and whose primitives are still to be tested (-1: none)
 };
 
-template <typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd) {
+template <bool SHARED = false, typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd) {
     w.inv = mk<real>(real(1) / rd.x, real(1) / rd.y, real(1) / rd.z);
     // 1/dir infinite on some axis (zero or denormal component): slab distances can be NaN, where only the
     // compare/select form reproduces Aabb::hit
     w.exact_box = (r_abs(w.inv.x) == r_inf(real(0))) || (r_abs(w.inv.y) == r_inf(real(0))) || (r_abs(w.inv.z) == r_inf(real(0)));
     w.dd = len2(rd);
+    w.rda = SHARED ? shared_rcp(w.dd) : quot_divide<real>();
     w.idx = 0; w.best_t = r_inf(real(0)); w.best = -1; w.pending = -1;
     w.oct = (rd.x < real(0) ? 1 : 0) | (rd.y < real(0) ? 2 : 0) | (rd.z < real(0) ? 4 : 0);
 }
@@ -1282,7 +1363,26 @@ CR_D bool screen_box_miss_exact(const float* b, Pair<float> fox, Pair<float> foy
     return hi <= lo;
 }
 
-template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false>
+// Where Sphere::hit's shared reciprocal lives (sphere_quot): 0 -- nowhere, the kernel divides; 1 -- WalkState::rda, made once per
+// segment in walk_begin<true>; 2 -- made in walk_round at the head of each leaf phase, live inside the primitive loop only.
+// Decided kernel by kernel from the compiler's allocation (scripts/kernel_resources.py; the table is in DESIGN.md section 3.10):
+// no kernel may gain a spill.  The f64 render kernels that walk on screening records with the tree in LDS or its top there take
+// form 1 -- the headline's, the 1M-sphere frame's, their region, batch and listed twins.  Of the other f64 render kernels, those
+// with the whole tree in global memory or its top in LDS without the screen gain an SGPR spill under some sum order or camera and
+// the keyed ones (ANIM) with relaxed sums 6-12 spilled VGPRs; the guide-layer kernels (aov_kernel.hpp: one segment per sample,
+// nothing to share) would spill too: those divide, as do the f32 kernels and the cross-check pipelines.
+// -DCR_QUOT_FORM=0|1|2 builds one form into the same kernels (profiles/experiments/shared_reciprocal_ab.txt).
+template <typename real, int RES, bool ANIM, bool SCREEN> constexpr int quot_form() {
+    constexpr bool fits = std::is_same<real, double>::value && !ANIM && SCREEN && RES != RES_GLOBAL;
+#ifdef CR_QUOT_FORM
+    return fits ? CR_QUOT_FORM : 0;
+#else
+    return fits ? 1 : 0;
+#endif
+}
+
+// SHARE: the caller began the walk with walk_begin<quot_form() == 1>; the guide-layer kernels and the cross-check pipelines do not.
+template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false, bool SHARE = false>
 CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, const Prim<real>* prims, V3<real> ro, V3<real> rd, real rtime,
                      WalkState<real>& w, bool walking, uint32_t budget, unsigned long long& c_node, uint32_t& c_prim, Diag* dg = nullptr,
                      const void* lds_screen = nullptr) {
@@ -1429,6 +1529,8 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
     w.pending = -1;
     if (leaf >= 0) {
         CR_DIAG_HIT(dg, DG_LEAFPH_WAVE, DG_LEAFPH_LANE);
+        constexpr int QF = SHARE ? quot_form<real, RES, ANIM, SCREEN>() : 0;
+        const real ra = QF == 1 ? w.rda : (QF == 2 ? shared_rcp(w.dd) : quot_divide<real>());
         auto test = [&](int32_t pi) {
             const Prim<real>& p = prims[pi];
             c_prim++;
@@ -1439,7 +1541,7 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             const int32_t kind = A.uniform_kind >= 0 ? A.uniform_kind : p.kind();   // a scalar test; one load fewer per primitive when it holds
             if (kind == 0) {
                 if (ANIM && p.key_count) timeline_eval(A.keys + p.key_first, p.key_count, rtime, g0, g1, g2, g3);
-                h = sphere_t<RES == RES_LDS || (std::is_same<real, double>::value && !ANIM)>(g0, g1, g2, g3, ro, rd, w.dd, tmin, w.best_t, t, dg);
+                h = sphere_t<RES == RES_LDS || (std::is_same<real, double>::value && !ANIM), QF != 0>(g0, g1, g2, g3, ro, rd, w.dd, tmin, w.best_t, t, dg, ra);
             } else {
                 V3<real> a = mk<real>(g0, g1, g2), b = mk<real>(g3, p.g[4], p.g[5]), c = mk<real>(p.g[6], p.g[7], p.g[8]);
                 if (ANIM && p.key_count) {
@@ -1645,7 +1747,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
     unsigned long long c_node = 0;
     // walk state, kept across rounds: a lane whose walk is cut short resumes where it stopped
     WalkState<real> ws;
-    ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
+    ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.rda = quot_divide<real>(); ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
     const int32_t n_entries = A.n_entries;
 
     Diag* dgp = nullptr;
@@ -1761,7 +1863,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
             if (depth_left == 0) finished = true;   // ray_color: depth == 0 -> black
             else {
                 c_seg++;
-                walk_begin(ws, rd);
+                walk_begin<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, rd);
                 state = n_entries > 0 ? ST_WALK : ST_SHADE;
             }
         }
@@ -1771,7 +1873,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         // shading changes.
         if (__ballot(state == ST_WALK)) {
             for (;;) {
-                walk_round<real, RES, ANIM, ORD, SCREEN>(A, lds_entries, prims, ro, rd, rtime, ws, state == ST_WALK, A.walk_round_steps, c_node, c_prim, dgp, lds_screen);
+                walk_round<real, RES, ANIM, ORD, SCREEN, true>(A, lds_entries, prims, ro, rd, rtime, ws, state == ST_WALK, A.walk_round_steps, c_node, c_prim, dgp, lds_screen);
                 if (state == ST_WALK && ws.idx >= n_entries && ws.pending < 0) state = ST_SHADE;
                 const uint64_t walking = __ballot(state == ST_WALK);
                 if (!walking || 64u - (uint32_t)__popcll(walking) >= A.walk_exit_lanes) break;

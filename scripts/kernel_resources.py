@@ -2,7 +2,8 @@
 same sources and flags as crucible_amd/csrc/Makefile, every translation unit, remarks merged): allocated VGPRs / SGPRs, scratch
 bytes, spill counts, waves per SIMD.  A kernel that two units emit is an error.
 rocprofv3's `arch_vgpr_count` halves the allocation on gfx950 (64 for a 128-VGPR kernel); this is the figure bench.py reports.
-usage: python scripts/kernel_resources.py > profiles/r03_kernel_resources.json   (CPU only, ~1 min on 8 cores)"""
+usage: python scripts/kernel_resources.py > profiles/r03_kernel_resources.json   (CPU only, ~1 min on 8 cores)
+EXTRA="-DNAME=VALUE ..." adds flags, as the Makefile's EXTRA does (variant builds of an experiment)."""
 import concurrent.futures, json, os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,7 +11,7 @@ csrc = os.path.join(ROOT, "crucible_amd", "csrc")
 units = [os.path.join(csrc, u + ".hip") for u in re.search(r"^UNITS := (.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()]
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
        "-fhip-fp32-correctly-rounded-divide-sqrt", "-fvisibility=hidden", "-Wno-unused-function", "--offload-device-only", "-c",
-       "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null"]
+       "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null"] + os.environ.get("EXTRA", "").split()
 with concurrent.futures.ThreadPoolExecutor(max_workers=12) as pool:
     texts = list(pool.map(lambda src: subprocess.run(cmd + [src], capture_output=True, text=True, cwd=csrc).stderr, units))
 out, unit_of = {}, {}
