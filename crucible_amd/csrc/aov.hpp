@@ -38,9 +38,10 @@ template <typename real> struct AovArgs {
     const real* frame_times;
 };
 
-// aov_f32.hip, aov_f64.hip: the residency ladder of the guide kernels (the render's own choices, render.hpp walk_ladder:
-// the whole scene in LDS, the top window, global memory; screening records where the render walks on them).  The trace
-// kernel is launched on the handle's stream; *res receives the residency (CrStats.scene_in_lds).
+// aov_f32.hip, aov_f64.hip: the residency ladder of the guide kernels.  It asks the rule the render's walk_ladder asks
+// (residency.hpp choose_residency: the whole scene in LDS, the top window, global memory; screening records where the
+// render walks on them), so both stage the same records.  The trace kernel is launched on the handle's stream; *res
+// receives the residency (CrStats.scene_in_lds).
 template <typename real>
 int32_t aov_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res);
 

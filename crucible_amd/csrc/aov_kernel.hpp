@@ -1,7 +1,8 @@
 // aov_kernel.hpp -- the guide pass's first-hit kernels for gfx950 and their launch: made of the megakernel's parts
 // (pathtrace.hpp: camera_ray, walk_begin / walk_round, CR_CHECKER_LEAF, image_lookup, shade's sky) around a much
 // smaller body -- a primary ray per work item, its closest hit, four values, no path state.  Included by aov_f32.hip
-// and aov_f64.hip only, each of which instantiates aov_ladder for its precision, so no kernel is emitted twice.
+// and aov_f64.hip only, each of which instantiates aov_ladder for its precision, so no kernel is emitted twice.  Which
+// kernel runs -- the scene's residency, screening records or wrappers -- is residency.hpp's rule, the render's own.
 #pragma once
 #include "aov.hpp"
 
@@ -319,33 +320,17 @@ int32_t aov_variant(CrHandle* h, AovArgs<real>& a, size_t lds_bytes, const WalkC
     return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, false>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, false>(h, a, lds_bytes, res);
 }
 
-// walk_ladder's choices (render.hpp) for the guide kernels; the 6-waves-per-SIMD entry point has no counterpart here
+// The guide kernels' residency ladder: the rule walk_ladder asks (residency.hpp), so a guide pass stages what the render
+// stages; the 6-waves-per-SIMD entry point has no counterpart here, so the query's latency inputs stay at never
 template <typename real, bool ORD>
 int32_t aov_ladder_ord(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
-    constexpr bool f32 = std::is_same<real, float>::value;
-    constexpr bool can_screen = !(ORD && f32);   // an ordered f32 tree has no screening records
-    KernelArgs<real>& k = a.k;
-    if (ds.n_entries > 0 && (w.plain_lds || w.screen_lds)) {
-        k.lds_entries = ds.n_entries;
-        if constexpr (can_screen) if (w.screen_lds) return aov_variant<real, RES_LDS, ORD, true>(h, a, w.lds_all_screen, w, res);
-        k.screen = nullptr;
-        return aov_variant<real, RES_LDS, ORD, false>(h, a, ds.lds_bytes, w, res);
-    }
-    const size_t window_rec = w.screen ? sizeof(std::conditional_t<ORD, ScreenEntryO, ScreenEntry>) : sizeof(typename EntryOf<real, ORD>::type);
-    const int32_t top = (int32_t)std::min<size_t>((size_t)ds.n_entries, h->lds_top_bytes / window_rec);
-    if (top > 0) {
-        k.lds_entries = top;
-        size_t bytes = (size_t)top * window_rec;
-        if constexpr (!ORD) {
-            const size_t side = r16((size_t)ds.n_mats * sizeof(Mat<real>)) + r16((size_t)ds.n_texs * sizeof(Tex<real>));
-            if (side <= h->lds_side_limit) { k.lds_side = 1; bytes = r16(bytes) + side; }
-        }
-        if constexpr (can_screen) if (w.screen) return aov_variant<real, RES_TOP, ORD, true>(h, a, bytes, w, res);
-        return aov_variant<real, RES_TOP, ORD, false>(h, a, bytes, w, res);
-    }
-    k.lds_entries = 0;
-    if constexpr (can_screen) if (w.screen) return aov_variant<real, RES_GLOBAL, ORD, true>(h, a, 0, w, res);
-    return aov_variant<real, RES_GLOBAL, ORD, false>(h, a, 0, w, res);
+    const Residency r = choose_residency(residency_query<real, ORD>(h, ds, w));
+    a.k.lds_entries = r.lds_entries;
+    if (r.lds_side) a.k.lds_side = 1;
+    if (r.clear_screen) a.k.screen = nullptr;
+    return residency_dispatch<!(ORD && std::is_same<real, float>::value), false>(r, [&](auto rs, auto screen, auto) {
+        return aov_variant<real, decltype(rs)::value, ORD, decltype(screen)::value>(h, a, r.lds_bytes, w, res);
+    });
 }
 
 template <typename real>

@@ -8,7 +8,7 @@
 //   sah_device.hip     the device-side SAH builder of CR_BVH_BUILD_DEVICE (sah_device.hpp, hipcub)
 //   scene.hip          cr_upload_scene, refit.hpp's box kernels, the screening records, cr_update_primitives (update.hpp)
 //   render.hip         render_typed: a render's kernel arguments up to the choice of ladder; the stats epilogue
-//   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder)
+//   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder over residency.hpp's rule)
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
 //   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
@@ -180,7 +180,6 @@ struct CrHandle {
     size_t lds_side_limit = 16 * 1024;   // RES_TOP: materials + textures join the LDS window up to this size (CRUCIBLE_LDS_SIDE_KB; 0 = never)
     size_t lds_top_bytes = 128 * 1024;  // LDS spent on the top of a tree that does not fit whole (CRUCIBLE_LDS_TOP_KB; 0 = none): 4096 32-byte records
                                         // (f32 wrappers, or the f64 kernels' screening records) -- one 1024-thread workgroup per CU has the LDS to itself; teapot +2.5 %
-    bool lds_top_set = false;           // CRUCIBLE_LDS_TOP_KB given
     int blocks_per_cu_override = 0;
     int block_override = 0;
     // Wave scheduling of the walk (speed only).  -1 = chosen per scene: sphere scenes 10 / 56, scenes with triangles 8 / 40 --
@@ -222,7 +221,6 @@ inline void drop_frame_trees(CrHandle* h) {
     h->s32.last_walk = kWalkNone; h->s64.last_walk = kWalkNone;
 }
 
-inline size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline size_t real_size(int32_t real_type) { return real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float); }
 
 // CR_SUM_RELAXED's fixed-point scale 2^S for n samples per pixel: n * 2^S < 2^63, S = 52 up to 2047 samples
@@ -275,6 +273,25 @@ struct WalkChoice {
     bool screen_lds, plain_lds;     // the whole scene fits in LDS with screening records / with its wrappers
     size_t lds_all_screen;          // LDS bytes of the whole scene with screening records in the wrappers' place
 };
+
+// What a ladder asks residency.hpp's choose_residency about this tree on this handle.  The answer depends on the launch as
+// well where the 6-waves-per-SIMD entry point may run: walk_ladder fills whole_frame and adaptive in, the guide pass, which
+// has no such kernel, leaves them at never.
+template <typename real, bool ORD>
+ResidencyQuery residency_query(const CrHandle* h, const DevScene<real>& ds, const WalkChoice& w) {
+    constexpr bool f32 = std::is_same<real, float>::value;
+    ResidencyQuery q = {};
+    q.n_entries = ds.n_entries;
+    q.entry_rec = sizeof(typename EntryOf<real, ORD>::type); q.screen_rec = sizeof(typename ScreenOf<ORD>::type);
+    q.ordered = ORD; q.can_screen = !(ORD && f32);
+    q.screen = w.screen; q.screen_lds = w.screen_lds; q.plain_lds = w.plain_lds;
+    q.lds_bytes = ds.lds_bytes; q.lds_all_screen = w.lds_all_screen;
+    q.side_bytes = r16((size_t)ds.n_mats * sizeof(Mat<real>)) + r16((size_t)ds.n_texs * sizeof(Tex<real>));
+    q.lds_top_bytes = h->lds_top_bytes; q.lds_side_limit = h->lds_side_limit;
+    q.f32 = f32; q.latency_entries = h->latency_entries; q.latency_top_bytes = h->latency_top_bytes;
+    q.latency_slot_bytes = fx_lds_bytes(LatencyBlock, 4);
+    return q;
+}
 
 // build.hip
 template <typename real> int32_t build_dev_scene(CrHandle* h);

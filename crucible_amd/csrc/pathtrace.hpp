@@ -22,6 +22,7 @@
 #define CR_HD __host__ __device__ __forceinline__
 #define CR_D __device__ __forceinline__
 #include "fastdiv.hpp"
+#include "residency.hpp"   // RES_GLOBAL / RES_LDS / RES_TOP, where the scene is read from, and the rule that picks one
 
 namespace cr {
 
@@ -1123,10 +1124,6 @@ CR_D bool shade(const KernelArgs<real>& A, const Prim<real>* prims, const Mat<re
     }
     return true;
 }
-
-// Where the scene is read from: RES_GLOBAL everything through L2; RES_LDS entries | primitives |
-// materials | textures staged in LDS; RES_TOP only the first lds_entries wrappers (top levels) in LDS.
-enum : int { RES_GLOBAL = 0, RES_LDS = 1, RES_TOP = 2 };
 
 // RES_TOP reads a wrapper from the LDS window or from global memory.  A select between the two pointers compiles to
 // one flat_load, which is unordered against both counters (every use waits for vmcnt(0) and lgkmcnt(0)) and pays the

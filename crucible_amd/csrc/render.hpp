@@ -1,7 +1,8 @@
 // render.hpp -- the megakernel's host side for one precision and one sum order: launch() sets a pathtrace.hpp kernel up
-// and runs it, launch_variant() picks the kernel kind, walk_ladder() picks the scene's residency.  Included by the
-// render_*.hip units only, each of which instantiates walk_ladder (both tree orders) for its <real, RELAX>, so the
-// kernels of the four combinations compile side by side and no kernel is emitted twice.
+// and runs it, launch_variant() picks the kernel kind, walk_ladder() turns the scene's residency (residency.hpp's rule,
+// which the guide pass shares) into the kernel that stages it.  Included by the render_*.hip units only, each of which
+// instantiates walk_ladder (both tree orders) for its <real, RELAX>, so the kernels of the four combinations compile side
+// by side and no kernel is emitted twice.
 #pragma once
 #include "handle.hpp"
 
@@ -15,6 +16,24 @@ int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size
     HIP_TRY(h, hipGetLastError());
     return CR_OK;
 }
+
+#ifdef CR_DIAG
+// a build with -DCR_DIAG: the launch's clocks and DG_ counters, one line on stderr per render that asks for stats
+inline int32_t diag_dump(CrHandle* h, int block, uint32_t grid) {
+    uint64_t d[64];
+    HIP_TRY(h, hipMemcpy(d, h->counters.p, sizeof d, hipMemcpyDeviceToHost));
+    const char* names[] = {"box_wave", "box_lane", "prim_wave", "prim_lane", "round_wave", "round_lane", "leafph_wave", "leafph_lane",
+                           "shade_wave", "shade_lane", "lamb_lane", "metal_lane", "diel_lane", "sky_lane", "ruv_wave", "ruv_lane",
+                           "regen_wave", "regen_lane", "outer_wave", "unwind_wave", "unwind_lane", "hitsh_wave", "hitsh_lane", "band_wave", "band_lane",
+                           "root2_wave", "root2_lane", "quot_wave", "quot_lane", "quotdiv_wave", "quotdiv_lane"};
+    static_assert(sizeof names / sizeof names[0] == DG_N, "one name per DG_ counter");
+    fprintf(stderr, "[diag] block=%d grid=%u clk_regen=%llu clk_trace=%llu clk_shade=%llu clk_total=%llu", block, grid,
+            (unsigned long long)d[9], (unsigned long long)d[10], (unsigned long long)d[11], (unsigned long long)d[12]);
+    for (int i = 0; i < DG_N; i++) fprintf(stderr, " %s=%llu", names[i], (unsigned long long)d[16 + i]);
+    fprintf(stderr, "\n");
+    return CR_OK;
+}
+#endif
 
 // LIST: the passes of cr_render_adaptive_* -- pathtrace_kernel_listed, handed to adaptive_passes (adaptive.hip)
 template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool LIST = false>
@@ -33,7 +52,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     const int32_t n_samples = fb.ad ? fb.ad->pass_samples : args.sample_end - args.sample_begin;
     int tile_lw = h->sg_lw, tile_lh = h->sg_lh;
     if (fb.ad && (tile_lw > fb.ad->block_log2 || tile_lh > fb.ad->block_log2)) tile_lw = tile_lh = -1;
-    if (tile_lw < 0) { const int ns = n_samples >= 4 ? 4 : (n_samples >= 2 ? 2 : 1); tile_lw = ns == 4 ? 2 : 3; tile_lh = ns == 1 ? 3 : 2; }
+    if (tile_lw < 0) default_tile(n_samples, tile_lw, tile_lh);
     // RELAX: the waves' accumulator slots follow the scene in LDS (2 x 384 B per wave for a 16-pixel tile); a tile too
     // large for what the scene leaves free falls back to 16 pixels (the surplus sample slots of its groups stay empty)
     const size_t fx_off = RES != RES_GLOBAL ? ((scene_lds_bytes + 15) & ~(size_t)15) : 0;
@@ -61,7 +80,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         const size_t per_sample = npix * 3 * sizeof(real);
         batch = (int32_t)std::min<size_t>((size_t)(s_end - s_begin), RELAX ? (size_t)INT32_MAX : std::max<size_t>(1, h->sample_buf_limit / per_sample));
         int lw = tile_lw, lh = tile_lh;
-        if (!RELAX && h->sg_lw < 0) { const int ns = batch >= 4 ? 4 : (batch >= 2 ? 2 : 1); lw = ns == 4 ? 2 : 3; lh = ns == 1 ? 3 : 2; }   // by the batch, which the buffer may have cut
+        if (!RELAX && h->sg_lw < 0) default_tile(batch, lw, lh);   // by the batch, which the buffer may have cut
         const uint32_t ns = 64u >> (lw + lh);
         args.sg_lw = (uint32_t)lw; args.sg_lh = (uint32_t)lh;
         set_tiles(args, (args.reg_w + (1u << lw) - 1) >> lw, (args.reg_h + (1u << lh) - 1) >> lh);
@@ -114,6 +133,13 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         if (!fb.ad) HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, (size_t)fb.n * npix * 3 * sizeof(unsigned long long), h->stream));
     }
     HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
+    // one launch of the kernel on `args` as they stand: the work counter starts at zero
+    auto run = [&](uint32_t blocks) -> int32_t {
+        HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
+        HIP_TRY(h, hipGetLastError());
+        return CR_OK;
+    };
     if constexpr (LIST) {
         // cr_render_adaptive_*: the passes are adaptive_passes' (adaptive.hip), each one a launch of this kernel over the tiles
         // it names, into the accumulator it names; the counters add up over the passes
@@ -125,13 +151,8 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
             set_groups(args, groups_of(s1 - s0));
             args.sg_total = (uint32_t)((uint64_t)n_tiles * args.sg_groups * 64u);
             const uint32_t pass_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block));
-            const uint64_t per_wave = (uint64_t)args.sg_total / std::max<uint64_t>(1, (uint64_t)pass_grid * block / 64);   // the chunk: as below
-            const uint64_t c = h->sg_chunk_override > 0 ? (uint64_t)h->sg_chunk_override : std::min<uint64_t>(1024, std::max<uint64_t>(64, per_wave / 128));
-            args.sg_chunk = (uint32_t)((c + 63) / 64 * 64);
-            HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
-            hipLaunchKernelGGL(kern, dim3(pass_grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
-            HIP_TRY(h, hipGetLastError());
-            return CR_OK;
+            args.sg_chunk = work_chunk(args.sg_total, pass_grid, (uint64_t)block, h->sg_chunk_override);
+            return run(pass_grid);
         };
         const AdaptiveFrame fr = {args.cam.W, args.cam.H, args.samples_total, args.sg_lw, args.sg_lh, args.tiles_x, args.tiles_y, args.fx_scale,
                                   (void*)args.out, std::is_same<real, double>::value, args.n_entries, RES};
@@ -139,9 +160,8 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     }
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     if (!args.sg_on) {
-        HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
-        HIP_TRY(h, hipGetLastError());
+        int32_t rc = run(grid);
+        if (rc != CR_OK) return rc;
     } else {
         args.sample_buf = (real*)h->sample_buf.p;
         unsigned long long* const fx_frame0 = args.fx_acc;
@@ -158,16 +178,8 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
                 args.sample_begin = (int32_t)b0; args.sample_end = b1;
                 set_groups(args, groups_of(b1 - (int32_t)b0));
                 args.sg_total = (uint32_t)((uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn * args.sg_groups * 64u);
-                {   // 1024 items per atomic keeps the counter quiet on long launches; a short launch (a small frame, or one
-                    // GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most
-                    // 1/128 of its share
-                    const uint64_t per_wave = (uint64_t)args.sg_total / std::max<uint64_t>(1, (uint64_t)grid * block / 64);
-                    const uint64_t c = h->sg_chunk_override > 0 ? (uint64_t)h->sg_chunk_override : std::min<uint64_t>(1024, std::max<uint64_t>(64, per_wave / 128));
-                    args.sg_chunk = (uint32_t)((c + 63) / 64 * 64);
-                }
-                HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
-                HIP_TRY(h, hipGetLastError());
+                args.sg_chunk = work_chunk(args.sg_total, grid, (uint64_t)block, h->sg_chunk_override);
+                { int32_t rc = run(grid); if (rc != CR_OK) return rc; }
                 if constexpr (!RELAX) {   // (relaxed: the sums stay in fx_acc until the last batch)
                     const size_t fin_threads = ((size_t)args.tiles_x * args.tiles_y) << (args.sg_lw + args.sg_lh);
                     hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((fin_threads + 255) / 256)), dim3(256), 0, h->stream, args,
@@ -188,19 +200,8 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         int32_t rc = finish_stats(h, stats, (uint64_t)npix * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, RES);
         if (rc != CR_OK) return rc;
 #ifdef CR_DIAG
-        {
-            uint64_t d[64];
-            HIP_TRY(h, hipMemcpy(d, h->counters.p, sizeof d, hipMemcpyDeviceToHost));
-            const char* names[] = {"box_wave", "box_lane", "prim_wave", "prim_lane", "round_wave", "round_lane", "leafph_wave", "leafph_lane",
-                                   "shade_wave", "shade_lane", "lamb_lane", "metal_lane", "diel_lane", "sky_lane", "ruv_wave", "ruv_lane",
-                                   "regen_wave", "regen_lane", "outer_wave", "unwind_wave", "unwind_lane", "hitsh_wave", "hitsh_lane", "band_wave", "band_lane",
-                                   "root2_wave", "root2_lane", "quot_wave", "quot_lane", "quotdiv_wave", "quotdiv_lane"};
-            static_assert(sizeof names / sizeof names[0] == DG_N, "one name per DG_ counter");
-            fprintf(stderr, "[diag] block=%d grid=%u clk_regen=%llu clk_trace=%llu clk_shade=%llu clk_total=%llu", block, grid,
-                    (unsigned long long)d[9], (unsigned long long)d[10], (unsigned long long)d[11], (unsigned long long)d[12]);
-            for (int i = 0; i < DG_N; i++) fprintf(stderr, " %s=%llu", names[i], (unsigned long long)d[16 + i]);
-            fprintf(stderr, "\n");
-        }
+        rc = diag_dump(h, block, grid);
+        if (rc != CR_OK) return rc;
 #endif
     }
     return CR_OK;
@@ -221,43 +222,23 @@ int32_t launch_variant(CrHandle* h, const KernelArgs<real>& a, size_t lds_bytes,
     return launch<real, RES, false, ORD, LATENCY, false, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
 }
 
-// The residency ladder: the whole scene in LDS, else a window of the tree's top there (RES_TOP), else everything through
-// L2.  ORD: the near-child-first walk over EntryO / ScreenEntryO records.  What the tree orders really differ in: an ordered
-// f32 tree has no screening records (make_screen), so its SCREEN kernels do not exist; the window's record type; and
-// the side tables join the window on unordered trees only.
+// The residency ladder: residency.hpp's rule settles the residency, the window and whether the walk runs on screening
+// records (the whole scene in LDS, else a window of the tree's top there, else everything through L2); this is its answer
+// as a kernel.  ORD: the near-child-first walk over EntryO / ScreenEntryO records.
 template <typename real, bool ORD, bool RELAX>
 int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb) {
     constexpr bool f32 = std::is_same<real, float>::value;   // the double kernel needs far more than 80 VGPRs: it halves there
-    constexpr bool can_screen = !(ORD && f32);
-    if (ds.n_entries > 0 && (w.plain_lds || w.screen_lds)) {
-        a.lds_entries = ds.n_entries;
-        if constexpr (can_screen) if (w.screen_lds) return launch_variant<real, RES_LDS, ORD, false, RELAX, true>(h, a, w.lds_all_screen, stats, w, fb);
-        a.screen = nullptr;
-        return launch_variant<real, RES_LDS, ORD, false, RELAX>(h, a, ds.lds_bytes, stats, w, fb);
-    }
+    ResidencyQuery q = residency_query<real, ORD>(h, ds, w);
     // (the 6-waves-per-SIMD kernels render whole frames: a region of such a tree runs on the regular kernel, the same bytes)
-    const bool whole = !a.reg_x0 && !a.reg_y0 && a.reg_w == (uint32_t)a.cam.W && a.reg_h == (uint32_t)a.cam.H;
-    const bool latency = f32 && whole && !fb.ad && h->latency_entries > 0 && ds.n_entries > h->latency_entries;
-    // a window of screening records holds twice the wrappers
-    const size_t window_rec = w.screen ? sizeof(std::conditional_t<ORD, ScreenEntryO, ScreenEntry>) : sizeof(typename EntryOf<real, ORD>::type);
-    const int32_t top = (int32_t)std::min<size_t>((size_t)ds.n_entries, (latency ? h->latency_top_bytes : h->lds_top_bytes) / window_rec);
-    if (top > 0) {   // large scene: the top levels of the tree in LDS, everything else through L2
-        a.lds_entries = top;
-        size_t bytes = (size_t)top * window_rec;
-        if constexpr (!ORD) {   // materials and textures ride along when they are small (the tree can be large with two materials)
-            const size_t side = r16((size_t)ds.n_mats * sizeof(Mat<real>)) + r16((size_t)ds.n_texs * sizeof(Tex<real>));
-            // (the 6-waves-per-SIMD entry point runs three 512-thread groups per CU: window, side tables and the relaxed sums' slots of all three share 160 KB)
-            const size_t third = (size_t)160 * 1024 / 3 - 16, used = bytes + fx_lds_bytes(LatencyBlock, 4);
-            const size_t side_cap = latency ? (third > used ? third - used : 0) : h->lds_side_limit;
-            if (side <= std::min(h->lds_side_limit, side_cap)) { a.lds_side = 1; bytes = r16(bytes) + side; }
-        }
-        if constexpr (f32) if (latency) return launch_variant<real, RES_TOP, ORD, true, RELAX>(h, a, bytes, stats, w, fb);
-        if constexpr (can_screen) if (w.screen) return launch_variant<real, RES_TOP, ORD, false, RELAX, true>(h, a, bytes, stats, w, fb);
-        return launch_variant<real, RES_TOP, ORD, false, RELAX>(h, a, bytes, stats, w, fb);
-    }
-    a.lds_entries = 0;
-    if constexpr (can_screen) if (w.screen) return launch_variant<real, RES_GLOBAL, ORD, false, RELAX, true>(h, a, 0, stats, w, fb);
-    return launch_variant<real, RES_GLOBAL, ORD, false, RELAX>(h, a, 0, stats, w, fb);
+    q.whole_frame = !a.reg_x0 && !a.reg_y0 && a.reg_w == (uint32_t)a.cam.W && a.reg_h == (uint32_t)a.cam.H;
+    q.adaptive = fb.ad != nullptr;
+    const Residency r = choose_residency(q);
+    a.lds_entries = r.lds_entries;
+    if (r.lds_side) a.lds_side = 1;
+    if (r.clear_screen) a.screen = nullptr;
+    return residency_dispatch<!(ORD && f32), f32>(r, [&](auto res, auto screen, auto latency) {
+        return launch_variant<real, decltype(res)::value, ORD, decltype(latency)::value, RELAX, decltype(screen)::value>(h, a, r.lds_bytes, stats, w, fb);
+    });
 }
 
 // a unit's instantiations: the ladders of both tree orders, and with them every kernel of <real, RELAX>

@@ -1,0 +1,119 @@
+// residency.hpp -- how much of a scene a launch stages in LDS: one rule, choose_residency, for the render
+// kernels' ladder (render.hpp walk_ladder) and the guide kernels' (aov_kernel.hpp aov_ladder_ord), which only fill a query
+// and dispatch on the answer; and launch()'s two small rules, the work chunk and the default tile.  Free of the HIP runtime
+// and of the record types -- sizes arrive as numbers --, so that a plain C++ compiler can check it
+// (tests/residency_check.cpp), as it checks fastdiv.hpp, tree.hpp and adaptive.hpp.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#if !defined(CR_HD)          // a plain C++ compiler; the library defines it in pathtrace.hpp
+#define CR_HD inline
+#endif
+
+namespace cr {
+
+// Where the scene is read from: RES_GLOBAL everything through L2; RES_LDS entries | primitives |
+// materials | textures staged in LDS; RES_TOP only the first lds_entries wrappers (top levels) in LDS.
+enum : int { RES_GLOBAL = 0, RES_LDS = 1, RES_TOP = 2 };
+
+CR_HD size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+struct ResidencyQuery {
+    int32_t n_entries;
+    size_t entry_rec, screen_rec;        // bytes of one wrapper / one screening record of the tree's order
+    bool ordered;
+    bool can_screen;                     // false for an ordered f32 tree: it has no screening records, so no SCREEN kernels
+    bool screen, screen_lds, plain_lds;  // WalkChoice: walk on screening records; the whole scene fits with them / with its wrappers
+    size_t lds_bytes, lds_all_screen;    // LDS bytes of the whole scene with its wrappers / with screening records in their place
+    size_t side_bytes;                   // r16(materials) + r16(textures)
+    size_t lds_top_bytes, lds_side_limit;   // the handle's window and its limit for the side tables
+    // The 6-waves-per-SIMD entry point: f32 trees of more than latency_entries wrappers, whole frames outside adaptive runs,
+    // on a window of latency_top_bytes.  Its three 512-thread groups per CU share 160 KB: window, side tables and
+    // latency_slot_bytes of relaxed sums' slots each.  The guide pass leaves whole_frame false: never.
+    bool f32, whole_frame, adaptive;
+    int32_t latency_entries;
+    size_t latency_top_bytes, latency_slot_bytes;
+};
+
+struct Residency {
+    int res;               // RES_*
+    bool screen;           // a SCREEN kernel runs: the window (or the whole tree) holds screening records
+    bool latency;          // the 6-waves-per-SIMD entry point runs (RES_TOP only, never a SCREEN kernel)
+    int32_t lds_entries;   // records staged: all, the window's, none
+    int32_t lds_side;      // RES_TOP: materials and textures follow the window
+    size_t lds_bytes;      // the scene's LDS bytes
+    bool clear_screen;     // the plain RES_LDS kernel: the caller nulls its screening pointer
+};
+
+// The ladder: the whole scene in LDS, else a window of the tree's top there (RES_TOP), else everything through L2.  What
+// the tree orders differ in: an ordered f32 tree has no SCREEN kernels; the window's record size; and the side tables
+// join the window on unordered trees only.
+CR_HD Residency choose_residency(const ResidencyQuery& q) {
+    Residency r = {RES_GLOBAL, q.can_screen && q.screen, false, 0, 0, 0, false};
+    if (q.n_entries > 0 && (q.plain_lds || q.screen_lds)) {
+        r.res = RES_LDS;
+        r.lds_entries = q.n_entries;
+        r.screen = q.can_screen && q.screen_lds;
+        r.lds_bytes = r.screen ? q.lds_all_screen : q.lds_bytes;
+        r.clear_screen = !r.screen;
+        return r;
+    }
+    const bool latency = q.f32 && q.whole_frame && !q.adaptive && q.latency_entries > 0 && q.n_entries > q.latency_entries;
+    // a window of screening records holds twice the wrappers
+    const size_t window_rec = q.screen ? q.screen_rec : q.entry_rec;
+    const size_t fit = (latency ? q.latency_top_bytes : q.lds_top_bytes) / window_rec;
+    const int32_t top = (int32_t)((size_t)q.n_entries < fit ? (size_t)q.n_entries : fit);
+    if (top <= 0) return r;
+    // large scene: the top levels of the tree in LDS, everything else through L2
+    r.res = RES_TOP;
+    r.lds_entries = top;
+    r.latency = latency;
+    r.screen = r.screen && !latency;
+    r.lds_bytes = (size_t)top * window_rec;
+    if (!q.ordered) {   // materials and textures ride along when they are small (the tree can be large with two materials)
+        const size_t third = (size_t)160 * 1024 / 3 - 16, used = r.lds_bytes + q.latency_slot_bytes;
+        const size_t cap = latency ? (third > used ? third - used : 0) : q.lds_side_limit;
+        if (q.side_bytes <= (q.lds_side_limit < cap ? q.lds_side_limit : cap)) { r.lds_side = 1; r.lds_bytes = r16(r.lds_bytes) + q.side_bytes; }
+    }
+    return r;
+}
+
+// f(res, screen, latency) with the choice as std::integral_constant tags, so that a ladder names its kernel once.  Only
+// what choose_residency can answer is instantiated: SCREEN where CAN_SCREEN, latency where CAN_LATENCY and then RES_TOP
+// without SCREEN alone.
+template <bool CAN_SCREEN, bool CAN_LATENCY, typename F>
+auto residency_dispatch(const Residency& r, F&& f) {
+    using no = std::false_type;
+    auto by_screen = [&](auto res) {
+        if constexpr (CAN_SCREEN) if (r.screen) return f(res, std::true_type{}, no{});
+        return f(res, no{}, no{});
+    };
+    if (r.res == RES_LDS) return by_screen(std::integral_constant<int, RES_LDS>{});
+    if (r.res == RES_TOP) {
+        if constexpr (CAN_LATENCY) if (r.latency) return f(std::integral_constant<int, RES_TOP>{}, no{}, std::true_type{});
+        return by_screen(std::integral_constant<int, RES_TOP>{});
+    }
+    return by_screen(std::integral_constant<int, RES_GLOBAL>{});
+}
+
+// launch(): work items per atomic on the work counter.  1024 keeps the counter quiet on long launches; a short launch (a
+// small frame, or one GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most
+// 1/128 of its share, and at least one wave's round.  chunk_override: CRUCIBLE_SG_CHUNK.
+CR_HD uint32_t work_chunk(uint64_t sg_total, uint64_t grid, uint64_t block, int chunk_override) {
+    const uint64_t waves = grid * block / 64, per_wave = sg_total / (waves > 1 ? waves : 1);
+    const uint64_t share = per_wave / 128;
+    const uint64_t c = chunk_override > 0 ? (uint64_t)chunk_override : (share < 64 ? 64 : (share > 1024 ? 1024 : share));
+    return (uint32_t)((c + 63) / 64 * 64);
+}
+
+// launch(): the default work tile of 2^lw x 2^lh pixels times 64 >> (lw + lh) samples, by the samples n a launch renders:
+// 4 x 4 x 4, wider tiles of fewer samples when there are fewer than 4
+CR_HD void default_tile(int64_t n, int& lw, int& lh) {
+    lw = n >= 4 ? 2 : 3;
+    lh = n >= 2 ? 2 : 3;
+}
+
+}   // namespace cr

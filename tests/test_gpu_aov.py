@@ -246,6 +246,36 @@ def test_the_interval_starts_at_0_001(renderer, oracles, rt, tag):
     assert (got["depth"] < 0.02).any() and (got["depth"] > 1.0).any()
 
 
+@pytest.mark.parametrize("rt,tag", REALS, ids=[t for _, t in REALS])
+def test_the_guide_pass_stages_what_the_render_stages(hiplib, monkeypatch, rt, tag):
+    """The render's ladder and the guide pass's ask one rule (crucible_amd/csrc/residency.hpp): on a handle of each
+    residency -- the whole scene in LDS, a 1 KB window with and without the side tables, global memory, no screening
+    records -- the guide pass reports the render's scene_in_lds, and its planes are the default handle's bit for bit."""
+    from test_gpu_variants import GLOBAL, IN_LDS, NO_SCREEN, RES_GLOBAL, RES_LDS, RES_TOP, WINDOW, matrix_scene
+    sc = matrix_scene("static")
+    cam = sc.scene_cam
+    assert (cam.image_width, cam.image_height, cam.samples) == (24, 16, 3)
+    envs = [("default", {}, RES_LDS), ("window", WINDOW, RES_TOP), ("global", GLOBAL, RES_GLOBAL),
+            ("window, side tables in global memory", dict(WINDOW, CRUCIBLE_LDS_SIDE_KB="0"), RES_TOP), ("no screen", NO_SCREEN, RES_LDS)]
+    want = None
+    for name, env, res in envs:
+        with monkeypatch.context() as m:
+            for k, v in env.items():
+                m.setenv(k, v)
+            r = Renderer(0)   # the knobs are read in cr_create
+        try:
+            r.upload_scene(sc.flatten())
+            _, rst = r.render(cam, seed=SEED, real_type=rt)
+            got, st = r.render_aov(cam, seed=SEED, real_type=rt)
+        finally:
+            r.close()
+        assert st["scene_in_lds"] == rst["scene_in_lds"] == IN_LDS[res], (name, st["scene_in_lds"], rst["scene_in_lds"])
+        assert sorted(got) == sorted(NAMES)
+        if want is None:
+            want = got
+        same(got, want, name)
+
+
 # ---- layers and shards
 @pytest.mark.parametrize("rt,tag", REALS, ids=[t for _, t in REALS])
 def test_every_layer_mask_and_the_device_form(renderer, rt, tag):

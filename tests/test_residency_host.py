@@ -1,0 +1,166 @@
+"""crucible_amd/csrc/residency.hpp, the rule that settles how much of a scene a launch stages in LDS (shared by the render's
+walk_ladder and the guide pass's aov_ladder_ord) and launch()'s chunk and tile rules, checked without a device:
+tests/residency_check.cpp compiles the header with g++ (plain, and with -fsanitize=address,undefined) and prints the
+decision of each case.  The expected decisions below are written out by hand from the rule, not computed
+by a second copy of it: (res, screen, latency, lds_entries, lds_side, lds_bytes, clear_screen)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GLOBAL, LDS, TOP = 0, 1, 2
+
+# bytes of a wrapper record and of a screening record, per tree (an ordered f32 tree has no screening records and no SCREEN
+# kernels: can_screen is false there, and the ladder still hands the ordered screening record's size over)
+F64 = dict(entry_rec=64, screen_rec=32, ordered=0, can_screen=1, f32=0)
+F64_ORD = dict(entry_rec=96, screen_rec=64, ordered=1, can_screen=1, f32=0)
+F32 = dict(entry_rec=32, screen_rec=32, ordered=0, can_screen=1, f32=1)
+F32_ORD = dict(entry_rec=64, screen_rec=64, ordered=1, can_screen=0, f32=1)
+
+FIELDS = ("n_entries entry_rec screen_rec ordered can_screen screen screen_lds plain_lds lds_bytes lds_all_screen side_bytes "
+          "lds_top_bytes lds_side_limit f32 whole_frame adaptive latency_entries latency_top_bytes latency_slot_bytes").split()
+# a handle's defaults: a 128 KB window, side tables up to 16 KB, the 6-waves-per-SIMD entry point never (its window 48 KB,
+# its slots fx_lds_bytes(512, 4) = 6144); a whole frame outside an adaptive run; a tree too large for LDS, walked on its
+# screening records
+DEFAULTS = dict(screen=1, screen_lds=0, plain_lds=0, lds_bytes=9000, lds_all_screen=5800, side_bytes=0, lds_top_bytes=128 * 1024,
+                lds_side_limit=16 * 1024, whole_frame=1, adaptive=0, latency_entries=0, latency_top_bytes=48 * 1024, latency_slot_bytes=6144)
+
+
+def R(tree, n_entries, **kw):
+    q = dict(DEFAULTS, **tree)
+    q.update(kw, n_entries=n_entries)
+    assert sorted(q) == sorted(FIELDS)
+    return "R " + " ".join(str(int(q[k])) for k in FIELDS)
+
+
+@pytest.fixture(scope="module")
+def exes(tmp_path_factory):
+    out = tmp_path_factory.mktemp("residency_check")
+    built = []
+    for tag, extra in (("plain", ()), ("san", ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))):
+        exe = str(out / f"residency_check_{tag}")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "crucible_amd", "csrc"),
+                               "-o", exe, os.path.join(ROOT, "tests", "residency_check.cpp")])
+        built.append(exe)
+    return built
+
+
+def check(exes, tmp_path, cases):
+    """cases: (name, the case's line, the expected numbers); both builds print them."""
+    path = str(tmp_path / "cases.txt")
+    with open(path, "w") as f:
+        f.write("".join(line + "\n" for _, line, _ in cases))
+    outs = []
+    for exe in exes:
+        res = subprocess.run([exe, path], capture_output=True, timeout=120)
+        assert res.returncode == 0 and not res.stderr, (exe, res.returncode, res.stderr.decode())
+        outs.append(res.stdout.decode())
+    assert outs[0] == outs[1]
+    got = [tuple(int(x) for x in line.split()) for line in outs[0].splitlines()]
+    assert len(got) == len(cases)
+    for (name, _, want), g in zip(cases, got):
+        assert g == tuple(want), (name, g, want)
+
+
+def test_lds_row(exes, tmp_path):
+    check(exes, tmp_path, [
+        ("both fit: the screen wins", R(F64, 100, screen_lds=1, plain_lds=1), (LDS, 1, 0, 100, 0, 5800, 0)),
+        ("screen_lds off: the plain kernel, and the screening pointer goes", R(F64, 100, plain_lds=1), (LDS, 0, 0, 100, 0, 9000, 1)),
+        ("only the screen fits", R(F64, 100, screen_lds=1), (LDS, 1, 0, 100, 0, 5800, 0)),
+        ("ordered f64", R(F64_ORD, 100, screen_lds=1, plain_lds=1), (LDS, 1, 0, 100, 0, 5800, 0)),
+        ("no SCREEN kernels: plain even if screen_lds were set", R(F32_ORD, 100, screen_lds=1, plain_lds=1), (LDS, 0, 0, 100, 0, 9000, 1)),
+        ("the side tables are part of lds_bytes: lds_side stays 0", R(F32, 100, plain_lds=1, screen=0, side_bytes=64), (LDS, 0, 0, 100, 0, 9000, 1)),
+        ("the 6-waves-per-SIMD entry point is not asked", R(F32, 100, plain_lds=1, screen=0, latency_entries=1), (LDS, 0, 0, 100, 0, 9000, 1)),
+        ("no entries, everything fits: GLOBAL", R(F64, 0, screen=0, screen_lds=1, plain_lds=1), (GLOBAL, 0, 0, 0, 0, 0, 0)),
+        ("no entries, a window: GLOBAL", R(F64, 0, screen=0), (GLOBAL, 0, 0, 0, 0, 0, 0)),
+    ])
+
+
+def test_window_size(exes, tmp_path):
+    KB = dict(lds_top_bytes=1024)
+    check(exes, tmp_path, [
+        ("128 KB of 32-byte screening records", R(F64, 10000), (TOP, 1, 0, 4096, 1, 131072, 0)),
+        ("128 KB of 64-byte wrappers", R(F64, 10000, screen=0), (TOP, 0, 0, 2048, 1, 131072, 0)),
+        ("1 KB, f64 screen", R(F64, 10000, **KB), (TOP, 1, 0, 32, 1, 1024, 0)),
+        ("1 KB, f64 wrappers", R(F64, 10000, screen=0, **KB), (TOP, 0, 0, 16, 1, 1024, 0)),
+        ("1 KB, ordered f64 screen", R(F64_ORD, 10000, **KB), (TOP, 1, 0, 16, 0, 1024, 0)),
+        ("1 KB, ordered f64 wrappers: 10 of 96 bytes", R(F64_ORD, 10000, screen=0, **KB), (TOP, 0, 0, 10, 0, 960, 0)),
+        ("1 KB, f32", R(F32, 10000, **KB), (TOP, 1, 0, 32, 1, 1024, 0)),
+        ("1 KB, ordered f32: wrappers, no SCREEN kernel", R(F32_ORD, 10000, screen=0, **KB), (TOP, 0, 0, 16, 0, 1024, 0)),
+        ("a window below one record", R(F64, 10000, lds_top_bytes=31), (GLOBAL, 1, 0, 0, 0, 0, 0)),
+        ("exactly one record", R(F64, 10000, lds_top_bytes=32), (TOP, 1, 0, 1, 1, 32, 0)),
+        ("a tree below the window", R(F64, 5), (TOP, 1, 0, 5, 1, 160, 0)),
+    ])
+
+
+def test_side_tables(exes, tmp_path):
+    check(exes, tmp_path, [
+        ("at the limit: they join", R(F64, 10000, side_bytes=16384), (TOP, 1, 0, 4096, 1, 147456, 0)),
+        ("16 bytes over: they stay out", R(F64, 10000, side_bytes=16400), (TOP, 1, 0, 4096, 0, 131072, 0)),
+        ("limit 0", R(F64, 10000, side_bytes=16, lds_side_limit=0), (TOP, 1, 0, 4096, 0, 131072, 0)),
+        ("limit 0, no tables: 0 <= 0 joins", R(F64, 10000, side_bytes=0, lds_side_limit=0), (TOP, 1, 0, 4096, 1, 131072, 0)),
+        ("an ordered tree never takes them", R(F64_ORD, 10000, side_bytes=64), (TOP, 1, 0, 2048, 0, 131072, 0)),
+        ("an ordered tree, no tables", R(F64_ORD, 10000, side_bytes=0), (TOP, 1, 0, 2048, 0, 131072, 0)),
+        # (every record size of the library is a multiple of 16; 40 bytes shows the rounding: 25 records, 1000 -> 1008 bytes)
+        ("the window is rounded up to 16 before they follow", R(dict(F64, entry_rec=40), 10000, screen=0, lds_top_bytes=1024, side_bytes=32),
+         (TOP, 0, 0, 25, 1, 1040, 0)),
+        ("no rounding without them", R(dict(F64, entry_rec=40), 10000, screen=0, lds_top_bytes=1024, side_bytes=32, lds_side_limit=16),
+         (TOP, 0, 0, 25, 0, 1000, 0)),
+    ])
+
+
+def test_latency(exes, tmp_path):
+    small = dict(latency_entries=1, latency_top_bytes=1024)     # two 32-byte records: used = 64 + 6144, cap = 54597 - 6208 = 48389
+    large = dict(latency_entries=1000)                          # 48 KB: 1536 records, used = 49152 + 6144 = 55296 > 54597, cap 0
+    mid = dict(latency_entries=1000, latency_top_bytes=40960)   # 1280 records, used = 47104, cap = 7493
+    check(exes, tmp_path, [
+        ("on: two records", R(F32, 2, **small), (TOP, 0, 1, 2, 1, 64, 0)),
+        ("the handle's limit binds", R(F32, 2, side_bytes=16384, **small), (TOP, 0, 1, 2, 1, 16448, 0)),
+        ("over the handle's limit", R(F32, 2, side_bytes=16400, **small), (TOP, 0, 1, 2, 0, 64, 0)),
+        ("never a SCREEN kernel, with or without w.screen", R(F32, 2, screen=0, **small), (TOP, 0, 1, 2, 1, 64, 0)),
+        ("ordered: no side tables", R(F32_ORD, 2, screen=0, **small), (TOP, 0, 1, 2, 0, 128, 0)),
+        ("48 KB: 1536 records, cap 0, no tables join", R(F32, 100000, **large), (TOP, 0, 1, 1536, 1, 49152, 0)),
+        ("48 KB: cap 0, any table stays out", R(F32, 100000, side_bytes=16, **large), (TOP, 0, 1, 1536, 0, 49152, 0)),
+        ("40 KB: the share of 160 KB binds, 7488 <= 7493", R(F32, 100000, side_bytes=7488, **mid), (TOP, 0, 1, 1280, 1, 48448, 0)),
+        ("40 KB: 7504 > 7493", R(F32, 100000, side_bytes=7504, **mid), (TOP, 0, 1, 1280, 0, 40960, 0)),
+        ("its window holds no record: GLOBAL on the regular kernel", R(F32, 100000, latency_entries=1000, latency_top_bytes=31), (GLOBAL, 1, 0, 0, 0, 0, 0)),
+        # off: the handle's own window (128 KB) and the regular kernels
+        ("off: n == latency_entries", R(F32, 2, latency_entries=2, latency_top_bytes=1024), (TOP, 1, 0, 2, 1, 64, 0)),
+        ("off: a region", R(F32, 100000, whole_frame=0, **large), (TOP, 1, 0, 4096, 1, 131072, 0)),
+        ("off: an adaptive run", R(F32, 100000, adaptive=1, **large), (TOP, 1, 0, 4096, 1, 131072, 0)),
+        ("off: f64", R(F64, 100000, **large), (TOP, 1, 0, 4096, 1, 131072, 0)),
+        ("off: latency_entries = 0", R(F32, 100000, latency_entries=0), (TOP, 1, 0, 4096, 1, 131072, 0)),
+        ("off: the guide pass (no whole frame, not adaptive)", R(F32, 2, whole_frame=0, **small), (TOP, 1, 0, 2, 1, 64, 0)),
+    ])
+
+
+def test_global_row(exes, tmp_path):
+    none = dict(lds_top_bytes=0)
+    check(exes, tmp_path, [
+        ("screen", R(F64, 10000, **none), (GLOBAL, 1, 0, 0, 0, 0, 0)),
+        ("no screen", R(F64, 10000, screen=0, **none), (GLOBAL, 0, 0, 0, 0, 0, 0)),
+        ("ordered f64", R(F64_ORD, 10000, **none), (GLOBAL, 1, 0, 0, 0, 0, 0)),
+        ("f32", R(F32, 10000, **none), (GLOBAL, 1, 0, 0, 0, 0, 0)),
+        ("no SCREEN kernels, whatever w.screen says", R(F32_ORD, 10000, screen=1, **none), (GLOBAL, 0, 0, 0, 0, 0, 0)),
+        ("the side tables do not matter", R(F64, 10000, side_bytes=64, **none), (GLOBAL, 1, 0, 0, 0, 0, 0)),
+    ])
+
+
+def test_chunk_and_tile(exes, tmp_path):
+    check(exes, tmp_path, [
+        ("the override wins, rounded to whole rounds", "C 1000000 256 256 100", (128,)),
+        ("the override wins over the clamp", "C 1000000 256 256 4096", (4096,)),
+        ("lower clamp: 6400 items over 40 waves, 160 / 128 = 1", "C 6400 10 256 0", (64,)),
+        ("upper clamp: 2^30 items over 4096 waves, 262144 / 128 = 2048", "C 1073741824 256 1024 0", (1024,)),
+        ("just inside: 131072 items over one wave, 1024", "C 131072 1 64 0", (1024,)),
+        ("rounding: 51200 items over 4 waves, 12800 / 128 = 100", "C 51200 1 256 0", (128,)),
+        ("a multiple of 64 stays: 24576 / 128 = 192", "C 24576 1 64 0", (192,)),
+        ("grid * block < 64 counts as one wave: 25600 / 128 = 200", "C 25600 1 32 0", (256,)),
+        ("no work", "C 0 1 256 0", (64,)),
+        ("1 sample: 8 x 8", "T 1", (3, 3)),
+        ("2 samples: 8 x 4", "T 2", (3, 2)),
+        ("3 samples: 8 x 4", "T 3", (3, 2)),
+        ("4 samples: 4 x 4", "T 4", (2, 2)),
+        ("many samples: 4 x 4", "T 2147483647", (2, 2)),
+    ])
