@@ -1,5 +1,6 @@
-// adaptive.hip -- cr_render_adaptive_* (include/crucible_hip.h): a frame whose blocks of pixels stop taking
-// samples once their two half-frame sums agree.  The entry points' checks, the pass loop around the render kernel that
+// adaptive.hip -- cr_render_adaptive_* and cr_render_adaptive_frames_* (include/crucible_hip.h): a frame,
+// or a batch of frames under one pass loop, whose blocks of pixels stop taking samples once their two half-frame sums
+// agree.  The entry points' checks, the pass loop around the render kernel that
 // launch() (render.hpp) hands over, the judge kernel (one wave per block: the difference sum, the verdict, the next list
 // of active tiles) and the finalize kernel (per-pixel means by each block's own sample count, the count plane).
 #include "handle.hpp"
@@ -8,26 +9,33 @@
 namespace cr {
 
 struct JudgeArgs {
-    const unsigned long long* E;
+    const unsigned long long* E;         // frame f's sums at f * frame_words, in both
     const unsigned long long* O;
+    size_t frame_words;                  // W * H * 3
     int32_t W, H;
-    uint32_t block_log2, n_blocks;
+    uint32_t block_log2, n_blocks;       // n_blocks: of one frame
+    uint32_t n_frames;                   // the pass loop's frames: n_frames * n_blocks blocks, frame after frame (adaptive_batch_block)
     uint32_t lw, lh, tiles_x, tiles_y;   // the render kernel's tiles: their sides divide the block's
     double tolerance, scale12;           // scale12 = 2^(S - 12)
     uint32_t qp;                         // q * P: the samples in each half
     int32_t n;                           // samples per pixel taken so far (2 q P)
-    int32_t* block_n;                    // per block: 0 while active, else the sample count it stopped at
-    int32_t* next_list;                  // tiles of the blocks that stay active, tiles_x * tiles_y slots
+    int32_t* block_n;                    // per block of every frame: 0 while active, else the sample count it stopped at
+    int32_t* next_list;                  // tiles of the blocks that stay active (batch-wide numbers), n_frames * tiles_x * tiles_y slots
     uint32_t* cursor;                    // slots of next_list in use: the active tiles the host reads back
 };
 
 // One wave per block.  An active block's D_b is an integer sum, so the order of the wave's reduction does not matter; a
 // block that stays active appends its tiles to the next list at a range it takes from the one cursor (the order of the
-// list varies from run to run; nothing observable depends on it).
+// list varies from run to run; nothing observable depends on it).  A block sees its own frame's sums and nothing else, so
+// its verdict does not depend on the frames it shares the launch with.
 __global__ void __launch_bounds__(256) adaptive_judge_kernel(const JudgeArgs a) {
-    const uint32_t b = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
-    if (b >= a.n_blocks) return;
-    if (a.block_n[b] != 0) return;   // stopped earlier: final
+    const uint32_t g = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (g >= a.n_frames * a.n_blocks) return;
+    if (a.block_n[g] != 0) return;   // stopped earlier: final
+    uint32_t f, b;
+    adaptive_batch_block(g, a.n_blocks, f, b);
+    const unsigned long long* const E = a.E + (size_t)f * a.frame_words;
+    const unsigned long long* const O = a.O + (size_t)f * a.frame_words;
     uint32_t x0, y0, bw, bh;
     adaptive_block_rect(a.W, a.H, a.block_log2, b, x0, y0, bw, bh);
     const uint32_t row_words = bw * 3u, words = row_words * bh;
@@ -35,35 +43,36 @@ __global__ void __launch_bounds__(256) adaptive_judge_kernel(const JudgeArgs a) 
     for (uint32_t k = lane; k < words; k += 64u) {
         const uint32_t row = k / row_words, col = k - row * row_words;
         const size_t i = ((size_t)(y0 + row) * (size_t)a.W + x0) * 3 + col;   // y0 + row < H, x0 * 3 + col < W * 3
-        d += adaptive_term(a.E[i], a.O[i]);
+        d += adaptive_term(E[i], O[i]);
     }
     for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off);
     if (adaptive_stops(d, adaptive_threshold(a.tolerance, a.scale12, a.qp, bw * bh))) {
-        if (lane == 0) a.block_n[b] = a.n;
+        if (lane == 0) a.block_n[g] = a.n;
         return;
     }
-    // the block's tiles inside the frame's tile grid (blocks and tiles are both anchored at pixel (0, 0))
-    const uint32_t tx0 = x0 >> a.lw, ty0 = y0 >> a.lh, B = 1u << a.block_log2;
-    const uint32_t tw = min(B >> a.lw, a.tiles_x - tx0), th = min(B >> a.lh, a.tiles_y - ty0), cnt = tw * th;
+    // the block's tiles inside its frame's rows of the batch's tile grid
+    uint32_t tx0, ty0, tw, th;
+    adaptive_block_tiles(x0, y0, a.block_log2, a.lw, a.lh, a.tiles_x, a.tiles_y, tx0, ty0, tw, th);
+    const uint32_t cnt = tw * th;
     uint32_t base = 0;
     if (lane == 0) base = atomicAdd(a.cursor, cnt);
     base = (uint32_t)__shfl((int)base, 0);
-    // the blocks partition the tile grid, so base + cnt <= tiles_x * tiles_y, the list's size
-    for (uint32_t k = lane; k < cnt; k += 64u) {
-        const uint32_t r = k / tw;
-        a.next_list[base + k] = (int32_t)((ty0 + r) * a.tiles_x + tx0 + (k - r * tw));
-    }
+    // the blocks partition each frame's tile grid, so base + cnt <= n_frames * tiles_x * tiles_y, the list's size
+    for (uint32_t k = lane; k < cnt; k += 64u) a.next_list[base + k] = (int32_t)adaptive_block_tile(f, a.tiles_x, a.tiles_y, tx0, ty0, tw, k);
 }
 
 // ((mag(E) + mag(O)) * 2^-S) / n_b in fx_finalize_kernel's arithmetic, NaN where either flag is set; the count plane.
+// n_frames frames, one after the other in E, O, out and counts; block_n holds n_blocks words per frame.
 template <typename real>
 __global__ void __launch_bounds__(256) adaptive_finalize_kernel(const unsigned long long* E, const unsigned long long* O, const int32_t* block_n,
-                                                                real* out, int32_t* counts, int32_t W, int32_t H, uint32_t block_log2,
-                                                                int32_t samples, double inv_scale) {
+                                                                real* out, int32_t* counts, int32_t W, int32_t H, uint32_t n_frames, uint32_t n_blocks,
+                                                                uint32_t block_log2, int32_t samples, double inv_scale) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)W * (size_t)H * 3) return;
-    const uint32_t px = (uint32_t)(i / 3), y = px / (uint32_t)W, x = px - y * (uint32_t)W;
-    const int32_t stopped = block_n[(y >> block_log2) * adaptive_blocks_x(W, block_log2) + (x >> block_log2)];
+    const size_t frame_pix = (size_t)W * (size_t)H;
+    if (i >= (size_t)n_frames * frame_pix * 3) return;
+    const size_t gp = i / 3, f = gp / frame_pix;
+    const uint32_t px = (uint32_t)(gp - f * frame_pix), y = px / (uint32_t)W, x = px - y * (uint32_t)W;
+    const int32_t stopped = block_n[f * n_blocks + (y >> block_log2) * adaptive_blocks_x(W, block_log2) + (x >> block_log2)];
     const int32_t n = stopped ? stopped : samples;   // still active at the end: all of them
     const unsigned long long e = E[i], o = O[i];
     const unsigned long long m = (e & ~kFxNaN) + (o & ~kFxNaN);   // below 2^63: the sums of at most `samples` samples
@@ -71,7 +80,7 @@ __global__ void __launch_bounds__(256) adaptive_finalize_kernel(const unsigned l
     s = s / (double)n;
     if ((e | o) & kFxNaN) s = __builtin_nan("");
     out[i] = (real)s;
-    if (counts && i == (size_t)px * 3) counts[px] = n;
+    if (counts && i == gp * 3) counts[gp] = n;
 }
 
 static int32_t elapsed_into(CrHandle* h, hipEvent_t a, hipEvent_t b, double& sum) {
@@ -82,26 +91,23 @@ static int32_t elapsed_into(CrHandle* h, hipEvent_t a, hipEvent_t b, double& sum
     return CR_OK;
 }
 
-int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame& fr, const AdaptivePass& pass) {
+// what the pass loops of one call add up to (CrAdaptiveStats)
+struct AdaptiveTotals {
+    uint64_t samples = 0;
+    int32_t passes = 0, blocks = 0, stopped = 0;
+    double render_ms = 0, judge_ms = 0;
+};
+
+// One pass loop: frames [f0, f0 + fn) of the call, whose tiles fit one launch's work counter together.  The frames' sums
+// live in the handle's accumulators (E of the fn frames, then O), their means go to the frames' slice of the output.
+static int32_t adaptive_pass_loop(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame& fr, const AdaptivePass& pass, int32_t f0, int32_t fn,
+                                  AdaptiveTotals& tot) {
     const uint32_t L = (uint32_t)run.block_log2;
-    if (fr.lw > L || fr.lh > L) return fail(h, CR_ERR_UNSUPPORTED, "the work tile does not divide the adaptive block");
     const int32_t P = run.pass_samples, S = fr.samples;
-    const size_t words = (size_t)fr.W * (size_t)fr.H * 3;
-    const uint32_t n_tiles = fr.tiles_x * fr.tiles_y;
-    const uint32_t bx_n = adaptive_blocks_x(fr.W, L), n_blocks = bx_n * adaptive_blocks_y(fr.H, L);
-    auto need = [&](DevBuf& buf, size_t bytes, const char* what) -> int32_t {
-        const hipError_t e = buf.ensure(bytes);
-        if (e == hipSuccess) return CR_OK;
-        (void)hipGetLastError();
-        return fail(h, CR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
+    const size_t frame_pix = (size_t)fr.W * (size_t)fr.H, frame_words = frame_pix * 3, words = (size_t)fn * frame_words;
+    const uint32_t n_tiles = (uint32_t)fn * fr.tiles_x * fr.tiles_y;   // (fits: launch() sized the loop by the 32-bit work counter)
+    const uint32_t frame_blocks = adaptive_blocks_x(fr.W, L) * adaptive_blocks_y(fr.H, L), n_blocks = (uint32_t)fn * frame_blocks;
     int32_t rc;
-    if ((rc = need(h->ad_acc, 2 * words * sizeof(unsigned long long), "adaptive accumulators")) != CR_OK) return rc;
-    if ((rc = need(h->ad_lists, 2 * (size_t)n_tiles * sizeof(int32_t), "adaptive tile lists")) != CR_OK) return rc;
-    if ((rc = need(h->ad_block_n, (size_t)n_blocks * sizeof(int32_t), "adaptive block counts")) != CR_OK) return rc;
-    if ((rc = need(h->ad_ctrl, 16, "adaptive cursor")) != CR_OK) return rc;
-    if (!h->ad_ev0) HIP_TRY(h, hipEventCreate(&h->ad_ev0));
-    if (!h->ad_ev1) HIP_TRY(h, hipEventCreate(&h->ad_ev1));
     unsigned long long* const E = (unsigned long long*)h->ad_acc.p;
     unsigned long long* const O = E + words;
     int32_t* const lists = (int32_t*)h->ad_lists.p;
@@ -111,21 +117,20 @@ int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame
     int exp2 = 0;
     (void)std::frexp(fr.fx_scale, &exp2);   // fx_scale = 2^(exp2 - 1)
     JudgeArgs ja;
-    ja.E = E; ja.O = O; ja.W = fr.W; ja.H = fr.H; ja.block_log2 = L; ja.n_blocks = n_blocks;
+    ja.E = E; ja.O = O; ja.frame_words = frame_words; ja.W = fr.W; ja.H = fr.H; ja.block_log2 = L; ja.n_blocks = frame_blocks; ja.n_frames = (uint32_t)fn;
     ja.lw = fr.lw; ja.lh = fr.lh; ja.tiles_x = fr.tiles_x; ja.tiles_y = fr.tiles_y;
     ja.tolerance = run.tolerance; ja.scale12 = std::ldexp(1.0, exp2 - 1 - 12);
     ja.block_n = (int32_t*)h->ad_block_n.p; ja.cursor = (uint32_t*)h->ad_ctrl.p;
 
     const int32_t* list = nullptr;   // the first passes render every tile, in order
     uint32_t active = n_tiles;
-    int cur = 0, passes = 0;
-    double render_ms = 0, judge_ms = 0;
+    int cur = 0;
     bool span_open = false;          // ev0 .. ev1 spans the render launches since the last judgement
     for (int32_t n = 0, q = 1; n < S && active > 0; q++) {
         if (!span_open) { HIP_TRY(h, hipEventRecord(h->ev0, h->stream)); span_open = true; }
-        if ((rc = pass(list, active, n, n + P, E)) != CR_OK) return rc;
-        if ((rc = pass(list, active, n + P, n + 2 * P, O)) != CR_OK) return rc;
-        n += 2 * P; passes += 2;
+        if ((rc = pass(f0, fn, list, active, n, n + P, E)) != CR_OK) return rc;
+        if ((rc = pass(f0, fn, list, active, n + P, n + 2 * P, O)) != CR_OK) return rc;
+        n += 2 * P; tot.passes += 2;
         if (n < run.min_samples || n >= S) continue;
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
         span_open = false;
@@ -139,41 +144,71 @@ int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame
         uint32_t left = 0;
         HIP_TRY(h, hipMemcpyAsync(&left, h->ad_ctrl.p, 4, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (left > n_tiles) return fail(h, CR_ERR_HIP, "adaptive judge: more active tiles than the frame has");
-        if ((rc = elapsed_into(h, h->ev0, h->ev1, render_ms)) != CR_OK) return rc;
-        if ((rc = elapsed_into(h, h->ad_ev0, h->ad_ev1, judge_ms)) != CR_OK) return rc;
+        if (left > n_tiles) return fail(h, CR_ERR_HIP, "adaptive judge: more active tiles than the frames have");
+        if ((rc = elapsed_into(h, h->ev0, h->ev1, tot.render_ms)) != CR_OK) return rc;
+        if ((rc = elapsed_into(h, h->ad_ev0, h->ad_ev1, tot.judge_ms)) != CR_OK) return rc;
         list = next; cur ^= 1; active = left;
     }
     if (span_open) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     HIP_TRY(h, hipEventRecord(h->ad_ev0, h->stream));
-    const unsigned fin_grid = (unsigned)((words + 255) / 256);
+    const unsigned fin_grid = (unsigned)((words + 255) / 256);   // (E and O exist: 16 bytes per word, so far fewer than 2^39 words)
     const double inv_scale = 1.0 / fr.fx_scale;
-    if (fr.f64) hipLaunchKernelGGL((adaptive_finalize_kernel<double>), dim3(fin_grid), dim3(256), 0, h->stream, E, O, ja.block_n, (double*)fr.out, run.d_counts,
-                                   fr.W, fr.H, L, S, inv_scale);
-    else hipLaunchKernelGGL((adaptive_finalize_kernel<float>), dim3(fin_grid), dim3(256), 0, h->stream, E, O, ja.block_n, (float*)fr.out, run.d_counts,
-                            fr.W, fr.H, L, S, inv_scale);
+    int32_t* const counts = run.d_counts ? run.d_counts + (size_t)f0 * frame_pix : nullptr;
+    if (fr.f64) hipLaunchKernelGGL((adaptive_finalize_kernel<double>), dim3(fin_grid), dim3(256), 0, h->stream, E, O, ja.block_n,
+                                   (double*)fr.out + (size_t)f0 * frame_words, counts, fr.W, fr.H, (uint32_t)fn, frame_blocks, L, S, inv_scale);
+    else hipLaunchKernelGGL((adaptive_finalize_kernel<float>), dim3(fin_grid), dim3(256), 0, h->stream, E, O, ja.block_n,
+                            (float*)fr.out + (size_t)f0 * frame_words, counts, fr.W, fr.H, (uint32_t)fn, frame_blocks, L, S, inv_scale);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipEventRecord(h->ad_ev1, h->stream));
     std::vector<int32_t> block_n(n_blocks);
     HIP_TRY(h, hipMemcpyAsync(block_n.data(), h->ad_block_n.p, (size_t)n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (span_open && (rc = elapsed_into(h, h->ev0, h->ev1, render_ms)) != CR_OK) return rc;
-    if ((rc = elapsed_into(h, h->ad_ev0, h->ad_ev1, judge_ms)) != CR_OK) return rc;
-    if (!run.stats) return CR_OK;
-    uint64_t samples = 0;
-    int32_t stopped = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) {
-        uint32_t x0, y0, bw, bh;
+    if (span_open && (rc = elapsed_into(h, h->ev0, h->ev1, tot.render_ms)) != CR_OK) return rc;
+    if ((rc = elapsed_into(h, h->ad_ev0, h->ad_ev1, tot.judge_ms)) != CR_OK) return rc;
+    for (uint32_t g = 0; g < n_blocks; g++) {
+        uint32_t f, b, x0, y0, bw, bh;
+        adaptive_batch_block(g, frame_blocks, f, b);
         adaptive_block_rect(fr.W, fr.H, L, b, x0, y0, bw, bh);
-        samples += (uint64_t)bw * bh * (uint64_t)(block_n[b] ? block_n[b] : S);
-        stopped += block_n[b] != 0;
+        tot.samples += (uint64_t)bw * bh * (uint64_t)(block_n[g] ? block_n[g] : S);
+        tot.stopped += block_n[g] != 0;
     }
+    tot.blocks += (int32_t)n_blocks;
+    return CR_OK;
+}
+
+// The pass loops of one call: one over all frames where a pass over all their tiles fits the work counter
+// (fr.frames_per_launch, launch()'s arithmetic), else consecutive ones over as many whole frames as do.
+int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame& fr, const AdaptivePass& pass) {
+    const uint32_t L = (uint32_t)run.block_log2;
+    if (fr.lw > L || fr.lh > L) return fail(h, CR_ERR_UNSUPPORTED, "the work tile does not divide the adaptive block");
+    const int32_t cap = std::max(1, std::min(fr.frames_per_launch, fr.n_frames));   // frames per pass loop
+    const size_t words = (size_t)cap * (size_t)fr.W * (size_t)fr.H * 3;
+    const size_t n_tiles = (size_t)cap * fr.tiles_x * fr.tiles_y;
+    const size_t n_blocks = (size_t)cap * adaptive_blocks_x(fr.W, L) * adaptive_blocks_y(fr.H, L);
+    auto need = [&](DevBuf& buf, size_t bytes, const char* what) -> int32_t {
+        const hipError_t e = buf.ensure(bytes);
+        if (e == hipSuccess) return CR_OK;
+        (void)hipGetLastError();
+        return fail(h, CR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    };
+    int32_t rc;
+    if ((rc = need(h->ad_acc, 2 * words * sizeof(unsigned long long), "adaptive accumulators")) != CR_OK) return rc;
+    if ((rc = need(h->ad_lists, 2 * n_tiles * sizeof(int32_t), "adaptive tile lists")) != CR_OK) return rc;
+    if ((rc = need(h->ad_block_n, n_blocks * sizeof(int32_t), "adaptive block counts")) != CR_OK) return rc;
+    if ((rc = need(h->ad_ctrl, 16, "adaptive cursor")) != CR_OK) return rc;
+    if (!h->ad_ev0) HIP_TRY(h, hipEventCreate(&h->ad_ev0));
+    if (!h->ad_ev1) HIP_TRY(h, hipEventCreate(&h->ad_ev1));
+    AdaptiveTotals tot;
+    for (int32_t f0 = 0; f0 < fr.n_frames; f0 += cap)
+        if ((rc = adaptive_pass_loop(h, run, fr, pass, f0, std::min(cap, fr.n_frames - f0), tot)) != CR_OK) return rc;
+    if (!run.stats) return CR_OK;
     CrAdaptiveStats* st = run.stats;
     memset(st, 0, sizeof *st);
-    if ((rc = finish_stats(h, &st->render, samples, fr.n_entries, fr.scene_in_lds)) != CR_OK) return rc;
-    st->render.kernel_ms = render_ms;   // (finish_stats saw the last run of passes only: the sum over all of them)
-    st->judge_ms = judge_ms;
-    st->passes = passes; st->blocks = (int32_t)n_blocks; st->blocks_stopped = stopped;
+    // (the work counters add up over every launch of the call; finish_stats' time is the last run of passes only)
+    if ((rc = finish_stats(h, &st->render, tot.samples, fr.n_entries, fr.scene_in_lds)) != CR_OK) return rc;
+    st->render.kernel_ms = tot.render_ms;
+    st->judge_ms = tot.judge_ms;
+    st->passes = tot.passes; st->blocks = tot.blocks; st->blocks_stopped = tot.stopped;
     return CR_OK;
 }
 
@@ -200,19 +235,59 @@ static int32_t validate_adaptive(CrHandle* h, const CrCameraDesc* cam, const CrR
     return CR_OK;
 }
 
-static int32_t adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* d_out, int32_t* d_counts,
-                               CrAdaptiveStats* stats) {
+// frames == nullptr: the one frame params->frame; else the batch `frames` (cr_render_adaptive_frames_*)
+static int32_t adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
+                               int32_t n_frames, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
     HIP_TRY(h, hipSetDevice(h->device));
     const AdaptiveRun run = {ap->min_samples, ap->pass_samples, ap->block_log2 ? ap->block_log2 : 4, ap->tolerance, d_counts, stats};
     h->cam_pending_slot = -1;
-    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, nullptr, nullptr, 1, nullptr, &run)
-                                             : render_typed<float>(h, cam, p, d_out, nullptr, nullptr, 1, nullptr, &run);
+    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, nullptr, frames, n_frames, nullptr, &run)
+                                             : render_typed<float>(h, cam, p, d_out, nullptr, frames, n_frames, nullptr, &run);
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
         const hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
         h->cam_pending_slot = -1;
         if (e != hipSuccess && rc == CR_OK) { h->error = std::string("hipEventRecord: ") + hipGetErrorString(e); rc = CR_ERR_HIP; }
     }
     return rc;
+}
+
+// cr_render_adaptive_host / cr_render_adaptive_frames_host: render into the handle's buffers, copy back, check the means frame by frame
+static int32_t adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
+                             int32_t n_frames, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n_pix = (size_t)cam->image_width * (size_t)cam->image_height, frame_bytes = n_pix * 3 * real_size(p->real_type);
+    const size_t bytes = frame_bytes * (size_t)n_frames, count_bytes = n_pix * (size_t)n_frames * sizeof(int32_t);
+    hipError_t e = h->out_buf.ensure(bytes);
+    if (e == hipSuccess && h_counts) e = h->ad_counts.ensure(count_bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
+    int32_t rc = adaptive_device(h, cam, p, ap, frames, n_frames, h->out_buf.p, h_counts ? (int32_t*)h->ad_counts.p : nullptr, stats);
+    if (rc != CR_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h_counts) HIP_TRY(h, hipMemcpyAsync(h_counts, h->ad_counts.p, count_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    uint64_t bad = 0;
+    int32_t first_bad = -1;
+    for (int32_t k = 0; k < n_frames; k++) {
+        const uint64_t b = bad_pixels((const char*)h_out + (size_t)k * frame_bytes, p->real_type, n_pix);
+        if (b && first_bad < 0) first_bad = k;
+        bad += b;
+    }
+    if (stats) stats->render.nan_pixels = bad;
+    if (bad && !frames) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+    if (bad)
+        return fail(h, CR_ERR_NAN, "frame " + std::to_string(frames[first_bad]) + " (entry " + std::to_string(first_bad) +
+                                       " of the batch): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+    return CR_OK;
+}
+
+// the checks of cr_render_adaptive_frames_*: a single call's, then the batch's own
+static int32_t validate_adaptive_frames(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
+                                        int32_t n_frames, const void* out) {
+    const int32_t rc = validate_adaptive(h, cam, p, ap, out);
+    if (rc != CR_OK) return rc;
+    if (!frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
+    if (n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
+    return CR_OK;
 }
 
 }   // namespace cr
@@ -224,27 +299,25 @@ extern "C" {
 int32_t cr_render_adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* d_out,
                                   int32_t* d_counts, CrAdaptiveStats* stats) {
     const int32_t rc = validate_adaptive(h, cam, p, ap, d_out);
-    return rc != CR_OK ? rc : adaptive_device(h, cam, p, ap, d_out, d_counts, stats);
+    return rc != CR_OK ? rc : adaptive_device(h, cam, p, ap, nullptr, 1, d_out, d_counts, stats);
 }
 
 int32_t cr_render_adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* h_out,
                                 int32_t* h_counts, CrAdaptiveStats* stats) {
-    int32_t rc = validate_adaptive(h, cam, p, ap, h_out);
-    if (rc != CR_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n_pix = (size_t)cam->image_width * (size_t)cam->image_height, bytes = n_pix * 3 * real_size(p->real_type);
-    hipError_t e = h->out_buf.ensure(bytes);
-    if (e == hipSuccess && h_counts) e = h->ad_counts.ensure(n_pix * sizeof(int32_t));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
-    rc = adaptive_device(h, cam, p, ap, h->out_buf.p, h_counts ? (int32_t*)h->ad_counts.p : nullptr, stats);
-    if (rc != CR_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (h_counts) HIP_TRY(h, hipMemcpyAsync(h_counts, h->ad_counts.p, n_pix * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const uint64_t bad = bad_pixels(h_out, p->real_type, n_pix);
-    if (stats) stats->render.nan_pixels = bad;
-    if (bad) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
-    return CR_OK;
+    const int32_t rc = validate_adaptive(h, cam, p, ap, h_out);
+    return rc != CR_OK ? rc : adaptive_host(h, cam, p, ap, nullptr, 1, h_out, h_counts, stats);
+}
+
+int32_t cr_render_adaptive_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                         const int32_t* frames, int32_t n_frames, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
+    const int32_t rc = validate_adaptive_frames(h, cam, p, ap, frames, n_frames, d_out);
+    return rc != CR_OK ? rc : adaptive_device(h, cam, p, ap, frames, n_frames, d_out, d_counts, stats);
+}
+
+int32_t cr_render_adaptive_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                       const int32_t* frames, int32_t n_frames, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
+    const int32_t rc = validate_adaptive_frames(h, cam, p, ap, frames, n_frames, h_out);
+    return rc != CR_OK ? rc : adaptive_host(h, cam, p, ap, frames, n_frames, h_out, h_counts, stats);
 }
 
 }   // extern "C"

@@ -39,6 +39,26 @@ CR_HD void adaptive_block_rect(int32_t W, int32_t H, uint32_t block_log2, uint32
     bw = (uint32_t)W - x0 < B ? (uint32_t)W - x0 : B;
     bh = (uint32_t)H - y0 < B ? (uint32_t)H - y0 : B;
 }
+// A batch of frames (cr_render_adaptive_frames_*): the judge numbers the blocks of all frames in one row,
+// frame after frame -- global block g is block b of frame f ...
+CR_HD void adaptive_batch_block(uint32_t g, uint32_t n_blocks, uint32_t& f, uint32_t& b) { f = g / n_blocks; b = g - f * n_blocks; }
+// ... and names a tile as the render kernel's batch does: frame f owns the tile rows [f * tiles_y, (f + 1) * tiles_y)
+CR_HD uint32_t adaptive_batch_tile(uint32_t f, uint32_t tiles_x, uint32_t tiles_y, uint32_t tx, uint32_t ty) { return (f * tiles_y + ty) * tiles_x + tx; }
+// The tiles of 2^lw x 2^lh pixels (lw, lh <= block_log2; tiles_x x tiles_y of them cover the frame) of the block whose
+// first pixel is (x0, y0): tw columns from tx0, th rows from ty0.  Blocks and tiles are both anchored at pixel (0, 0),
+// so the blocks' tiles partition the tile grid.
+CR_HD void adaptive_block_tiles(uint32_t x0, uint32_t y0, uint32_t block_log2, uint32_t lw, uint32_t lh, uint32_t tiles_x, uint32_t tiles_y,
+                                uint32_t& tx0, uint32_t& ty0, uint32_t& tw, uint32_t& th) {
+    const uint32_t B = 1u << block_log2;
+    tx0 = x0 >> lw; ty0 = y0 >> lh;
+    tw = (B >> lw) < tiles_x - tx0 ? (B >> lw) : tiles_x - tx0;
+    th = (B >> lh) < tiles_y - ty0 ? (B >> lh) : tiles_y - ty0;
+}
+// the k-th (row by row) of those tw * th tiles, as frame f's batch-wide tile number
+CR_HD uint32_t adaptive_block_tile(uint32_t f, uint32_t tiles_x, uint32_t tiles_y, uint32_t tx0, uint32_t ty0, uint32_t tw, uint32_t k) {
+    const uint32_t r = k / tw;
+    return adaptive_batch_tile(f, tiles_x, tiles_y, tx0 + (k - r * tw), ty0 + r);
+}
 // does a block with difference sum d stop?
 CR_HD bool adaptive_stops(uint64_t d, uint64_t t) { return d <= t; }
 

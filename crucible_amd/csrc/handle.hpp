@@ -12,7 +12,7 @@
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
 //   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
-//   adaptive.hip       cr_render_adaptive_*: the pass loop, the judge and finalize kernels (adaptive.hpp)
+//   adaptive.hip       cr_render_adaptive_*, cr_render_adaptive_frames_*: the pass loop, the judge and finalize kernels (adaptive.hpp)
 //   api.hip            cr_create / cr_destroy, cr_render_*, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
 #pragma once
 #include "../../include/crucible_hip.h"
@@ -140,7 +140,8 @@ struct CrHandle {
     DevBuf aov_acc, aov_flags;   // cr_render_aov_*: per pixel 8 x u64 (albedo, normal, coverage sums; depth) and the channels' NaN bits
     DevBuf fx_acc;               // CR_SUM_RELAXED: per-pixel fixed-point sums (3 x u64 per pixel; per frame of a batch)
     // cr_render_adaptive_* (adaptive.hip): the two half-frame accumulators E and O (relaxed sums, apart from fx_acc), the two
-    // tile lists, each block's final sample count, the judge's cursor, the count plane of the host form; the judge's events
+    // tile lists, each block's final sample count, the judge's cursor, the count plane of the host form; the judge's events.
+    // cr_render_adaptive_frames_*: of all frames of a pass loop -- E of every frame, then O of every frame
     DevBuf ad_acc, ad_lists, ad_block_n, ad_ctrl, ad_counts;
     hipEvent_t ad_ev0 = nullptr, ad_ev1 = nullptr;
     // cr_render_frames_*: a batch's per-frame ray times travel through one pinned host buffer, refilled only after the
@@ -250,20 +251,23 @@ template <typename real> struct FrameBatch {
 struct AdaptiveRun {
     int32_t min_samples, pass_samples, block_log2;
     double tolerance;
-    int32_t* d_counts;          // may be null
+    int32_t* d_counts;          // may be null; frame after frame
     CrAdaptiveStats* stats;     // may be null
 };
-// ... and what launch() settled: the frame, the render kernel's tile shape and tile counts, the scale of the sums
+// ... and what launch() settled: the frame, the render kernel's tile shape and tile counts, the scale of the sums; of a
+// batch (cr_render_adaptive_frames_*) the frame count and how many whole frames one launch's work counter holds
 struct AdaptiveFrame {
     int32_t W, H, samples;
+    int32_t n_frames, frames_per_launch;
     uint32_t lw, lh, tiles_x, tiles_y;
     double fx_scale;
     void* out;
     bool f64;
     int32_t n_entries, scene_in_lds;
 };
-// one launch of the render kernel: samples [s0, s1) of the n_tiles tiles `tile_list` names (nullptr: all, in order) into `acc`
-using AdaptivePass = std::function<int32_t(const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc)>;
+// one launch of the render kernel over frames [f0, f0 + fn) of the batch: samples [s0, s1) of the n_tiles tiles `tile_list`
+// names (batch-wide numbers, frame f0 first; nullptr: all, in order) into `acc` (frame f0's sums first)
+using AdaptivePass = std::function<int32_t(int32_t f0, int32_t fn, const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc)>;
 int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame& fr, const AdaptivePass& pass);
 
 // What render_typed settled before the residency ladder (render.hpp)

@@ -177,7 +177,8 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
 
 // One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*), or the
 // pixels `region` of one frame (cr_render_region_*, whose entry has checked the sum order and the pipeline), or one frame to
-// a noise target (cr_render_adaptive_*, whose entry has checked the same: `adaptive`, adaptive.hip).
+// a noise target (cr_render_adaptive_*, whose entry has checked the same: `adaptive`, adaptive.hip), or a batch of frames
+// to one (cr_render_adaptive_frames_*: `adaptive` with `frames`; a batch's rules hold, refit boxes among them).
 template <typename real>
 int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames,
                      const CrRegion* region, const AdaptiveRun* adaptive) {

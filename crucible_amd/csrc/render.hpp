@@ -145,16 +145,19 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         // it names, into the accumulator it names; the counters add up over the passes
         if (!args.sg_on) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
         h->last_block = block; h->last_grid = (int)grid;
-        const AdaptivePass pass = [&](const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc) -> int32_t {
+        // (cr_render_adaptive_frames_*: a pass loop's frames [f0, f0 + fn) of the batch, at most fpl, as the loop below sets them)
+        const AdaptivePass pass = [&](int32_t f0, int32_t fn, const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc) -> int32_t {
             args.tile_list = tile_list; args.sample_begin = s0; args.sample_end = s1; args.fx_acc = acc;
-            args.n_frames = 1; args.frame_times = nullptr;
+            args.n_frames = (uint32_t)fn;
+            args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
+            args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
             set_groups(args, groups_of(s1 - s0));
             args.sg_total = (uint32_t)((uint64_t)n_tiles * args.sg_groups * 64u);
             const uint32_t pass_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block));
             args.sg_chunk = work_chunk(args.sg_total, pass_grid, (uint64_t)block, h->sg_chunk_override);
             return run(pass_grid);
         };
-        const AdaptiveFrame fr = {args.cam.W, args.cam.H, args.samples_total, args.sg_lw, args.sg_lh, args.tiles_x, args.tiles_y, args.fx_scale,
+        const AdaptiveFrame fr = {args.cam.W, args.cam.H, args.samples_total, fb.n, fpl, args.sg_lw, args.sg_lh, args.tiles_x, args.tiles_y, args.fx_scale,
                                   (void*)args.out, std::is_same<real, double>::value, args.n_entries, RES};
         return adaptive_passes(h, *fb.ad, fr, pass);
     }

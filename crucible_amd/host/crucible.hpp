@@ -451,8 +451,8 @@ public:
     // A frame to a noise target (cr_render_adaptive_host): scene_cam.samples is the maximum per pixel, blocks of `block`
     // pixels square stop once their two half-frame means differ by at most `tolerance` on average (include/crucible_hip.h has
     // the exact rule).  render_frame then keeps the samples each pixel took and the call's stats; sample_map = true has
-    // render_image write the counts as <frame>.samples.pfm.  Whole frames on one device, one call per frame of a movie; needs
-    // relaxed sums.
+    // render_image and render_movie_frames write the counts as <frame>.samples.pfm.  Whole frames on one device; a movie with
+    // frames_per_launch > 1 renders each batch under one pass loop (cr_render_adaptive_frames_host).  Needs relaxed sums.
     bool has_adaptive = false, sample_map = false;
     CrAdaptiveParams adaptive = {0, 0, 0, 0, 0.0};
     mutable std::vector<int32_t> adaptive_counts;
@@ -642,6 +642,29 @@ public:
         buf.resize((size_t)scene_cam.image_width * scene_cam.image_height * 3 * frs.size());
         return cr_render_frames_host(h, &cd, &p, frs.data(), (int32_t)frs.size(), buf.data(), stats);
     }
+    // The frames `frs` to the noise target in one call (cr_render_adaptive_frames_host): frame k at k * W*H*3 reals in `buf`,
+    // its counts at k * W*H in `counts`; the call's stats stay in adaptive_stats.
+    int32_t render_adaptive_frames(CrHandle* h, std::vector<double>& buf, std::vector<int32_t>& counts, const std::vector<int32_t>& frs, CrStats* stats) const {
+        std::vector<CrKeyframe> fk, ak;
+        CrCameraDesc cd = camera_desc(fk, ak);
+        CrRenderParams p = render_params(0);   // the frame indices come from frs
+        const size_t n_pix = (size_t)scene_cam.image_width * scene_cam.image_height;
+        buf.resize(n_pix * 3 * frs.size());
+        counts.resize(n_pix * frs.size());
+        CrAdaptiveStats as;
+        memset(&as, 0, sizeof as);
+        const int32_t rc = cr_render_adaptive_frames_host(h, &cd, &p, &adaptive, frs.data(), (int32_t)frs.size(), buf.data(), counts.data(), &as);
+        if (rc != CR_OK) return rc;   // (a refused batch leaves the last call's stats)
+        adaptive_stats = as;
+        if (stats) *stats = as.render;
+        return rc;
+    }
+    // <fname>.samples.pfm: the samples each pixel of an adaptive frame took, one f32 channel
+    int32_t write_sample_map(const std::string& fname, const int32_t* counts) const {
+        const size_t n_pix = (size_t)scene_cam.image_width * scene_cam.image_height;
+        const std::vector<float> map(counts, counts + n_pix);
+        return cr_write_pfm((fname + ".samples.pfm").c_str(), map.data(), CR_REAL_F32, (int32_t)scene_cam.image_width, (int32_t)scene_cam.image_height, 1);
+    }
     // Guide layers (cr_render_aov_host): the planes of `aov_layers` for the frame, one after the other, into `buf`.
     int32_t aov_layers = 0;   // CR_AOV_* mask: > 0 writes <frame>.<layer>.pfm next to every frame file
     size_t aov_reals() const {
@@ -697,10 +720,7 @@ public:
         double t1 = now_ms();
         timing.render_ms += t1 - t0;
         if (rc == CR_OK) { rc = write_frame(fname, buf); timing.write_ms += now_ms() - t1; timing.frames++; }
-        if (rc == CR_OK && has_adaptive && sample_map) {   // the samples each pixel took, one f32 channel
-            const std::vector<float> map(adaptive_counts.begin(), adaptive_counts.end());
-            rc = cr_write_pfm((fname + ".samples.pfm").c_str(), map.data(), CR_REAL_F32, (int32_t)scene_cam.image_width, (int32_t)scene_cam.image_height, 1);
-        }
+        if (rc == CR_OK && has_adaptive && sample_map) rc = write_sample_map(fname, adaptive_counts.data());
         if (rc == CR_OK && aov_layers) {
             std::vector<double> planes(aov_reals());
             rc = render_aov(h, planes.data());
@@ -721,8 +741,9 @@ public:
         return rc;
     }
     // render_movie (scene/mod.rs:295-322) for the frames first, first + step, ... on one handle, frames_per_launch of
-    // them per call (cr_render_frames_host; a library that refuses the batch -- reference order, refit boxes -- gets one
-    // frame per call, the same files; the batch's guide layers come from one cr_render_aov_frames_host call either way,
+    // them per call (cr_render_frames_host, or cr_render_adaptive_frames_host for frames to a noise target; a library that
+    // refuses the batch -- reference order, refit boxes -- gets one frame per call, the same files, the <frame>.samples.pfm
+    // of sample_map among them; the batch's guide layers come from one cr_render_aov_frames_host call either way,
     // unless the library refuses that one too -- refit boxes -- and gets one cr_render_aov_host call per frame).  Batch b is encoded and written by a helper thread while batch b+1 renders (two
     // buffers; SURVEY 8(f) row 3 -- the reference formats and writes each frame before starting the next).  render_ms:
     // time this thread spent inside renders; write_ms: time the helper threads spent encoding and writing (overlapped,
@@ -730,12 +751,13 @@ public:
     int32_t render_movie_frames(CrHandle* h, const std::string& fname, size_t first, size_t step, size_t frames, size_t digits,
                                 CrStats* stats, Timing* tm) const {
         std::vector<double> bufs[2], guides[2];   // guides: the batch's guide planes, frame after frame
+        std::vector<int32_t> maps[2];             // an adaptive batch's counts, frame after frame
         std::thread writers[2];
         int32_t write_rc[2] = {CR_OK, CR_OK};
         double write_ms[2] = {0, 0};
         int32_t rc = CR_OK;
         // (a region: one region call per frame, the batch calls take whole frames)
-        bool batched = frames_per_launch > 1 && !has_region && !has_adaptive, guides_batched = frames_per_launch > 1 && !has_region;
+        bool batched = frames_per_launch > 1 && !has_region, guides_batched = frames_per_launch > 1 && !has_region;
         const size_t rs = real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float);
         size_t k = 0;
         for (size_t fr = first; rc == CR_OK && fr < frames; k++) {
@@ -747,18 +769,21 @@ public:
             memset(&st, 0, sizeof st);
             const double t0 = now_ms();
             double kernel_ms = 0;
+            const size_t n_pix = (size_t)scene_cam.image_width * scene_cam.image_height;
             if (batched) {
-                rc = render_frames(h, bufs[slot], batch, &st);
+                rc = has_adaptive ? render_adaptive_frames(h, bufs[slot], maps[slot], batch, &st) : render_frames(h, bufs[slot], batch, &st);
                 kernel_ms = st.kernel_ms;
                 if (rc == CR_ERR_UNSUPPORTED) batched = false;
             }
             if (!batched) {   // one frame per call into the batch's buffer (a batch of several: its guide layers still share a call)
                 std::vector<double> one;
                 bufs[slot].resize((frame_bytes() * batch.size() + sizeof(double) - 1) / sizeof(double));
+                if (has_adaptive) maps[slot].resize(n_pix * batch.size());
                 rc = CR_OK;
                 for (size_t i = 0; i < batch.size() && rc == CR_OK; i++) {
                     rc = render_frame(h, one, &st, (int64_t)batch[i]);
                     if (rc == CR_OK) { memcpy((char*)bufs[slot].data() + i * frame_bytes(), one.data(), frame_bytes()); kernel_ms += st.kernel_ms; }
+                    if (rc == CR_OK && has_adaptive) std::copy(adaptive_counts.begin(), adaptive_counts.end(), maps[slot].begin() + (ptrdiff_t)(i * n_pix));
                 }
             }
             if (tm) { tm->render_ms += now_ms() - t0; tm->kernel_ms += kernel_ms; tm->frames += batch.size(); }
@@ -785,11 +810,12 @@ public:
                 stems.push_back(fname + "/artifacts/image" + std::string(digits - num.size(), '0') + num);
             }
             fr = (size_t)batch.back() + step;
-            writers[slot] = std::thread([this, stems, slot, &bufs, &guides, &write_rc, &write_ms] {
+            writers[slot] = std::thread([this, stems, slot, n_pix, &bufs, &guides, &maps, &write_rc, &write_ms] {
                 const double w0 = now_ms();
                 const size_t guide_bytes = aov_reals() * (real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float));
                 for (size_t i = 0; i < stems.size() && write_rc[slot] == CR_OK; i++) {
                     write_rc[slot] = write_frame(stems[i], (const char*)bufs[slot].data() + i * frame_bytes());
+                    if (write_rc[slot] == CR_OK && has_adaptive && sample_map) write_rc[slot] = write_sample_map(stems[i], maps[slot].data() + i * n_pix);
                     if (write_rc[slot] == CR_OK && aov_layers) write_rc[slot] = write_aov(stems[i], (const char*)guides[slot].data() + i * guide_bytes);
                 }
                 write_ms[slot] += now_ms() - w0;

@@ -16,7 +16,7 @@
 // --adaptive tol[,min[,pass[,block]]] (render to a noise target through cr_render_adaptive_host: --samples is the maximum per pixel,
 // blocks of `block` pixels square (8, 16, 32; default 16) stop once their two half-frame means differ by at most tol on average,
 // judged every 2 * pass samples (default 8) from min samples on (default 4 * pass); needs relaxed sums and whole frames on one
-// device; a movie renders frame by frame; --sample-map also writes <frame>.samples.pfm, the samples each pixel took; --timing
+// device; a movie renders --frames-per-launch frames per cr_render_adaptive_frames_host call; --sample-map also writes <frame>.samples.pfm, the samples each pixel took; --timing
 // adds the passes, the blocks stopped and the samples taken),
 // --repeat N --timing (measurement: render_scene N times in this process, one JSON line of wall-clock phases each --
 // the shape of the reference's criterion benchmark, benches/renderer_benchmark.rs:16-42 -- the first is the cold one).

@@ -339,6 +339,39 @@ class Renderer:
                                                        C.byref(st) if want_stats else None))
         return st.as_dict()
 
+    def render_adaptive_frames(self, cam, frames, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples, pass_samples, block=16,
+                               want_counts=True, want_stats=True, sum_order=None):
+        """cr_render_adaptive_frames_host: the frames `frames` (frame indices; cam.frame is not used) to a noise target
+        under one pass loop -- a pass renders the active tiles of all frames in one launch.  Frame k and its counts are
+        render_adaptive() at frame frames[k] bit for bit.  Returns (images (n, H, W, 3), counts (n, H, W) int32 or None,
+        stats dict of the whole call, shaped like render_adaptive's)."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
+        ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
+        fr, fr_ptr = frame_list(frames)
+        out = np.empty((max(1, fr.size), cam.image_height, cam.image_width, 3), dtype=np_real(real_type))
+        counts = np.empty((max(1, fr.size), cam.image_height, cam.image_width), dtype=np.int32) if want_counts else None
+        st = A.CrAdaptiveStats()
+        self._check(self.lib.cr_render_adaptive_frames_host(self.h, C.byref(cd), C.byref(p), C.byref(ap), fr_ptr, fr.size,
+                                                            out.ctypes.data_as(C.c_void_p),
+                                                            counts.ctypes.data_as(C.c_void_p) if want_counts else None,
+                                                            C.byref(st) if want_stats else None))
+        return out, counts, st.as_dict()
+
+    def render_adaptive_frames_device(self, cam, frames, d_ptr, d_counts=None, *, seed, real_type=A.CR_REAL_F32, tolerance,
+                                      min_samples, pass_samples, block=16, want_stats=True, sum_order=None):
+        """cr_render_adaptive_frames_device: the frames into device memory at `d_ptr` (n*W*H*3 reals, frame after frame)
+        and, if given, the counts at `d_counts` (n*W*H int32).  Synchronous.  Returns the stats dict of render_adaptive."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
+        ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
+        fr, fr_ptr = frame_list(frames)
+        st = A.CrAdaptiveStats()
+        self._check(self.lib.cr_render_adaptive_frames_device(self.h, C.byref(cd), C.byref(p), C.byref(ap), fr_ptr, fr.size,
+                                                              C.c_void_p(d_ptr), C.c_void_p(d_counts) if d_counts else None,
+                                                              C.byref(st) if want_stats else None))
+        return st.as_dict()
+
     def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
         """cr_fixed_sums_to_rgb: summed CR_OUTPUT_FIXED_SUM words of a whole frame (device pointer, W*H*3 uint64) ->
         its per-pixel means at device pointer `d_out` (W*H*3 reals), exactly the relaxed frame.  Asynchronous on the

@@ -480,7 +480,8 @@ class Scene:
         self.frames_per_launch = 1   # render_movie: N > 1 renders N frames per call through Renderer.render_frames
         self.aov_layers = 0          # CR_AOV_* mask or layer names: writes <frame>.<layer>.pfm next to every frame file
         # set_adaptive: frames to a noise target through Renderer.render_adaptive (scene_cam.samples is the maximum per
-        # pixel; needs relaxed sums; a movie renders frame by frame); sample_map also writes <frame>.samples.pfm
+        # pixel; needs relaxed sums; a movie with frames_per_launch > 1 renders its batches through
+        # Renderer.render_adaptive_frames); sample_map also writes <frame>.samples.pfm
         self.adaptive = None
         self.sample_map = False
 
@@ -720,20 +721,24 @@ class Scene:
             r.upload_scene(self.flatten())
             n = max(1, int(self.frames_per_launch))
             # the frames and the guide layers of a batch each come from one call, until the library refuses that call
-            # (frames: reference order or refit boxes; guide layers: refit boxes): then one call per frame, the same files
+            # (frames: reference order or refit boxes; guide layers: refit boxes): then one call per frame, the same files.
+            # Adaptive frames batch the same way (Renderer.render_adaptive_frames: one pass loop for the batch's frames)
             batched = guides_batched = n > 1
-            if self.adaptive is not None:
-                batched = False   # an adaptive frame is one call
+            from .renderer import write_pfm
             cam = self.scene_cam
             frame = 0
             while frame < frames:
                 # the camera's frame counter for each file, as the one-frame loop advances it
                 first = cam.frame
                 batch = [first + k for k in range(min(n, frames - frame) if batched or (layers and guides_batched) else 1)]
-                imgs = None
+                imgs = maps = None
                 if batched:
                     try:
-                        imgs, _ = r.render_frames(cam, batch, seed=self.seed, real_type=self.real_type)
+                        if self.adaptive is not None:
+                            imgs, maps, _ = r.render_adaptive_frames(cam, batch, seed=self.seed, real_type=self.real_type,
+                                                                     want_counts=self.sample_map, **self.adaptive)
+                        else:
+                            imgs, _ = r.render_frames(cam, batch, seed=self.seed, real_type=self.real_type)
                     except CrucibleError as e:
                         if e.code != A.CR_ERR_UNSUPPORTED:
                             raise
@@ -750,6 +755,8 @@ class Scene:
                     cam.frame = f
                     stem = os.path.join(fname, "artifacts", f"image{frame:0{digits}d}")
                     img = imgs[k] if imgs is not None else self._render_frame(r, stem)[0]
+                    if maps is not None:
+                        write_pfm(stem + ".samples.pfm", maps[k].astype("float32"))
                     r.write_ppm(stem + ".ppm", img)
                     if layers:
                         self._write_aov(stem, guides[k] if guides is not None else

@@ -631,6 +631,53 @@ CR_API int32_t cr_render_adaptive_device(CrHandle* h, const CrCameraDesc* cam, c
 CR_API int32_t cr_render_adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
                                        const CrAdaptiveParams* adaptive, void* h_out_rgb, int32_t* h_counts, CrAdaptiveStats* stats);
 
+/*
+ * A batch of movie frames to a noise target, under one pass loop: what cr_render_frames_device is to cr_render_device,
+ * for cr_render_adaptive_device.
+ *
+ * Frames.  frames[k] is the frame index params->frame would carry; params->frame itself is ignored.  Any list works:
+ * consecutive, strided, descending, repeated (a repeated frame has its own accumulators and gives the same bytes twice).
+ * Output.  n_frames consecutive frames, frame k at k * image_width*image_height*3 reals.  `counts` may be NULL, else it
+ * receives n_frames * image_width*image_height int32_t, frame k at k * image_width*image_height.
+ * Bit-exactness.  Frame k and its counts are BIT FOR BIT what cr_render_adaptive_device writes for the same camera,
+ * params and adaptive params with frame = frames[k]: in f32 and f64, for every bvh_mode and residency, at any
+ * params->samples (the single call uses the same scale 2^S, so this includes S < 52).  The stopping rule is per block
+ * and in exact integers, so a frame does not depend on the frames it shares its launches with.
+ *
+ * The pass loop.  One loop serves the whole batch: pass p renders the samples [pP, (p+1)P) of the active tiles of all
+ * frames in one launch (even passes into E, odd into O), a judged pair judges every active block of every frame in one
+ * judge launch, and one 4-byte read-back gives the batch's active-tile count.  The loop ends when no tile of any frame is
+ * active, or at params->samples; a frame whose blocks have all stopped simply has no tile in the list any more.
+ *
+ * stats, over the whole call: render's counters and samples are summed over the frames, kernel_ms over all passes;
+ * passes is the number of launches of the render kernel; blocks and blocks_stopped are summed over the frames;
+ * bvh_entries and scene_in_lds are as for one frame.
+ *
+ * Memory.  The handle keeps 48 bytes per pixel per frame (E of all frames, then O of all frames), two tile lists of the
+ * batch's tile count and one word per block per frame; all of it grows on demand, and a batch too large for device
+ * memory is CR_ERR_HIP.
+ * Work counter.  One pass over all tiles of the batch must fit the launch's 32-bit work counter.  A batch that does not
+ * fit runs as consecutive sub-batches of whole frames, each its own pass loop writing its slice of the output (the
+ * memory above is then a sub-batch's): the frames' bytes are unchanged by the split, and passes adds up over the
+ * sub-batches.  A frame that alone does not fit is refused exactly as cr_render_adaptive_device refuses it.
+ *
+ * Refusals, all checked before anything changes (a refused call leaves the handle as it was).  CR_ERR_INVALID_ARG:
+ * everything cr_render_adaptive_device refuses, with the same codes, plus a null `frames` or n_frames < 1.
+ * CR_ERR_UNSUPPORTED: what cr_render_adaptive_device answers so, and a call that would refit or rebuild boxes --
+ * refit_boxes with keyed primitives or HitList elements, or CR_REFIT_REBUILD where it would build: boxes are per
+ * frame and a batch shares one set, the rule of cr_render_frames_device (render such frames one at a time).  refit_boxes
+ * on a scene where it changes nothing is accepted.  Synchronous, like cr_render_adaptive_device.
+ */
+CR_API int32_t cr_render_adaptive_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                                const CrAdaptiveParams* adaptive, const int32_t* frames, int32_t n_frames,
+                                                void* d_out_rgb, int32_t* d_counts, CrAdaptiveStats* stats);
+
+/* Same, into HOST buffers.  The Color::new check of cr_render_host runs frame by frame: stats->render.nan_pixels counts
+ * all frames, and CR_ERR_NAN's message names the first failing frame, as cr_render_frames_host's does. */
+CR_API int32_t cr_render_adaptive_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                              const CrAdaptiveParams* adaptive, const int32_t* frames, int32_t n_frames,
+                                              void* h_out_rgb, int32_t* h_counts, CrAdaptiveStats* stats);
+
 /* The wrapper tree the device walks for `real_type`, as BVHWrapper's shape (src/objects/bvhwrapper.rs:7-11):
  * wrapper k has boxes[6k..6k+5] = xmin,xmax,ymin,ymax,zmin,zmax (exact values of `real_type`) and
  * children[2k], children[2k+1] = left, right: >= 0 another wrapper's index, < 0 the bitwise complement of a
