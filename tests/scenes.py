@@ -110,6 +110,18 @@ def moving_scene(width=96, samples=6, frame=0, null_motion=False, depth=8):
     return sc
 
 
+def nan_window_scene(frame, samples=16):
+    """moving_scene at 37 x 29 pixels whose camera has no basis for the ray times in [0.97, 1): look_from jumps onto look_at
+    at t = 0.97 and back at t = 1 (NERP keys).  Frame 0 draws ray times in [0, 1), so the samples whose time falls into the
+    window miss with a NaN direction and the gradient sky makes their colour NaN -- flags beside ordinary magnitudes, in some
+    pixels and some samples only; every other frame is ordinary."""
+    sc = moving_scene(samples=samples, frame=frame)
+    sc.scene_cam.image_width, sc.scene_cam.image_height = 37, 29
+    sc.cam_translate_point((0.0, 0.7, 0.0), 0.97, NERP, WORLD, "from")
+    sc.cam_translate_point((0.0, 3.0, 9.0), 1.0, NERP, WORLD, "from")
+    return sc
+
+
 def scaled_scene(width=96, samples=6, frame=0, depth=8):
     """Triangles under every non-sphere scale builder (scene_animator.rs:38-229): ScaleX / ScaleY / ScaleZ keys, LERP and
     NERP, scale_point and scale_all_uniform (whose Z key wins, timeline/mod.rs:249-255), mixed with translations; 1 fps

@@ -1,6 +1,7 @@
 """The fuzz corpora of tests/test_gpu_fuzz.py through the entry points that came after them: the guide layers
 (cr_render_aov_*), the frame batches (cr_render_frames_*, cr_render_aov_frames_*), the device-built SAH tree when it is
-rendered, and CR_REFIT_REBUILD.  No tolerance anywhere: every plane against tests/test_gpu_aov.py's model over the oracle's
+rendered, and CR_REFIT_REBUILD (the region and adaptive calls, cr_render_region_*, cr_render_aov_region_*, cr_render_adaptive_*
+and cr_render_adaptive_frames_*: tests/test_gpu_fuzz_regions_adaptive.py).  No tolerance anywhere: every plane against tests/test_gpu_aov.py's model over the oracle's
 probes (bytes, and the positions of the NaNs on their own), every beauty frame against the oracle's, every batch against
 its single calls, work counters against the oracle's depth-1 render of the same scene and tree.
 
