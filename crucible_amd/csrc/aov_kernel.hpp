@@ -127,7 +127,7 @@ CR_D void aov_body(const AovArgs<real>& G) {
                 if constexpr (BATCH) camera_ray<real, true>(A, cam_i, cam_j, sample, rng, ro, rd, rtime, frame_time);
                 else camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
                 c_seg++;
-                walk_begin(ws, rd);
+                walk_begin(ws, rd, tree_walks_exact(A));
                 walking = n_entries > 0;
             }
             // Hittables::hit on (0.001, inf): rounds of the walk until every lane has its closest hit

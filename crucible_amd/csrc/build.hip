@@ -116,6 +116,7 @@ int32_t finish_boxes(CrHandle* h, DevScene<real>& ds, std::vector<Entry<real>>& 
             for (size_t i = 0; i < eo.size(); i++) for (int k = 0; k < 6; k++) entries[i].b[k] = eo[i].b[k];
         }
     }
+    ds.nan_planes = has_nan_plane(entries);
     if (ds.n_entries > 0) {
         int32_t rc = make_screen(h, ds, ds.entries.p, ds.screen, &ds.screen_usable);
         if (rc != CR_OK) return rc;

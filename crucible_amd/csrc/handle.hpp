@@ -68,6 +68,7 @@ template <typename real> struct DevScene {
     DevBuf screen, screen_refit;             // f64, unordered trees: the f32 screening records of entries / entries_refit
     DevBuf screen_overflow;                  // f64: one int, set by the record kernels when a box plane lies beyond the f32 range
     bool screen_usable = true;               // f64: `screen` may be walked on (no box plane beyond the f32 range)
+    bool nan_planes = false;                 // a construction-time box has a plane that is not a number (f32: inf - inf): every ray walks with Aabb::hit's own form
     bool ordered = false;                    // CR_BVH_SAH_ORDERED: `entries` holds EntryO records
     size_t entry_bytes = sizeof(Entry<real>);
     std::vector<int8_t> host_axis;           // ordered: split axis per wrapper (-1 leaf), same order as host_entries
@@ -87,7 +88,7 @@ template <typename real> struct DevScene {
     bool frame_valid = false;
     real frame_ta = real(0), frame_tb = real(0);
     DevBuf frame_map;                        // a frame build's index tables on the device (input positions, then gather sources)
-    void release() { frame_map.release(); frame_valid = false; last_walk = kWalkNone; desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
+    void release() { frame_map.release(); frame_valid = false; last_walk = kWalkNone; desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; nan_planes = false; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
 };
 
 }   // namespace cr
@@ -311,6 +312,11 @@ int32_t build_sah_device(CrHandle* h, const double* boxes, int32_t n, std::vecto
 int32_t build_sah_device_resident(CrHandle* h, int32_t n, std::vector<SahNodeRec>& nodes, std::vector<int32_t>& order, SahDeviceStats& st);
 // scene.hip
 template <typename real> int32_t run_box_kernels(CrHandle* h, DevScene<real>& ds, void* entries, real ta, real tb, bool use_keys);
+// A box plane of these wrappers that is not a number (DevScene::nan_planes; KernelArgs::exact_boxes)
+template <typename real> inline bool has_nan_plane(const std::vector<Entry<real>>& entries) {
+    for (const Entry<real>& e : entries) for (int k = 0; k < 6; k++) if (e.b[k] != e.b[k]) return true;
+    return false;
+}
 int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevBuf& out, bool* usable);
 int32_t make_screen(CrHandle* h, DevScene<float>& ds, const void* entries, DevBuf& out, bool* usable);
 int32_t validate_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags);

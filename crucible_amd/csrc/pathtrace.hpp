@@ -353,9 +353,16 @@ template <typename real> struct KernelArgs {
     // addresses in fx_acc (a whole frame's).  nullptr, as prepare_args leaves it: every tile of the launch, in order.  The word
     // follows the record's last one, so no other argument moved.
     const int32_t* tile_list;
+    // A box of the tree has a plane that is not a number.  Only an f32 tree can (a sphere whose centre AND radius round to
+    // infinity: inf - inf; cr_upload_scene and cr_update_primitives take finite f64 values only), and only in its
+    // construction-time boxes (a refit unites no sample box that is not a number).  The min/max forms of the box test pass
+    // over a NaN where Aabb::hit's comparisons fail on it, so every ray of such a launch walks like a ray with an infinite
+    // 1/direction: walk_begin's exact_box.  Read by the f32 kernels alone (tree_walks_exact); the word follows the record's
+    // last one, so no other argument moved.
+    int32_t exact_boxes;
 };
-static_assert(sizeof(KernelArgs<float>) == 488 && sizeof(KernelArgs<double>) == 608 && offsetof(KernelArgs<float>, tile_list) == 480 &&
-              offsetof(KernelArgs<double>, tile_list) == 600, "the region's words fill padding, the tile list follows the record: 8 bytes more");
+static_assert(sizeof(KernelArgs<float>) == 496 && sizeof(KernelArgs<double>) == 616 && offsetof(KernelArgs<float>, tile_list) == 480 &&
+              offsetof(KernelArgs<double>, tile_list) == 600, "the region's words fill padding, the tile list and exact_boxes follow the record");
 static_assert(offsetof(KernelArgs<float>, work_counter) == 304 && offsetof(KernelArgs<float>, out) == 368 && offsetof(KernelArgs<float>, fx_acc) == 408 &&
               offsetof(KernelArgs<float>, fd_tiles_y) == 464, "the region's words fill padding: no argument moved");
 template <typename real> inline void set_tiles(KernelArgs<real>& a, uint32_t tiles_x, uint32_t tiles_y) {
@@ -1254,11 +1261,15 @@ template <typename real> struct WalkState {
     int32_t pending;     // a leaf wrapper whose box was hit and whose primitives are still to be tested (-1: none)
 };
 
-template <bool SHARED = false, typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd) {
+// KernelArgs::exact_boxes, for the kernels that can meet such a tree: the f64 kernels compile to what they were
+CR_D bool tree_walks_exact(const KernelArgs<float>& A) { return A.exact_boxes != 0; }
+CR_D constexpr bool tree_walks_exact(const KernelArgs<double>&) { return false; }
+
+template <bool SHARED = false, typename real> CR_D void walk_begin(WalkState<real>& w, V3<real> rd, bool exact_tree = false) {
     w.inv = mk<real>(real(1) / rd.x, real(1) / rd.y, real(1) / rd.z);
     // 1/dir infinite on some axis (zero or denormal component): slab distances can be NaN, where only the
-    // compare/select form reproduces Aabb::hit
-    w.exact_box = (r_abs(w.inv.x) == r_inf(real(0))) || (r_abs(w.inv.y) == r_inf(real(0))) || (r_abs(w.inv.z) == r_inf(real(0)));
+    // compare/select form reproduces Aabb::hit; exact_tree: a box plane can be (tree_walks_exact)
+    w.exact_box = exact_tree || (r_abs(w.inv.x) == r_inf(real(0))) || (r_abs(w.inv.y) == r_inf(real(0))) || (r_abs(w.inv.z) == r_inf(real(0)));
     w.dd = len2(rd);
     w.rda = SHARED ? shared_rcp(w.dd) : quot_divide<real>();
     w.idx = 0; w.best_t = r_inf(real(0)); w.best = -1; w.pending = -1;
@@ -1746,6 +1757,12 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
     WalkState<real> ws;
     ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.rda = quot_divide<real>(); ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
     const int32_t n_entries = A.n_entries;
+    // read once, into a scalar register that stays: a load at every walk_begin would wait with the LDS reads around it
+    uint32_t exact_tree = tree_walks_exact(A) ? 1u : 0u;
+    if constexpr (std::is_same<real, float>::value) {
+        exact_tree = (uint32_t)__builtin_amdgcn_readfirstlane((int)exact_tree);
+        asm volatile("" : "+s"(exact_tree));
+    }
 
     Diag* dgp = nullptr;
     CR_DIAG_ONLY(Diag dg_store; for (int i = 0; i < DG_N; i++) dg_store.v[i] = 0; dgp = &dg_store;
@@ -1860,7 +1877,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
             if (depth_left == 0) finished = true;   // ray_color: depth == 0 -> black
             else {
                 c_seg++;
-                walk_begin<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, rd);
+                walk_begin<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, rd, exact_tree != 0u);
                 state = n_entries > 0 ? ST_WALK : ST_SHADE;
             }
         }

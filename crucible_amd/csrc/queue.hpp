@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(1024) queue_kernel(const KernelArgs<real> A) {
                     ro = mk<real>(s_ray[slot], s_ray[S + slot], s_ray[2 * S + slot]);
                     rd = mk<real>(s_ray[3 * S + slot], s_ray[4 * S + slot], s_ray[5 * S + slot]);
                     if (ANIM) rtime = s_ray[6 * S + slot];
-                    walk_begin(ws, rd);
+                    walk_begin(ws, rd, tree_walks_exact(A));
                     has_ray = true;
                 }
             }

@@ -91,7 +91,9 @@ template <typename real> CR_HD real timeline_pad(const Prim<real>& p, const Key<
 
 // A sample box with a coordinate that is not a number is not united (a zero-length LERP key evaluated exactly at its
 // own start gives 0/0): the rule would otherwise depend on the order of its unions.  Ray times are drawn from a
-// continuum, so the instant itself carries no rays.
+// continuum, so the instant itself carries no rays.  That holds for sample boxes only: the construction-time box (use_keys =
+// false) is taken as it is -- in f32 a sphere whose centre and radius are both infinite has a plane inf - inf, and a fresh
+// build keeps it (tree.hpp prim_box), so cr_update_primitives and the device builders keep it too.
 template <typename real> CR_HD bool box_is_number(const real blo[3], const real bhi[3]) {
     return blo[0] == blo[0] && blo[1] == blo[1] && blo[2] == blo[2] && bhi[0] == bhi[0] && bhi[1] == bhi[1] && bhi[2] == bhi[2];
 }
@@ -125,7 +127,7 @@ CR_HD void prim_box_at2(const Prim<real>& p, const Key<real>* keys, real t, bool
         bhi[a] = r_fmax(v[0][a], r_fmax(v[1][a], v[2][a])) + pad;
         blo[a] = r_fmin(v[0][a], r_fmin(v[1][a], v[2][a])) - pad;
     }
-    if (box_is_number(blo, bhi)) enclose(lo, hi, blo, bhi);
+    if (!use_keys || box_is_number(blo, bhi)) enclose(lo, hi, blo, bhi);
 }
 
 template <typename real>
@@ -143,7 +145,7 @@ CR_HD void prim_box_at(const Prim<real>& p, const Key<real>* keys, real t, bool 
             if (l <= h) { blo[a] = l - pad; bhi[a] = h + pad; } else { blo[a] = h - pad; bhi[a] = l + pad; }
         }
     }
-    if (box_is_number(blo, bhi)) enclose(lo, hi, blo, bhi);
+    if (!use_keys || box_is_number(blo, bhi)) enclose(lo, hi, blo, bhi);
 }
 
 // The sample times of the refit rule, indexed: 0 = ta, 1 = tb, then three per key (its start with the key active,

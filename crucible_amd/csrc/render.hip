@@ -122,6 +122,7 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.seed_mixed = mix64(p->seed + RNG_GAMMA);
     frame_times(p, a.current_time, a.shutter_length);   // ray_casting.rs:77-79
     a.output_sum = p->output_sum;
+    a.exact_boxes = (!refit && ds.nan_planes) ? 1 : 0;   // the boxes of a refit hold no NaN (refit.hpp box_is_number)
     if (frames) {   // each frame's times as a single render of it computes them (the shutter is the same for all)
         times.resize((size_t)n_frames);
         CrRenderParams q = *p;

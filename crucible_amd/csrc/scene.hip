@@ -114,6 +114,7 @@ static int32_t refit_updated(CrHandle* h, const int32_t* d_index, const double* 
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         for (size_t i = 0; i < eo.size(); i++) for (int k = 0; k < 6; k++) ds.host_entries[i].b[k] = eo[i].b[k];
     }
+    ds.nan_planes = has_nan_plane(ds.host_entries);
     return CR_OK;
 }
 

@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) wf_extend_kernel(const 
                     ro = mk<real>(W.ray[slot], W.ray[N + slot], W.ray[2 * (size_t)N + slot]);
                     rd = mk<real>(W.ray[3 * (size_t)N + slot], W.ray[4 * (size_t)N + slot], W.ray[5 * (size_t)N + slot]);
                     if (ANIM) rtime = W.ray[6 * (size_t)N + slot];
-                    walk_begin(ws, rd);
+                    walk_begin(ws, rd, tree_walks_exact(A));
                     has_ray = true;
                 }
             }

@@ -1312,7 +1312,7 @@ static real timeline_pad(const Hittable* h) {
     const real pad = b * ((real)(4 * h->tl.n_keys + 32) * eps);
     return pad == pad ? pad : R_INF;
 }
-static Aabb prim_box_samples(const Hittable* h, real ta, real tb);
+static Aabb prim_box_samples(const Hittable* h, real ta, real tb, real pad);
 static Aabb prim_box_over(const Hittable* h, real ta, real tb) {
     if (h->kind == H_HITLIST) {   /* the visible objects' boxes, united in the list's order */
         Aabb l = aabb_empty();
@@ -1320,16 +1320,20 @@ static Aabb prim_box_over(const Hittable* h, real ta, real tb) {
         return l;
     }
     if (h->tl.n_keys == 0) return unite_sample(aabb_empty(), prim_box_at(h, ta, 0));
-    Aabb b = prim_box_samples(h, ta, tb);
-    if (!(b.x.min <= b.x.max)) return b;   /* no sample was a number */
-    const real pad = timeline_pad(h);
-    b.x.min = b.x.min - pad; b.x.max = b.x.max + pad;
-    b.y.min = b.y.min - pad; b.y.max = b.y.max + pad;
-    b.z.min = b.z.min - pad; b.z.max = b.z.max + pad;
-    return b;
+    return prim_box_samples(h, ta, tb, timeline_pad(h));
 }
-static Aabb prim_box_samples(const Hittable* h, real ta, real tb) {
-    Aabb b = unite_sample(aabb_empty(), prim_box_at(h, ta, 0));
+/* Every sample box is grown by the pad before it is judged and united, as refit.hpp does it: an infinite pad (a key value
+ * beyond the range of `real`) on an infinite coordinate gives inf - inf, and that sample is then not united at all.
+ * Grown after the union instead, such a box would keep a plane that is not a number and take its leaf's other primitive
+ * out of reach.  For finite values both orders give the same bits (rounding is monotone). */
+static Aabb grown(Aabb s, real pad) {
+    s.x.min = s.x.min - pad; s.x.max = s.x.max + pad;
+    s.y.min = s.y.min - pad; s.y.max = s.y.max + pad;
+    s.z.min = s.z.min - pad; s.z.max = s.z.max + pad;
+    return s;
+}
+static Aabb prim_box_samples(const Hittable* h, real ta, real tb, real pad) {
+    Aabb b = unite_sample(aabb_empty(), grown(prim_box_at(h, ta, 0), pad));
     int scaled = 0;
     for (int i = 0; i < h->tl.n_keys; i++) scaled |= h->tl.keys[i].channel >= CR_KEY_SCALE_X;
     if (scaled) {   /* translate and scale parts sampled independently, every pair united (refit.hpp) */
@@ -1338,18 +1342,18 @@ static Aabb prim_box_samples(const Hittable* h, real ta, real tb) {
             real t1, t2; int s1, s2;
             if (!refit_sample(h, ta, tb, i, &t1, &s1)) continue;
             for (int j = 0; j < n; j++)
-                if (refit_sample(h, ta, tb, j, &t2, &s2)) b = unite_sample(b, prim_box_at2(h, t1, s1, t2, s2));
+                if (refit_sample(h, ta, tb, j, &t2, &s2)) b = unite_sample(b, grown(prim_box_at2(h, t1, s1, t2, s2), pad));
         }
         return b;
     }
-    b = unite_sample(b, prim_box_at(h, tb, 0));
+    b = unite_sample(b, grown(prim_box_at(h, tb, 0), pad));
     for (int i = 0; i < h->tl.n_keys; i++) {
         const Key* k = &h->tl.keys[i];
         if (ta < k->t0 && k->t0 <= tb) {
-            b = unite_sample(b, prim_box_at(h, k->t0, 0));
-            b = unite_sample(b, prim_box_at(h, k->t0, 1));
+            b = unite_sample(b, grown(prim_box_at(h, k->t0, 0), pad));
+            b = unite_sample(b, grown(prim_box_at(h, k->t0, 1), pad));
         }
-        if (ta < k->t1 && k->t1 < tb) b = unite_sample(b, prim_box_at(h, k->t1, 0));
+        if (ta < k->t1 && k->t1 < tb) b = unite_sample(b, grown(prim_box_at(h, k->t1, 0), pad));
     }
     return b;
 }

@@ -72,19 +72,32 @@ def apply_edit(flat, idx, rows):
 
 
 def prim_box(kind, v, dtype):
-    """Construction-time box (lo (3,), hi (3,)) of one primitive, computed in `dtype`."""
-    g = np.asarray(v, dtype=np.float64).astype(dtype)
-    if kind == A.CR_PRIM_SPHERE:
-        r = g[3]
-        a, b = g[:3] + (-r), g[:3] + r
-        return np.minimum(a, b), np.maximum(a, b)
+    """Construction-time box (lo (3,), hi (3,)) of one primitive, computed in `dtype`.  A sphere's is Aabb::new_from_points
+    (bvh.rs:44-64) of centre - r and centre + r, a compare and select: when one of them is not a number (inf - inf, an f32
+    centre and radius that are both infinite) the comparison fails and the box is (centre + r, centre - r).  A triangle's is
+    f64::min / f64::max over the vertices (triangle.rs:28-35), which pass over a NaN."""
+    with np.errstate(over="ignore", invalid="ignore"):       # coordinates beyond the range of `dtype` become infinite, as on the device
+        g = np.asarray(v, dtype=np.float64).astype(dtype)
+        if kind == A.CR_PRIM_SPHERE:
+            r = g[3]
+            a, b = g[:3] + (-r), g[:3] + r
+            ordered = a <= b
+            return np.where(ordered, a, b), np.where(ordered, b, a)
     pts = g.reshape(3, 3)
-    return pts.min(axis=0), pts.max(axis=0)
+    return np.fmin.reduce(pts, axis=0), np.fmax.reduce(pts, axis=0)
+
+
+def tight_enclose(lo, hi, clo, chi):
+    """Interval::tight_enclose (utils.rs:629-633) per axis: `a.min <= b.min ? a.min : b.min`, `a.max >= b.max ? a.max : b.max`.
+    Not np.minimum / np.maximum: a comparison with a NaN fails, so the second operand's NaN is taken and the first's dropped."""
+    with np.errstate(invalid="ignore"):
+        return np.where(lo <= clo, lo, clo), np.where(hi >= chi, hi, chi)
 
 
 def model_boxes(children, kind, v, dtype):
     """boxes (n, 6) in `dtype` (xmin, xmax, ymin, ymax, zmin, zmax) of the wrapper tree `children` (cr_export_bvh's
-    shape: >= 0 a wrapper, < 0 the complement of a primitive's index; children are numbered after their parent)."""
+    shape: >= 0 a wrapper, < 0 the complement of a primitive's index; children are numbered after their parent): a
+    wrapper's box is the tight_enclose of its left child's box and its right child's, in that order (bvh.rs:67-73)."""
     n = len(children)
     lo = np.full((n, 3), np.inf, dtype=dtype)
     hi = np.full((n, 3), -np.inf, dtype=dtype)
@@ -95,20 +108,23 @@ def model_boxes(children, kind, v, dtype):
                 clo, chi = lo[c], hi[c]
             else:
                 clo, chi = prim_box(kind[~c], v[~c], dtype)
-            lo[k] = np.minimum(lo[k], clo)
-            hi[k] = np.maximum(hi[k], chi)
+            lo[k], hi[k] = tight_enclose(lo[k], hi[k], clo, chi)
     boxes = np.empty((n, 6), dtype=dtype)
     boxes[:, 0::2] = lo
     boxes[:, 1::2] = hi
     return boxes
 
 
-def oracle_tree(o, flat):
+def oracle_tree(o, flat, cam=None, seed=0):
     """The oracle's own reference-built tree of `flat`: (boxes (n, 6) in the oracle's real, children (n, 2) in
     cr_export_bvh's shape).  oracle_bvh_dump numbers wrappers in walk order, marks a wrapper child -1 and names a
-    primitive by its index; the wrapper indices follow from the walk order."""
+    primitive by its index; the wrapper indices follow from the walk order.
+    cam: the boxes the oracle walks for that camera's frame -- the refitted ones with cam.refit_boxes -- instead of the
+    construction-time ones (oracle_render leaves the boxes of its frame in the scene: a one-pixel render sets them)."""
     h = o.scene_create(flat)
     try:
+        if cam is not None:
+            o.render(h, cam, seed=seed, pix_begin=0, pix_end=1, n_threads=1)
         cap = 2 * max(1, flat.desc.n_prims) + 8
         boxes = np.zeros((cap, 6), dtype=o.np_real)
         kids = np.zeros((cap, 2), dtype=np.int32)
