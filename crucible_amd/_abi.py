@@ -164,6 +164,12 @@ SYMBOLS = {
     "cr_render_adaptive_frames_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
                                                    C.POINTER(CrAdaptiveParams), C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                                    C.c_void_p, C.POINTER(CrAdaptiveStats)]),
+    "cr_render_adaptive_region_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
+                                                     C.POINTER(CrAdaptiveParams), C.POINTER(CrRegion), C.c_void_p, C.c_void_p,
+                                                     C.POINTER(CrAdaptiveStats)]),
+    "cr_render_adaptive_region_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
+                                                   C.POINTER(CrAdaptiveParams), C.POINTER(CrRegion), C.c_void_p, C.c_void_p,
+                                                   C.POINTER(CrAdaptiveStats)]),
     "cr_export_bvh": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_int32)]),
     "cr_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),

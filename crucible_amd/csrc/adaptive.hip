@@ -1,7 +1,7 @@
-// adaptive.hip -- cr_render_adaptive_* and cr_render_adaptive_frames_* (include/crucible_hip.h): a frame,
-// or a batch of frames under one pass loop, whose blocks of pixels stop taking samples once their two half-frame sums
-// agree.  The entry points' checks, the pass loop around the render kernel that
-// launch() (render.hpp) hands over, the judge kernel (one wave per block: the difference sum, the verdict, the next list
+// adaptive.hip -- cr_render_adaptive_*, cr_render_adaptive_frames_* and cr_render_adaptive_region_* (include/crucible_hip.h,
+// DESIGN.md 6.11 - 6.13): a frame, a batch of frames under one pass loop, or a region of a frame judged as if it were the
+// frame, whose blocks of pixels stop taking samples once their two half-frame sums agree.  The entry points' checks, the
+// pass loop around the render kernel that launch() (render.hpp) hands over, the judge kernel (one wave per block: the difference sum, the verdict, the next list
 // of active tiles) and the finalize kernel (per-pixel means by each block's own sample count, the count plane).
 #include "handle.hpp"
 #include "adaptive.hpp"
@@ -12,7 +12,7 @@ struct JudgeArgs {
     const unsigned long long* E;         // frame f's sums at f * frame_words, in both
     const unsigned long long* O;
     size_t frame_words;                  // W * H * 3
-    int32_t W, H;
+    int32_t W, H;                        // the pixels the passes cover: a region's own (its blocks and tiles start at its origin), else the frame's
     uint32_t block_log2, n_blocks;       // n_blocks: of one frame
     uint32_t n_frames;                   // the pass loop's frames: n_frames * n_blocks blocks, frame after frame (adaptive_batch_block)
     uint32_t lw, lh, tiles_x, tiles_y;   // the render kernel's tiles: their sides divide the block's
@@ -213,8 +213,10 @@ int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame
 }
 
 // the checks of cr_render_adaptive_*, in the header's order; nothing has changed when one of them refuses
-static int32_t validate_adaptive(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const void* out) {
-    int32_t rc = validate_render(h, cam, p);
+// region_call: cr_render_adaptive_region_* -- validate_render checks `region` as it does for cr_render_region_*
+static int32_t validate_adaptive(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const void* out,
+                                 const CrRegion* region = nullptr, bool region_call = false) {
+    int32_t rc = validate_render(h, cam, p, region, region_call);
     if (rc != CR_OK) return rc;
     if (!ap) return fail(h, CR_ERR_INVALID_ARG, "adaptive params are null");
     if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
@@ -232,17 +234,23 @@ static int32_t validate_adaptive(CrHandle* h, const CrCameraDesc* cam, const CrR
     if (p->sample_begin != 0 || p->sample_count != p->samples)
         return fail(h, CR_ERR_UNSUPPORTED, "cr_render_adaptive judges all samples of a pixel: sample_begin must be 0 and sample_count == samples");
     if (p->output_sum != 0) return fail(h, CR_ERR_UNSUPPORTED, "cr_render_adaptive writes means (output_sum 0)");
+    // tiles must partition blocks: a work tile that CRUCIBLE_SG_TILE names and that is wider or taller than the block is
+    // refused here, where the whole-frame calls give way to the default shape
+    const int32_t L = ap->block_log2 ? ap->block_log2 : 4;
+    if (region_call && (h->sg_lw > L || h->sg_lh > L))
+        return fail(h, CR_ERR_UNSUPPORTED, "cr_render_adaptive_region: the work tile CRUCIBLE_SG_TILE names does not fit the adaptive block");
     return CR_OK;
 }
 
 // frames == nullptr: the one frame params->frame; else the batch `frames` (cr_render_adaptive_frames_*)
+// region != nullptr: those pixels of the one frame, judged as if they were the frame (cr_render_adaptive_region_*)
 static int32_t adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
-                               int32_t n_frames, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
+                               int32_t n_frames, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats, const CrRegion* region = nullptr) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const AdaptiveRun run = {ap->min_samples, ap->pass_samples, ap->block_log2 ? ap->block_log2 : 4, ap->tolerance, d_counts, stats};
+    const AdaptiveRun run = {ap->min_samples, ap->pass_samples, ap->block_log2 ? ap->block_log2 : 4, ap->tolerance, d_counts, stats, region != nullptr};
     h->cam_pending_slot = -1;
-    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, nullptr, frames, n_frames, nullptr, &run)
-                                             : render_typed<float>(h, cam, p, d_out, nullptr, frames, n_frames, nullptr, &run);
+    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, nullptr, frames, n_frames, region, &run)
+                                             : render_typed<float>(h, cam, p, d_out, nullptr, frames, n_frames, region, &run);
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
         const hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
         h->cam_pending_slot = -1;
@@ -251,16 +259,18 @@ static int32_t adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRen
     return rc;
 }
 
-// cr_render_adaptive_host / cr_render_adaptive_frames_host: render into the handle's buffers, copy back, check the means frame by frame
+// cr_render_adaptive_host / cr_render_adaptive_frames_host / cr_render_adaptive_region_host: render into the handle's buffers,
+// copy back, check the means frame by frame (a region's output, counts and check are of the region's pixels)
 static int32_t adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
-                             int32_t n_frames, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
+                             int32_t n_frames, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats, const CrRegion* region = nullptr) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n_pix = (size_t)cam->image_width * (size_t)cam->image_height, frame_bytes = n_pix * 3 * real_size(p->real_type);
+    const size_t n_pix = region ? (size_t)region->width * (size_t)region->height : (size_t)cam->image_width * (size_t)cam->image_height;
+    const size_t frame_bytes = n_pix * 3 * real_size(p->real_type);
     const size_t bytes = frame_bytes * (size_t)n_frames, count_bytes = n_pix * (size_t)n_frames * sizeof(int32_t);
     hipError_t e = h->out_buf.ensure(bytes);
     if (e == hipSuccess && h_counts) e = h->ad_counts.ensure(count_bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
-    int32_t rc = adaptive_device(h, cam, p, ap, frames, n_frames, h->out_buf.p, h_counts ? (int32_t*)h->ad_counts.p : nullptr, stats);
+    int32_t rc = adaptive_device(h, cam, p, ap, frames, n_frames, h->out_buf.p, h_counts ? (int32_t*)h->ad_counts.p : nullptr, stats, region);
     if (rc != CR_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
     if (h_counts) HIP_TRY(h, hipMemcpyAsync(h_counts, h->ad_counts.p, count_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -306,6 +316,18 @@ int32_t cr_render_adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRe
                                 int32_t* h_counts, CrAdaptiveStats* stats) {
     const int32_t rc = validate_adaptive(h, cam, p, ap, h_out);
     return rc != CR_OK ? rc : adaptive_host(h, cam, p, ap, nullptr, 1, h_out, h_counts, stats);
+}
+
+int32_t cr_render_adaptive_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                         const CrRegion* region, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
+    const int32_t rc = validate_adaptive(h, cam, p, ap, d_out, region, true);
+    return rc != CR_OK ? rc : adaptive_device(h, cam, p, ap, nullptr, 1, d_out, d_counts, stats, region);
+}
+
+int32_t cr_render_adaptive_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                       const CrRegion* region, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
+    const int32_t rc = validate_adaptive(h, cam, p, ap, h_out, region, true);
+    return rc != CR_OK ? rc : adaptive_host(h, cam, p, ap, nullptr, 1, h_out, h_counts, stats, region);
 }
 
 int32_t cr_render_adaptive_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,

@@ -59,6 +59,27 @@ CR_HD uint32_t adaptive_block_tile(uint32_t f, uint32_t tiles_x, uint32_t tiles_
     const uint32_t r = k / tw;
     return adaptive_batch_tile(f, tiles_x, tiles_y, tx0 + (k - r * tw), ty0 + r);
 }
+// A region of a frame (cr_render_adaptive_region_*): the region is judged as if it were the frame, so the
+// functions above take the region's width and height and work in region-local pixels; the blocks (and the render
+// kernel's tiles) are anchored at the region's origin.  Block b of the region (rx0, ry0, rw, rh), in the frame's pixels:
+CR_HD void adaptive_region_block_rect(int32_t rx0, int32_t ry0, int32_t rw, int32_t rh, uint32_t block_log2, uint32_t b,
+                                      uint32_t& x0, uint32_t& y0, uint32_t& bw, uint32_t& bh) {
+    adaptive_block_rect(rw, rh, block_log2, b, x0, y0, bw, bh);
+    x0 += (uint32_t)rx0; y0 += (uint32_t)ry0;
+}
+// Are the region's blocks blocks of the W x H frame, partial ones included?  The origin on multiples of the block's side,
+// and the right and the bottom edge each on such a multiple or on the frame's edge.  Then image and counts of the region
+// are the frame's own adaptive render on those pixels, and regions like that which tile a frame give that frame.
+// (the region lies inside the frame: the entry point has checked it)
+CR_HD bool adaptive_region_aligned(int32_t W, int32_t H, int32_t rx0, int32_t ry0, int32_t rw, int32_t rh, uint32_t block_log2) {
+    const int64_t m = ((int64_t)1 << block_log2) - 1, x1 = (int64_t)rx0 + rw, y1 = (int64_t)ry0 + rh;
+    return !(rx0 & m) && !(ry0 & m) && (!(x1 & m) || x1 == W) && (!(y1 & m) || y1 == H);
+}
+// ... and block b of such a region is this block of the frame
+CR_HD uint32_t adaptive_region_frame_block(int32_t W, int32_t rx0, int32_t ry0, int32_t rw, uint32_t block_log2, uint32_t b) {
+    const uint32_t bx_n = adaptive_blocks_x(rw, block_log2), by = b / bx_n, bx = b - by * bx_n;
+    return (((uint32_t)ry0 >> block_log2) + by) * adaptive_blocks_x(W, block_log2) + ((uint32_t)rx0 >> block_log2) + bx;
+}
 // does a block with difference sum d stop?
 CR_HD bool adaptive_stops(uint64_t d, uint64_t t) { return d <= t; }
 

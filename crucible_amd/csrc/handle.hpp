@@ -254,11 +254,12 @@ struct AdaptiveRun {
     double tolerance;
     int32_t* d_counts;          // may be null; frame after frame
     CrAdaptiveStats* stats;     // may be null
+    bool split_passes;          // cr_render_adaptive_region_*: a pass the work counter does not hold runs as several launches (else it is refused)
 };
 // ... and what launch() settled: the frame, the render kernel's tile shape and tile counts, the scale of the sums; of a
 // batch (cr_render_adaptive_frames_*) the frame count and how many whole frames one launch's work counter holds
 struct AdaptiveFrame {
-    int32_t W, H, samples;
+    int32_t W, H, samples;      // W x H: the pixels the passes cover -- the region's (cr_render_adaptive_region_*), else the frame's
     int32_t n_frames, frames_per_launch;
     uint32_t lw, lh, tiles_x, tiles_y;
     double fx_scale;

@@ -94,7 +94,9 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
             if (batch <= 0) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
             // a frame that needs sample batches on its own renders frame by frame
             if (batch == s_end - s_begin) fpl = (int32_t)std::min<uint64_t>((uint64_t)fb.n, max_groups / (((uint64_t)batch + ns - 1) / ns));
-            if (fb.ad && batch < s_end - s_begin) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter at this pass_samples");
+            // (cr_render_adaptive_region_*: such a pass runs as consecutive launches of `batch` samples, as a region render's samples do)
+            if (fb.ad && !fb.ad->split_passes && batch < s_end - s_begin)
+                return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter at this pass_samples");
             if (args.output_sum != CR_OUTPUT_FIXED_SUM && !fb.ad) {   // (adaptive_passes keeps its own two accumulators)
                 const hipError_t e = h->fx_acc.ensure((size_t)fb.n * npix * 3 * sizeof(unsigned long long));
                 if (e != hipSuccess) {
@@ -147,17 +149,25 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         h->last_block = block; h->last_grid = (int)grid;
         // (cr_render_adaptive_frames_*: a pass loop's frames [f0, f0 + fn) of the batch, at most fpl, as the loop below sets them)
         const AdaptivePass pass = [&](int32_t f0, int32_t fn, const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc) -> int32_t {
-            args.tile_list = tile_list; args.sample_begin = s0; args.sample_end = s1; args.fx_acc = acc;
+            args.tile_list = tile_list; args.fx_acc = acc;
             args.n_frames = (uint32_t)fn;
             args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
             args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
-            set_groups(args, groups_of(s1 - s0));
-            args.sg_total = (uint32_t)((uint64_t)n_tiles * args.sg_groups * 64u);
-            const uint32_t pass_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block));
-            args.sg_chunk = work_chunk(args.sg_total, pass_grid, (uint64_t)block, h->sg_chunk_override);
-            return run(pass_grid);
+            // one launch, unless the work counter holds fewer samples of the tiles than the pass has (split_passes; batch >= 1)
+            for (int64_t b0 = s0; b0 < s1; b0 += batch) {
+                const int32_t b1 = (int32_t)std::min<int64_t>(s1, b0 + batch);
+                args.sample_begin = (int32_t)b0; args.sample_end = b1;
+                set_groups(args, groups_of(b1 - (int32_t)b0));
+                args.sg_total = (uint32_t)((uint64_t)n_tiles * args.sg_groups * 64u);
+                const uint32_t pass_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block));
+                args.sg_chunk = work_chunk(args.sg_total, pass_grid, (uint64_t)block, h->sg_chunk_override);
+                const int32_t rc = run(pass_grid);
+                if (rc != CR_OK) return rc;
+            }
+            return CR_OK;
         };
-        const AdaptiveFrame fr = {args.cam.W, args.cam.H, args.samples_total, fb.n, fpl, args.sg_lw, args.sg_lh, args.tiles_x, args.tiles_y, args.fx_scale,
+        // (the pass loop judges the launch's pixels: a region's blocks and tiles share its origin)
+        const AdaptiveFrame fr = {(int32_t)args.reg_w, (int32_t)args.reg_h, args.samples_total, fb.n, fpl, args.sg_lw, args.sg_lh, args.tiles_x, args.tiles_y, args.fx_scale,
                                   (void*)args.out, std::is_same<real, double>::value, args.n_entries, RES};
         return adaptive_passes(h, *fb.ad, fr, pass);
     }

@@ -451,8 +451,10 @@ public:
     // A frame to a noise target (cr_render_adaptive_host): scene_cam.samples is the maximum per pixel, blocks of `block`
     // pixels square stop once their two half-frame means differ by at most `tolerance` on average (include/crucible_hip.h has
     // the exact rule).  render_frame then keeps the samples each pixel took and the call's stats; sample_map = true has
-    // render_image and render_movie_frames write the counts as <frame>.samples.pfm.  Whole frames on one device; a movie with
+    // render_image and render_movie_frames write the counts as <frame>.samples.pfm.  On one device; a movie with
     // frames_per_launch > 1 renders each batch under one pass loop (cr_render_adaptive_frames_host).  Needs relaxed sums.
+    // With set_region: the region to the noise target (cr_render_adaptive_region_host), judged as if it were the frame --
+    // counts, sample map and stats are the region's.
     bool has_adaptive = false, sample_map = false;
     CrAdaptiveParams adaptive = {0, 0, 0, 0, 0.0};
     mutable std::vector<int32_t> adaptive_counts;
@@ -625,13 +627,14 @@ public:
         CrCameraDesc cd = camera_desc(fk, ak);
         CrRenderParams p = render_params(frame < 0 ? (size_t)scene_cam.frame : (size_t)frame);
         buf.resize(std::max<size_t>(1, out_width() * out_height() * 3));
-        if (has_region) return cr_render_region_host(h, &cd, &p, &region, buf.data(), stats);
-        if (has_adaptive) {
-            adaptive_counts.resize((size_t)scene_cam.image_width * scene_cam.image_height);
-            const int32_t rc = cr_render_adaptive_host(h, &cd, &p, &adaptive, buf.data(), adaptive_counts.data(), &adaptive_stats);
+        if (has_adaptive) {   // (with a region: the region to the noise target, counts and stats of its own blocks)
+            adaptive_counts.resize(std::max<size_t>(1, out_width() * out_height()));
+            const int32_t rc = has_region ? cr_render_adaptive_region_host(h, &cd, &p, &adaptive, &region, buf.data(), adaptive_counts.data(), &adaptive_stats)
+                                          : cr_render_adaptive_host(h, &cd, &p, &adaptive, buf.data(), adaptive_counts.data(), &adaptive_stats);
             if (stats) *stats = adaptive_stats.render;
             return rc;
         }
+        if (has_region) return cr_render_region_host(h, &cd, &p, &region, buf.data(), stats);
         return cr_render_host(h, &cd, &p, buf.data(), stats);
     }
     // The frames `frs` in one call: frame k at k * W*H*3 reals of `real_type` in `buf`.
@@ -659,11 +662,11 @@ public:
         if (stats) *stats = as.render;
         return rc;
     }
-    // <fname>.samples.pfm: the samples each pixel of an adaptive frame took, one f32 channel
+    // <fname>.samples.pfm: the samples each pixel of an adaptive frame (or region) took, one f32 channel
     int32_t write_sample_map(const std::string& fname, const int32_t* counts) const {
-        const size_t n_pix = (size_t)scene_cam.image_width * scene_cam.image_height;
+        const size_t n_pix = out_width() * out_height();
         const std::vector<float> map(counts, counts + n_pix);
-        return cr_write_pfm((fname + ".samples.pfm").c_str(), map.data(), CR_REAL_F32, (int32_t)scene_cam.image_width, (int32_t)scene_cam.image_height, 1);
+        return cr_write_pfm((fname + ".samples.pfm").c_str(), map.data(), CR_REAL_F32, (int32_t)out_width(), (int32_t)out_height(), 1);
     }
     // Guide layers (cr_render_aov_host): the planes of `aov_layers` for the frame, one after the other, into `buf`.
     int32_t aov_layers = 0;   // CR_AOV_* mask: > 0 writes <frame>.<layer>.pfm next to every frame file
@@ -769,7 +772,7 @@ public:
             memset(&st, 0, sizeof st);
             const double t0 = now_ms();
             double kernel_ms = 0;
-            const size_t n_pix = (size_t)scene_cam.image_width * scene_cam.image_height;
+            const size_t n_pix = out_width() * out_height();   // of one frame's files: the region's with a region (never batched)
             if (batched) {
                 rc = has_adaptive ? render_adaptive_frames(h, bufs[slot], maps[slot], batch, &st) : render_frames(h, bufs[slot], batch, &st);
                 kernel_ms = st.kernel_ms;

@@ -15,8 +15,9 @@
 // region's planes; a movie applies it to every frame, one call per frame; needs relaxed sums; --timing names the region),
 // --adaptive tol[,min[,pass[,block]]] (render to a noise target through cr_render_adaptive_host: --samples is the maximum per pixel,
 // blocks of `block` pixels square (8, 16, 32; default 16) stop once their two half-frame means differ by at most tol on average,
-// judged every 2 * pass samples (default 8) from min samples on (default 4 * pass); needs relaxed sums and whole frames on one
-// device; a movie renders --frames-per-launch frames per cr_render_adaptive_frames_host call; --sample-map also writes <frame>.samples.pfm, the samples each pixel took; --timing
+// judged every 2 * pass samples (default 8) from min samples on (default 4 * pass); needs relaxed sums and one device; with
+// --region the region is rendered to the noise target through cr_render_adaptive_region_host, its blocks anchored at its origin,
+// and files, sample map and figures are the region's; no --aov; a movie renders --frames-per-launch frames per cr_render_adaptive_frames_host call; --sample-map also writes <frame>.samples.pfm, the samples each pixel took; --timing
 // adds the passes, the blocks stopped and the samples taken),
 // --repeat N --timing (measurement: render_scene N times in this process, one JSON line of wall-clock phases each --
 // the shape of the reference's criterion benchmark, benches/renderer_benchmark.rs:16-42 -- the first is the cold one).
@@ -164,7 +165,7 @@ int main(int argc, char** argv) {
             const int got = sscanf(adaptive.c_str(), "%lf,%d,%d,%d%c", &tol, &min_samples, &pass, &block, &tail);
             if (got < 1 || got > 4) { fprintf(stderr, "--adaptive takes tol[,min[,pass[,block]]]\n"); return 2; }
             if (got < 2) min_samples = 4 * pass;
-            if (!region.empty() || !aov.empty()) { fprintf(stderr, "--adaptive renders whole beauty frames (no --region, no --aov)\n"); return 2; }
+            if (!aov.empty()) { fprintf(stderr, "--adaptive renders beauty frames or regions of them (no --aov)\n"); return 2; }
             if (!movie && (gpus > 1 || use_group)) { fprintf(stderr, "--adaptive renders on one device (a group splits a frame by samples)\n"); return 2; }
             scene.set_adaptive(tol, min_samples, pass, block);   // the library checks the rest
             scene.sample_map = sample_map;

@@ -281,14 +281,23 @@ class Renderer:
         return st.as_dict() if want_stats else None
 
     def render_tiled(self, cam, tile=(1024, 1024), *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
-                     output_sum=False, sum_order=None):
+                     output_sum=False, sum_order=None, adaptive=None):
         """A whole frame assembled from render_region() calls over tiles of `tile` = (tw, th) pixels (edge tiles are
         smaller): render()'s frame bit for bit, and the way to a frame of more than 2^26 pixels (up to 2^31 - 1).  Returns
         (image (H, W, 3), stats dict: the regions' counters, samples, nan_pixels and kernel_ms summed; the rest from the
-        last region)."""
+        last region).
+
+        adaptive=dict(tolerance=, min_samples=, pass_samples=, block=16): each tile through render_adaptive_region()
+        instead -- render_adaptive()'s frame and counts bit for bit.  The tile's sides must be multiples of `block`
+        (ValueError otherwise: the tiles' blocks would not be the frame's and the result would depend on the tiling).
+        Returns (image, counts (H, W) int32, stats dict shaped like render_adaptive's: the counters, samples, nan_pixels,
+        kernel_ms, judge_ms, passes, blocks and blocks_stopped summed over the calls; the rest from the last)."""
         tw, th = int(tile[0]), int(tile[1])
         if tw < 1 or th < 1:
             raise ValueError("render_tiled: tile sizes must be positive")
+        if adaptive is not None:
+            return self._render_tiled_adaptive(cam, tw, th, dict(adaptive), seed=seed, real_type=real_type, sample_begin=sample_begin,
+                                               sample_count=sample_count, output_sum=output_sum, sum_order=sum_order)
         H, W = cam.image_height, cam.image_width
         dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
         out = np.empty((H, W, 3), dtype=dtype)
@@ -307,6 +316,36 @@ class Renderer:
                     for k in ("upload_ms", "bvh_entries", "scene_in_lds"):
                         total[k] = st[k]
         return out, total
+
+    def _render_tiled_adaptive(self, cam, tw, th, adaptive, *, seed, real_type, sample_begin, sample_count, output_sum, sum_order):
+        """render_tiled(adaptive=...): the checks need no device and come before the first call."""
+        block = int(adaptive.pop("block", 16) or 16)
+        if tw % block or th % block:
+            raise ValueError(f"render_tiled: an adaptive tile's sides must be multiples of the block's ({block}): {tw}x{th} "
+                             "would make the frame depend on the tiling")
+        if sample_begin != 0 or sample_count is not None or output_sum:
+            raise ValueError("render_tiled: an adaptive frame takes all samples of a pixel and comes as means")
+        H, W = cam.image_height, cam.image_width
+        out = np.empty((H, W, 3), dtype=np_real(real_type))
+        counts = np.empty((H, W), dtype=np.int32)
+        total = None
+        for y0 in range(0, H, th):
+            for x0 in range(0, W, tw):
+                w, h = min(tw, W - x0), min(th, H - y0)
+                img, cnt, st = self.render_adaptive_region(cam, (x0, y0, w, h), seed=seed, real_type=real_type, block=block,
+                                                           sum_order=sum_order, **adaptive)
+                out[y0:y0 + h, x0:x0 + w] = img
+                counts[y0:y0 + h, x0:x0 + w] = cnt
+                if total is None:
+                    total = st
+                    continue
+                for k in ("judge_ms", "passes", "blocks", "blocks_stopped"):
+                    total[k] += st[k]
+                for k in ("samples", "segments", "node_tests", "prim_tests", "texel_fetches", "nan_pixels", "kernel_ms"):
+                    total["render"][k] += st["render"][k]
+                for k in ("upload_ms", "bvh_entries", "scene_in_lds"):
+                    total["render"][k] = st["render"][k]
+        return out, counts, total
 
     def render_adaptive(self, cam, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples, pass_samples, block=16,
                         want_counts=True, want_stats=True, sum_order=None):
@@ -369,6 +408,41 @@ class Renderer:
         st = A.CrAdaptiveStats()
         self._check(self.lib.cr_render_adaptive_frames_device(self.h, C.byref(cd), C.byref(p), C.byref(ap), fr_ptr, fr.size,
                                                               C.c_void_p(d_ptr), C.c_void_p(d_counts) if d_counts else None,
+                                                              C.byref(st) if want_stats else None))
+        return st.as_dict()
+
+    def render_adaptive_region(self, cam, region, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples, pass_samples, block=16,
+                               want_counts=True, want_stats=True, sum_order=None):
+        """cr_render_adaptive_region_host: the pixels `region` = (x0, y0, w, h) of the frame `cam` describes to a noise
+        target, judged as if the region were the frame (blocks anchored at its origin).  A region whose origin lies on
+        multiples of `block` and whose right and bottom edge lie on such multiples or on the frame's edge gives
+        render_adaptive()'s pixels and counts bit for bit; region=None passes a null pointer (the library refuses it).
+        Returns (image (h, w, 3), counts (h, w) int32 or None, stats dict shaped like render_adaptive's, over the region's
+        blocks)."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
+        ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
+        reg, (w, h) = region_arg(region)
+        out = np.empty((max(1, h), max(1, w), 3), dtype=np_real(real_type))
+        counts = np.empty((max(1, h), max(1, w)), dtype=np.int32) if want_counts else None
+        st = A.CrAdaptiveStats()
+        self._check(self.lib.cr_render_adaptive_region_host(self.h, C.byref(cd), C.byref(p), C.byref(ap), reg,
+                                                            out.ctypes.data_as(C.c_void_p),
+                                                            counts.ctypes.data_as(C.c_void_p) if want_counts else None,
+                                                            C.byref(st) if want_stats else None))
+        return out, counts, st.as_dict()
+
+    def render_adaptive_region_device(self, cam, region, d_ptr, d_counts=None, *, seed, real_type=A.CR_REAL_F32, tolerance,
+                                      min_samples, pass_samples, block=16, want_stats=True, sum_order=None):
+        """cr_render_adaptive_region_device: the region into device memory at `d_ptr` (w*h*3 reals) and, if given, its
+        counts at `d_counts` (w*h int32).  Synchronous.  Returns the stats dict of render_adaptive_region."""
+        cd = cam.desc()
+        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
+        ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
+        reg, _ = region_arg(region)
+        st = A.CrAdaptiveStats()
+        self._check(self.lib.cr_render_adaptive_region_device(self.h, C.byref(cd), C.byref(p), C.byref(ap), reg, C.c_void_p(d_ptr),
+                                                              C.c_void_p(d_counts) if d_counts else None,
                                                               C.byref(st) if want_stats else None))
         return st.as_dict()
 

@@ -678,6 +678,54 @@ CR_API int32_t cr_render_adaptive_frames_host(CrHandle* h, const CrCameraDesc* c
                                               const CrAdaptiveParams* adaptive, const int32_t* frames, int32_t n_frames,
                                               void* h_out_rgb, int32_t* h_counts, CrAdaptiveStats* stats);
 
+/*
+ * A region of a frame to a noise target: what cr_render_region_device is to cr_render_device, for
+ * cr_render_adaptive_device.  An editor re-renders what an edit touched at the frame's own noise level, a frame beyond
+ * 2^26 pixels is rendered adaptively region by region, and a farm splits an adaptive frame by pixels across handles.
+ *
+ * Region and camera.  cam->image_width and image_height stay the whole frame's, and the RNG streams are keyed by the
+ * frame's pixel index (y0 + j) * image_width + (x0 + i), as for cr_render_region_*.  The output is width*height*3 reals,
+ * row-major; `counts` (may be NULL) receives width*height int32_t.
+ * The rule is cr_render_adaptive_device's, unchanged, applied to the region as if it were the frame: the blocks of
+ * 2^block_log2 pixels are anchored at the region's origin (x0, y0), blocks at the region's right and bottom edge are
+ * partial, N_b counts the block's pixels inside the region, S is that of params->samples.
+ *
+ * Consequences.
+ *   1. With params->samples <= 2047 every pixel is BIT FOR BIT the pixel of cr_render_region_device with
+ *      samples = counts[pixel] under CR_SUM_RELAXED, hence the pixel of the whole frame's plain render at that count.
+ *   2. Where x0 and y0 are multiples of the block's side and the region's right and bottom edge each fall on such a
+ *      multiple or on the frame's edge, the region's blocks are the frame's blocks: image and counts are BIT FOR BIT the
+ *      corresponding pixels of cr_render_adaptive_device for the same arguments, and a frame tiled by such regions is
+ *      the whole-frame adaptive frame, pixel for pixel and count for count.  Any other region is still deterministic,
+ *      but its blocks are not the frame's, so its counts may differ from the frame's.
+ *   3. A region that is the whole frame gives cr_render_adaptive_device's bytes, counts and stats.
+ *   4. stats->render's four work counters and samples are those of the region's blocks; blocks and blocks_stopped count
+ *      the region's blocks.  Over a partition that satisfies (2), samples, the counters, blocks and blocks_stopped add
+ *      up to the whole-frame call's; passes does not: the whole-frame call's is the maximum over the partition.
+ *   5. min_samples == params->samples is exactly cr_render_region_*, counters included.
+ *
+ * Refusals, all checked before anything changes (a refused call leaves the handle as it was): everything
+ * cr_render_adaptive_device refuses, with the same codes, and everything cr_render_region_device refuses about the
+ * region, with the same codes (a null `region`, sizes below 1, a negative origin, overhang with the sums formed in 64
+ * bits, more than 2^26 pixels in the region).  The frame itself may have up to 2^31 - 1 pixels, as for regions.
+ * CR_ERR_UNSUPPORTED also for a work tile named through CRUCIBLE_SG_TILE that is wider or taller than the block (the
+ * whole-frame call renders such a block on the default tile).  A pass over the region's tiles that the 32-bit work
+ * counter does not hold runs as consecutive launches of fewer samples, with the same bytes and counters, and counts once
+ * in stats->passes.  refit_boxes 0, 1 and CR_REFIT_REBUILD work: the boxes or the tree are prepared once per call.
+ *
+ * Synchronous.  The handle keeps 48 bytes per pixel of the region.  cr_export_render_bvh, cr_last_kernel_ms and
+ * cr_frame_build_info behave as after cr_render_adaptive_device.
+ */
+CR_API int32_t cr_render_adaptive_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                                const CrAdaptiveParams* adaptive, const CrRegion* region,
+                                                void* d_out_rgb, int32_t* d_counts, CrAdaptiveStats* stats);
+
+/* Same, into HOST buffers of the region's size; the Color::new check of cr_render_host applies to the region's pixels
+ * (stats->render.nan_pixels, CR_ERR_NAN). */
+CR_API int32_t cr_render_adaptive_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params,
+                                              const CrAdaptiveParams* adaptive, const CrRegion* region,
+                                              void* h_out_rgb, int32_t* h_counts, CrAdaptiveStats* stats);
+
 /* The wrapper tree the device walks for `real_type`, as BVHWrapper's shape (src/objects/bvhwrapper.rs:7-11):
  * wrapper k has boxes[6k..6k+5] = xmin,xmax,ymin,ymax,zmin,zmax (exact values of `real_type`) and
  * children[2k], children[2k+1] = left, right: >= 0 another wrapper's index, < 0 the bitwise complement of a
