@@ -1,8 +1,9 @@
-// adaptive.hip -- cr_render_adaptive_*, cr_render_adaptive_frames_* and cr_render_adaptive_region_* (include/crucible_hip.h,
-// DESIGN.md 6.11 - 6.13): a frame, a batch of frames under one pass loop, or a region of a frame judged as if it were the
-// frame, whose blocks of pixels stop taking samples once their two half-frame sums agree.  The entry points' checks, the
-// pass loop around the render kernel that launch() (render.hpp) hands over, the judge kernel (one wave per block: the difference sum, the verdict, the next list
-// of active tiles) and the finalize kernel (per-pixel means by each block's own sample count, the count plane).
+// adaptive.hip -- the adaptive family behind cr_render_adaptive_*, cr_render_adaptive_frames_* and cr_render_adaptive_region_*
+// (include/crucible_hip.h; the entry points are in api.hip): a frame, a batch of frames under one pass
+// loop, or a region of a frame judged as if it were the frame, whose blocks of pixels stop taking samples once their two
+// half-frame sums agree.  The family's argument checks, the pass loop around the render kernel that launch() (render.hpp)
+// hands over, the judge kernel (one wave per block: the difference sum, the verdict, the next list of active tiles) and the
+// finalize kernel (per-pixel means by each block's own sample count, the count plane).
 #include "handle.hpp"
 #include "adaptive.hpp"
 
@@ -212,12 +213,9 @@ int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame
     return CR_OK;
 }
 
-// the checks of cr_render_adaptive_*, in the header's order; nothing has changed when one of them refuses
-// region_call: cr_render_adaptive_region_* -- validate_render checks `region` as it does for cr_render_region_*
-static int32_t validate_adaptive(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const void* out,
-                                 const CrRegion* region = nullptr, bool region_call = false) {
-    int32_t rc = validate_render(h, cam, p, region, region_call);
-    if (rc != CR_OK) return rc;
+// The adaptive family's own checks, in the header's order, after validate_render's and before a batch's (api.hip
+// validate_call); nothing has changed when one of them refuses
+int32_t validate_adaptive(CrHandle* h, const CrRenderParams* p, const CrAdaptiveParams* ap, const void* out, const RenderCall& call) {
     if (!ap) return fail(h, CR_ERR_INVALID_ARG, "adaptive params are null");
     if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
     if (ap->block_log2 != 0 && (ap->block_log2 < 3 || ap->block_log2 > 5)) return fail(h, CR_ERR_INVALID_ARG, "block_log2 must be 0, 3, 4 or 5");
@@ -237,109 +235,9 @@ static int32_t validate_adaptive(CrHandle* h, const CrCameraDesc* cam, const CrR
     // tiles must partition blocks: a work tile that CRUCIBLE_SG_TILE names and that is wider or taller than the block is
     // refused here, where the whole-frame calls give way to the default shape
     const int32_t L = ap->block_log2 ? ap->block_log2 : 4;
-    if (region_call && (h->sg_lw > L || h->sg_lh > L))
+    if (call.region_call && (h->sg_lw > L || h->sg_lh > L))
         return fail(h, CR_ERR_UNSUPPORTED, "cr_render_adaptive_region: the work tile CRUCIBLE_SG_TILE names does not fit the adaptive block");
     return CR_OK;
 }
 
-// frames == nullptr: the one frame params->frame; else the batch `frames` (cr_render_adaptive_frames_*)
-// region != nullptr: those pixels of the one frame, judged as if they were the frame (cr_render_adaptive_region_*)
-static int32_t adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
-                               int32_t n_frames, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats, const CrRegion* region = nullptr) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    const AdaptiveRun run = {ap->min_samples, ap->pass_samples, ap->block_log2 ? ap->block_log2 : 4, ap->tolerance, d_counts, stats, region != nullptr};
-    h->cam_pending_slot = -1;
-    int32_t rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, nullptr, frames, n_frames, region, &run)
-                                             : render_typed<float>(h, cam, p, d_out, nullptr, frames, n_frames, region, &run);
-    if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
-        const hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
-        h->cam_pending_slot = -1;
-        if (e != hipSuccess && rc == CR_OK) { h->error = std::string("hipEventRecord: ") + hipGetErrorString(e); rc = CR_ERR_HIP; }
-    }
-    return rc;
-}
-
-// cr_render_adaptive_host / cr_render_adaptive_frames_host / cr_render_adaptive_region_host: render into the handle's buffers,
-// copy back, check the means frame by frame (a region's output, counts and check are of the region's pixels)
-static int32_t adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
-                             int32_t n_frames, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats, const CrRegion* region = nullptr) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n_pix = region ? (size_t)region->width * (size_t)region->height : (size_t)cam->image_width * (size_t)cam->image_height;
-    const size_t frame_bytes = n_pix * 3 * real_size(p->real_type);
-    const size_t bytes = frame_bytes * (size_t)n_frames, count_bytes = n_pix * (size_t)n_frames * sizeof(int32_t);
-    hipError_t e = h->out_buf.ensure(bytes);
-    if (e == hipSuccess && h_counts) e = h->ad_counts.ensure(count_bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
-    int32_t rc = adaptive_device(h, cam, p, ap, frames, n_frames, h->out_buf.p, h_counts ? (int32_t*)h->ad_counts.p : nullptr, stats, region);
-    if (rc != CR_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (h_counts) HIP_TRY(h, hipMemcpyAsync(h_counts, h->ad_counts.p, count_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    uint64_t bad = 0;
-    int32_t first_bad = -1;
-    for (int32_t k = 0; k < n_frames; k++) {
-        const uint64_t b = bad_pixels((const char*)h_out + (size_t)k * frame_bytes, p->real_type, n_pix);
-        if (b && first_bad < 0) first_bad = k;
-        bad += b;
-    }
-    if (stats) stats->render.nan_pixels = bad;
-    if (bad && !frames) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
-    if (bad)
-        return fail(h, CR_ERR_NAN, "frame " + std::to_string(frames[first_bad]) + " (entry " + std::to_string(first_bad) +
-                                       " of the batch): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
-    return CR_OK;
-}
-
-// the checks of cr_render_adaptive_frames_*: a single call's, then the batch's own
-static int32_t validate_adaptive_frames(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, const int32_t* frames,
-                                        int32_t n_frames, const void* out) {
-    const int32_t rc = validate_adaptive(h, cam, p, ap, out);
-    if (rc != CR_OK) return rc;
-    if (!frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
-    if (n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
-    return CR_OK;
-}
-
 }   // namespace cr
-
-using namespace cr;
-
-extern "C" {
-
-int32_t cr_render_adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* d_out,
-                                  int32_t* d_counts, CrAdaptiveStats* stats) {
-    const int32_t rc = validate_adaptive(h, cam, p, ap, d_out);
-    return rc != CR_OK ? rc : adaptive_device(h, cam, p, ap, nullptr, 1, d_out, d_counts, stats);
-}
-
-int32_t cr_render_adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* h_out,
-                                int32_t* h_counts, CrAdaptiveStats* stats) {
-    const int32_t rc = validate_adaptive(h, cam, p, ap, h_out);
-    return rc != CR_OK ? rc : adaptive_host(h, cam, p, ap, nullptr, 1, h_out, h_counts, stats);
-}
-
-int32_t cr_render_adaptive_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
-                                         const CrRegion* region, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
-    const int32_t rc = validate_adaptive(h, cam, p, ap, d_out, region, true);
-    return rc != CR_OK ? rc : adaptive_device(h, cam, p, ap, nullptr, 1, d_out, d_counts, stats, region);
-}
-
-int32_t cr_render_adaptive_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
-                                       const CrRegion* region, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
-    const int32_t rc = validate_adaptive(h, cam, p, ap, h_out, region, true);
-    return rc != CR_OK ? rc : adaptive_host(h, cam, p, ap, nullptr, 1, h_out, h_counts, stats, region);
-}
-
-int32_t cr_render_adaptive_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
-                                         const int32_t* frames, int32_t n_frames, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
-    const int32_t rc = validate_adaptive_frames(h, cam, p, ap, frames, n_frames, d_out);
-    return rc != CR_OK ? rc : adaptive_device(h, cam, p, ap, frames, n_frames, d_out, d_counts, stats);
-}
-
-int32_t cr_render_adaptive_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
-                                       const int32_t* frames, int32_t n_frames, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
-    const int32_t rc = validate_adaptive_frames(h, cam, p, ap, frames, n_frames, h_out);
-    return rc != CR_OK ? rc : adaptive_host(h, cam, p, ap, frames, n_frames, h_out, h_counts, stats);
-}
-
-}   // extern "C"

@@ -46,13 +46,15 @@ __global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long l
     if (layers & CR_AOV_COVERAGE) o[i] = value(kAovCoverage);
 }
 
-// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_aov_frames_*):
-// the batch's frames lie one behind the other in the accumulators, in the flags and in the output.  region: the pixels
+// One frame (call.frames == nullptr: params->frame), or the frames call.frames in one batch (cr_render_aov_frames_*):
+// the batch's frames lie one behind the other in the accumulators, in the flags and in the output.  call.region: the pixels
 // of the one frame that the pass covers (cr_render_aov_region_*) -- accumulators, flags and planes are then the region's
 // size, and the pass runs as a batch of one frame on the BATCH kernels, which carry the region's offsets.
 template <typename real>
-int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats, const int32_t* frames,
-                  int32_t n_frames, const CrRegion* region) {
+int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, void* d_out, CrStats* stats) {
+    const int32_t* const frames = call.frames;
+    const CrRegion* const region = call.region;
+    const int32_t n_frames = call.n_frames, layers = call.layers;
     DevScene<real>* walk = nullptr;
     bool refit = false;
     int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // as a render decides it
@@ -61,7 +63,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
                                            "(render such frames one at a time)");
     DevScene<real>& ds = *walk;
-    const size_t frame_pix = region ? (size_t)region->width * (size_t)region->height : (size_t)cd->image_width * (size_t)cd->image_height;
+    const size_t frame_pix = call.frame_pixels(cd);
     const size_t npix = frame_pix * (size_t)n_frames;   // (at most 2^26 * 2^31: the byte counts below fit in 64 bits)
     hipError_t e = h->aov_acc.ensure(npix * kAovWords * sizeof(unsigned long long));
     if (e == hipSuccess) e = h->aov_flags.ensure(npix * sizeof(uint32_t));
@@ -74,7 +76,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         FrameBatch<real> fb;
         std::vector<real> times;
         // the walk is the megakernel's under every pipeline setting: the cross-check pipelines have no guide pass of their own
-        rc = prepare_args<real>(h, cd, p, ds, refit, true, d_out, frames, n_frames, times, a.k, w, fb, region);
+        rc = prepare_args<real>(h, cd, p, call, ds, refit, true, d_out, times, a.k, w, fb);
         if (rc != CR_OK) return rc;
         if (region) {   // the BATCH kernels read a frame's first ray time from the device's table
             rc = stage_frame_times(h, &a.k.current_time, sizeof(real));
@@ -100,8 +102,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         rc = aov_ladder<real>(h, a, ds, w, &res);
         if (rc != CR_OK) return rc;
     }
-    const size_t frame_reals = frame_pix * (size_t)((layers & CR_AOV_ALBEDO ? 3 : 0) + (layers & CR_AOV_NORMAL ? 3 : 0) + (layers & CR_AOV_DEPTH ? 1 : 0) +
-                                                    (layers & CR_AOV_COVERAGE ? 1 : 0));
+    const size_t frame_reals = frame_pix * call.layer_channels();
     for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += 65535) {   // (a grid has at most 65535 rows)
         const size_t fn = std::min<size_t>(65535, (size_t)n_frames - f0);
         hipLaunchKernelGGL((aov_finalize_kernel<real>), dim3((unsigned)((frame_pix + 255) / 256), (unsigned)fn), dim3(256), 0, h->stream,
@@ -113,7 +114,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
     return stats ? finish_stats(h, stats, (uint64_t)npix * (uint64_t)p->sample_count, ds.n_entries, res) : CR_OK;
 }
 
-template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
-template int32_t aov_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, int32_t, void*, CrStats*, const int32_t*, int32_t, const CrRegion*);
+template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, const RenderCall&, void*, CrStats*);
+template int32_t aov_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, const RenderCall&, void*, CrStats*);
 
 }   // namespace cr

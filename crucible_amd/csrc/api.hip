@@ -1,5 +1,6 @@
 // api.hip -- the handle's life and the render entry points of include/crucible_hip.h: cr_create reads the CRUCIBLE_*
-// knobs, cr_render_* validate and hand over to render_typed (render.hip) or aov_typed (aov.hip); the error strings behind cr_last_error.
+// knobs; every cr_render_* entry point builds a RenderCall (handle.hpp), which is checked once and handed to render_typed
+// (render.hip) or aov_typed (aov.hip) once, into device or host memory; the error strings behind cr_last_error.
 //
 // Nothing here falls back to a CPU renderer: without a HIP device cr_create fails.
 #include "handle.hpp"
@@ -55,18 +56,35 @@ int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
     return CR_OK;
 }
 
-// cr_render_device / cr_render_frames_device after their own argument checks (frames == nullptr: params->frame)
-// layers != 0: the guide pass of cr_render_aov_* instead of the render
-// region != nullptr: those pixels of the one frame (cr_render_region_*, cr_render_aov_region_*)
-static int32_t render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats,
-                      const int32_t* frames, int32_t n_frames, int32_t layers = 0, const CrRegion* region = nullptr) {
+// The checks of every cr_render_* entry point: a render's, then the family's own in the order each family has had them --
+// a call with two faults reports the first.  render: frames, n_frames, out, the region's sum order.  guide layers: frames,
+// n_frames, the layer mask, out, the fixed-point refusal.  adaptive: validate_adaptive's (out among them), then frames, n_frames.
+static int32_t validate_call(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const RenderCall& call, const void* out,
+                             const CrAdaptiveParams* ap) {
+    int32_t rc = validate_render(h, cam, p, call.region, call.region_call);
+    if (rc != CR_OK) return rc;
+    if (call.family == kCallAdaptive && (rc = validate_adaptive(h, p, ap, out, call)) != CR_OK) return rc;
+    if (call.batch && !call.frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
+    if (call.batch && call.n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
+    if (call.family == kCallAdaptive) return CR_OK;
+    const int32_t all = CR_AOV_ALBEDO | CR_AOV_NORMAL | CR_AOV_DEPTH | CR_AOV_COVERAGE;
+    if (call.family == kCallGuide && (call.layers == 0 || (call.layers & ~all))) return fail(h, CR_ERR_INVALID_ARG, "layers must be a non-empty mask of CR_AOV_*");
+    if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
+    if (call.family == kCallGuide && p->output_sum == CR_OUTPUT_FIXED_SUM)
+        return fail(h, CR_ERR_UNSUPPORTED, "guide layers come as reals (output_sum 0 or 1), not as fixed-point words");
+    if (call.family == kCallRender && call.region_call && (resolve_sum_order(h, p) != CR_SUM_RELAXED || h->pipeline != 0))
+        return fail(h, CR_ERR_UNSUPPORTED, "cr_render_region needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
+                                           "sequential over samples; the region's offsets live in the relaxed kernels)");
+    return CR_OK;
+}
+
+// A checked call into device memory: the family's typed function of the params' precision, then the camera-key slot's release
+static int32_t call_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const RenderCall& call, void* d_out, CrStats* stats) {
     HIP_TRY(h, hipSetDevice(h->device));
     h->cam_pending_slot = -1;
-    int32_t rc;
-    if (layers) rc = p->real_type == CR_REAL_F64 ? aov_typed<double>(h, cam, p, layers, d_out, stats, frames, n_frames, region)
-                                                     : aov_typed<float>(h, cam, p, layers, d_out, stats, frames, n_frames, region);
-    else rc = p->real_type == CR_REAL_F64 ? render_typed<double>(h, cam, p, d_out, stats, frames, n_frames, region)
-                                          : render_typed<float>(h, cam, p, d_out, stats, frames, n_frames, region);
+    const bool f64 = p->real_type == CR_REAL_F64;
+    int32_t rc = call.layers ? (f64 ? aov_typed<double>(h, cam, p, call, d_out, stats) : aov_typed<float>(h, cam, p, call, d_out, stats))
+                             : (f64 ? render_typed<double>(h, cam, p, call, d_out, stats) : render_typed<float>(h, cam, p, call, d_out, stats));
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
         hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
         h->cam_pending_slot = -1;
@@ -89,77 +107,79 @@ uint64_t bad_pixels(const void* rgb, int32_t real_type, size_t n_pix) {
     return bad;
 }
 
-// cr_render_host / cr_render_frames_host: render into the handle's buffer, copy back, check the means frame by frame
-static int32_t render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* h_out, CrStats* stats,
-                    const int32_t* frames, int32_t n_frames, const CrRegion* region = nullptr) {
+// A checked call into host memory: into the handle's buffers (the output's; the counts' when an adaptive call asks for
+// them), copy back, and where the family's output is a frame of colour means, check them frame by frame
+static int32_t call_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, RenderCall call, void* h_out, CrStats* stats) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (region ? (size_t)region->width * region->height : (size_t)cam->image_width * cam->image_height) * 3;   // reals (or words) per frame
-    const size_t frame_bytes = n * (p->output_sum == CR_OUTPUT_FIXED_SUM ? sizeof(uint64_t) : real_size(p->real_type));
-    const size_t bytes = frame_bytes * (size_t)n_frames;
-    const hipError_t e = h->out_buf.ensure(bytes);
+    const size_t n_pix = call.frame_pixels(cam), frame_bytes = call.frame_bytes(cam, p);
+    const size_t bytes = frame_bytes * (size_t)call.n_frames, count_bytes = n_pix * (size_t)call.n_frames * sizeof(int32_t);
+    AdaptiveRun run = {};            // the caller's run with the counts in the handle's buffer
+    int32_t* h_counts = nullptr;
+    hipError_t e = h->out_buf.ensure(bytes);
+    if (call.adaptive) {
+        run = *call.adaptive;
+        h_counts = run.d_counts;
+        if (e == hipSuccess && h_counts) e = h->ad_counts.ensure(count_bytes);
+        run.d_counts = h_counts ? (int32_t*)h->ad_counts.p : nullptr;
+        call.adaptive = &run;
+    }
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
+    // a render whose caller gave no stats runs with a local CrStats; guide layers and adaptive calls pass the null on
     CrStats local;
-    int32_t rc = render_device(h, cam, p, h->out_buf.p, stats ? stats : &local, frames, n_frames, 0, region);
+    const bool render = call.family == kCallRender;
+    int32_t rc = call_device(h, cam, p, call, h->out_buf.p, render && !stats ? &local : stats);
     if (rc != CR_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h_counts) HIP_TRY(h, hipMemcpyAsync(h_counts, h->ad_counts.p, count_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!p->output_sum) {
-        uint64_t bad = 0;
-        int32_t first_bad = -1;
-        for (int32_t k = 0; k < n_frames; k++) {
-            const uint64_t b = bad_pixels((const char*)h_out + (size_t)k * frame_bytes, p->real_type, n / 3);
-            if (b && first_bad < 0) first_bad = k;
-            bad += b;
-        }
-        if (stats) stats->nan_pixels = bad;
-        if (bad && !frames) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
-        if (bad)
-            return fail(h, CR_ERR_NAN, "frame " + std::to_string(frames[first_bad]) + " (entry " + std::to_string(first_bad) +
-                                           " of the batch): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+    // the pixel check is for colour means: guide layers have none, and a render's sums (output_sum != 0; an adaptive
+    // call's is 0) are not means
+    if (call.layers || p->output_sum) return CR_OK;
+    uint64_t bad = 0;
+    int32_t first_bad = -1;
+    for (int32_t k = 0; k < call.n_frames; k++) {
+        const uint64_t b = bad_pixels((const char*)h_out + (size_t)k * frame_bytes, p->real_type, n_pix);
+        if (b && first_bad < 0) first_bad = k;
+        bad += b;
     }
+    // nan_pixels lands in the render's CrStats, or in the CrStats inside the adaptive call's
+    CrStats* const into = !call.adaptive ? stats : (run.stats ? &run.stats->render : nullptr);
+    if (into) into->nan_pixels = bad;
+    if (bad && !call.frames) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+    if (bad)
+        return fail(h, CR_ERR_NAN, "frame " + std::to_string(call.frames[first_bad]) + " (entry " + std::to_string(first_bad) +
+                                       " of the batch): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
     return CR_OK;
 }
 
-// The four cr_render_* entry points: their argument checks in one order, then the render (batch: `frames` is checked too)
-// region_call: cr_render_region_* (`region` is checked too, and what a region render needs of the handle and the params)
-static int32_t render_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, bool batch, const int32_t* frames, int32_t n_frames,
-                            bool host, void* out, CrStats* stats, const CrRegion* region = nullptr, bool region_call = false) {
-    int32_t rc = validate_render(h, cam, p, region, region_call);
+// What an adaptive entry point was given beside a render's arguments
+struct AdaptiveAsk {
+    const CrAdaptiveParams* ap = nullptr;
+    int32_t* counts = nullptr;          // may be null; device or host memory as the output is
+    CrAdaptiveStats* stats = nullptr;   // may be null
+};
+
+constexpr bool kDevice = false, kHost = true;   // run_call's `host`
+
+// Every cr_render_* entry point: the checks, then the call into device or host memory (an adaptive call's stats are `ask`'s)
+static int32_t run_call(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, RenderCall call, bool host, void* out, CrStats* stats,
+                        const AdaptiveAsk& ask = {}) {
+    const int32_t rc = validate_call(h, cam, p, call, out, ask.ap);
     if (rc != CR_OK) return rc;
-    if (batch && !frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
-    if (batch && n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
-    if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
-    if (region_call && (resolve_sum_order(h, p) != CR_SUM_RELAXED || h->pipeline != 0))
-        return fail(h, CR_ERR_UNSUPPORTED, "cr_render_region needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
-                                           "sequential over samples; the region's offsets live in the relaxed kernels)");
-    return host ? render_host(h, cam, p, out, stats, frames, n_frames, region) : render_device(h, cam, p, out, stats, frames, n_frames, 0, region);
+    AdaptiveRun run = {};
+    if (call.family == kCallAdaptive) {
+        run = {ask.ap->min_samples, ask.ap->pass_samples, ask.ap->block_log2 ? ask.ap->block_log2 : 4, ask.ap->tolerance, ask.counts, ask.stats, call.region != nullptr};
+        call.adaptive = &run;
+    }
+    return host ? call_host(h, cam, p, call, out, stats) : call_device(h, cam, p, call, out, stats);
 }
 
-// cr_render_aov_*, cr_render_aov_frames_* (batch: `frames` is checked too): a render's argument checks, then the pass's
-// own; the host form goes through the handle's output buffer
-static int32_t aov_entry(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, bool batch, const int32_t* frames, int32_t n_frames,
-                         bool host, void* out, CrStats* stats, const CrRegion* region = nullptr, bool region_call = false) {
-    int32_t rc = validate_render(h, cam, p, region, region_call);
-    if (rc != CR_OK) return rc;
-    if (batch && !frames) return fail(h, CR_ERR_INVALID_ARG, "frames is null");
-    if (batch && n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
-    const int32_t all = CR_AOV_ALBEDO | CR_AOV_NORMAL | CR_AOV_DEPTH | CR_AOV_COVERAGE;
-    if (layers == 0 || (layers & ~all)) return fail(h, CR_ERR_INVALID_ARG, "layers must be a non-empty mask of CR_AOV_*");
-    if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
-    if (p->output_sum == CR_OUTPUT_FIXED_SUM) return fail(h, CR_ERR_UNSUPPORTED, "guide layers come as reals (output_sum 0 or 1), not as fixed-point words");
-    if (!host) return render_device(h, cam, p, out, stats, frames, n_frames, layers, region);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t channels = (layers & CR_AOV_ALBEDO ? 3 : 0) + (layers & CR_AOV_NORMAL ? 3 : 0) + (layers & CR_AOV_DEPTH ? 1 : 0) + (layers & CR_AOV_COVERAGE ? 1 : 0);
-    const size_t frame_pix = region ? (size_t)region->width * region->height : (size_t)cam->image_width * cam->image_height;
-    const size_t bytes = (size_t)n_frames * frame_pix * channels * real_size(p->real_type);
-    const hipError_t e = h->out_buf.ensure(bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
-    rc = render_device(h, cam, p, h->out_buf.p, stats, frames, n_frames, layers, region);
-    if (rc != CR_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CR_OK;
-}
+// The descriptors the entry points start from: the shape, then the family
+static RenderCall one_frame() { return RenderCall(); }
+static RenderCall batch_of(const int32_t* frames, int32_t n_frames) { RenderCall c; c.frames = frames; c.n_frames = n_frames; c.batch = true; return c; }
+static RenderCall region_of(const CrRegion* region) { RenderCall c; c.region = region; c.region_call = true; return c; }
+static RenderCall guide(RenderCall c, int32_t layers) { c.family = kCallGuide; c.layers = layers; return c; }
+static RenderCall adaptive(RenderCall c) { c.family = kCallAdaptive; return c; }
 
 }   // namespace cr
 
@@ -252,58 +272,91 @@ void cr_destroy(CrHandle* h) {
     delete h;
 }
 
+// The eighteen render entry points: three families (render, guide layers, adaptive) in three shapes (one frame, a batch
+// of frames, a region of a frame) into device or host memory -- each a RenderCall and where its results go.
+
 int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats) {
-    return render_entry(h, cam, p, false, nullptr, 1, false, d_out, stats);
+    return run_call(h, cam, p, one_frame(), kDevice, d_out, stats);
 }
 
 int32_t cr_render_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* h_out, CrStats* stats) {
-    return render_entry(h, cam, p, false, nullptr, 1, true, h_out, stats);
+    return run_call(h, cam, p, one_frame(), kHost, h_out, stats);
 }
 
 int32_t cr_render_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
                                 void* d_out, CrStats* stats) {
-    return render_entry(h, cam, p, true, frames, n_frames, false, d_out, stats);
+    return run_call(h, cam, p, batch_of(frames, n_frames), kDevice, d_out, stats);
 }
 
 int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
                               void* h_out, CrStats* stats) {
-    return render_entry(h, cam, p, true, frames, n_frames, true, h_out, stats);
+    return run_call(h, cam, p, batch_of(frames, n_frames), kHost, h_out, stats);
+}
+
+int32_t cr_render_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, void* d_out, CrStats* stats) {
+    return run_call(h, cam, p, region_of(region), kDevice, d_out, stats);
+}
+
+int32_t cr_render_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, void* h_out, CrStats* stats) {
+    return run_call(h, cam, p, region_of(region), kHost, h_out, stats);
 }
 
 int32_t cr_render_aov_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, false, nullptr, 1, false, d_out, stats);
+    return run_call(h, cam, p, guide(one_frame(), layers), kDevice, d_out, stats);
 }
 
 int32_t cr_render_aov_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, void* h_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, false, nullptr, 1, true, h_out, stats);
+    return run_call(h, cam, p, guide(one_frame(), layers), kHost, h_out, stats);
 }
 
 int32_t cr_render_aov_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames, int32_t n_frames,
                                     void* d_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, true, frames, n_frames, false, d_out, stats);
+    return run_call(h, cam, p, guide(batch_of(frames, n_frames), layers), kDevice, d_out, stats);
 }
 
 int32_t cr_render_aov_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames, int32_t n_frames,
                                   void* h_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, true, frames, n_frames, true, h_out, stats);
-}
-
-int32_t cr_render_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, void* d_out, CrStats* stats) {
-    return render_entry(h, cam, p, false, nullptr, 1, false, d_out, stats, region, true);
-}
-
-int32_t cr_render_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, void* h_out, CrStats* stats) {
-    return render_entry(h, cam, p, false, nullptr, 1, true, h_out, stats, region, true);
+    return run_call(h, cam, p, guide(batch_of(frames, n_frames), layers), kHost, h_out, stats);
 }
 
 int32_t cr_render_aov_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,
                                     void* d_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, false, nullptr, 1, false, d_out, stats, region, true);
+    return run_call(h, cam, p, guide(region_of(region), layers), kDevice, d_out, stats);
 }
 
 int32_t cr_render_aov_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,
                                   void* h_out, CrStats* stats) {
-    return aov_entry(h, cam, p, layers, false, nullptr, 1, true, h_out, stats, region, true);
+    return run_call(h, cam, p, guide(region_of(region), layers), kHost, h_out, stats);
+}
+
+int32_t cr_render_adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* d_out,
+                                  int32_t* d_counts, CrAdaptiveStats* stats) {
+    return run_call(h, cam, p, adaptive(one_frame()), kDevice, d_out, nullptr, {ap, d_counts, stats});
+}
+
+int32_t cr_render_adaptive_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* h_out,
+                                int32_t* h_counts, CrAdaptiveStats* stats) {
+    return run_call(h, cam, p, adaptive(one_frame()), kHost, h_out, nullptr, {ap, h_counts, stats});
+}
+
+int32_t cr_render_adaptive_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                         const int32_t* frames, int32_t n_frames, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
+    return run_call(h, cam, p, adaptive(batch_of(frames, n_frames)), kDevice, d_out, nullptr, {ap, d_counts, stats});
+}
+
+int32_t cr_render_adaptive_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                       const int32_t* frames, int32_t n_frames, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
+    return run_call(h, cam, p, adaptive(batch_of(frames, n_frames)), kHost, h_out, nullptr, {ap, h_counts, stats});
+}
+
+int32_t cr_render_adaptive_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                         const CrRegion* region, void* d_out, int32_t* d_counts, CrAdaptiveStats* stats) {
+    return run_call(h, cam, p, adaptive(region_of(region)), kDevice, d_out, nullptr, {ap, d_counts, stats});
+}
+
+int32_t cr_render_adaptive_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap,
+                                       const CrRegion* region, void* h_out, int32_t* h_counts, CrAdaptiveStats* stats) {
+    return run_call(h, cam, p, adaptive(region_of(region)), kHost, h_out, nullptr, {ap, h_counts, stats});
 }
 
 int32_t cr_fixed_sums_to_rgb(CrHandle* h, const uint64_t* d_sums, int32_t width, int32_t height, int32_t samples, int32_t real_type,

@@ -12,8 +12,8 @@
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
 //   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
-//   adaptive.hip       cr_render_adaptive_*, cr_render_adaptive_frames_*: the pass loop, the judge and finalize kernels (adaptive.hpp)
-//   api.hip            cr_create / cr_destroy, cr_render_*, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
+//   adaptive.hip       the adaptive family behind its entry points: its argument checks, the pass loop, the judge and finalize kernels (adaptive.hpp)
+//   api.hip            cr_create / cr_destroy, all cr_render_* entry points over one RenderCall, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
 #pragma once
 #include "../../include/crucible_hip.h"
 #include "pathtrace.hpp"
@@ -272,6 +272,31 @@ struct AdaptiveFrame {
 using AdaptivePass = std::function<int32_t(int32_t f0, int32_t fn, const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc)>;
 int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame& fr, const AdaptivePass& pass);
 
+// What one cr_render_* call covers, as its entry point settled it (api.hip) and as render_typed, aov_typed and prepare_args
+// take it.  A new shape or family is a field here, not a parameter of every function underneath.
+enum CallFamily { kCallRender, kCallGuide, kCallAdaptive };
+struct RenderCall {
+    // the shape
+    const int32_t* frames = nullptr;          // a batch's frame indices; nullptr: the one frame params->frame, and n_frames is 1
+    int32_t n_frames = 1;
+    const CrRegion* region = nullptr;         // the pixels of the one frame that the call covers; nullptr: the whole frame
+    bool batch = false, region_call = false;  // the entry point is a cr_render_*_frames_* / cr_render_*_region_* call: the checks ask, the pointer may be null
+    // the family
+    CallFamily family = kCallRender;          // the entry point's: the checks ask before `layers` and `adaptive` can tell
+    int32_t layers = 0;                       // the guide pass's CR_AOV_* mask; 0: a render
+    const AdaptiveRun* adaptive = nullptr;    // a render to a noise target (adaptive.hip); nullptr: all samples of every pixel
+
+    size_t frame_pixels(const CrCameraDesc* cd) const {   // of one frame of the output
+        return region ? (size_t)region->width * (size_t)region->height : (size_t)cd->image_width * (size_t)cd->image_height;
+    }
+    size_t layer_channels() const {   // reals per pixel of the planes `layers` names
+        return (size_t)((layers & CR_AOV_ALBEDO ? 3 : 0) + (layers & CR_AOV_NORMAL ? 3 : 0) + (layers & CR_AOV_DEPTH ? 1 : 0) + (layers & CR_AOV_COVERAGE ? 1 : 0));
+    }
+    size_t frame_bytes(const CrCameraDesc* cd, const CrRenderParams* p) const {   // of one frame of the output: reals, or a render's fixed-point words
+        return frame_pixels(cd) * (layers ? layer_channels() : 3) * (p->output_sum == CR_OUTPUT_FIXED_SUM ? sizeof(uint64_t) : real_size(p->real_type));
+    }
+};
+
 // What render_typed settled before the residency ladder (render.hpp)
 struct WalkChoice {
     bool anim, cam_keys;            // the kernel kind: keyed primitives, camera keys alone, neither
@@ -328,12 +353,10 @@ int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_lar
                    const char* what, int& block, int& per_cu);
 int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes);   // ray times into the handle's device table (times_dev), in stream order
 template <typename real>
-int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames,
-                     const CrRegion* region = nullptr, const AdaptiveRun* adaptive = nullptr);
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, void* d_out, CrStats* stats);
 template <typename real>
-int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, DevScene<real>& ds, bool refit, bool mega, void* d_out,
-                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb,
-                     const CrRegion* region = nullptr);
+int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, DevScene<real>& ds, bool refit, bool mega,
+                     void* d_out, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb);
 // render_f32_reference.hip, render_f32_relaxed.hip, render_f64_reference.hip, render_f64_relaxed.hip (render.hpp)
 template <typename real, bool ORD, bool RELAX>
 int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb);
@@ -343,10 +366,11 @@ int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size
 template <typename real> int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>& ds, bool anim, CrStats* stats);
 template <typename real> int32_t render_queue(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, bool anim, CrStats* stats, bool* launched);
 int32_t check_queue_abort(CrHandle* h);
-// aov.hip: the guide pass (cr_render_aov_*, cr_render_aov_frames_*) after its argument checks; aov_f32.hip, aov_f64.hip: its kernels (aov.hpp)
+// aov.hip: the guide pass (call.layers) after its argument checks; aov_f32.hip, aov_f64.hip: its kernels (aov.hpp)
 template <typename real>
-int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, int32_t layers, void* d_out, CrStats* stats, const int32_t* frames,
-                  int32_t n_frames, const CrRegion* region = nullptr);
+int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, void* d_out, CrStats* stats);
+// adaptive.hip: the adaptive family's own argument checks, after validate_render's
+int32_t validate_adaptive(CrHandle* h, const CrRenderParams* p, const CrAdaptiveParams* ap, const void* out, const RenderCall& call);
 // api.hip
 int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region = nullptr, bool region_call = false);
 int32_t fixed_sums_to_rgb(CrHandle* h, const unsigned long long* sums, size_t n, int32_t samples, bool f64, void* out);

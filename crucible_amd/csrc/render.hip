@@ -68,12 +68,13 @@ int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
 // What a render settles before its kernels are chosen, shared with the guide pass (aov.hip): the kernel arguments (scene
 // tables, camera and its key slot, sample range, ray times -- of a batch's frames too --, this frame's refitted boxes and
 // screening records, the walk's scheduling knobs) and the kernel kind.  mega: the walk runs in a megakernel-style kernel
-// (screening records, parked leaves); the cross-check pipelines walk without either.  region: the pixels of the frame that
-// the launch covers (cr_render_region_*, cr_render_aov_region_*); nullptr: all of them.
+// (screening records, parked leaves); the cross-check pipelines walk without either.  call: its frames and the pixels of
+// the frame that the launch covers (call.region; nullptr: all of them).
 template <typename real>
-int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, DevScene<real>& ds, bool refit, bool mega, void* d_out,
-                     const int32_t* frames, int32_t n_frames, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb,
-                     const CrRegion* region) {
+int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, DevScene<real>& ds, bool refit, bool mega,
+                     void* d_out, std::vector<real>& times, KernelArgs<real>& a, WalkChoice& w, FrameBatch<real>& fb) {
+    const int32_t* const frames = call.frames;
+    const CrRegion* const region = call.region;
     memset(&a, 0, sizeof a);
     a.entries = (const Entry<real>*)ds.entries.p; a.prims = (const Prim<real>*)ds.prims.p; a.leaf_runs = ds.has_leaf_runs ? (const int32_t*)ds.leaf_runs.p : nullptr;
     a.mats = (const Mat<real>*)ds.mats.p; a.texs = (const Tex<real>*)ds.texs.p;
@@ -124,13 +125,13 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.output_sum = p->output_sum;
     a.exact_boxes = (!refit && ds.nan_planes) ? 1 : 0;   // the boxes of a refit hold no NaN (refit.hpp box_is_number)
     if (frames) {   // each frame's times as a single render of it computes them (the shutter is the same for all)
-        times.resize((size_t)n_frames);
+        times.resize((size_t)call.n_frames);
         CrRenderParams q = *p;
-        for (int32_t k = 0; k < n_frames; k++) { q.frame = frames[k]; frame_times(&q, times[(size_t)k], a.shutter_length); }
+        for (int32_t k = 0; k < call.n_frames; k++) { q.frame = frames[k]; frame_times(&q, times[(size_t)k], a.shutter_length); }
         int32_t rc = stage_frame_times(h, times.data(), times.size() * sizeof(real));
         if (rc != CR_OK) return rc;
         a.current_time = times[0];
-        fb.n = n_frames; fb.times = times.data(); fb.d_times = (const real*)h->times_dev.p;
+        fb.n = call.n_frames; fb.times = times.data(); fb.d_times = (const real*)h->times_dev.p;
     }
     if (refit) {   // refit.hpp: wrapper boxes for this frame's ray times [current_time, current_time + shutter_length]
         const size_t bytes = (size_t)ds.n_entries * ds.entry_bytes;
@@ -176,23 +177,22 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     return CR_OK;
 }
 
-// One frame (frames == nullptr: params->frame), or the n_frames frames `frames` in one batch (cr_render_frames_*), or the
-// pixels `region` of one frame (cr_render_region_*, whose entry has checked the sum order and the pipeline), or one frame to
-// a noise target (cr_render_adaptive_*, whose entry has checked the same: `adaptive`, adaptive.hip), or a batch of frames
-// to one (cr_render_adaptive_frames_*: `adaptive` with `frames`; a batch's rules hold, refit boxes among them).
+// One frame (call.frames == nullptr: params->frame), or the frames call.frames in one batch (cr_render_frames_*), or the
+// pixels call.region of one frame (cr_render_region_*, whose entry has checked the sum order and the pipeline), or one frame
+// to a noise target (cr_render_adaptive_*, whose entry has checked the same: call.adaptive, adaptive.hip), or a batch of
+// frames to one (cr_render_adaptive_frames_*: call.adaptive with call.frames; a batch's rules hold, refit boxes among them).
 template <typename real>
-int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, void* d_out, CrStats* stats, const int32_t* frames, int32_t n_frames,
-                     const CrRegion* region, const AdaptiveRun* adaptive) {
+int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, void* d_out, CrStats* stats) {
     DevScene<real>* walk = nullptr;
     bool refit = false;
-    int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // the base tree, or the frame's own (CR_REFIT_REBUILD)
+    int32_t rc = select_tree<real>(h, p, call.frames != nullptr, &walk, &refit);   // the base tree, or the frame's own (CR_REFIT_REBUILD)
     if (rc != CR_OK) return rc;
     DevScene<real>& ds = *walk;
     const int sum_order = resolve_sum_order(h, p);
     const bool fixed = p->output_sum == CR_OUTPUT_FIXED_SUM;
     if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
         return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
-    if (frames) {
+    if (call.frames) {
         if (sum_order != CR_SUM_RELAXED || h->pipeline != 0)
             return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
                                                "sequential over samples and would need a per-sample buffer per frame)");
@@ -203,8 +203,7 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     if (p->sample_count == 0) {
         // An empty shard (more ranks than samples): the sum of no samples, and 0 / samples for the mean, are both
         // zero -- cast_ray's loop body never runs (ray_casting.rs:82).  No kernel is launched.
-        const size_t frame_pix = region ? (size_t)region->width * (size_t)region->height : (size_t)cd->image_width * (size_t)cd->image_height;
-        const size_t bytes = (size_t)n_frames * frame_pix * 3 * (fixed ? sizeof(unsigned long long) : sizeof(real));
+        const size_t bytes = (size_t)call.n_frames * call.frame_bytes(cd, p);
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
         HIP_TRY(h, hipMemsetAsync(d_out, 0, bytes, h->stream));
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -214,9 +213,9 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     WalkChoice w;
     FrameBatch<real> fb;
     std::vector<real> times;
-    rc = prepare_args<real>(h, cd, p, ds, refit, h->pipeline == 0, d_out, frames, n_frames, times, a, w, fb, region);
+    rc = prepare_args<real>(h, cd, p, call, ds, refit, h->pipeline == 0, d_out, times, a, w, fb);
     if (rc != CR_OK) return rc;
-    if (adaptive) { fb.ad = adaptive; w.cam_keys = true; }   // the active-tile list lives where the region's offsets do: a scene without keys runs on CAMK
+    if (call.adaptive) { fb.ad = call.adaptive; w.cam_keys = true; }   // the active-tile list lives where the region's offsets do: a scene without keys runs on CAMK
     dev_scene<real>(h).last_walk = walk != &dev_scene<real>(h) ? kWalkFrame : (refit ? kWalkRefit : kWalkBase);
     // relaxed sums exist in the megakernel; the alternative pipelines are reference-order cross-checks
     if (sum_order == CR_SUM_RELAXED && h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_SUM_RELAXED is implemented by the megakernel pipeline only");
@@ -237,9 +236,9 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     return relax ? walk_ladder<real, false, true>(h, a, ds, w, stats, fb) : walk_ladder<real, false, false>(h, a, ds, w, stats, fb);
 }
 
-template int32_t prepare_args<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<float>&, bool, bool, void*, const int32_t*, int32_t, std::vector<float>&, KernelArgs<float>&, WalkChoice&, FrameBatch<float>&, const CrRegion*);
-template int32_t prepare_args<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, DevScene<double>&, bool, bool, void*, const int32_t*, int32_t, std::vector<double>&, KernelArgs<double>&, WalkChoice&, FrameBatch<double>&, const CrRegion*);
-template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*, const AdaptiveRun*);
-template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, void*, CrStats*, const int32_t*, int32_t, const CrRegion*, const AdaptiveRun*);
+template int32_t prepare_args<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, const RenderCall&, DevScene<float>&, bool, bool, void*, std::vector<float>&, KernelArgs<float>&, WalkChoice&, FrameBatch<float>&);
+template int32_t prepare_args<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, const RenderCall&, DevScene<double>&, bool, bool, void*, std::vector<double>&, KernelArgs<double>&, WalkChoice&, FrameBatch<double>&);
+template int32_t render_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, const RenderCall&, void*, CrStats*);
+template int32_t render_typed<double>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, const RenderCall&, void*, CrStats*);
 
 }   // namespace cr

@@ -99,28 +99,33 @@ class Renderer:
         self._check(self.lib.cr_update_primitives(self.h, idx, v.ctypes.data_as(C.POINTER(C.c_double)), n,
                                                   A.CR_UPDATE_REBUILD if rebuild else A.CR_UPDATE_REFIT))
 
+    def _args(self, cam, seed, real_type, sample_begin=0, sample_count=None, output_sum=False, sum_order=None):
+        """(CrCameraDesc, CrRenderParams) of a call; sum_order=None: this renderer's."""
+        return cam.desc(), cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
+
+    def _call(self, name, args, *rest, want_stats, stats=A.CrStats):
+        """The entry point `name` with (handle, camera, params, *rest, stats or a null pointer), checked.  Returns the
+        stats struct (zeros without want_stats)."""
+        cd, p = args
+        st = stats()
+        self._check(getattr(self.lib, name)(self.h, C.byref(cd), C.byref(p), *rest, C.byref(st) if want_stats else None))
+        return st
+
     def render(self, cam, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
                want_stats=True, sum_order=None):
         """Render into a host array (H, W, 3) of f32/f64 -- of uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM.
         Returns (image, stats dict)."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
-        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
-        out = np.empty((cam.image_height, cam.image_width, 3), dtype=dtype)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_host(self.h, C.byref(cd), C.byref(p), out.ctypes.data_as(C.c_void_p),
-                                            C.byref(st) if want_stats else None))
+        out, _ = frame_arrays((cam.image_height, cam.image_width), out_dtype(output_sum, real_type))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_host", args, host_ptr(out), want_stats=want_stats)
         return out, st.as_dict()
 
     def render_device(self, cam, d_ptr, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
                       output_sum=False, want_stats=False, sum_order=None):
         """Render into device memory at `d_ptr` (W*H*3 reals, or uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM).
         Asynchronous unless want_stats."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_device(self.h, C.byref(cd), C.byref(p), C.c_void_p(d_ptr),
-                                              C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_device", args, C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
     def render_frames(self, cam, frames, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
@@ -128,27 +133,19 @@ class Renderer:
         """cr_render_frames_host: the frames `frames` (frame indices; cam.frame is not used) in one launch, as an
         (F, H, W, 3) host array of f32/f64 -- of uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM.  Frame k equals
         render() at frame frames[k] bit for bit.  Needs CR_SUM_RELAXED.  Returns (frames array, stats dict)."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
-        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
-        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
-        out = np.empty((max(1, fr.size), cam.image_height, cam.image_width, 3), dtype=dtype)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_frames_host(self.h, C.byref(cd), C.byref(p), fr.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                   fr.size, out.ctypes.data_as(C.c_void_p),
-                                                   C.byref(st) if want_stats else None))
+        fr, fr_ptr = frame_list(frames)
+        out, _ = frame_arrays((max(1, fr.size), cam.image_height, cam.image_width), out_dtype(output_sum, real_type))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_frames_host", args, fr_ptr, fr.size, host_ptr(out), want_stats=want_stats)
         return out, st.as_dict()
 
     def render_frames_device(self, cam, frames, d_ptr, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
                              sample_count=None, output_sum=False, want_stats=False, sum_order=None):
         """cr_render_frames_device: the frames `frames` into device memory at `d_ptr` (F*W*H*3 reals, or uint64 words
         with output_sum=A.CR_OUTPUT_FIXED_SUM), frame after frame.  Asynchronous unless want_stats."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
-        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_frames_device(self.h, C.byref(cd), C.byref(p), fr.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                     fr.size, C.c_void_p(d_ptr), C.byref(st) if want_stats else None))
+        fr, fr_ptr = frame_list(frames)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_frames_device", args, fr_ptr, fr.size, C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
     def render_aov(self, cam, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
@@ -158,29 +155,18 @@ class Renderer:
         arrays keyed "albedo" (H, W, 3), "normal" (H, W, 3; decode 2 e - 1), "depth" (H, W), "coverage" (H, W) -- the
         requested ones --, stats dict)."""
         layers = aov_mask(layers)
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
         H, W = cam.image_height, cam.image_width
-        planes = [(n, c) for n, bit, c in A.AOV_LAYERS if layers & bit]
-        buf = np.empty(max(1, W * H * sum(c for _, c in planes)), dtype=np_real(real_type))
-        st = A.CrStats()
-        self._check(self.lib.cr_render_aov_host(self.h, C.byref(cd), C.byref(p), layers, buf.ctypes.data_as(C.c_void_p),
-                                                C.byref(st) if want_stats else None))
-        out, o = {}, 0
-        for n, c in planes:
-            out[n] = buf[o:o + W * H * c].reshape((H, W, 3) if c == 3 else (H, W))
-            o += W * H * c
-        return out, st.as_dict()
+        buf, planes = guide_buffer(layers, real_type, W, H)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        st = self._call("cr_render_aov_host", args, layers, host_ptr(buf), want_stats=want_stats)
+        return guide_planes(buf, planes, W, H), st.as_dict()
 
     def render_aov_device(self, cam, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
                           sample_count=None, output_sum=False, want_stats=False):
         """cr_render_aov_device: the requested planes, one after the other in ascending bit order, into device memory at
         `d_ptr`.  Asynchronous unless want_stats."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_aov_device(self.h, C.byref(cd), C.byref(p), aov_mask(layers), C.c_void_p(d_ptr),
-                                                  C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        st = self._call("cr_render_aov_device", args, aov_mask(layers), C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
     def render_aov_frames(self, cam, frames, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
@@ -189,35 +175,20 @@ class Renderer:
         used) in one launch.  Returns (list of per-frame dicts shaped like render_aov's, stats dict of the whole call);
         frame k equals render_aov() at frame frames[k] bit for bit."""
         layers = aov_mask(layers)
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
         fr, fr_ptr = frame_list(frames)
         H, W = cam.image_height, cam.image_width
-        planes = [(n, c) for n, bit, c in A.AOV_LAYERS if layers & bit]
-        stride = W * H * sum(c for _, c in planes)
-        buf = np.empty(max(1, stride * fr.size), dtype=np_real(real_type))
-        st = A.CrStats()
-        self._check(self.lib.cr_render_aov_frames_host(self.h, C.byref(cd), C.byref(p), layers, fr_ptr, fr.size,
-                                                       buf.ctypes.data_as(C.c_void_p), C.byref(st) if want_stats else None))
-        out = []
-        for k in range(fr.size):
-            frame, o = {}, k * stride
-            for n, c in planes:
-                frame[n] = buf[o:o + W * H * c].reshape((H, W, 3) if c == 3 else (H, W))
-                o += W * H * c
-            out.append(frame)
-        return out, st.as_dict()
+        buf, planes = guide_buffer(layers, real_type, W, H, fr.size)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        st = self._call("cr_render_aov_frames_host", args, layers, fr_ptr, fr.size, host_ptr(buf), want_stats=want_stats)
+        return [guide_planes(buf, planes, W, H, k) for k in range(fr.size)], st.as_dict()
 
     def render_aov_frames_device(self, cam, frames, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32,
                                  sample_begin=0, sample_count=None, output_sum=False, want_stats=False):
         """cr_render_aov_frames_device: frame after frame into device memory at `d_ptr`, each frame's requested planes
         one after the other in ascending bit order.  Asynchronous unless want_stats."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
         fr, fr_ptr = frame_list(frames)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_aov_frames_device(self.h, C.byref(cd), C.byref(p), aov_mask(layers), fr_ptr, fr.size,
-                                                         C.c_void_p(d_ptr), C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        st = self._call("cr_render_aov_frames_device", args, aov_mask(layers), fr_ptr, fr.size, C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
     def render_region(self, cam, region, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
@@ -226,26 +197,19 @@ class Renderer:
         array of f32/f64 -- of uint64 words with output_sum=A.CR_OUTPUT_FIXED_SUM.  Pixel (i, j) equals pixel
         (x0 + i, y0 + j) of render() bit for bit; region=None passes a null pointer (the library refuses it).  Needs
         CR_SUM_RELAXED.  Returns (image, stats dict of the region's samples)."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
         reg, (w, h) = region_arg(region)
-        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
-        out = np.empty((max(1, h), max(1, w), 3), dtype=dtype)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_region_host(self.h, C.byref(cd), C.byref(p), reg, out.ctypes.data_as(C.c_void_p),
-                                                   C.byref(st) if want_stats else None))
+        out, _ = frame_arrays((max(1, h), max(1, w)), out_dtype(output_sum, real_type))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_region_host", args, reg, host_ptr(out), want_stats=want_stats)
         return out, st.as_dict()
 
     def render_region_device(self, cam, region, d_ptr, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
                              output_sum=False, want_stats=False, sum_order=None):
         """cr_render_region_device: the region into device memory at `d_ptr` (w*h*3 reals, or uint64 words with
         output_sum=A.CR_OUTPUT_FIXED_SUM).  Asynchronous unless want_stats."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
         reg, _ = region_arg(region)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_region_device(self.h, C.byref(cd), C.byref(p), reg, C.c_void_p(d_ptr),
-                                                     C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_region_device", args, reg, C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
     def render_aov_region(self, cam, region, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
@@ -253,31 +217,20 @@ class Renderer:
         """cr_render_aov_region_host: render_aov's planes over the pixels `region` = (x0, y0, w, h): a dict of (h, w, 3) /
         (h, w) host arrays, each the crop of render_aov's plane bit for bit, and the stats dict of the region's samples."""
         layers = aov_mask(layers)
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, sum_order)
         reg, (w, h) = region_arg(region)
         w, h = max(1, w), max(1, h)
-        planes = [(n, c) for n, bit, c in A.AOV_LAYERS if layers & bit]
-        buf = np.empty(max(1, w * h * sum(c for _, c in planes)), dtype=np_real(real_type))
-        st = A.CrStats()
-        self._check(self.lib.cr_render_aov_region_host(self.h, C.byref(cd), C.byref(p), layers, reg, buf.ctypes.data_as(C.c_void_p),
-                                                       C.byref(st) if want_stats else None))
-        out, o = {}, 0
-        for n, c in planes:
-            out[n] = buf[o:o + w * h * c].reshape((h, w, 3) if c == 3 else (h, w))
-            o += w * h * c
-        return out, st.as_dict()
+        buf, planes = guide_buffer(layers, real_type, w, h)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_region_host", args, layers, reg, host_ptr(buf), want_stats=want_stats)
+        return guide_planes(buf, planes, w, h), st.as_dict()
 
     def render_aov_region_device(self, cam, region, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
                                  sample_count=None, output_sum=False, want_stats=False, sum_order=A.CR_SUM_DEFAULT):
         """cr_render_aov_region_device: the region's requested planes, one after the other in ascending bit order, into
         device memory at `d_ptr`.  Asynchronous unless want_stats."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, sample_begin, sample_count, output_sum, sum_order)
         reg, _ = region_arg(region)
-        st = A.CrStats()
-        self._check(self.lib.cr_render_aov_region_device(self.h, C.byref(cd), C.byref(p), aov_mask(layers), reg, C.c_void_p(d_ptr),
-                                                         C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_region_device", args, aov_mask(layers), reg, C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
     def render_tiled(self, cam, tile=(1024, 1024), *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
@@ -299,8 +252,7 @@ class Renderer:
             return self._render_tiled_adaptive(cam, tw, th, dict(adaptive), seed=seed, real_type=real_type, sample_begin=sample_begin,
                                                sample_count=sample_count, output_sum=output_sum, sum_order=sum_order)
         H, W = cam.image_height, cam.image_width
-        dtype = np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
-        out = np.empty((H, W, 3), dtype=dtype)
+        out = np.empty((H, W, 3), dtype=out_dtype(output_sum, real_type))
         total = None
         for y0 in range(0, H, th):
             for x0 in range(0, W, tw):
@@ -308,13 +260,7 @@ class Renderer:
                 img, st = self.render_region(cam, (x0, y0, w, h), seed=seed, real_type=real_type, sample_begin=sample_begin,
                                              sample_count=sample_count, output_sum=output_sum, sum_order=sum_order)
                 out[y0:y0 + h, x0:x0 + w] = img
-                if total is None:
-                    total = dict(st)
-                else:
-                    for k in ("samples", "segments", "node_tests", "prim_tests", "texel_fetches", "nan_pixels", "kernel_ms"):
-                        total[k] += st[k]
-                    for k in ("upload_ms", "bvh_entries", "scene_in_lds"):
-                        total[k] = st[k]
+                total = add_stats(total, st)
         return out, total
 
     def _render_tiled_adaptive(self, cam, tw, th, adaptive, *, seed, real_type, sample_begin, sample_count, output_sum, sum_order):
@@ -336,15 +282,7 @@ class Renderer:
                                                            sum_order=sum_order, **adaptive)
                 out[y0:y0 + h, x0:x0 + w] = img
                 counts[y0:y0 + h, x0:x0 + w] = cnt
-                if total is None:
-                    total = st
-                    continue
-                for k in ("judge_ms", "passes", "blocks", "blocks_stopped"):
-                    total[k] += st[k]
-                for k in ("samples", "segments", "node_tests", "prim_tests", "texel_fetches", "nan_pixels", "kernel_ms"):
-                    total["render"][k] += st["render"][k]
-                for k in ("upload_ms", "bvh_entries", "scene_in_lds"):
-                    total["render"][k] = st["render"][k]
+                total = add_stats(total, st)
         return out, counts, total
 
     def render_adaptive(self, cam, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples, pass_samples, block=16,
@@ -354,28 +292,21 @@ class Renderer:
         `tolerance` (the exact rule: include/crucible_hip.h).  Needs CR_SUM_RELAXED.  Returns (image (H, W, 3), counts
         (H, W) int32 or None, stats dict: passes, blocks, blocks_stopped, judge_ms, and the render's CrStats under
         "render")."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
         ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
-        out = np.empty((cam.image_height, cam.image_width, 3), dtype=np_real(real_type))
-        counts = np.empty((cam.image_height, cam.image_width), dtype=np.int32) if want_counts else None
-        st = A.CrAdaptiveStats()
-        self._check(self.lib.cr_render_adaptive_host(self.h, C.byref(cd), C.byref(p), C.byref(ap), out.ctypes.data_as(C.c_void_p),
-                                                     counts.ctypes.data_as(C.c_void_p) if want_counts else None,
-                                                     C.byref(st) if want_stats else None))
+        out, counts = frame_arrays((cam.image_height, cam.image_width), np_real(real_type), want_counts)
+        args = self._args(cam, seed, real_type, sum_order=sum_order)
+        st = self._call("cr_render_adaptive_host", args, C.byref(ap), host_ptr(out), host_ptr(counts),
+                        want_stats=want_stats, stats=A.CrAdaptiveStats)
         return out, counts, st.as_dict()
 
     def render_adaptive_device(self, cam, d_ptr, d_counts=None, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples,
                                pass_samples, block=16, want_stats=True, sum_order=None):
         """cr_render_adaptive_device: the frame into device memory at `d_ptr` (W*H*3 reals) and, if given, the counts at
         `d_counts` (W*H int32).  Synchronous.  Returns the stats dict of render_adaptive."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
         ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
-        st = A.CrAdaptiveStats()
-        self._check(self.lib.cr_render_adaptive_device(self.h, C.byref(cd), C.byref(p), C.byref(ap), C.c_void_p(d_ptr),
-                                                       C.c_void_p(d_counts) if d_counts else None,
-                                                       C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sum_order=sum_order)
+        st = self._call("cr_render_adaptive_device", args, C.byref(ap), C.c_void_p(d_ptr), dev_ptr(d_counts),
+                        want_stats=want_stats, stats=A.CrAdaptiveStats)
         return st.as_dict()
 
     def render_adaptive_frames(self, cam, frames, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples, pass_samples, block=16,
@@ -384,31 +315,23 @@ class Renderer:
         under one pass loop -- a pass renders the active tiles of all frames in one launch.  Frame k and its counts are
         render_adaptive() at frame frames[k] bit for bit.  Returns (images (n, H, W, 3), counts (n, H, W) int32 or None,
         stats dict of the whole call, shaped like render_adaptive's)."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
         ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
         fr, fr_ptr = frame_list(frames)
-        out = np.empty((max(1, fr.size), cam.image_height, cam.image_width, 3), dtype=np_real(real_type))
-        counts = np.empty((max(1, fr.size), cam.image_height, cam.image_width), dtype=np.int32) if want_counts else None
-        st = A.CrAdaptiveStats()
-        self._check(self.lib.cr_render_adaptive_frames_host(self.h, C.byref(cd), C.byref(p), C.byref(ap), fr_ptr, fr.size,
-                                                            out.ctypes.data_as(C.c_void_p),
-                                                            counts.ctypes.data_as(C.c_void_p) if want_counts else None,
-                                                            C.byref(st) if want_stats else None))
+        out, counts = frame_arrays((max(1, fr.size), cam.image_height, cam.image_width), np_real(real_type), want_counts)
+        args = self._args(cam, seed, real_type, sum_order=sum_order)
+        st = self._call("cr_render_adaptive_frames_host", args, C.byref(ap), fr_ptr, fr.size, host_ptr(out), host_ptr(counts),
+                        want_stats=want_stats, stats=A.CrAdaptiveStats)
         return out, counts, st.as_dict()
 
     def render_adaptive_frames_device(self, cam, frames, d_ptr, d_counts=None, *, seed, real_type=A.CR_REAL_F32, tolerance,
                                       min_samples, pass_samples, block=16, want_stats=True, sum_order=None):
         """cr_render_adaptive_frames_device: the frames into device memory at `d_ptr` (n*W*H*3 reals, frame after frame)
         and, if given, the counts at `d_counts` (n*W*H int32).  Synchronous.  Returns the stats dict of render_adaptive."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
         ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
         fr, fr_ptr = frame_list(frames)
-        st = A.CrAdaptiveStats()
-        self._check(self.lib.cr_render_adaptive_frames_device(self.h, C.byref(cd), C.byref(p), C.byref(ap), fr_ptr, fr.size,
-                                                              C.c_void_p(d_ptr), C.c_void_p(d_counts) if d_counts else None,
-                                                              C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sum_order=sum_order)
+        st = self._call("cr_render_adaptive_frames_device", args, C.byref(ap), fr_ptr, fr.size, C.c_void_p(d_ptr), dev_ptr(d_counts),
+                        want_stats=want_stats, stats=A.CrAdaptiveStats)
         return st.as_dict()
 
     def render_adaptive_region(self, cam, region, *, seed, real_type=A.CR_REAL_F32, tolerance, min_samples, pass_samples, block=16,
@@ -419,31 +342,23 @@ class Renderer:
         render_adaptive()'s pixels and counts bit for bit; region=None passes a null pointer (the library refuses it).
         Returns (image (h, w, 3), counts (h, w) int32 or None, stats dict shaped like render_adaptive's, over the region's
         blocks)."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
         ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
         reg, (w, h) = region_arg(region)
-        out = np.empty((max(1, h), max(1, w), 3), dtype=np_real(real_type))
-        counts = np.empty((max(1, h), max(1, w)), dtype=np.int32) if want_counts else None
-        st = A.CrAdaptiveStats()
-        self._check(self.lib.cr_render_adaptive_region_host(self.h, C.byref(cd), C.byref(p), C.byref(ap), reg,
-                                                            out.ctypes.data_as(C.c_void_p),
-                                                            counts.ctypes.data_as(C.c_void_p) if want_counts else None,
-                                                            C.byref(st) if want_stats else None))
+        out, counts = frame_arrays((max(1, h), max(1, w)), np_real(real_type), want_counts)
+        args = self._args(cam, seed, real_type, sum_order=sum_order)
+        st = self._call("cr_render_adaptive_region_host", args, C.byref(ap), reg, host_ptr(out), host_ptr(counts),
+                        want_stats=want_stats, stats=A.CrAdaptiveStats)
         return out, counts, st.as_dict()
 
     def render_adaptive_region_device(self, cam, region, d_ptr, d_counts=None, *, seed, real_type=A.CR_REAL_F32, tolerance,
                                       min_samples, pass_samples, block=16, want_stats=True, sum_order=None):
         """cr_render_adaptive_region_device: the region into device memory at `d_ptr` (w*h*3 reals) and, if given, its
         counts at `d_counts` (w*h int32).  Synchronous.  Returns the stats dict of render_adaptive_region."""
-        cd = cam.desc()
-        p = cam.params(seed, real_type, 0, None, False, self.sum_order if sum_order is None else sum_order)
         ap = adaptive_arg(tolerance, min_samples, pass_samples, block)
         reg, _ = region_arg(region)
-        st = A.CrAdaptiveStats()
-        self._check(self.lib.cr_render_adaptive_region_device(self.h, C.byref(cd), C.byref(p), C.byref(ap), reg, C.c_void_p(d_ptr),
-                                                              C.c_void_p(d_counts) if d_counts else None,
-                                                              C.byref(st) if want_stats else None))
+        args = self._args(cam, seed, real_type, sum_order=sum_order)
+        st = self._call("cr_render_adaptive_region_device", args, C.byref(ap), reg, C.c_void_p(d_ptr), dev_ptr(d_counts),
+                        want_stats=want_stats, stats=A.CrAdaptiveStats)
         return st.as_dict()
 
     def fixed_sums_to_rgb(self, d_sums, d_out, *, width, height, samples, real_type=A.CR_REAL_F32):
@@ -515,6 +430,60 @@ class Renderer:
         rc = fn(path.encode(), img.ctypes.data_as(C.c_void_p), rt, img.shape[1], img.shape[0])
         if rc != A.CR_OK:
             raise CrucibleError(rc, "cannot write " + path)
+
+
+def out_dtype(output_sum, real_type):
+    """A render's output words: reals, or uint64 with output_sum=A.CR_OUTPUT_FIXED_SUM."""
+    return np.uint64 if output_sum == A.CR_OUTPUT_FIXED_SUM else np_real(real_type)
+
+
+def frame_arrays(dims, dtype, want_counts=False):
+    """The host output of a render or an adaptive call over `dims` = (H, W), (F, H, W) or a region's (h, w): (colours
+    dims + (3,), the int32 count plane(s) `dims` or None)."""
+    return np.empty(tuple(dims) + (3,), dtype=dtype), (np.empty(tuple(dims), dtype=np.int32) if want_counts else None)
+
+
+def guide_buffer(layers, real_type, w, h, n=1):
+    """(flat host buffer for the planes of the mask `layers` over n frames of w x h pixels, [(name, channels)] of the planes
+    in buffer order)."""
+    planes = [(name, c) for name, bit, c in A.AOV_LAYERS if layers & bit]
+    return np.empty(max(1, n * w * h * sum(c for _, c in planes)), dtype=np_real(real_type)), planes
+
+
+def guide_planes(buf, planes, w, h, k=0):
+    """Frame k of a guide buffer as a dict of named planes: (h, w, 3) or (h, w) views into `buf`."""
+    out, o = {}, k * w * h * sum(c for _, c in planes)
+    for name, c in planes:
+        out[name] = buf[o:o + w * h * c].reshape((h, w, 3) if c == 3 else (h, w))
+        o += w * h * c
+    return out
+
+
+_SUMMED = ("samples", "segments", "node_tests", "prim_tests", "texel_fetches", "nan_pixels", "kernel_ms")
+
+
+def add_stats(total, st):
+    """A tile's stats dict added into the running `total` (None before the first tile): counters, samples, nan_pixels
+    and times summed, the rest from the last tile.  An adaptive call's dict carries the render's under "render"."""
+    if total is None:
+        return dict(st)
+    for k in ("judge_ms", "passes", "blocks", "blocks_stopped"):
+        if k in st:
+            total[k] += st[k]
+    into, new = total.get("render", total), st.get("render", st)
+    for k in _SUMMED:
+        into[k] += new[k]
+    for k in ("upload_ms", "bvh_entries", "scene_in_lds"):
+        into[k] = new[k]
+    return total
+
+
+def host_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def dev_ptr(d):
+    return C.c_void_p(d) if d else None
 
 
 def frame_list(frames):
