@@ -1559,6 +1559,17 @@ EXPORT int32_t oracle_world_hit(Scene* sc, const real* orig, const real* dir, re
     if (!hittable_hit(sc->world, &r, iv, &h, &cn)) return 0;
     rec_out(&h, out10); *mat = h.mat; return 1;
 }
+/* the same probe with the ray's own work: counts2 = {node_tests, prim_tests}, as oracle_render adds them into CrStats
+ * (prim_tests: a span-1 wrapper's object counted once).  Filled on a miss too. */
+EXPORT int32_t oracle_world_hit_counted(Scene* sc, const real* orig, const real* dir, real tm, real tmin, real tmax, real* out10, int32_t* mat,
+                                        uint64_t* counts2) {
+    Ray r = {v3(orig[0], orig[1], orig[2]), v3(dir[0], dir[1], dir[2]), tm};
+    Interval iv = {tmin, tmax}; HitRecord h; Counters cn; memset(&cn, 0, sizeof cn);
+    const int hit = hittable_hit(sc->world, &r, iv, &h, &cn);
+    counts2[0] = cn.node_tests; counts2[1] = cn.prim_tests_dedup;
+    if (!hit) return 0;
+    rec_out(&h, out10); *mat = h.mat; return 1;
+}
 
 /* scatter with an explicit RNG key; out: attenuation(3), scattered origin(3), dir(3), draws used */
 EXPORT int32_t oracle_scatter(const Scene* sc, int32_t mat, const real* orig, const real* dir, const real* rec10,

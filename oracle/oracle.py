@@ -66,6 +66,7 @@ class Oracle:
         L.oracle_sphere_hit.argtypes = [P, P, P, R, R, P]
         L.oracle_triangle_hit.argtypes = [P, P, P, R, R, P]
         L.oracle_world_hit.argtypes = [P, P, P, R, R, R, P, P]
+        L.oracle_world_hit_counted.argtypes = [P, P, P, R, R, R, P, P, P]
         L.oracle_scatter.argtypes = [P, C.c_int32, P, P, P, C.c_uint64, C.c_uint32, C.c_uint32, P]
         L.oracle_texture_value.argtypes = [P, C.c_int32, R, R, P, P]
         L.oracle_sky.argtypes = [P, P, P]
@@ -131,6 +132,18 @@ class Oracle:
         rc = self.lib.oracle_set_tree(scene_h, boxes.ctypes.data, kids.ctypes.data,
                                       None if axis is None else axis.ctypes.data, len(kids))
         assert rc == 0, "malformed wrapper tree"
+
+    def world_hit_counted(self, scene_h, orig, dirn, tm=0.0, tmin=0.001, tmax=np.inf):
+        """Closest hit of one ray through the scene's tree with the ray's own work: (hit, rec10, mat, node_tests,
+        prim_tests); rec10 and mat are meaningful on a hit only, the counts always (CrStats' node_tests / prim_tests of
+        that ray alone)."""
+        o, d = self.arr(orig), self.arr(dirn)
+        rec = np.zeros(10, dtype=self.np_real)
+        mat = C.c_int32(-1)
+        counts = np.zeros(2, dtype=np.uint64)
+        hit = self.lib.oracle_world_hit_counted(scene_h, self._p(o), self._p(d), self.real(tm), self.real(tmin), self.real(tmax),
+                                                self._p(rec), C.byref(mat), self._p(counts))
+        return bool(hit), rec, mat.value, int(counts[0]), int(counts[1])
 
     def render(self, scene_h, cam, *, seed, sample_begin=0, sample_count=None, output_sum=False, pix_begin=0,
                pix_end=None, n_threads=None, sum_order=A.CR_SUM_REFERENCE_ORDER):
