@@ -154,6 +154,18 @@ SYMBOLS = {
                                                 C.POINTER(CrRegion), C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_aov_region_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
                                               C.POINTER(CrRegion), C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_counts_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32, C.c_void_p,
+                                                C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_counts_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_counts_frames_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                                       C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_counts_frames_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                                     C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_counts_region_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                                       C.POINTER(CrRegion), C.c_void_p, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_counts_region_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
+                                                     C.POINTER(CrRegion), C.c_void_p, C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_adaptive_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),
                                               C.POINTER(CrAdaptiveParams), C.c_void_p, C.c_void_p, C.POINTER(CrAdaptiveStats)]),
     "cr_render_adaptive_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams),

@@ -11,21 +11,29 @@ namespace cr {
 // times 2^-S, divided by the frame's sample count unless the shard's sum is asked for -- with the word's sign put back;
 // a flagged channel is NaN.  Depth: the complement of the largest word, +inf where no sample hit.
 // blockIdx.y: the frame of a batch, whose planes begin frame_reals reals after the previous frame's.
-template <typename real>
-__global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long long* acc, const uint32_t* flags, real* out, size_t npix, int32_t layers,
-                                                           double inv_scale, double count, int32_t output_sum, size_t frame_reals) {
+// COUNTS (aov_counts_finalize_kernel): the divisor is the pixel's own clamped count, `count` the clamp's maximum; a pixel
+// without samples is not divided (aov_counts.hpp) -- its sums are zero and stay +0.0, its depth +inf.
+template <typename real, bool COUNTS>
+CR_D void aov_finalize_pixel(const unsigned long long* acc, const uint32_t* flags, real* out, size_t npix, int32_t layers,
+                             double inv_scale, double count, int32_t output_sum, size_t frame_reals, const int32_t* counts) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npix) return;
     acc += (size_t)blockIdx.y * npix * kAovWords;
     flags += (size_t)blockIdx.y * npix;
     out += (size_t)blockIdx.y * frame_reals;
+    bool divide = !output_sum;
+    if constexpr (COUNTS) {
+        const uint32_t n_p = aov_count_clamp(counts[(size_t)blockIdx.y * npix + i], (int32_t)count);
+        divide = aov_count_divides(n_p, output_sum);
+        count = (double)n_p;
+    }
     const unsigned long long* w = acc + i * kAovWords;
     const uint32_t bad = flags[i];
     auto value = [&](uint32_t c) -> real {
         const long long v = (long long)w[c];
         const unsigned long long m = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
         double s = ((double)(uint32_t)(m >> 32) * 4294967296.0 + (double)(uint32_t)m) * inv_scale;
-        if (!output_sum) s = s / count;
+        if (divide) s = s / count;
         if (v < 0) s = -s;
         if ((bad >> c) & 1u) s = __builtin_nan("");
         return (real)s;
@@ -46,10 +54,26 @@ __global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long l
     if (layers & CR_AOV_COVERAGE) o[i] = value(kAovCoverage);
 }
 
+template <typename real>
+__global__ void __launch_bounds__(256) aov_finalize_kernel(const unsigned long long* acc, const uint32_t* flags, real* out, size_t npix, int32_t layers,
+                                                           double inv_scale, double count, int32_t output_sum, size_t frame_reals) {
+    aov_finalize_pixel<real, false>(acc, flags, out, npix, layers, inv_scale, count, output_sum, frame_reals, nullptr);
+}
+
+template <typename real>
+__global__ void __launch_bounds__(256) aov_counts_finalize_kernel(const unsigned long long* acc, const uint32_t* flags, real* out, size_t npix, int32_t layers,
+                                                                  double inv_scale, double count, int32_t output_sum, size_t frame_reals,
+                                                                  const int32_t* counts) {
+    aov_finalize_pixel<real, true>(acc, flags, out, npix, layers, inv_scale, count, output_sum, frame_reals, counts);
+}
+
 // One frame (call.frames == nullptr: params->frame), or the frames call.frames in one batch (cr_render_aov_frames_*):
 // the batch's frames lie one behind the other in the accumulators, in the flags and in the output.  call.region: the pixels
 // of the one frame that the pass covers (cr_render_aov_region_*) -- accumulators, flags and planes are then the region's
 // size, and the pass runs as a batch of one frame on the BATCH kernels, which carry the region's offsets.
+// call.counts (cr_render_aov_counts_*; device memory): the samples each pixel takes -- the COUNTS kernels, which are BATCH
+// kernels, so one frame runs as a batch of one; the finalize divides by the pixel's count, and stats->samples is the
+// kernel's own count of the primary rays it cast, since the host does not see the plane.
 template <typename real>
 int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, void* d_out, CrStats* stats) {
     const int32_t* const frames = call.frames;
@@ -78,7 +102,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         // the walk is the megakernel's under every pipeline setting: the cross-check pipelines have no guide pass of their own
         rc = prepare_args<real>(h, cd, p, call, ds, refit, true, d_out, times, a.k, w, fb);
         if (rc != CR_OK) return rc;
-        if (region) {   // the BATCH kernels read a frame's first ray time from the device's table
+        if (region || (call.counts && !frames)) {   // the BATCH kernels read a frame's first ray time from the device's table
             rc = stage_frame_times(h, &a.k.current_time, sizeof(real));
             if (rc != CR_OK) return rc;
         }
@@ -89,7 +113,8 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
         a.layers = layers;
         a.groups = ((uint32_t)p->sample_count + 3u) >> 2;
         if (frames) { a.n_frames = (uint32_t)n_frames; a.frame_times = fb.d_times; }
-        else if (region) { a.n_frames = 1u; a.frame_times = (const real*)h->times_dev.p; }
+        else if (region || call.counts) { a.n_frames = 1u; a.frame_times = (const real*)h->times_dev.p; }
+        a.counts = call.counts;
         const size_t need = aov_lds_bytes(MaxBlock<real>::value);   // the waves' slots share the LDS
         w.screen_lds = w.screen && h->screen_lds && w.lds_all_screen + need <= h->lds_limit;
         w.plain_lds = ds.lds_bytes + need <= h->lds_limit;
@@ -99,19 +124,28 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
     HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     if (p->sample_count > 0) {
-        rc = aov_ladder<real>(h, a, ds, w, &res);
+        rc = call.counts ? aov_counts_ladder<real>(h, a, ds, w, &res) : aov_ladder<real>(h, a, ds, w, &res);
         if (rc != CR_OK) return rc;
     }
     const size_t frame_reals = frame_pix * call.layer_channels();
     for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += 65535) {   // (a grid has at most 65535 rows)
         const size_t fn = std::min<size_t>(65535, (size_t)n_frames - f0);
-        hipLaunchKernelGGL((aov_finalize_kernel<real>), dim3((unsigned)((frame_pix + 255) / 256), (unsigned)fn), dim3(256), 0, h->stream,
-                           (const unsigned long long*)h->aov_acc.p + f0 * frame_pix * kAovWords, (const uint32_t*)h->aov_flags.p + f0 * frame_pix,
-                           (real*)d_out + f0 * frame_reals, frame_pix, layers, 1.0 / fx_scale_for(p->samples), (double)p->samples, p->output_sum, frame_reals);
+        const dim3 grid((unsigned)((frame_pix + 255) / 256), (unsigned)fn);
+        const unsigned long long* const acc = (const unsigned long long*)h->aov_acc.p + f0 * frame_pix * kAovWords;
+        const uint32_t* const flags = (const uint32_t*)h->aov_flags.p + f0 * frame_pix;
+        if (call.counts)
+            hipLaunchKernelGGL((aov_counts_finalize_kernel<real>), grid, dim3(256), 0, h->stream, acc, flags, (real*)d_out + f0 * frame_reals, frame_pix, layers,
+                               1.0 / fx_scale_for(p->samples), (double)p->samples, p->output_sum, frame_reals, call.counts + f0 * frame_pix);
+        else
+            hipLaunchKernelGGL((aov_finalize_kernel<real>), grid, dim3(256), 0, h->stream, acc, flags, (real*)d_out + f0 * frame_reals, frame_pix, layers,
+                               1.0 / fx_scale_for(p->samples), (double)p->samples, p->output_sum, frame_reals);
         HIP_TRY(h, hipGetLastError());
     }
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    return stats ? finish_stats(h, stats, (uint64_t)npix * (uint64_t)p->sample_count, ds.n_entries, res) : CR_OK;
+    if (!stats) return CR_OK;
+    rc = finish_stats(h, stats, (uint64_t)npix * (uint64_t)p->sample_count, ds.n_entries, res);
+    if (rc == CR_OK && call.counts) stats->samples = stats->segments;   // the sum of the clamped counts, as the kernel counted it
+    return rc;
 }
 
 template int32_t aov_typed<float>(CrHandle*, const CrCameraDesc*, const CrRenderParams*, const RenderCall&, void*, CrStats*);

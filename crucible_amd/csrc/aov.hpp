@@ -1,6 +1,7 @@
 // aov.hpp -- the guide pass (cr_render_aov_*): first-hit albedo, normal, depth and coverage per pixel.  What its units
 // share: the kernel's arguments, the accumulator layout and the entry into the kernels' residency ladder.  The kernels
-// themselves are in aov_kernel.hpp (aov_f32.hip and aov_f64.hip emit them), the host side and the finalize kernel in aov.hip.
+// themselves are in aov_kernel.hpp (aov_f32.hip and aov_f64.hip emit them, aov_counts_f32.hip and aov_counts_f64.hip those at
+// a count plane), the host side and the finalize kernel in aov.hip.
 //
 // A work item is one (pixel, sample): 64 consecutive items are a 4 x 4 pixel tile times 4 consecutive samples, one wave's
 // round.  A wave takes a UNIT from the launch's work counter -- `unit_groups` consecutive sample groups of one tile --, adds
@@ -12,6 +13,7 @@
 // A value that is not finite (or too large for a word) sets the channel's bit in the pixel's flag word instead.
 #pragma once
 #include "handle.hpp"
+#include "aov_counts.hpp"
 
 namespace cr {
 
@@ -36,6 +38,9 @@ template <typename real> struct AovArgs {
     uint32_t n_frames;
     uint32_t frame_tiles;
     const real* frame_times;
+    // cr_render_aov_counts_* (the COUNTS kernels, which are BATCH kernels): pixel p of frame f takes the samples
+    // [0, aov_count_clamp(counts[f * reg_w * reg_h + p], samples)); the plane has the accumulators' layout.  Else not read.
+    const int32_t* counts;
 };
 
 // aov_f32.hip, aov_f64.hip: the residency ladder of the guide kernels.  It asks the rule the render's walk_ladder asks
@@ -44,5 +49,8 @@ template <typename real> struct AovArgs {
 // receives the residency (CrStats.scene_in_lds).
 template <typename real>
 int32_t aov_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res);
+// aov_counts_f32.hip, aov_counts_f64.hip: the same ladder over the COUNTS kernels (a.counts is set; a.n_frames >= 1)
+template <typename real>
+int32_t aov_counts_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res);
 
 }   // namespace cr

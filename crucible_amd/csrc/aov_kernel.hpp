@@ -1,7 +1,8 @@
 // aov_kernel.hpp -- the guide pass's first-hit kernels for gfx950 and their launch: made of the megakernel's parts
 // (pathtrace.hpp: camera_ray, walk_begin / walk_round, CR_CHECKER_LEAF, image_lookup, shade's sky) around a much
 // smaller body -- a primary ray per work item, its closest hit, four values, no path state.  Included by aov_f32.hip
-// and aov_f64.hip only, each of which instantiates aov_ladder for its precision, so no kernel is emitted twice.  Which
+// and aov_f64.hip, each of which instantiates aov_ladder for its precision, and by aov_counts_f32.hip and aov_counts_f64.hip,
+// which instantiate aov_counts_ladder (the kernels at a count plane), so no kernel is emitted twice.  Which
 // kernel runs -- the scene's residency, screening records or wrappers -- is residency.hpp's rule, the render's own.
 #pragma once
 #include "aov.hpp"
@@ -27,9 +28,13 @@ CR_D bool aov_word(double x, double scale, long long& v) {
 // The BATCH kernels also render a region (cr_render_aov_region_*, as a batch of one frame): their tiles are anchored at
 // (k.reg_x0, k.reg_y0), the accumulators and flags hold k.reg_w x k.reg_h pixels per frame, and camera_ray alone sees the
 // frame's own pixel.  A whole frame is the region (0, 0, W, H).
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH>
+// COUNTS (with BATCH only): the kernels of cr_render_aov_counts_* -- pixel p takes the samples [0, n_p), n_p its clamped
+// value of the plane G.counts (aov_counts.hpp has the rules).  A unit reads its tile's sixteen counts, the wave forms
+// their maximum as a scalar, and the group loop ends where that maximum ends: whole rounds disappear, not only lanes.
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS = false>
 CR_D void aov_body(const AovArgs<real>& G) {
     using EntryT = typename EntryOf<real, ORD>::type;
+    static_assert(BATCH || !COUNTS, "the COUNTS kernels are BATCH kernels");
     const KernelArgs<real>& A = G.k;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const Entry<real>* lds_entries = nullptr;
@@ -113,10 +118,21 @@ CR_D void aov_body(const AovArgs<real>& G) {
         // BATCH: inside the region, and the frame's own pixel for camera_ray (one integer each)
         const bool in_image = BATCH ? pix_i < A.reg_w && pix_j < A.reg_h : pix_i < (uint32_t)cam.W && pix_j < (uint32_t)cam.H;
         const uint32_t cam_i = BATCH ? A.reg_x0 + pix_i : pix_i, cam_j = BATCH ? A.reg_y0 + pix_j : pix_j;
-        for (uint32_t g = g0; g < g1; g++) {
+        // COUNTS: the pixel's count (sixteen addresses per tile, inside the region only) and the tile's largest, a scalar
+        uint32_t n_p = 0, g_end = g1;
+        if constexpr (COUNTS) {
+            if (in_image) n_p = aov_count_clamp(G.counts[frame_pix + ((size_t)pix_j * (size_t)A.reg_w + pix_i)], A.sample_end - A.sample_begin);
+            uint32_t tile_max = n_p;   // (n_p depends on lane & 15 alone -- a round's four sample rows hold the same pixels --, so four steps cover the tile)
+            for (int off = 8; off > 0; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)tile_max, off); tile_max = o > tile_max ? o : tile_max; }
+            tile_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_max);
+            g_end = aov_count_group_end(g1, tile_max);
+            if (g0 >= g_end) continue;   // nothing of this tile in the unit's range: neither the slot nor the accumulators are touched
+        }
+        for (uint32_t g = g0; g < g_end; g++) {
             const uint32_t s_off = g * 4u + (lane >> 4);   // begin + offset may pass INT32_MAX in the last group's padding: the offset decides
             const int32_t sample = (int32_t)((uint32_t)A.sample_begin + s_off);
-            const bool active = in_image && s_off < (uint32_t)(A.sample_end - A.sample_begin);   // else: padding of an edge tile or of the last group
+            // else: padding of an edge tile or of the last group (COUNTS: n_p is 0 outside the image, one per-lane bound)
+            const bool active = COUNTS ? s_off < n_p : in_image && s_off < (uint32_t)(A.sample_end - A.sample_begin);
             V3<real> ro = mk<real>(0, 0, 0), rd = mk<real>(0, 0, 1);
             real rtime = 0;
             uint64_t rng = 0;
@@ -257,6 +273,19 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) aov_kernel(const AovArg
     aov_body<real, RES, ANIM, ORD, SCREEN, BATCH>(*(const AovArgs<real>*)(const __attribute__((address_space(4))) AovArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
+// The kernels at a count plane (aov_counts_f32.hip, aov_counts_f64.hip): kernels of their own, so that the names of
+// aov_kernel's instantiations stay what they were
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+__global__ void __launch_bounds__(MaxBlock<real>::value) aov_counts_kernel(const AovArgs<real> G) {
+    aov_body<real, RES, ANIM, ORD, SCREEN, true, true>(*(const AovArgs<real>*)(const __attribute__((address_space(4))) AovArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS>
+auto aov_kernel_of() -> void (*)(const AovArgs<real>) {
+    if constexpr (COUNTS) return aov_counts_kernel<real, RES, ANIM, ORD, SCREEN>;
+    else return aov_kernel<real, RES, ANIM, ORD, SCREEN, BATCH>;
+}
+
 #endif   // __HIPCC__
 
 // One launch: persistent workgroups (one LDS copy of the scene each), the waves' slots behind the scene, units handed
@@ -264,9 +293,11 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) aov_kernel(const AovArg
 // A batch (a.n_frames frames, the BATCH kernels) is sized as one piece of work: the eight units per wave count the units
 // of all its frames, which share one ramp-up and one tail.  Its units are capped by the handle's work_counter_max; a
 // batch with more runs as consecutive launches of whole frames, each on its own part of the accumulators.
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH>
+// COUNTS: sized from params->samples all the same -- the host does not see a device plane --, so a unit beyond its tile's
+// largest count costs one counter fetch and sixteen loads; each launch's frames read their own part of the plane.
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS = false>
 int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* res) {
-    void (*kern)(const AovArgs<real>) = aov_kernel<real, RES, ANIM, ORD, SCREEN, BATCH>;
+    void (*kern)(const AovArgs<real>) = aov_kernel_of<real, RES, ANIM, ORD, SCREEN, BATCH, COUNTS>();
     const int max_block = MaxBlock<real>::value;
     const size_t off = RES != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
     a.acc_lds_off = (uint32_t)off;
@@ -289,6 +320,7 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
     unsigned long long* const acc = a.acc;
     uint32_t* const flags = a.flags;
     const real* const times = a.frame_times;
+    const int32_t* const counts = a.counts;
     for (uint64_t f0 = 0; f0 < n_frames; f0 += per_launch) {
         const uint64_t fn = std::min<uint64_t>(per_launch, n_frames - f0);
         if constexpr (BATCH) {
@@ -296,6 +328,7 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
             a.frame_times = times + f0;
             a.acc = acc + f0 * npix * kAovWords;
             a.flags = flags + f0 * npix;
+            if constexpr (COUNTS) a.counts = counts + f0 * npix;
         }
         a.n_units = (uint32_t)(fn * frame_units);
         uint32_t grid = (uint32_t)(h->n_cus * per_cu);
@@ -313,29 +346,38 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
 
 // keyed primitives and leaves that hold a list walk with the ANIM decode (render.hip); a keyed camera needs no kernel of its own here
 // a.n_frames != 0: a batch (cr_render_aov_frames_*), on the BATCH kernels whatever its length
-template <typename real, int RES, bool ORD, bool SCREEN>
+template <typename real, int RES, bool ORD, bool SCREEN, bool COUNTS = false>
 int32_t aov_variant(CrHandle* h, AovArgs<real>& a, size_t lds_bytes, const WalkChoice& w, int* res) {
-    if (a.n_frames)
-        return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, true>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, true>(h, a, lds_bytes, res);
-    return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, false>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, false>(h, a, lds_bytes, res);
+    if constexpr (COUNTS)   // (a.n_frames >= 1: a single frame is a batch of one here)
+        return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, true, true>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, true, true>(h, a, lds_bytes, res);
+    else {   // (inside the else: a COUNTS unit instantiates none of these)
+        if (a.n_frames)
+            return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, true>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, true>(h, a, lds_bytes, res);
+        return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, false>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, false>(h, a, lds_bytes, res);
+    }
 }
 
 // The guide kernels' residency ladder: the rule walk_ladder asks (residency.hpp), so a guide pass stages what the render
 // stages; the 6-waves-per-SIMD entry point has no counterpart here, so the query's latency inputs stay at never
-template <typename real, bool ORD>
+template <typename real, bool ORD, bool COUNTS = false>
 int32_t aov_ladder_ord(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
     const Residency r = choose_residency(residency_query<real, ORD>(h, ds, w));
     a.k.lds_entries = r.lds_entries;
     if (r.lds_side) a.k.lds_side = 1;
     if (r.clear_screen) a.k.screen = nullptr;
     return residency_dispatch<!(ORD && std::is_same<real, float>::value), false>(r, [&](auto rs, auto screen, auto) {
-        return aov_variant<real, decltype(rs)::value, ORD, decltype(screen)::value>(h, a, r.lds_bytes, w, res);
+        return aov_variant<real, decltype(rs)::value, ORD, decltype(screen)::value, COUNTS>(h, a, r.lds_bytes, w, res);
     });
 }
 
 template <typename real>
 int32_t aov_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
     return ds.ordered ? aov_ladder_ord<real, true>(h, a, ds, w, res) : aov_ladder_ord<real, false>(h, a, ds, w, res);
+}
+
+template <typename real>
+int32_t aov_counts_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
+    return ds.ordered ? aov_ladder_ord<real, true, true>(h, a, ds, w, res) : aov_ladder_ord<real, false, true>(h, a, ds, w, res);
 }
 
 }   // namespace cr

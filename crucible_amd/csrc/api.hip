@@ -58,7 +58,8 @@ int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
 
 // The checks of every cr_render_* entry point: a render's, then the family's own in the order each family has had them --
 // a call with two faults reports the first.  render: frames, n_frames, out, the region's sum order.  guide layers: frames,
-// n_frames, the layer mask, out, the fixed-point refusal.  adaptive: validate_adaptive's (out among them), then frames, n_frames.
+// n_frames, the layer mask, out, the fixed-point refusal; at a count plane after those the plane, then the shard.
+// adaptive: validate_adaptive's (out among them), then frames, n_frames.
 static int32_t validate_call(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const RenderCall& call, const void* out,
                              const CrAdaptiveParams* ap) {
     int32_t rc = validate_render(h, cam, p, call.region, call.region_call);
@@ -68,10 +69,14 @@ static int32_t validate_call(CrHandle* h, const CrCameraDesc* cam, const CrRende
     if (call.batch && call.n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_frames must be at least 1");
     if (call.family == kCallAdaptive) return CR_OK;
     const int32_t all = CR_AOV_ALBEDO | CR_AOV_NORMAL | CR_AOV_DEPTH | CR_AOV_COVERAGE;
-    if (call.family == kCallGuide && (call.layers == 0 || (call.layers & ~all))) return fail(h, CR_ERR_INVALID_ARG, "layers must be a non-empty mask of CR_AOV_*");
+    if (call.guide() && (call.layers == 0 || (call.layers & ~all))) return fail(h, CR_ERR_INVALID_ARG, "layers must be a non-empty mask of CR_AOV_*");
     if (!out) return fail(h, CR_ERR_INVALID_ARG, "output buffer is null");
-    if (call.family == kCallGuide && p->output_sum == CR_OUTPUT_FIXED_SUM)
+    if (call.guide() && p->output_sum == CR_OUTPUT_FIXED_SUM)
         return fail(h, CR_ERR_UNSUPPORTED, "guide layers come as reals (output_sum 0 or 1), not as fixed-point words");
+    if (call.family == kCallGuideCounts && !call.counts) return fail(h, CR_ERR_INVALID_ARG, "counts is null");
+    if (call.family == kCallGuideCounts && (p->sample_begin != 0 || p->sample_count != p->samples))
+        return fail(h, CR_ERR_UNSUPPORTED, "guide layers at a count plane take a pixel's samples from sample 0 (sample_begin 0, sample_count == samples), "
+                                           "as the adaptive calls do");
     if (call.family == kCallRender && call.region_call && (resolve_sum_order(h, p) != CR_SUM_RELAXED || h->pipeline != 0))
         return fail(h, CR_ERR_UNSUPPORTED, "cr_render_region needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
                                            "sequential over samples; the region's offsets live in the relaxed kernels)");
@@ -108,7 +113,7 @@ uint64_t bad_pixels(const void* rgb, int32_t real_type, size_t n_pix) {
 }
 
 // A checked call into host memory: into the handle's buffers (the output's; the counts' when an adaptive call asks for
-// them), copy back, and where the family's output is a frame of colour means, check them frame by frame
+// them; a guide call's count plane, copied in on the stream before the launch), copy back, and where the family's output is a frame of colour means, check them frame by frame
 static int32_t call_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, RenderCall call, void* h_out, CrStats* stats) {
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n_pix = call.frame_pixels(cam), frame_bytes = call.frame_bytes(cam, p);
@@ -123,7 +128,12 @@ static int32_t call_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderPar
         run.d_counts = h_counts ? (int32_t*)h->ad_counts.p : nullptr;
         call.adaptive = &run;
     }
+    if (e == hipSuccess && call.counts) e = h->aov_counts.ensure(count_bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("output buffer: ") + hipGetErrorString(e)); }
+    if (call.counts) {
+        HIP_TRY(h, hipMemcpyAsync(h->aov_counts.p, call.counts, count_bytes, hipMemcpyHostToDevice, h->stream));
+        call.counts = (const int32_t*)h->aov_counts.p;
+    }
     // a render whose caller gave no stats runs with a local CrStats; guide layers and adaptive calls pass the null on
     CrStats local;
     const bool render = call.family == kCallRender;
@@ -179,6 +189,7 @@ static RenderCall one_frame() { return RenderCall(); }
 static RenderCall batch_of(const int32_t* frames, int32_t n_frames) { RenderCall c; c.frames = frames; c.n_frames = n_frames; c.batch = true; return c; }
 static RenderCall region_of(const CrRegion* region) { RenderCall c; c.region = region; c.region_call = true; return c; }
 static RenderCall guide(RenderCall c, int32_t layers) { c.family = kCallGuide; c.layers = layers; return c; }
+static RenderCall guide_at(RenderCall c, int32_t layers, const int32_t* counts) { c.family = kCallGuideCounts; c.layers = layers; c.counts = counts; return c; }
 static RenderCall adaptive(RenderCall c) { c.family = kCallAdaptive; return c; }
 
 }   // namespace cr
@@ -251,7 +262,7 @@ void cr_destroy(CrHandle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->s32.release(); h->s64.release(); h->f32.release(); h->f64.release(); h->update_stage.release(); h->sah_work.release();
     h->images.release(); h->texels.release(); h->work_counter.release(); h->counters.release();
-    h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release(); h->aov_acc.release(); h->aov_flags.release();
+    h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release(); h->aov_acc.release(); h->aov_flags.release(); h->aov_counts.release();
     h->wf_job.release(); h->wf_rng.release(); h->wf_ray.release(); h->wf_depth.release(); h->wf_hit_t.release(); h->wf_hit_prim.release();
     h->wf_chunk.release(); h->wf_ctrl.release(); h->wf_samples.release(); h->wf_acc.release();
     for (int i = 0; i < CrHandle::kCamSlots; i++) {
@@ -272,8 +283,9 @@ void cr_destroy(CrHandle* h) {
     delete h;
 }
 
-// The eighteen render entry points: three families (render, guide layers, adaptive) in three shapes (one frame, a batch
-// of frames, a region of a frame) into device or host memory -- each a RenderCall and where its results go.
+// The twenty-four render entry points: four families (render, guide layers, adaptive, guide layers at a count plane) in
+// three shapes (one frame, a batch of frames, a region of a frame) into device or host memory -- each a RenderCall and
+// where its results go.
 
 int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats) {
     return run_call(h, cam, p, one_frame(), kDevice, d_out, stats);
@@ -327,6 +339,36 @@ int32_t cr_render_aov_region_device(CrHandle* h, const CrCameraDesc* cam, const 
 int32_t cr_render_aov_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,
                                   void* h_out, CrStats* stats) {
     return run_call(h, cam, p, guide(region_of(region), layers), kHost, h_out, stats);
+}
+
+int32_t cr_render_aov_counts_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* d_counts,
+                                    void* d_out, CrStats* stats) {
+    return run_call(h, cam, p, guide_at(one_frame(), layers, d_counts), kDevice, d_out, stats);
+}
+
+int32_t cr_render_aov_counts_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* h_counts,
+                                  void* h_out, CrStats* stats) {
+    return run_call(h, cam, p, guide_at(one_frame(), layers, h_counts), kHost, h_out, stats);
+}
+
+int32_t cr_render_aov_counts_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames,
+                                           int32_t n_frames, const int32_t* d_counts, void* d_out, CrStats* stats) {
+    return run_call(h, cam, p, guide_at(batch_of(frames, n_frames), layers, d_counts), kDevice, d_out, stats);
+}
+
+int32_t cr_render_aov_counts_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames,
+                                         int32_t n_frames, const int32_t* h_counts, void* h_out, CrStats* stats) {
+    return run_call(h, cam, p, guide_at(batch_of(frames, n_frames), layers, h_counts), kHost, h_out, stats);
+}
+
+int32_t cr_render_aov_counts_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,
+                                           const int32_t* d_counts, void* d_out, CrStats* stats) {
+    return run_call(h, cam, p, guide_at(region_of(region), layers, d_counts), kDevice, d_out, stats);
+}
+
+int32_t cr_render_aov_counts_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,
+                                         const int32_t* h_counts, void* h_out, CrStats* stats) {
+    return run_call(h, cam, p, guide_at(region_of(region), layers, h_counts), kHost, h_out, stats);
 }
 
 int32_t cr_render_adaptive_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrAdaptiveParams* ap, void* d_out,

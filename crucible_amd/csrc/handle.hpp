@@ -11,6 +11,7 @@
 //   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder over residency.hpp's rule)
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
 //   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp)
+//   aov_counts_f32.hip, aov_counts_f64.hip   the first-hit kernels at a count plane, cr_render_aov_counts_* (aov_kernel.hpp's COUNTS axis; aov_counts.hpp: its integer rules)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
 //   adaptive.hip       the adaptive family behind its entry points: its argument checks, the pass loop, the judge and finalize kernels (adaptive.hpp)
 //   api.hip            cr_create / cr_destroy, all cr_render_* entry points over one RenderCall, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
@@ -139,6 +140,7 @@ struct CrHandle {
     int cam_next = 0, cam_pending_slot = -1;
     DevBuf sample_buf, sg_acc;   // sample-granular megakernel: per-sample colours of a batch, running sums between batches
     DevBuf aov_acc, aov_flags;   // cr_render_aov_*: per pixel 8 x u64 (albedo, normal, coverage sums; depth) and the channels' NaN bits
+    DevBuf aov_counts;           // cr_render_aov_counts_*_host: the caller's count plane on the device (4 bytes per pixel per frame), grow-only
     DevBuf fx_acc;               // CR_SUM_RELAXED: per-pixel fixed-point sums (3 x u64 per pixel; per frame of a batch)
     // cr_render_adaptive_* (adaptive.hip): the two half-frame accumulators E and O (relaxed sums, apart from fx_acc), the two
     // tile lists, each block's final sample count, the judge's cursor, the count plane of the host form; the judge's events.
@@ -274,7 +276,7 @@ int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame
 
 // What one cr_render_* call covers, as its entry point settled it (api.hip) and as render_typed, aov_typed and prepare_args
 // take it.  A new shape or family is a field here, not a parameter of every function underneath.
-enum CallFamily { kCallRender, kCallGuide, kCallAdaptive };
+enum CallFamily { kCallRender, kCallGuide, kCallAdaptive, kCallGuideCounts };   // kCallGuideCounts: a guide call at a count plane (`counts`)
 struct RenderCall {
     // the shape
     const int32_t* frames = nullptr;          // a batch's frame indices; nullptr: the one frame params->frame, and n_frames is 1
@@ -285,6 +287,9 @@ struct RenderCall {
     CallFamily family = kCallRender;          // the entry point's: the checks ask before `layers` and `adaptive` can tell
     int32_t layers = 0;                       // the guide pass's CR_AOV_* mask; 0: a render
     const AdaptiveRun* adaptive = nullptr;    // a render to a noise target (adaptive.hip); nullptr: all samples of every pixel
+    const int32_t* counts = nullptr;          // kCallGuideCounts: the samples each pixel takes, laid out as the adaptive sibling writes its counts;
+                                              // device memory once call_device runs (call_host stages the caller's plane)
+    bool guide() const { return family == kCallGuide || family == kCallGuideCounts; }
 
     size_t frame_pixels(const CrCameraDesc* cd) const {   // of one frame of the output
         return region ? (size_t)region->width * (size_t)region->height : (size_t)cd->image_width * (size_t)cd->image_height;

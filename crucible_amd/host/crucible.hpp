@@ -674,18 +674,27 @@ public:
         const size_t ch = (aov_layers & CR_AOV_ALBEDO ? 3 : 0) + (aov_layers & CR_AOV_NORMAL ? 3 : 0) + (aov_layers & CR_AOV_DEPTH ? 1 : 0) + (aov_layers & CR_AOV_COVERAGE ? 1 : 0);
         return out_width() * out_height() * ch;
     }
-    int32_t render_aov(CrHandle* h, void* planes, CrStats* stats = nullptr, int64_t frame = -1) const {
+    // guide_at_counts: with set_adaptive, the guide files come from cr_render_aov_counts_*_host over the counts of the
+    // adaptive call -- the layers of exactly the primary rays the adaptive frame's pixels used -- instead of from the
+    // plain guide pass at scene_cam.samples (the default, which keeps the files of earlier versions).
+    bool guide_at_counts = false;
+    // counts: the samples each pixel takes (the frame's or the region's plane); nullptr: scene_cam.samples everywhere
+    int32_t render_aov(CrHandle* h, void* planes, CrStats* stats = nullptr, int64_t frame = -1, const int32_t* counts = nullptr) const {
         std::vector<CrKeyframe> fk, ak;
         CrCameraDesc cd = camera_desc(fk, ak);
         CrRenderParams p = render_params(frame < 0 ? (size_t)scene_cam.frame : (size_t)frame);
+        if (counts && has_region) return cr_render_aov_counts_region_host(h, &cd, &p, aov_layers, &region, counts, planes, stats);
+        if (counts) return cr_render_aov_counts_host(h, &cd, &p, aov_layers, counts, planes, stats);
         if (has_region) return cr_render_aov_region_host(h, &cd, &p, aov_layers, &region, planes, stats);
         return cr_render_aov_host(h, &cd, &p, aov_layers, planes, stats);
     }
     // The guide layers of the frames `frs` in one call (cr_render_aov_frames_host): frame k at k * aov_reals() reals in `planes`.
-    int32_t render_aov_frames(CrHandle* h, void* planes, const std::vector<int32_t>& frs, CrStats* stats = nullptr) const {
+    // counts: the frames' count planes one after the other (cr_render_aov_counts_frames_host)
+    int32_t render_aov_frames(CrHandle* h, void* planes, const std::vector<int32_t>& frs, CrStats* stats = nullptr, const int32_t* counts = nullptr) const {
         std::vector<CrKeyframe> fk, ak;
         CrCameraDesc cd = camera_desc(fk, ak);
         CrRenderParams p = render_params(0);   // the frame indices come from frs
+        if (counts) return cr_render_aov_counts_frames_host(h, &cd, &p, aov_layers, frs.data(), (int32_t)frs.size(), counts, planes, stats);
         return cr_render_aov_frames_host(h, &cd, &p, aov_layers, frs.data(), (int32_t)frs.size(), planes, stats);
     }
     // <fname>.albedo.pfm, .normal.pfm, .depth.pfm, .coverage.pfm: the requested planes of one frame
@@ -726,7 +735,7 @@ public:
         if (rc == CR_OK && has_adaptive && sample_map) rc = write_sample_map(fname, adaptive_counts.data());
         if (rc == CR_OK && aov_layers) {
             std::vector<double> planes(aov_reals());
-            rc = render_aov(h, planes.data());
+            rc = render_aov(h, planes.data(), nullptr, -1, has_adaptive && guide_at_counts ? adaptive_counts.data() : nullptr);
             if (rc == CR_OK) rc = write_aov(fname, planes.data());
         }
         return rc;
@@ -793,15 +802,16 @@ public:
             if (stats) *stats = st;
             if (rc == CR_OK && aov_layers) {
                 guides[slot].resize((aov_reals() * rs * batch.size() + sizeof(double) - 1) / sizeof(double));
+                const int32_t* const counts = has_adaptive && guide_at_counts ? maps[slot].data() : nullptr;   // the adaptive batch's, frame after frame
                 if (guides_batched) {
-                    rc = render_aov_frames(h, guides[slot].data(), batch);
+                    rc = render_aov_frames(h, guides[slot].data(), batch, nullptr, counts);
                     if (rc == CR_ERR_UNSUPPORTED) guides_batched = false;
                     else if (tm) tm->guide_calls++;
                 }
                 if (!guides_batched) {
                     rc = CR_OK;
                     for (size_t i = 0; i < batch.size() && rc == CR_OK; i++) {
-                        rc = render_aov(h, (void*)((char*)guides[slot].data() + i * aov_reals() * rs), nullptr, (int64_t)batch[i]);
+                        rc = render_aov(h, (void*)((char*)guides[slot].data() + i * aov_reals() * rs), nullptr, (int64_t)batch[i], counts ? counts + i * n_pix : nullptr);
                         if (tm) tm->guide_calls++;
                     }
                 }

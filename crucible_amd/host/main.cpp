@@ -17,8 +17,11 @@
 // blocks of `block` pixels square (8, 16, 32; default 16) stop once their two half-frame means differ by at most tol on average,
 // judged every 2 * pass samples (default 8) from min samples on (default 4 * pass); needs relaxed sums and one device; with
 // --region the region is rendered to the noise target through cr_render_adaptive_region_host, its blocks anchored at its origin,
-// and files, sample map and figures are the region's; no --aov; a movie renders --frames-per-launch frames per cr_render_adaptive_frames_host call; --sample-map also writes <frame>.samples.pfm, the samples each pixel took; --timing
+// and files, sample map and figures are the region's; no --aov -- the guide layers of an adaptive frame are --adaptive-aov's; a movie renders --frames-per-launch frames per cr_render_adaptive_frames_host call; --sample-map also writes <frame>.samples.pfm, the samples each pixel took; --timing
 // adds the passes, the blocks stopped and the samples taken),
+// --adaptive-aov albedo,normal,depth,coverage (with --adaptive only: <frame>.<layer>.pfm from cr_render_aov_counts_*_host over the counts
+// of the adaptive call -- every pixel's layers from exactly the primary rays its beauty value used; a frame, a --region, or a movie's
+// batches of --frames-per-launch frames),
 // --repeat N --timing (measurement: render_scene N times in this process, one JSON line of wall-clock phases each --
 // the shape of the reference's criterion benchmark, benches/renderer_benchmark.rs:16-42 -- the first is the cold one).
 #include "crucible.hpp"
@@ -59,7 +62,7 @@ int main(int argc, char** argv) {
     RefitMode refit = false;
     int gpus = 1, repeat = 1;
     long frames_per_launch = 1;
-    std::string sum_order = "default", aov, region, adaptive;
+    std::string sum_order = "default", aov, region, adaptive, adaptive_aov;
     bool sample_map = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -92,6 +95,7 @@ int main(int argc, char** argv) {
         else if (a == "--aov") aov = next();
         else if (a == "--region") region = next();
         else if (a == "--adaptive") adaptive = next();
+        else if (a == "--adaptive-aov") adaptive_aov = next();
         else if (a == "--sample-map") sample_map = true;
         else if (a == "--dump-desc") dump = next();
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
@@ -143,14 +147,18 @@ int main(int argc, char** argv) {
         scene.frame_format = format;
         if (sum_order != "default" && sum_order != "reference" && sum_order != "relaxed") { fprintf(stderr, "--sum-order takes default, reference or relaxed\n"); return 2; }
         scene.sum_order = sum_order == "reference" ? CR_SUM_REFERENCE_ORDER : (sum_order == "relaxed" ? CR_SUM_RELAXED : CR_SUM_DEFAULT);
-        for (size_t at = 0; !aov.empty() && at <= aov.size();) {   // a comma-separated list of layer names
-            const size_t end = std::min(aov.find(',', at), aov.size());
-            const std::string name = aov.substr(at, end - at);
-            const int32_t bit = name == "albedo" ? CR_AOV_ALBEDO : name == "normal" ? CR_AOV_NORMAL : name == "depth" ? CR_AOV_DEPTH : name == "coverage" ? CR_AOV_COVERAGE : 0;
-            if (!bit) { fprintf(stderr, "--aov takes a list of albedo, normal, depth, coverage\n"); return 2; }
-            scene.aov_layers |= bit;
-            at = end + 1;
+        if (!adaptive_aov.empty() && adaptive.empty()) { fprintf(stderr, "--adaptive-aov goes with --adaptive (the guide layers at the adaptive frame's counts)\n"); return 2; }
+        for (const std::string* list : {&aov, &adaptive_aov}) {   // each a comma-separated list of layer names
+            for (size_t at = 0; !list->empty() && at <= list->size();) {
+                const size_t end = std::min(list->find(',', at), list->size());
+                const std::string name = list->substr(at, end - at);
+                const int32_t bit = name == "albedo" ? CR_AOV_ALBEDO : name == "normal" ? CR_AOV_NORMAL : name == "depth" ? CR_AOV_DEPTH : name == "coverage" ? CR_AOV_COVERAGE : 0;
+                if (!bit) { fprintf(stderr, "%s takes a list of albedo, normal, depth, coverage\n", list == &aov ? "--aov" : "--adaptive-aov"); return 2; }
+                scene.aov_layers |= bit;
+                at = end + 1;
+            }
         }
+        scene.guide_at_counts = !adaptive_aov.empty();
         if (!region.empty()) {
             int x0 = 0, y0 = 0, rw = 0, rh = 0;
             char tail = 0;

@@ -233,6 +233,77 @@ class Renderer:
         st = self._call("cr_render_aov_region_device", args, aov_mask(layers), reg, C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
+    def render_aov_counts(self, cam, counts, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False, want_stats=True,
+                          sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_counts_host: render_aov's planes with pixel p taking the samples [0, n_p), n_p the value of the
+        (H, W) int32 plane `counts` clamped to [0, cam.samples] -- with render_adaptive's counts, the guide layers of
+        that adaptive frame.  A pixel with n_p >= 1 equals render_aov() at samples = n_p bit for bit (up to 2047
+        samples); n_p == 0 gives 0 and +inf depth.  counts=None passes a null pointer (the library refuses it).
+        Returns (dict of planes as render_aov, stats dict: samples == segments == the sum of n_p)."""
+        layers = aov_mask(layers)
+        H, W = cam.image_height, cam.image_width
+        plane = count_plane(counts, (H, W))
+        buf, planes = guide_buffer(layers, real_type, W, H)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_counts_host", args, layers, host_ptr(plane), host_ptr(buf), want_stats=want_stats)
+        return guide_planes(buf, planes, W, H), st.as_dict()
+
+    def render_aov_counts_device(self, cam, d_counts, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
+                                 want_stats=False, sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_counts_device: the plane at device pointer `d_counts` (W*H int32), the requested planes into device
+        memory at `d_ptr` as render_aov_device lays them out.  Asynchronous unless want_stats."""
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_counts_device", args, aov_mask(layers), dev_ptr(d_counts), C.c_void_p(d_ptr), want_stats=want_stats)
+        return st.as_dict() if want_stats else None
+
+    def render_aov_counts_frames(self, cam, frames, counts, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
+                                 want_stats=True, sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_counts_frames_host: the frames `frames` in one launch, frame k at the plane counts[k] ((n, H, W)
+        int32, as render_adaptive_frames returns it).  Returns (list of per-frame dicts, stats dict of the whole call);
+        frame k equals render_aov_counts() at frame frames[k] with counts[k] bit for bit."""
+        layers = aov_mask(layers)
+        fr, fr_ptr = frame_list(frames)
+        H, W = cam.image_height, cam.image_width
+        plane = count_plane(counts, (max(1, fr.size), H, W))
+        buf, planes = guide_buffer(layers, real_type, W, H, fr.size)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_counts_frames_host", args, layers, fr_ptr, fr.size, host_ptr(plane), host_ptr(buf), want_stats=want_stats)
+        return [guide_planes(buf, planes, W, H, k) for k in range(fr.size)], st.as_dict()
+
+    def render_aov_counts_frames_device(self, cam, frames, d_counts, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                                        output_sum=False, want_stats=False, sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_counts_frames_device: the planes at `d_counts` (n*W*H int32, frame after frame), the frames into
+        device memory at `d_ptr` as render_aov_frames_device lays them out.  Asynchronous unless want_stats."""
+        fr, fr_ptr = frame_list(frames)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_counts_frames_device", args, aov_mask(layers), fr_ptr, fr.size, dev_ptr(d_counts), C.c_void_p(d_ptr),
+                        want_stats=want_stats)
+        return st.as_dict() if want_stats else None
+
+    def render_aov_counts_region(self, cam, region, counts, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
+                                 want_stats=True, sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_counts_region_host: render_aov_counts over the pixels `region` = (x0, y0, w, h) with the (h, w) int32
+        plane `counts` of the region (as render_adaptive_region returns it): with the crop of a frame's plane, the crop of
+        render_aov_counts' planes bit for bit."""
+        layers = aov_mask(layers)
+        reg, (w, h) = region_arg(region)
+        w, h = max(1, w), max(1, h)
+        plane = count_plane(counts, (h, w))
+        buf, planes = guide_buffer(layers, real_type, w, h)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_counts_region_host", args, layers, reg, host_ptr(plane), host_ptr(buf), want_stats=want_stats)
+        return guide_planes(buf, planes, w, h), st.as_dict()
+
+    def render_aov_counts_region_device(self, cam, region, d_counts, d_ptr, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                                        output_sum=False, want_stats=False, sum_order=A.CR_SUM_DEFAULT):
+        """cr_render_aov_counts_region_device: the region's plane at `d_counts` (w*h int32), its requested planes into device
+        memory at `d_ptr`.  Asynchronous unless want_stats."""
+        reg, _ = region_arg(region)
+        args = self._args(cam, seed, real_type, sample_begin, sample_count, output_sum, sum_order)
+        st = self._call("cr_render_aov_counts_region_device", args, aov_mask(layers), reg, dev_ptr(d_counts), C.c_void_p(d_ptr),
+                        want_stats=want_stats)
+        return st.as_dict() if want_stats else None
+
     def render_tiled(self, cam, tile=(1024, 1024), *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
                      output_sum=False, sum_order=None, adaptive=None):
         """A whole frame assembled from render_region() calls over tiles of `tile` = (tw, th) pixels (edge tiles are
@@ -476,6 +547,17 @@ def add_stats(total, st):
     for k in ("upload_ms", "bvh_entries", "scene_in_lds"):
         into[k] = new[k]
     return total
+
+
+def count_plane(counts, shape):
+    """A count plane as the contiguous int32 array of `shape` that the guide calls at a count plane read; None stays None
+    (a null pointer, which the library refuses)."""
+    if counts is None:
+        return None
+    plane = np.ascontiguousarray(counts, dtype=np.int32)
+    if plane.shape != tuple(shape):
+        raise ValueError(f"count plane of shape {plane.shape}, expected {tuple(shape)}")
+    return plane
 
 
 def host_ptr(a):

@@ -481,9 +481,11 @@ class Scene:
         self.aov_layers = 0          # CR_AOV_* mask or layer names: writes <frame>.<layer>.pfm next to every frame file
         # set_adaptive: frames to a noise target through Renderer.render_adaptive (scene_cam.samples is the maximum per
         # pixel; needs relaxed sums; a movie with frames_per_launch > 1 renders its batches through
-        # Renderer.render_adaptive_frames); sample_map also writes <frame>.samples.pfm
+        # Renderer.render_adaptive_frames); sample_map also writes <frame>.samples.pfm; guide_at_counts: the guide files
+        # of aov_layers come from Renderer.render_aov_counts* over the adaptive call's counts
         self.adaptive = None
         self.sample_map = False
+        self.guide_at_counts = False
 
     @classmethod
     def new_image(cls, aspect_ratio, image_width, frame_rate, shutter_angle, thread_count):
@@ -581,19 +583,30 @@ class Scene:
         tl = self.scene_cam.look_from_tl if which == "from" else self.scene_cam.look_at_tl
         tl.translate_point(p, keyframe, it, space)
 
-    def set_adaptive(self, tolerance, min_samples, pass_samples, block=16):
+    def set_adaptive(self, tolerance, min_samples, pass_samples, block=16, guide_at_counts=False):
+        """Frames to a noise target.  guide_at_counts: with aov_layers, the guide files hold the layers of exactly the
+        primary rays each adaptive pixel used (Renderer.render_aov_counts over the adaptive call's counts); the default
+        keeps the plain guide pass at scene_cam.samples."""
         self.adaptive = dict(tolerance=float(tolerance), min_samples=int(min_samples), pass_samples=int(pass_samples), block=int(block))
+        self.guide_at_counts = bool(guide_at_counts)
+
+    def _guide_frame(self, r, layers, counts=None):
+        """The guide planes of the frame at the camera's counter: at `counts` (an adaptive frame's) when given."""
+        if counts is None:
+            return r.render_aov(self.scene_cam, layers, seed=self.seed, real_type=self.real_type)[0]
+        return r.render_aov_counts(self.scene_cam, counts, layers, seed=self.seed, real_type=self.real_type)[0]
 
     def _render_frame(self, r, stem=None):
-        """The frame at the camera's counter: (image, stats); an adaptive frame's sample map goes to <stem>.samples.pfm."""
+        """The frame at the camera's counter: (image, stats, the count plane of an adaptive frame whose guide layers are
+        taken at its counts, else None); an adaptive frame's sample map goes to <stem>.samples.pfm."""
         if self.adaptive is None:
-            return r.render(self.scene_cam, seed=self.seed, real_type=self.real_type)
+            return r.render(self.scene_cam, seed=self.seed, real_type=self.real_type) + (None,)
         from .renderer import write_pfm
-        img, counts, stats = r.render_adaptive(self.scene_cam, seed=self.seed, real_type=self.real_type, want_counts=self.sample_map,
-                                               **self.adaptive)
+        img, counts, stats = r.render_adaptive(self.scene_cam, seed=self.seed, real_type=self.real_type,
+                                               want_counts=self.sample_map or self.guide_at_counts, **self.adaptive)
         if self.sample_map and stem is not None:
             write_pfm(stem + ".samples.pfm", counts.astype("float32"))
-        return img, stats
+        return img, stats, counts if self.guide_at_counts else None
 
     # ---- flatten to the C ABI
     def flatten(self):
@@ -691,12 +704,11 @@ class Scene:
         r = renderer or Renderer(self.device)
         try:
             r.upload_scene(self.flatten())
-            img, stats = self._render_frame(r, fname)
+            img, stats, counts = self._render_frame(r, fname)
             r.write_ppm(fname + ".ppm", img)
             print(f"Successful render! Image stored at: {fname}.ppm")
             if aov_mask(self.aov_layers):
-                planes, _ = r.render_aov(self.scene_cam, self.aov_layers, seed=self.seed, real_type=self.real_type)
-                self._write_aov(fname, planes)
+                self._write_aov(fname, self._guide_frame(r, self.aov_layers, counts))
             return stats
         finally:
             if own:
@@ -722,7 +734,10 @@ class Scene:
             n = max(1, int(self.frames_per_launch))
             # the frames and the guide layers of a batch each come from one call, until the library refuses that call
             # (frames: reference order or refit boxes; guide layers: refit boxes): then one call per frame, the same files.
-            # Adaptive frames batch the same way (Renderer.render_adaptive_frames: one pass loop for the batch's frames)
+            # Adaptive frames batch the same way (Renderer.render_adaptive_frames: one pass loop for the batch's frames);
+            # with guide_at_counts their guide layers come from Renderer.render_aov_counts_frames over the batch's counts, or
+            # frame by frame from render_aov_counts where either batch call was refused.
+            at_counts = self.adaptive is not None and self.guide_at_counts and bool(layers)
             batched = guides_batched = n > 1
             from .renderer import write_pfm
             cam = self.scene_cam
@@ -731,12 +746,13 @@ class Scene:
                 # the camera's frame counter for each file, as the one-frame loop advances it
                 first = cam.frame
                 batch = [first + k for k in range(min(n, frames - frame) if batched or (layers and guides_batched) else 1)]
-                imgs = maps = None
+                imgs = maps = counts = None
                 if batched:
                     try:
                         if self.adaptive is not None:
-                            imgs, maps, _ = r.render_adaptive_frames(cam, batch, seed=self.seed, real_type=self.real_type,
-                                                                     want_counts=self.sample_map, **self.adaptive)
+                            imgs, counts, _ = r.render_adaptive_frames(cam, batch, seed=self.seed, real_type=self.real_type,
+                                                                       want_counts=self.sample_map or at_counts, **self.adaptive)
+                            maps = counts if self.sample_map else None
                         else:
                             imgs, _ = r.render_frames(cam, batch, seed=self.seed, real_type=self.real_type)
                     except CrucibleError as e:
@@ -744,9 +760,12 @@ class Scene:
                             raise
                         batched = False
                 guides = None
-                if layers and guides_batched:
+                if layers and guides_batched and not (at_counts and imgs is None):   # (counts of frames rendered one by one: below)
                     try:
-                        guides, _ = r.render_aov_frames(cam, batch, layers, seed=self.seed, real_type=self.real_type)
+                        if at_counts:
+                            guides, _ = r.render_aov_counts_frames(cam, batch, counts, layers, seed=self.seed, real_type=self.real_type)
+                        else:
+                            guides, _ = r.render_aov_frames(cam, batch, layers, seed=self.seed, real_type=self.real_type)
                     except CrucibleError as e:
                         if e.code != A.CR_ERR_UNSUPPORTED:
                             raise
@@ -754,13 +773,12 @@ class Scene:
                 for k, f in enumerate(batch):
                     cam.frame = f
                     stem = os.path.join(fname, "artifacts", f"image{frame:0{digits}d}")
-                    img = imgs[k] if imgs is not None else self._render_frame(r, stem)[0]
+                    img, plane = (imgs[k], counts[k] if at_counts else None) if imgs is not None else self._render_frame(r, stem)[::2]
                     if maps is not None:
                         write_pfm(stem + ".samples.pfm", maps[k].astype("float32"))
                     r.write_ppm(stem + ".ppm", img)
                     if layers:
-                        self._write_aov(stem, guides[k] if guides is not None else
-                                        r.render_aov(cam, layers, seed=self.seed, real_type=self.real_type)[0])
+                        self._write_aov(stem, guides[k] if guides is not None else self._guide_frame(r, layers, plane))
                     frame += 1
                 cam.frame = first + len(batch)
         finally:

@@ -566,6 +566,55 @@ CR_API int32_t cr_render_aov_region_host(CrHandle* h, const CrCameraDesc* cam, c
                                          const CrRegion* region, void* h_out, CrStats* stats);
 
 /*
+ * Guide layers at a count plane: the guide pass in which every pixel takes its own number of primary rays -- fed the
+ * `counts` of a cr_render_adaptive_* call, the albedo, normal, depth and coverage of exactly the primary rays that
+ * adaptive frame's beauty pixels used.  Each entry point is its cr_render_aov_* sibling with one more argument, `counts`
+ * (const int32_t*; device memory for the device forms, host memory for the host forms), in front of the output pointer.
+ * The plane is laid out as the adaptive sibling writes it: image_width*image_height values for a frame, width*height
+ * for a region, n_frames * image_width*image_height for a batch with frame k at k * image_width*image_height.
+ *
+ * Definition.  n_p = min(max(counts[p], 0), params->samples).  Pixel p takes the sample indices [0, n_p) of the stream
+ * rng_key(seed, frame pixel, s); everything else is cr_render_aov_device's definition.  The words are scaled by 2^S with
+ * S that of params->samples (the maximum), as everywhere.  Albedo, normal and coverage are (sum * 2^-S) / n_p with
+ * output_sum 0, in the arithmetic that finalizes every guide plane, and sum * 2^-S with output_sum 1.  A pixel with
+ * n_p == 0 writes +0.0 in those planes (nothing is divided by zero) and +inf depth.  Depth is the minimum over the
+ * samples taken.
+ *
+ * Consequences.  With params->samples <= 2047 (S = 52) every value of a pixel p with n_p >= 1 is BIT FOR BIT that of
+ * the sibling cr_render_aov_* call with params->samples = n_p: in f32 and f64, for every layer mask, bvh_mode, residency
+ * and CRUCIBLE_PIPELINE / CRUCIBLE_SUM_ORDER setting, and for refit_boxes as the sibling handles it.  A plane that is
+ * params->samples everywhere gives the sibling call's bytes and integer stats.
+ * stats: samples == segments == the sum of n_p over the call's pixels, taken from the kernel's own counter (the host
+ * does not read a device plane); node_tests, prim_tests and texel_fetches are the walk's own -- over a partition into
+ * rectangles on which the plane is constant they add up to those of the sibling region calls at those sample counts;
+ * kernel_ms, bvh_entries and scene_in_lds as for the sibling.
+ *
+ * Refusals, all checked before anything changes (a refused call leaves the handle as it was): the sibling's own, in its
+ * order and with its codes (a frames call that would refit or rebuild boxes is CR_ERR_UNSUPPORTED); after those a null
+ * `counts` is CR_ERR_INVALID_ARG; after that sample_begin != 0 or sample_count != samples is CR_ERR_UNSUPPORTED -- the
+ * plane counts from sample 0, as the adaptive calls do.  The values of the plane are never refused: they are clamped.
+ * The launch is sized from params->samples, so an all-zero plane still launches a kernel, which finds nothing to do.
+ * The device forms are asynchronous unless `stats` is non-NULL and read `counts` in stream order; the host forms are
+ * synchronous and copy the plane into a buffer the handle keeps (4 bytes per pixel per frame, grown on demand, freed by
+ * cr_destroy).  No Color::new check applies.  cr_export_render_bvh, cr_last_kernel_ms and cr_frame_build_info behave as
+ * after the sibling guide call.
+ */
+CR_API int32_t cr_render_aov_counts_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                           const int32_t* d_counts, void* d_out, CrStats* stats);
+CR_API int32_t cr_render_aov_counts_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                         const int32_t* h_counts, void* h_out, CrStats* stats);
+CR_API int32_t cr_render_aov_counts_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                                  const int32_t* frames, int32_t n_frames, const int32_t* d_counts, void* d_out,
+                                                  CrStats* stats);
+CR_API int32_t cr_render_aov_counts_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                                const int32_t* frames, int32_t n_frames, const int32_t* h_counts, void* h_out,
+                                                CrStats* stats);
+CR_API int32_t cr_render_aov_counts_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                                  const CrRegion* region, const int32_t* d_counts, void* d_out, CrStats* stats);
+CR_API int32_t cr_render_aov_counts_region_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* params, int32_t layers,
+                                                const CrRegion* region, const int32_t* h_counts, void* h_out, CrStats* stats);
+
+/*
  * A frame to a noise target: blocks of pixels stop taking samples once their two half-frame means agree.
  * params->samples is the MAXIMUM per pixel.  The output is image_width*image_height*3 reals, each pixel's mean over the
  * samples that pixel took; `counts` (may be NULL) receives image_width*image_height int32_t, the samples each pixel took.
