@@ -972,8 +972,11 @@ template <typename T> CR_D T load_rec(const T* p, bool in_lds) {
 template <typename real, bool ANIM, bool SIDE_SPLIT = false, bool RELAX = false>
 CR_D bool shade(const KernelArgs<real>& A, const Prim<real>* prims, const Mat<real>* mats, const Tex<real>* texs, V3<real>& ro, V3<real>& rd,
                 real rtime, uint64_t& rng, int32_t& depth_left, int32_t& stack_n, real best_t, int32_t best, uint32_t stack_stride,
-                uint32_t stack_slot, uint32_t& c_tex, V3<real>& col, Diag* dg = nullptr, V3<real>* thr = nullptr) {
+                uint32_t stack_slot, uint32_t& c_tex, V3<real>& col, Diag* dg = nullptr, V3<real>* thr = nullptr, const real* dd = nullptr) {
     CR_DIAG_HIT(dg, DG_SHADE_WAVE, DG_SHADE_LANE);
+    // unit(rd) of the incoming ray.  dd: the segment's |rd|^2 where the caller has it (WalkState::dd, walk_begin's len2(rd) of
+    // this rd: the same expression on the same operands, and -ffp-contract=off keeps it the same bits)
+    auto unit_rd = [&]() -> V3<real> { return divs(rd, r_sqrt(dd ? *dd : len2(rd))); };
     if (best >= 0) {
         CR_DIAG_HIT(dg, DG_HITSH_WAVE, DG_HITSH_LANE);
         const Prim<real>& p = prims[best];
@@ -1066,7 +1069,7 @@ CR_D bool shade(const KernelArgs<real>& A, const Prim<real>* prims, const Mat<re
         } else {                                            // dielectric.rs:30-55
             att = mk<real>(1, 1, 1);
             real ri = front ? m.albedo[0] : m.param;
-            V3<real> ud = unit(rd);
+            V3<real> ud = unit_rd();
             real cos_theta = -(r_fmin(dot(ud, n), real(1)));
             real sin_theta = r_sqrt(real(1) - cos_theta * cos_theta);
             bool refl = ri * sin_theta > real(1);
@@ -1097,7 +1100,7 @@ CR_D bool shade(const KernelArgs<real>& A, const Prim<real>* prims, const Mat<re
     }
     // sky (ray_casting.rs:133-151)
     CR_DIAG_LANE(dg, DG_SKY_LANE);
-    V3<real> ud = unit(rd);
+    V3<real> ud = unit_rd();
     if (A.sky_kind == 1) {
         real theta = r_atan2(ud.x, ud.z);
         real phi = r_asin(ud.y);
@@ -1249,7 +1252,14 @@ CR_D ScreenStepO fetch_screen_ordered(const ScreenEntryO* lds, const ScreenEntry
 }
 
 // The per-ray state of BVHWrapper::hit's walk, kept in registers so a walk can be suspended and resumed.
-template <typename real> struct WalkState {
+// What walk_begin_screened alone fills (the f64 kernels of lazy_inv(), which neither make nor read `inv` and `exact_box`);
+// an f32 walk has no such form and carries no such fields
+template <typename real> struct WalkScreened {};
+template <> struct WalkScreened<double> {
+    V3<float> invf;      // the screen's f32 1/direction (`if` in the derivation above screen_extents)
+    bool unscreened;     // the ray is outside screen_in_range: every step is Aabb::hit's compare/select form on the f64 record
+};
+template <typename real> struct WalkState : WalkScreened<real> {
     V3<real> inv;        // 1 / direction
     real dd;             // |direction|^2: Sphere::hit's `a`, the same for every sphere of the segment
     real rda;            // shared_rcp(dd) in the kernels that share it (quot_form() == 1), quot_divide() in the others
@@ -1275,6 +1285,10 @@ template <bool SHARED = false, typename real> CR_D void walk_begin(WalkState<rea
     w.idx = 0; w.best_t = r_inf(real(0)); w.best = -1; w.pending = -1;
     w.oct = (rd.x < real(0) ? 1 : 0) | (rd.y < real(0) ? 2 : 0) | (rd.z < real(0) ? 4 : 0);
 }
+// The same for the f64 SCREEN kernels of lazy_inv(): the screen's f32 1/direction without the three IEEE divisions, and the
+// ray's classification, once per segment (screen_inv, above screen_q, has the argument).  `inv` and `exact_box` are left as they
+// are: walk_round<..., LAZY_INV = true> reads neither, and divides 1.0 / rd itself where Aabb::hit's f64 form runs.
+template <bool SHARED = false, typename real> CR_D void walk_begin_screened(WalkState<real>& w, V3<real> ro, V3<real> rd);
 
 // One round of the while-while walk for the lanes with `walking` set: step through wrappers in the reference's
 // order (left child on a box hit, skip link on a miss) until the lane reaches a leaf wrapper, runs out of wrappers
@@ -1331,9 +1345,46 @@ CR_D void screen_extents(float ofx, float ofy, float ofz, float ifx, float ify, 
 CR_D bool screen_in_range(bool exact_box, float mo, float pmax, float pmin) {
     return !exact_box && pmin >= 0x1.0p-100f && pmax <= 0x1.0p100f && mo <= 0x1.0p100f;
 }
+// The f64 SCREEN kernels of lazy_inv() begin a walk with walk_begin_screened, which makes `if` without the IEEE division:
+//     r0 = v_rcp_f64(d),    r1 = fma(r0, fma(-d, r0, 1), r0),    if = (float)r1.
+// The derivation above takes if = inv (1 + I) with |I| <= u and rounds its constants up: 3.01u and 5.02u stand for 3u + u^2 and
+// 5u + 4u^2 + u^3 over 1 - 2u - u^2, i.e. for 3.0000004u and 5.0000007u.  With r1 = inv (1 + R) the rounding to f32 gives
+// |I| <= u + |R| (1 + u), which enters the bound wherever I does: at most twice in E's |t32| term and |o inv| term (B + I + B I,
+// W + I + P + ...).  2 |R| (1 + u) <= 0.009u, i.e. |R| <= 0.0045u = 2^-31.8, keeps both constants below 3.01u and 5.02u, so TH
+// stands as it is.  v_rcp_f64 is an approximation, not the rounded reciprocal (the compiler's own division refines it twice
+// before it trusts it); with r0 = inv (1 - e0) one Newton step gives r1 = inv (1 - e0^2) before its own two roundings of 2^-53
+// each, so |e0| <= 2^-21 is all the requirement asks of the instruction.  No published precision of the instruction is relied
+// on here: that the device meets the requirement is an empirical guarantee, the test's.  tests/test_gpu_screen_inv.py holds it to
+// |r1 d - 1| <= 2^-40 over every binade of the range, 2^8 under the requirement (measured: 2^-48.7 at worst, and (float)r1
+// equal to (float)(1.0 / d) for each of 3 * 10^6 components).  Outside the range nothing is asked of r1
+// but to leave the range: a zero, subnormal, infinite or NaN component makes r0 infinite, zero or NaN and r1 NaN or infinite
+// (inf - inf, 0 * inf inside the step), |d| beyond 2^+-100 makes |r1| leave [2^-100, 2^100] with it, and every comparison below
+// is false for a NaN.  Such a ray takes Aabb::hit's compare/select form on the f64 records, with 1.0 / d divided where that form
+// runs (walk_round's LAZY_INV): valid for every ray, so a ray within rounding of the range's ends may fall on either side.
+CR_D double screen_rcp1(double d) {   // r1
+    const double r0 = __builtin_amdgcn_rcp(d);
+    return __builtin_fma(r0, __builtin_fma(-d, r0, 1.0), r0);
+}
+CR_D float screen_inv(double d) { return (float)screen_rcp1(d); }
+CR_D float screen_inv(float d) { return 1.0f / d; }   // (never used: the f32 kernels' record is the box itself)
+CR_D bool screen_in_range_lazy(float mo, float ifx, float ify, float ifz) {
+    const float ax = __builtin_fabsf(ifx), ay = __builtin_fabsf(ify), az = __builtin_fabsf(ifz);
+    return ax >= 0x1.0p-100f && ax <= 0x1.0p100f && ay >= 0x1.0p-100f && ay <= 0x1.0p100f && az >= 0x1.0p-100f && az <= 0x1.0p100f &&
+           mo <= 0x1.0p100f;
+}
 CR_D float screen_q(float of, float inv_f) { return __builtin_fabsf(of * inv_f); }   // |of if| on one axis
 CR_D float screen_th0(float qx, float qy, float qz, float pmax) {
     return __builtin_fmaf(0x1.0p-20f, r_max(r_max(qx, qy), qz), __builtin_fmaf(pmax * 0x1.0p-100f, 0x1.0p-47f, 1e-35f));
+}
+template <bool SHARED, typename real> CR_D void walk_begin_screened(WalkState<real>& w, V3<real> ro, V3<real> rd) {
+    static_assert(std::is_same<real, double>::value, "the f32 kernels' record is the wrapper's own box: they begin with walk_begin");
+    w.invf = mk<float>(screen_inv(rd.x), screen_inv(rd.y), screen_inv(rd.z));
+    const float mo = r_max(r_max(__builtin_fabsf((float)ro.x), __builtin_fabsf((float)ro.y)), __builtin_fabsf((float)ro.z));
+    w.unscreened = !screen_in_range_lazy(mo, w.invf.x, w.invf.y, w.invf.z);
+    w.dd = len2(rd);
+    w.rda = SHARED ? shared_rcp(w.dd) : quot_divide<real>();
+    w.idx = 0; w.best_t = r_inf(real(0)); w.best = -1; w.pending = -1;
+    w.oct = (rd.x < real(0) ? 1 : 0) | (rd.y < real(0) ? 2 : 0) | (rd.z < real(0) ? 4 : 0);
 }
 // f64 kernels: hi32 - lo32 on the screening box b, and its TH in `th`.  The decision is d < -th (miss) or d > th (hit);
 // anything else (NaN included) is left to Aabb::hit in f64.
@@ -1389,14 +1440,50 @@ template <typename real, int RES, bool ANIM, bool SCREEN> constexpr int quot_for
 #endif
 }
 
+// -DCR_SPHERE_LOOP=0, -DCR_SHADE_DD=0: the A/B switches of the spheres-only primitive loop (walk_round) and of shade's reuse of
+// WalkState::dd in the render kernels (profiles/experiments/segment_setup_ab.txt)
+#ifndef CR_SPHERE_LOOP
+#define CR_SPHERE_LOOP 1
+#endif
+#ifndef CR_SHADE_DD
+#define CR_SHADE_DD 1
+#endif
+// Which kernels begin a segment with walk_begin_screened and walk with LAZY_INV: decided like quot_form(), from the compiler's
+// allocation and the A/B (DESIGN.md section 3.11 has the table) -- the static f64 render kernels that walk on screening records
+// of an unordered tree.  The keyed and batch kernels (ANIM, CAMK) would gain SGPR spills, the ordered-tree kernels measured
+// 0.8 % slower with it; they, the guide-layer kernels, the cross-check pipelines and every f32 kernel keep walk_begin.
+// -DCR_LAZY_INV=0 builds the kernels without it.
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK, bool SCREEN> constexpr bool lazy_inv() {
+#if defined(CR_LAZY_INV) && CR_LAZY_INV == 0
+    return false;
+#else
+    return std::is_same<real, double>::value && SCREEN && !ANIM && !ORD && !CAMK;
+#endif
+}
+// Which kernels test a scene of spheres alone in a loop of its own (walk_round's SPHERE_LOOP): by the same rule
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK, bool SCREEN> constexpr bool sphere_loop() {
+    return CR_SPHERE_LOOP && std::is_same<real, double>::value && SCREEN && RES == RES_LDS && !ANIM && !ORD && !CAMK;
+}
+
+// 1 / direction as walk_begin divides it, for Aabb::hit's f64 form where a LAZY_INV walk runs it
+// (the direction passes through an empty asm: the divisions are loop-invariant and free of side effects, and the optimiser
+// hoisted them out of the band branch and the rounds loop to where walk_begin had them, once per outer iteration)
+template <typename real> CR_D V3<real> inv_of(V3<real> rd) {
+    asm volatile("" : "+v"(rd.x), "+v"(rd.y), "+v"(rd.z));
+    return mk<real>(real(1) / rd.x, real(1) / rd.y, real(1) / rd.z);
+}
+
 // SHARE: the caller began the walk with walk_begin<quot_form() == 1>; the guide-layer kernels and the cross-check pipelines do not.
-template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false, bool SHARE = false>
+// LAZY_INV (f64 SCREEN kernels): the caller began it with walk_begin_screened; 1 / direction is divided where f64 needs it.
+// SPHERE_LOOP (sphere_loop()'s kernels): the leaf phase tests a scene of spheres alone in a loop of its own.
+template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false, bool SHARE = false, bool LAZY_INV = false, bool SPHERE_LOOP = false>
 CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, const Prim<real>* prims, V3<real> ro, V3<real> rd, real rtime,
                      WalkState<real>& w, bool walking, uint32_t budget, unsigned long long& c_node, uint32_t& c_prim, Diag* dg = nullptr,
                      const void* lds_screen = nullptr) {
     // f64: decisions on the f32 copy where f32 can decide; f32 (EXACT below): the record IS the wrapper's box, in the link layout of ScreenEntry
     constexpr bool EXACT = std::is_same<real, float>::value;
     static_assert(!(SCREEN && EXACT && ORD), "the f32 kernels use ScreenEntry records for unordered trees only");
+    static_assert(!LAZY_INV || (SCREEN && !EXACT), "LAZY_INV is a form of the f64 SCREEN kernels");
     const real tmin = real(0.001);
     const int32_t n_entries = A.n_entries;
     // SCREEN kernels keep only screening records in LDS: the rare f64 record is read from global memory
@@ -1407,15 +1494,20 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
         CR_DIAG_HIT(dg, DG_ROUND_WAVE, DG_ROUND_LANE);
         // SCREEN kernels: steps the f32 loop could not take -- one, for a lane it left at a box too close to call, or all of
         // them for a ray outside its range -- are made below with Aabb::hit's own compare/select form on the f64 records
-        uint32_t exact_steps = w.exact_box ? 0xffffffffu : 0u;
+        uint32_t exact_steps = 0u;
+        if constexpr (!LAZY_INV) exact_steps = w.exact_box ? 0xffffffffu : 0u;
         if constexpr (SCREEN) {
             const float ofx = (float)ro.x, ofy = (float)ro.y, ofz = (float)ro.z;
-            const float ifx = (float)w.inv.x, ify = (float)w.inv.y, ifz = (float)w.inv.z;
+            float ifx, ify, ifz;
+            if constexpr (LAZY_INV) { ifx = w.invf.x; ify = w.invf.y; ifz = w.invf.z; }
+            else { ifx = (float)w.inv.x; ify = (float)w.inv.y; ifz = (float)w.inv.z; }
             float mo, pmax, pmin;
-            screen_extents(ofx, ofy, ofz, ifx, ify, ifz, mo, pmax, pmin);
+            if constexpr (LAZY_INV) pmax = r_max(r_max(__builtin_fabsf(ifx), __builtin_fabsf(ify)), __builtin_fabsf(ifz));   // (classified at the segment's start)
+            else screen_extents(ofx, ofy, ofz, ifx, ify, ifz, mo, pmax, pmin);
             // (an f32 kernel's test on the record is Aabb::hit itself for every ray with finite 1/direction: no range to respect)
             bool screened;
-            if constexpr (EXACT) screened = !w.exact_box;
+            if constexpr (LAZY_INV) screened = !w.unscreened;   // walk_begin_screened decided, once per segment
+            else if constexpr (EXACT) screened = !w.exact_box;
             else screened = screen_in_range(w.exact_box, mo, pmax, pmin);
             if (!screened) exact_steps = 0xffffffffu;
             else {
@@ -1447,7 +1539,8 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
                             CR_DIAG_HIT(dg, DG_BAND_WAVE, DG_BAND_LANE);
                             const Entry<real> e = ORD ? fetch_entry_ordered<real, RES64>(lds_entries, A.entries, lds_n64, idx, w.oct)
                                                       : fetch_entry<real, RES64>(lds_entries, A.entries, lds_n64, idx);
-                            d = box_hit(e.b, ro, w.inv, tmin, w.best_t) ? 1.0f : -1.0f;
+                            if constexpr (LAZY_INV) d = box_hit(e.b, ro, inv_of(rd), tmin, w.best_t) ? 1.0f : -1.0f;
+                            else d = box_hit(e.b, ro, w.inv, tmin, w.best_t) ? 1.0f : -1.0f;
                         }
                     }
                     return d < 0.0f;
@@ -1516,11 +1609,15 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             }
             c_node += nodes;
         }
+        V3<real> inv_lazy = mk<real>(0, 0, 0);   // LAZY_INV: the divisions only where the loop runs
+        if constexpr (LAZY_INV) { if (exact_steps != 0u && w.idx < n_entries) inv_lazy = inv_of(rd); }
         for (; exact_steps != 0u && w.idx < n_entries; exact_steps--) {
             const Entry<real> e = ORD ? fetch_entry_ordered<real, RES64>(lds_entries, A.entries, lds_n64, w.idx, w.oct)
                                       : fetch_entry<real, RES64>(lds_entries, A.entries, lds_n64, w.idx);
             c_node++;
-            bool hit = box_hit(e.b, ro, w.inv, tmin, w.best_t);
+            bool hit;
+            if constexpr (LAZY_INV) hit = box_hit(e.b, ro, inv_lazy, tmin, w.best_t);
+            else hit = box_hit(e.b, ro, w.inv, tmin, w.best_t);
             w.idx = (hit && e.leaf < 0) ? (ORD ? ordered_near(e.leaf, w.oct) : -e.leaf) : e.skip;
             if (hit && e.leaf >= 0) { leaf = e.leaf; break; }
         }
@@ -1577,6 +1674,25 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
                 test(first);
                 asm volatile("" :: "v"(t0), "v"(t1));
                 if (count == 2) test(first + 1);
+            } else if constexpr (SPHERE_LOOP) {
+                // sphere_loop()'s kernels: a scene of spheres alone (book1: A.uniform_kind == 0, a scalar test made once per
+                // leaf phase and not in every test) runs a copy of the loop without the triangle test and the divergent region
+                // around it; the second record hangs on the leaf code's count bit, not on a second induction variable
+                static_assert(RES == RES_LDS && !ANIM, "the one-or-two-record loop on primitives in LDS");
+                if (A.uniform_kind == 0) {
+                    auto sphere = [&](int32_t pi) {   // `test`, for a record that is known to be a sphere
+                        const Prim<real>& p = prims[pi];
+                        c_prim++;
+                        CR_DIAG_HIT(dg, DG_PRIM_WAVE, DG_PRIM_LANE);
+                        real t;
+                        if (sphere_t<true, QF != 0>(p.g[0], p.g[1], p.g[2], p.g[3], ro, rd, w.dd, tmin, w.best_t, t, dg, ra)) { w.best_t = t; w.best = pi; }
+                    };
+                    sphere(first);
+                    if (leaf & 1) sphere(first + 1);
+                } else {
+                    test(first);
+                    if (leaf & 1) test(first + 1);
+                }
             } else
             for (int32_t k = 0; k < count; k++) test(first + k);
         } else {
@@ -1756,6 +1872,8 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
     // walk state, kept across rounds: a lane whose walk is cut short resumes where it stopped
     WalkState<real> ws;
     ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.rda = quot_divide<real>(); ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
+    constexpr bool LAZY = lazy_inv<real, RES, ANIM, ORD, CAMK, SCREEN>();   // walk_begin_screened / walk_round's LAZY_INV
+    if constexpr (LAZY) { ws.invf = mk<float>(0, 0, 0); ws.unscreened = false; }
     const int32_t n_entries = A.n_entries;
     // read once, into a scalar register that stays: a load at every walk_begin would wait with the LDS reads around it
     uint32_t exact_tree = tree_walks_exact(A) ? 1u : 0u;
@@ -1877,7 +1995,8 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
             if (depth_left == 0) finished = true;   // ray_color: depth == 0 -> black
             else {
                 c_seg++;
-                walk_begin<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, rd, exact_tree != 0u);
+                if constexpr (LAZY) walk_begin_screened<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, ro, rd);
+                else walk_begin<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, rd, exact_tree != 0u);
                 state = n_entries > 0 ? ST_WALK : ST_SHADE;
             }
         }
@@ -1887,7 +2006,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         // shading changes.
         if (__ballot(state == ST_WALK)) {
             for (;;) {
-                walk_round<real, RES, ANIM, ORD, SCREEN, true>(A, lds_entries, prims, ro, rd, rtime, ws, state == ST_WALK, A.walk_round_steps, c_node, c_prim, dgp, lds_screen);
+                walk_round<real, RES, ANIM, ORD, SCREEN, true, LAZY, sphere_loop<real, RES, ANIM, ORD, CAMK, SCREEN>()>(A, lds_entries, prims, ro, rd, rtime, ws, state == ST_WALK, A.walk_round_steps, c_node, c_prim, dgp, lds_screen);
                 if (state == ST_WALK && ws.idx >= n_entries && ws.pending < 0) state = ST_SHADE;
                 const uint64_t walking = __ballot(state == ST_WALK);
                 if (!walking || 64u - (uint32_t)__popcll(walking) >= A.walk_exit_lanes) break;
@@ -1899,7 +2018,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         // ---------------- shade
         if (tracing) {
             finished = shade<real, ANIM, RES == RES_TOP, RELAX>(A, prims, mats, texs, ro, rd, rtime, rng, depth_left, stack_n, ws.best_t, ws.best,
-                                         A.n_threads, gtid, c_tex, col, dgp, &thr);
+                                         A.n_threads, gtid, c_tex, col, dgp, &thr, CR_SHADE_DD ? &ws.dd : nullptr);
             state = ST_TRACE;   // scattered: a fresh ray to walk (overwritten below when the path finished)
         }
 
