@@ -189,6 +189,10 @@ SYMBOLS = {
                                          C.POINTER(C.c_int32)]),
     "cr_frame_build_info": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CrBuildInfo)]),
     "cr_update_primitives": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32]),
+    "cr_update_materials": (C.c_int32, [C.c_void_p, C.POINTER(CrMaterial), C.c_int32, C.POINTER(CrTexture), C.c_int32,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]),
+    "cr_update_image": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "cr_set_sky": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "cr_last_kernel_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double)]),
     "cr_synchronize": (C.c_int32, [C.c_void_p]),
     "cr_stream": (C.c_void_p, [C.c_void_p]),
@@ -211,6 +215,10 @@ SYMBOLS = {
     "cr_group_upload_scene": (C.c_int32, [C.c_void_p, C.POINTER(CrSceneDesc)]),
     "cr_group_update_primitives": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,
                                                C.c_int32]),
+    "cr_group_update_materials": (C.c_int32, [C.c_void_p, C.POINTER(CrMaterial), C.c_int32, C.POINTER(CrTexture), C.c_int32,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]),
+    "cr_group_update_image": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "cr_group_set_sky": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "cr_group_render": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_void_p,
                                     C.POINTER(CrGroupStats)]),
     "cr_group_render_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_void_p,

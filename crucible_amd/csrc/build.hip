@@ -125,12 +125,6 @@ int32_t finish_boxes(CrHandle* h, DevScene<real>& ds, std::vector<Entry<real>>& 
     return CR_OK;
 }
 
-// LDS a scene takes when it sits there whole: its wrappers, primitive records, materials and textures
-template <typename real> size_t scene_lds_bytes(const DevScene<real>& ds) {
-    return r16((size_t)ds.n_entries * ds.entry_bytes) + r16((size_t)ds.n_prims * sizeof(Prim<real>)) + r16((size_t)ds.n_mats * sizeof(Mat<real>)) +
-           r16((size_t)ds.n_texs * sizeof(Tex<real>));
-}
-
 // What a build did (cr_build_info, cr_frame_build_info); total_ms runs from t_begin to now
 static CrBuildInfo build_info(int32_t bvh_mode, bool on_device, int32_t n_wrappers, const SahDeviceStats& dev_stats, double tree_ms,
                               std::chrono::steady_clock::time_point t_begin) {
@@ -168,12 +162,9 @@ template <typename real>
 int32_t upload_scene(CrHandle* h, DevScene<real>& ds, const SceneBoxes<real>& in, const LeafLayout<real>& lay, const std::vector<int8_t>& axis, bool spliced) {
     const Builder<real>& b = in.b;
     // Device texture table, materials, textures and keyframes (pack.hpp)
-    const std::vector<int32_t> tex_remap = live_texture_remap(h->materials.data(), h->materials.size(), h->textures.data(), h->textures.size());
-    std::vector<Mat<real>> mats(h->materials.size());
-    for (size_t i = 0; i < mats.size(); i++) mats[i] = pack_mat<real>(h->materials[i], h->textures.data(), tex_remap.data());
+    std::vector<Mat<real>> mats;
     std::vector<Tex<real>> texs;
-    for (size_t i = 0; i < h->textures.size(); i++)
-        if (tex_remap[i] >= 0) texs.push_back(pack_tex<real>(h->textures[i], tex_remap.data()));
+    pack_side_tables<real>(h->materials, h->textures, mats, texs);
     std::vector<Key<real>> keys(h->keys.size());
     if (!keys.empty()) memset(keys.data(), 0, keys.size() * sizeof(Key<real>));
     for (size_t i = 0; i < h->keys.size(); i++) key_to_real(h->keys[i], keys[i]);
@@ -286,13 +277,9 @@ template <typename real> int32_t build_frame_scene(CrHandle* h, real ta, real tb
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier render may still walk the frame tree this build overwrites
     fs.frame_valid = false; fs.built = false;
     fs.info = CrBuildInfo();
-    // the side tables are the base tree's (not owned: a DevBuf without an allocation of its own releases nothing)
-    for (auto pr : {std::make_pair(&fs.mats, &base.mats), std::make_pair(&fs.texs, &base.texs), std::make_pair(&fs.keys, &base.keys)}) {
-        pr.first->p = pr.second->p; pr.first->raw = nullptr; pr.first->bytes = pr.second->bytes; pr.first->pad = pr.second->pad;
-    }
+    alias_side_tables(fs, base);   // the side tables are the base tree's
     fs.ordered = base.ordered; fs.animated = base.animated; fs.has_triangles = base.has_triangles; fs.has_spheres = base.has_spheres;
     fs.has_leaf_runs = false; fs.has_lists = false; fs.has_bvh_elements = false; fs.desc_pos_valid = false;
-    fs.n_mats = base.n_mats; fs.n_texs = base.n_texs; fs.n_scene_keys = base.n_scene_keys;
     const bool on_device = h->bvh_device && n >= 3;   // fewer are one leaf, written on the host (as in build_dev_scene)
     const dim3 block(256), grid((unsigned)((n + 255) / 256));
     HIP_TRY(h, fs.frame_map.ensure((size_t)n * 2 * sizeof(int32_t)));

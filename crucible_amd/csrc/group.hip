@@ -123,6 +123,45 @@ int32_t cr_group_update_primitives(CrGroup* g, const int32_t* prim_index, const 
     return CR_OK;
 }
 
+int32_t cr_group_update_materials(CrGroup* g, const CrMaterial* materials, int32_t n_materials, const CrTexture* textures, int32_t n_textures,
+                                  const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign) {
+    if (!g) return CR_ERR_INVALID_ARG;
+    DeviceGuard guard;
+    for (CrHandle* h : g->members) {   // every member is validated before any is changed
+        int32_t rc = validate_materials(h, materials, n_materials, textures, n_textures, prim_index, prim_material, n_assign);
+        if (rc != CR_OK) return gfail(g, rc, h->error);
+    }
+    for (CrHandle* h : g->members) {
+        int32_t rc = apply_materials(h, materials, n_materials, textures, n_textures, prim_index, prim_material, n_assign);
+        if (rc != CR_OK) return gfail(g, rc, h->error);
+    }
+    return CR_OK;
+}
+
+int32_t cr_group_update_image(CrGroup* g, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height, const uint8_t* rgb8) {
+    if (!g) return CR_ERR_INVALID_ARG;
+    DeviceGuard guard;
+    for (CrHandle* h : g->members) {
+        int32_t rc = validate_image(h, image, x0, y0, width, height, rgb8);
+        if (rc != CR_OK) return gfail(g, rc, h->error);
+    }
+    for (CrHandle* h : g->members) {
+        int32_t rc = apply_image(h, image, x0, y0, width, height, rgb8);
+        if (rc != CR_OK) return gfail(g, rc, h->error);
+    }
+    return CR_OK;
+}
+
+int32_t cr_group_set_sky(CrGroup* g, int32_t sky_kind, int32_t sky_image) {
+    if (!g) return CR_ERR_INVALID_ARG;
+    for (CrHandle* h : g->members) {
+        int32_t rc = validate_sky(h, sky_kind, sky_image);
+        if (rc != CR_OK) return gfail(g, rc, h->error);
+    }
+    for (CrHandle* h : g->members) apply_sky(h, sky_kind, sky_image);
+    return CR_OK;
+}
+
 // Failure handling.  Nothing is launched before every local member's arguments have been validated and its buffers exist,
 // so bad arguments fail the same way on every rank.  A member that fails later (its render, an allocation) does NOT leave:
 // with a collective, every member first takes part in a 4-byte ncclAllReduce(min) of "my render is fine" on the render's own

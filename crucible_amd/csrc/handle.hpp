@@ -6,7 +6,8 @@
 //                      the splice, the leaf layout, the export walk), the LBVH driver (lbvh.hpp, hipcub), cr_export_bvh, cr_build_info;
 //                      the per-frame tree of CR_REFIT_REBUILD (build_frame_scene), cr_export_render_bvh, cr_frame_build_info
 //   sah_device.hip     the device-side SAH builder of CR_BVH_BUILD_DEVICE (sah_device.hpp, hipcub)
-//   scene.hip          cr_upload_scene, refit.hpp's box kernels, the screening records, cr_update_primitives (update.hpp)
+//   scene.hip          cr_upload_scene (its descriptor checks: scene_checks.hpp, a header free of the HIP runtime), refit.hpp's box kernels,
+//                      the screening records, cr_update_primitives, cr_update_materials, cr_update_image, cr_set_sky (update.hpp)
 //   render.hip         render_typed: a render's kernel arguments up to the choice of ladder; the stats epilogue
 //   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder over residency.hpp's rule)
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
@@ -26,6 +27,7 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace cr {
@@ -80,7 +82,8 @@ template <typename real> struct DevScene {
                                              // `prims`, -1 where it has none (hidden); scenes without list elements only (cr_update_primitives)
     bool desc_pos_valid = false;
     CrBuildInfo info = {};                   // what the last build of this precision did (cr_build_info)
-    bool side_tables = false;                // mats / texs / keys hold the uploaded scene's (a rebuild after cr_update_primitives keeps them)
+    bool side_tables = false;                // mats / texs / keys hold the uploaded scene's, as cr_update_materials last repacked mats / texs (a rebuild
+                                             // after cr_update_primitives or cr_update_materials keeps them)
     // CR_REFIT_REBUILD (build.hip build_frame_scene).  On the base tree of a SAH mode: what a frame build starts from.
     std::vector<int32_t> in_desc;            // builder input position -> index in the caller's primitive list (the order the SAH builders see)
     std::vector<int32_t> base_order;         // leaf-order position -> builder input position (leaf_desc[i] = in_desc[base_order[i]])
@@ -119,11 +122,15 @@ struct CrHandle {
     int32_t sky_kind = 0, sky_image = -1, bvh_mode = 0;   // bvh_mode: the base mode, CrSceneDesc.bvh_mode's low byte
     bool bvh_device = false;          // CR_BVH_BUILD_DEVICE: the SAH modes build on the device (sah_device.hpp)
     bool has_list_elements = false;   // some CR_PRIM_LIST / CR_PRIM_BVH record: cr_update_primitives does not apply
-    DevBuf update_stage;              // cr_update_primitives: the call's rows (9 doubles each), then its indices
+    DevBuf update_stage;              // cr_update_primitives: the call's rows (9 doubles each), then its indices; cr_update_materials: its
+                                      // indices, then its materials; cr_update_image: its RGB8 bytes
     SahDeviceWork sah_work;           // build_sah_device's buffers, kept from build to build: CR_UPDATE_REBUILD sits in an edit loop
     // images are precision independent
     DevBuf images, texels;
     int32_t n_images = 0;
+    std::vector<int32_t> image_w, image_h;  // the images' sizes and texel offsets as uploaded (cr_update_image)
+    std::vector<uint32_t> image_offset;
+    size_t n_texels = 0;                    // words in `texels`
     DevScene<float> s32;
     DevScene<double> s64;
     DevScene<float> f32;              // CR_REFIT_REBUILD: the frame tree of each precision, beside the base tree
@@ -329,6 +336,19 @@ ResidencyQuery residency_query(const CrHandle* h, const DevScene<real>& ds, cons
     return q;
 }
 
+// LDS a scene takes when it sits there whole: its wrappers, primitive records, materials and textures
+template <typename real> inline size_t scene_lds_bytes(const DevScene<real>& ds) {
+    return r16((size_t)ds.n_entries * ds.entry_bytes) + r16((size_t)ds.n_prims * sizeof(Prim<real>)) + r16((size_t)ds.n_mats * sizeof(Mat<real>)) +
+           r16((size_t)ds.n_texs * sizeof(Tex<real>));
+}
+// A frame tree's side tables are the base tree's (not owned: a DevBuf without an allocation of its own releases nothing)
+template <typename real> inline void alias_side_tables(DevScene<real>& fs, const DevScene<real>& base) {
+    for (auto pr : {std::make_pair(&fs.mats, &base.mats), std::make_pair(&fs.texs, &base.texs), std::make_pair(&fs.keys, &base.keys)}) {
+        pr.first->p = pr.second->p; pr.first->raw = nullptr; pr.first->bytes = pr.second->bytes; pr.first->pad = pr.second->pad;
+    }
+    fs.n_mats = base.n_mats; fs.n_texs = base.n_texs; fs.n_scene_keys = base.n_scene_keys;
+}
+
 // build.hip
 template <typename real> int32_t build_dev_scene(CrHandle* h);
 // What a render or guide pass walks: builds the base tree, settles CrRenderParams.refit_boxes -- *refit: the
@@ -352,6 +372,15 @@ int32_t make_screen(CrHandle* h, DevScene<double>& ds, const void* entries, DevB
 int32_t make_screen(CrHandle* h, DevScene<float>& ds, const void* entries, DevBuf& out, bool* usable);
 int32_t validate_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags);
 int32_t apply_update(CrHandle* h, const int32_t* prim_index, const double* v, int32_t n, int32_t flags);
+// cr_update_materials, cr_update_image, cr_set_sky: everything that can refuse the call, then the edit itself
+int32_t validate_materials(CrHandle* h, const CrMaterial* materials, int32_t n_materials, const CrTexture* textures, int32_t n_textures,
+                           const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign);
+int32_t apply_materials(CrHandle* h, const CrMaterial* materials, int32_t n_materials, const CrTexture* textures, int32_t n_textures,
+                        const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign);
+int32_t validate_image(CrHandle* h, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height, const uint8_t* rgb8);
+int32_t apply_image(CrHandle* h, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height, const uint8_t* rgb8);
+int32_t validate_sky(CrHandle* h, int32_t sky_kind, int32_t sky_image);
+void apply_sky(CrHandle* h, int32_t sky_kind, int32_t sky_image);
 // render.hip
 int32_t finish_stats(CrHandle* h, CrStats* stats, uint64_t samples, int32_t bvh_entries, int32_t scene_in_lds);
 int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_large_override, size_t lds_base, size_t lds_per_wave,

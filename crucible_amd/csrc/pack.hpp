@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/crucible_hip.h"
 #include "pathtrace.hpp"
+#include "scene_checks.hpp"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -25,21 +26,7 @@ template <typename real> Prim<real> pack_prim(const CrPrimitive& p) {
     return q;
 }
 
-// Device texture table: only textures a non-solid lambertian can reach (a solid top-level texture is folded into its
-// material), re-indexed densely; children keep smaller indices.  Returns the new index of every texture, or -1.
-inline std::vector<int32_t> live_texture_remap(const CrMaterial* materials, size_t n_materials, const CrTexture* textures, size_t n_textures) {
-    std::vector<int32_t> tex_remap(n_textures, -1);
-    std::vector<char> live(n_textures, 0);
-    for (size_t i = 0; i < n_materials; i++) {
-        const CrMaterial& m = materials[i];
-        if (m.kind == CR_MAT_LAMBERTIAN && textures[m.texture].kind != CR_TEX_SOLID) live[m.texture] = 1;
-    }
-    for (size_t i = n_textures; i-- > 0;)   // parents have larger indices than children
-        if (live[i] && textures[i].kind == CR_TEX_CHECKER) { live[textures[i].even] = 1; live[textures[i].odd] = 1; }
-    int32_t next = 0;
-    for (size_t i = 0; i < live.size(); i++) if (live[i]) tex_remap[i] = next++;
-    return tex_remap;
-}
+// live_texture_remap, the device texture table's re-indexing, reads descriptors alone: scene_checks.hpp
 
 template <typename real> Mat<real> pack_mat(const CrMaterial& m, const CrTexture* textures, const int32_t* tex_remap) {
     Mat<real> o;
@@ -68,6 +55,17 @@ template <typename real> Tex<real> pack_tex(const CrTexture& t, const int32_t* t
     o.odd = t.kind == CR_TEX_CHECKER ? tex_remap[t.odd] : -1;
     for (int k = 0; k < 3; k++) o.color[k] = (real)t.color[k];
     return o;
+}
+
+// The device's material and texture tables of a description: what build_dev_scene uploads and cr_update_materials repacks
+template <typename real>
+void pack_side_tables(const std::vector<CrMaterial>& materials, const std::vector<CrTexture>& textures, std::vector<Mat<real>>& mats, std::vector<Tex<real>>& texs) {
+    const std::vector<int32_t> tex_remap = live_texture_remap(materials.data(), materials.size(), textures.data(), textures.size());
+    mats.resize(materials.size());
+    for (size_t i = 0; i < mats.size(); i++) mats[i] = pack_mat<real>(materials[i], textures.data(), tex_remap.data());
+    texs.clear();
+    for (size_t i = 0; i < textures.size(); i++)
+        if (tex_remap[i] >= 0) texs.push_back(pack_tex<real>(textures[i], tex_remap.data()));
 }
 
 // Images: RGB8 -> RGBA8 words, one flat texel array.  false when the texels do not fit 32-bit offsets.

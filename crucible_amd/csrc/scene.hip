@@ -1,10 +1,12 @@
 // scene.hip -- the scene on the handle: cr_upload_scene validates and deep-copies the description; the device steps
-// that upload, refit and update share (wrapper boxes bottom-up, refit.hpp; the f32 screening records); and
-// cr_update_primitives (update.hpp).
+// that upload, refit and update share (wrapper boxes bottom-up, refit.hpp; the f32 screening records);
+// cr_update_primitives (update.hpp); and cr_update_materials, cr_update_image, cr_set_sky,
+// which run the descriptor checks of scene_checks.hpp that cr_upload_scene runs.
 #include "handle.hpp"
 #include "refit.hpp"
 #include "screen.hpp"
 #include "pack.hpp"
+#include "scene_checks.hpp"
 #include "update.hpp"
 
 #include <chrono>
@@ -146,6 +148,132 @@ int32_t apply_update(CrHandle* h, const int32_t* prim_index, const double* v, in
     return rc;
 }
 
+// ---------------------------------------------------------------- cr_update_materials, cr_update_image, cr_set_sky
+// Everything that can refuse cr_update_materials, before anything changes: the call's own refusals, then cr_upload_scene's
+// checks of the description the edit would leave (scene_checks.hpp).
+int32_t validate_materials(CrHandle* h, const CrMaterial* materials, int32_t n_materials, const CrTexture* textures, int32_t n_textures,
+                           const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    SceneCheck c = check_materials_args(materials, n_materials, textures, n_textures, prim_index, prim_material, n_assign);
+    if (!c.ok()) return fail(h, c.code, c.msg);
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_update_materials before cr_upload_scene");
+    c = check_materials_update(h->prims.data(), (int64_t)h->prims.size(), h->materials.data(), (int32_t)h->materials.size(), h->textures.data(),
+                               (int32_t)h->textures.size(), h->n_images, materials, n_materials, textures, n_textures, prim_index, prim_material, n_assign);
+    return c.ok() ? CR_OK : fail(h, c.code, c.msg);
+}
+
+// The device's material and texture tables of one precision from the host copy, where that precision holds side tables at
+// all (else its next build packs them): the bytes an upload makes, n_mats / n_texs / lds_bytes with them, and the frame
+// tree's aliases.  A buffer that must grow is exchanged after the stream has drained; the copies are ordered on the stream.
+template <typename real>
+static int32_t repack_side_tables(CrHandle* h) {
+    DevScene<real>& ds = dev_scene<real>(h);
+    if (!ds.side_tables) return CR_OK;
+    std::vector<Mat<real>> mats;
+    std::vector<Tex<real>> texs;
+    pack_side_tables<real>(h->materials, h->textures, mats, texs);
+    const size_t mat_bytes = mats.size() * sizeof(Mat<real>), tex_bytes = texs.size() * sizeof(Tex<real>);
+    // a buffer goes when its table outgrows it, or shrinks below half of it (a table that grew once does not hold its
+    // largest size for the handle's life; an edit of a few records exchanges nothing)
+    auto misfit = [](const DevBuf& b, size_t need) { return need > b.bytes || 2 * need < b.bytes; };
+    const size_t mat_need = mat_bytes ? mat_bytes : 16, tex_need = tex_bytes ? tex_bytes : 16;
+    if (misfit(ds.mats, mat_need) || misfit(ds.texs, tex_need)) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // an earlier render may still read the buffer that goes
+        hipError_t e = hipSuccess;
+        if (misfit(ds.mats, mat_need)) { ds.mats.release(); e = ds.mats.ensure(mat_need); }
+        if (e == hipSuccess && misfit(ds.texs, tex_need)) { ds.texs.release(); e = ds.texs.ensure(tex_need); }
+        if (e != hipSuccess) {   // out of memory: the next use builds again and uploads the tables from the host copy
+            ds.side_tables = false; ds.built = false;
+            return fail(h, CR_ERR_HIP, std::string("cr_update_materials: ") + hipGetErrorString(e));
+        }
+    }
+    if (mat_bytes) HIP_TRY(h, hipMemcpyAsync(ds.mats.p, mats.data(), mat_bytes, hipMemcpyHostToDevice, h->stream));
+    if (tex_bytes) HIP_TRY(h, hipMemcpyAsync(ds.texs.p, texs.data(), tex_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // `mats` and `texs` are this function's
+    ds.n_mats = (int32_t)mats.size(); ds.n_texs = (int32_t)texs.size();
+    ds.lds_bytes = scene_lds_bytes(ds);
+    DevScene<real>& fs = frame_scene<real>(h);
+    if (fs.built) { alias_side_tables(fs, ds); fs.lds_bytes = scene_lds_bytes(fs); }
+    return CR_OK;
+}
+
+// The staged assignments into the primitive records of one built precision.  Without desc_pos (a scene with a HitList or
+// BVHWrapper element) the tree rebuilds at next use from the edited host copy instead; the side tables stay.
+template <typename real>
+static int32_t assign_updated(CrHandle* h, const int32_t* d_index, const int32_t* d_material, int32_t n) {
+    DevScene<real>& ds = dev_scene<real>(h);
+    if (!ds.built) return CR_OK;
+    if (!ds.desc_pos_valid) { ds.built = false; return CR_OK; }
+    if (ds.n_prims == 0) return CR_OK;
+    hipLaunchKernelGGL((assign_materials_kernel<real>), dim3((unsigned)((n + kUpdateBlock - 1) / kUpdateBlock)), dim3(kUpdateBlock), 0, h->stream,
+                       (Prim<real>*)ds.prims.p, ds.n_prims, (const int32_t*)ds.desc_pos.p, (int32_t)h->prims.size(), d_index, d_material, n);
+    HIP_TRY(h, hipGetLastError());
+    return CR_OK;
+}
+
+// After validate_materials: the edit itself.
+int32_t apply_materials(CrHandle* h, const CrMaterial* materials, int32_t n_materials, const CrTexture* textures, int32_t n_textures,
+                        const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign) {
+    if (!materials && !textures && n_assign == 0) return CR_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int32_t rc = CR_OK;
+    if (materials || textures) {   // the host copy first: the tables are packed from it
+        if (materials) h->materials.assign(materials, materials + n_materials);
+        if (textures) h->textures.assign(textures, textures + n_textures);
+        rc = repack_side_tables<float>(h);
+        if (rc == CR_OK) rc = repack_side_tables<double>(h);
+        if (rc != CR_OK) return rc;
+    }
+    if (n_assign == 0) return CR_OK;
+    drop_frame_trees(h);   // CR_REFIT_REBUILD's primitive records are gathered copies
+    const bool on_device = (h->s32.built && h->s32.desc_pos_valid) || (h->s64.built && h->s64.desc_pos_valid);
+    const size_t idx_bytes = (size_t)n_assign * sizeof(int32_t);
+    if (on_device) {   // one staged buffer: the indices, then the materials; the stream orders the copy after earlier renders
+        HIP_TRY(h, h->update_stage.ensure(2 * idx_bytes));
+        HIP_TRY(h, hipMemcpyAsync(h->update_stage.p, prim_index, idx_bytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync((char*)h->update_stage.p + idx_bytes, prim_material, idx_bytes, hipMemcpyHostToDevice, h->stream));
+    } else HIP_TRY(h, hipStreamSynchronize(h->stream));   // a rebuild frees and refills what an earlier render may still read
+    for (int32_t k = 0; k < n_assign; k++) h->prims[(size_t)prim_index[k]].material = prim_material[k];   // what a rebuild, a precision not built yet and a hidden primitive see
+    const int32_t* d_index = (const int32_t*)h->update_stage.p;
+    const int32_t* d_material = (const int32_t*)((const char*)h->update_stage.p + idx_bytes);
+    rc = assign_updated<float>(h, d_index, d_material, n_assign);
+    if (rc == CR_OK) rc = assign_updated<double>(h, d_index, d_material, n_assign);
+    hipError_t e = hipStreamSynchronize(h->stream);   // the caller's arrays and the staged buffer are free from here on
+    if (e != hipSuccess && rc == CR_OK) { h->error = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); rc = CR_ERR_HIP; }
+    return rc;
+}
+
+int32_t validate_image(CrHandle* h, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height, const uint8_t* rgb8) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_update_image before cr_upload_scene");
+    const SceneCheck c = check_image_update(image, h->n_images, h->image_w.data(), h->image_h.data(), x0, y0, width, height, rgb8);
+    return c.ok() ? CR_OK : fail(h, c.code, c.msg);
+}
+
+// The rectangle's bytes into update_stage on the stream, then pack_texels_kernel writes their words where pack_images put them
+int32_t apply_image(CrHandle* h, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height, const uint8_t* rgb8) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)width * (size_t)height;
+    HIP_TRY(h, h->update_stage.ensure(3 * n));
+    HIP_TRY(h, hipMemcpyAsync(h->update_stage.p, rgb8, 3 * n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(pack_texels_kernel, dim3((unsigned)((n + kUpdateBlock - 1) / kUpdateBlock)), dim3(kUpdateBlock), 0, h->stream,
+                       (uint32_t*)h->texels.p, h->n_texels, h->image_offset[(size_t)image], h->image_w[(size_t)image], x0, y0, width, height,
+                       (const uint8_t*)h->update_stage.p);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the caller's array and the staged buffer are free from here on
+    return CR_OK;
+}
+
+int32_t validate_sky(CrHandle* h, int32_t sky_kind, int32_t sky_image) {
+    if (!h) return CR_ERR_INVALID_ARG;
+    if (!h->has_scene) return fail(h, CR_ERR_NO_SCENE, "cr_set_sky before cr_upload_scene");
+    SceneCheck c = check_sky_kind(sky_kind);
+    if (c.ok()) c = check_sky_image(sky_kind, sky_image, h->n_images);
+    return c.ok() ? CR_OK : fail(h, c.code, c.msg);
+}
+// render_typed copies the two fields into a launch's KernelArgs: a render launched earlier keeps the sky it was launched with
+void apply_sky(CrHandle* h, int32_t sky_kind, int32_t sky_image) { h->sky_kind = sky_kind; h->sky_image = sky_image; }
+
 template int32_t run_box_kernels<float>(CrHandle*, DevScene<float>&, void*, float, float, bool);
 template int32_t run_box_kernels<double>(CrHandle*, DevScene<double>&, void*, double, double, bool);
 
@@ -164,37 +292,10 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
     if ((s->n_prims > 0 && !s->prims) || (s->n_materials > 0 && !s->materials) || (s->n_textures > 0 && !s->textures) ||
         (s->n_images > 0 && !s->images) || (s->n_keys > 0 && !s->keys))
         return fail(h, CR_ERR_INVALID_ARG, "a descriptor array is null although its count is not zero");
-    auto finite = [](double x) { return x == x && x != HUGE_VAL && x != -HUGE_VAL; };
-    for (int i = 0; i < s->n_textures; i++) {
-        const CrTexture& t = s->textures[i];
-        if (t.kind < CR_TEX_SOLID || t.kind > CR_TEX_IMAGE) return fail(h, CR_ERR_INVALID_ARG, "unknown texture kind");
-        // children before parents keeps the texture graph acyclic (Arc<Textures> cannot cycle either)
-        if (t.kind == CR_TEX_CHECKER && (t.even < 0 || t.even >= i || t.odd < 0 || t.odd >= i))
-            return fail(h, CR_ERR_INVALID_ARG, "checker sub-textures must have smaller indices");
-        if (t.kind == CR_TEX_IMAGE && (t.image < 0 || t.image >= s->n_images)) return fail(h, CR_ERR_INVALID_ARG, "texture image index out of range");
-        if (t.kind == CR_TEX_SOLID) for (int k = 0; k < 3; k++) if (!(t.color[k] >= 0.0 && t.color[k] <= 1.0))
-            return fail(h, CR_ERR_INVALID_ARG, "colour component outside [0,1]");   // Color::new, utils.rs:345-350
-    }
-    {   // the device resolves a checker chain iteratively with a bound of 32 levels (pathtrace.hpp, shade)
-        std::vector<int32_t> depth((size_t)s->n_textures, 0);
-        for (int i = 0; i < s->n_textures; i++) {
-            const CrTexture& t = s->textures[i];
-            if (t.kind != CR_TEX_CHECKER) continue;
-            depth[i] = 1 + std::max(depth[t.even], depth[t.odd]);
-            if (depth[i] > CR_MAX_CHECKER_DEPTH) return fail(h, CR_ERR_UNSUPPORTED, "checker textures nested deeper than CR_MAX_CHECKER_DEPTH (32)");
-        }
-    }
-    for (int i = 0; i < s->n_materials; i++) {
-        const CrMaterial& m = s->materials[i];
-        if (m.kind < CR_MAT_LAMBERTIAN || m.kind > CR_MAT_DIELECTRIC) return fail(h, CR_ERR_INVALID_ARG, "unknown material kind");
-        if (m.kind == CR_MAT_LAMBERTIAN && (m.texture < 0 || m.texture >= s->n_textures)) return fail(h, CR_ERR_INVALID_ARG, "material texture index out of range");
-        if (m.kind == CR_MAT_METAL) {
-            if (!(m.param <= 1.0)) return fail(h, CR_ERR_INVALID_ARG, "A metal cannot have a fuzz factor above 1.0");   // metal.rs:21
-            if (!(m.param >= 0.0)) return fail(h, CR_ERR_INVALID_ARG, "A metal cannot have a fuzz factor below 0.0");   // metal.rs:22
-            for (int k = 0; k < 3; k++) if (!(m.albedo[k] >= 0.0 && m.albedo[k] <= 1.0)) return fail(h, CR_ERR_INVALID_ARG, "colour component outside [0,1]");
-        }
-        if (!finite(m.param)) return fail(h, CR_ERR_INVALID_ARG, "material parameter is not finite");
-    }
+    auto finite = [](double x) { return check_finite(x); };
+    auto refuse = [&](const SceneCheck& c) { return fail(h, c.code, c.msg); };   // scene_checks.hpp: the checks cr_update_materials and cr_set_sky share
+    { const SceneCheck c = check_textures(s->textures, s->n_textures, s->n_images); if (!c.ok()) return refuse(c); }
+    { const SceneCheck c = check_materials(s->materials, s->n_materials, s->n_textures); if (!c.ok()) return refuse(c); }
     for (int i = 0; i < s->n_keys; i++) {
         const CrKeyframe& k = s->keys[i];
         if (k.channel < CR_KEY_TX || k.channel > CR_KEY_SCALE_Z || (k.interp != CR_KEY_NERP && k.interp != CR_KEY_LERP))
@@ -225,7 +326,7 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
         const CrPrimitive& p = s->prims[i];
         if (p.kind == CR_PRIM_LIST || p.kind == CR_PRIM_BVH) continue;
         if (p.kind != CR_PRIM_SPHERE && p.kind != CR_PRIM_TRIANGLE) return fail(h, CR_ERR_INVALID_ARG, "unknown primitive kind");
-        if (p.material < 0 || p.material >= s->n_materials) return fail(h, CR_ERR_INVALID_ARG, "primitive material index out of range");
+        { const SceneCheck c = check_prim_material(p.material, s->n_materials); if (!c.ok()) return refuse(c); }
         if (p.key_count < 0 || p.key_first < 0 || p.key_first + p.key_count > s->n_keys) return fail(h, CR_ERR_INVALID_ARG, "primitive keyframe range out of bounds");
         for (int k = 0; k < p.key_count; k++) {   // the Scene API type-checks scale keys (scene_animator.rs:38-183)
             const int32_t ch = s->keys[p.key_first + k].channel;
@@ -236,12 +337,12 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
         for (int k = 0; k < nv; k++) if (!finite(p.v[k])) return fail(h, CR_ERR_INVALID_ARG, "primitive coordinate is not finite");
         if (p.kind == CR_PRIM_SPHERE && !(p.v[3] >= 0.0)) return fail(h, CR_ERR_INVALID_ARG, "Cannot make a sphere with negative radius");   // sphere.rs:26
     }
-    if (s->sky_kind != CR_SKY_DEFAULT && s->sky_kind != CR_SKY_SPHERICAL) return fail(h, CR_ERR_INVALID_ARG, "unknown sky kind");
+    { const SceneCheck c = check_sky_kind(s->sky_kind); if (!c.ok()) return refuse(c); }
     const int32_t bvh_base = s->bvh_mode & 0xFF, bvh_flags = s->bvh_mode & ~0xFF;
     if (s->bvh_mode < 0 || bvh_base > CR_BVH_LBVH || (bvh_flags & ~CR_BVH_BUILD_DEVICE)) return fail(h, CR_ERR_INVALID_ARG, "unknown bvh_mode");
     if ((bvh_flags & CR_BVH_BUILD_DEVICE) && bvh_base == CR_BVH_REFERENCE)
         return fail(h, CR_ERR_UNSUPPORTED, "CR_BVH_BUILD_DEVICE: the reference tree's stable sort has no device form (use it with CR_BVH_SAH, CR_BVH_SAH_ORDERED or CR_BVH_LBVH)");
-    if (s->sky_kind == CR_SKY_SPHERICAL && (s->sky_image < 0 || s->sky_image >= s->n_images)) return fail(h, CR_ERR_INVALID_ARG, "sky image index out of range");
+    { const SceneCheck c = check_sky_image(s->sky_kind, s->sky_image, s->n_images); if (!c.ok()) return refuse(c); }
     for (int i = 0; i < s->n_images; i++)
         if (s->images[i].width < 1 || s->images[i].height < 1 || !s->images[i].rgb8) return fail(h, CR_ERR_INVALID_ARG, "bad image");
 
@@ -268,6 +369,9 @@ int32_t cr_upload_scene(CrHandle* h, const CrSceneDesc* s) {
     if (!refs.empty()) HIP_TRY(h, hipMemcpy(h->images.p, refs.data(), refs.size() * sizeof(ImageRef), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->texels.p, texels.data(), texels.size() * 4, hipMemcpyHostToDevice));
     h->n_images = s->n_images;
+    h->image_w.resize(refs.size()); h->image_h.resize(refs.size()); h->image_offset.resize(refs.size());
+    for (size_t i = 0; i < refs.size(); i++) { h->image_w[i] = refs[i].w; h->image_h[i] = refs[i].h; h->image_offset[i] = refs[i].offset; }
+    h->n_texels = texels.size();
     h->has_scene = true;
     h->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return CR_OK;
@@ -277,6 +381,26 @@ int32_t cr_update_primitives(CrHandle* h, const int32_t* prim_index, const doubl
     int32_t rc = validate_update(h, prim_index, v, n, flags);
     if (rc != CR_OK) return rc;
     return apply_update(h, prim_index, v, n, flags);
+}
+
+int32_t cr_update_materials(CrHandle* h, const CrMaterial* materials, int32_t n_materials, const CrTexture* textures, int32_t n_textures,
+                            const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign) {
+    int32_t rc = validate_materials(h, materials, n_materials, textures, n_textures, prim_index, prim_material, n_assign);
+    if (rc != CR_OK) return rc;
+    return apply_materials(h, materials, n_materials, textures, n_textures, prim_index, prim_material, n_assign);
+}
+
+int32_t cr_update_image(CrHandle* h, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height, const uint8_t* rgb8) {
+    int32_t rc = validate_image(h, image, x0, y0, width, height, rgb8);
+    if (rc != CR_OK) return rc;
+    return apply_image(h, image, x0, y0, width, height, rgb8);
+}
+
+int32_t cr_set_sky(CrHandle* h, int32_t sky_kind, int32_t sky_image) {
+    int32_t rc = validate_sky(h, sky_kind, sky_image);
+    if (rc != CR_OK) return rc;
+    apply_sky(h, sky_kind, sky_image);
+    return CR_OK;
 }
 
 }   // extern "C"

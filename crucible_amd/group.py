@@ -11,7 +11,7 @@ root, the root divides by the sample count.  Two ways to build one:
 import ctypes as C
 
 from . import _abi as A
-from .renderer import CrucibleError, load_library, update_arrays
+from .renderer import CrucibleError, image_arrays, load_library, material_arrays, update_arrays
 
 
 def shard(samples, member, n_members):
@@ -92,6 +92,19 @@ class RenderGroup:
         idx, v, n = update_arrays(indices, values)
         self._check(self.lib.cr_group_update_primitives(self.g, idx, v.ctypes.data_as(C.POINTER(C.c_double)), n,
                                                         A.CR_UPDATE_REBUILD if rebuild else A.CR_UPDATE_REFIT))
+
+    def update_materials(self, materials=None, textures=None, assign=None):
+        """cr_group_update_materials: Renderer.update_materials on every local member (all validated before any
+        changes)."""
+        self._check(self.lib.cr_group_update_materials(self.g, *material_arrays(materials, textures, assign)))
+
+    def update_image(self, index, rgb8, rect=None):
+        """cr_group_update_image: Renderer.update_image on every local member."""
+        self._check(self.lib.cr_group_update_image(self.g, index, *image_arrays(rgb8, rect)))
+
+    def set_sky(self, kind, image=-1):
+        """cr_group_set_sky: Renderer.set_sky on every local member."""
+        self._check(self.lib.cr_group_set_sky(self.g, kind, image))
 
     def render(self, cam, *, seed, real_type=A.CR_REAL_F64, sum_order=A.CR_SUM_DEFAULT):
         """Collective: returns (image (H, W, 3) on the root -- zeros elsewhere --, stats dict)."""

@@ -384,6 +384,29 @@ struct FlatScene {
     }
 };
 
+// In-place edits of the scene a handle holds (include/crucible_hip.h: cr_update_materials, cr_update_image, cr_set_sky), for a
+// host that keeps its handle between renders.  update_shading says "this description, same geometry": both tables and the
+// material of every sphere and triangle of `f`, whose primitives are those of the last upload.
+inline int32_t update_materials(CrHandle* h, const std::vector<CrMaterial>* materials, const std::vector<CrTexture>* textures,
+                                const std::vector<int32_t>& prim_index = {}, const std::vector<int32_t>& prim_material = {}) {
+    if (prim_index.size() != prim_material.size()) return CR_ERR_INVALID_ARG;
+    static const CrMaterial no_material{};   // an empty table is a table: a non-null pointer with a count of 0
+    static const CrTexture no_texture{};
+    return cr_update_materials(h, materials ? (materials->empty() ? &no_material : materials->data()) : nullptr, materials ? (int32_t)materials->size() : 0,
+                               textures ? (textures->empty() ? &no_texture : textures->data()) : nullptr, textures ? (int32_t)textures->size() : 0,
+                               prim_index.data(), prim_material.data(), (int32_t)prim_index.size());
+}
+inline int32_t update_shading(CrHandle* h, const FlatScene& f) {
+    std::vector<int32_t> index, material;
+    for (size_t i = 0; i < f.prims.size(); i++)
+        if (f.prims[i].kind == CR_PRIM_SPHERE || f.prims[i].kind == CR_PRIM_TRIANGLE) { index.push_back((int32_t)i); material.push_back(f.prims[i].material); }
+    return update_materials(h, &f.materials, &f.textures, index, material);
+}
+inline int32_t update_image(CrHandle* h, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height, const uint8_t* rgb8) {
+    return cr_update_image(h, image, x0, y0, width, height, rgb8);
+}
+inline int32_t set_sky(CrHandle* h, int32_t sky_kind, int32_t sky_image = -1) { return cr_set_sky(h, sky_kind, sky_image); }
+
 class SceneRng {   // SplitMix64, uniform = (u >> 11) * 2^-53; see DESIGN.md "RNG"
     uint64_t s;
 public:

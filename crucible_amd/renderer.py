@@ -59,6 +59,72 @@ def update_arrays(indices, values):
     return ptr, v, len(v)
 
 
+def _table(records, ctype):
+    """(ctypes array or None, count) of a table argument: None stays None (the table is kept); a ctypes array passes
+    through; any other sequence of `ctype` records is copied.  An empty table is still a table (one unused record)."""
+    if records is None:
+        return None, 0
+    if isinstance(records, C.Array) and records._type_ is ctype:
+        return records, len(records)
+    records = list(records)
+    return (ctype * max(1, len(records)))(*records), len(records)
+
+
+def material_arrays(materials=None, textures=None, assign=None):
+    """cr_update_materials' arguments after the handle: (materials, n_materials, textures, n_textures, prim_index,
+    prim_material, n_assign).  materials / textures: None (kept) or the whole new table, a sequence of A.CrMaterial /
+    A.CrTexture.  assign: None, a mapping {primitive index: material index} or a pair (indices, materials)."""
+    mats, n_m = _table(materials, A.CrMaterial)
+    texs, n_t = _table(textures, A.CrTexture)
+    if assign is None:
+        return mats, n_m, texs, n_t, None, None, 0
+    if hasattr(assign, "items"):
+        assign = (list(assign.keys()), list(assign.values()))
+    idx = np.ascontiguousarray(assign[0], dtype=np.int32).reshape(-1)
+    mat = np.ascontiguousarray(assign[1], dtype=np.int32).reshape(-1)
+    if idx.size != mat.size:
+        raise ValueError(f"update_materials: {idx.size} indices for {mat.size} materials")
+    ptrs = []
+    for a in (idx, mat):
+        ptr = a.ctypes.data_as(C.POINTER(C.c_int32))
+        ptr._keep = a
+        ptrs.append(ptr)
+    return mats, n_m, texs, n_t, ptrs[0], ptrs[1], int(idx.size)
+
+
+def shading_arrays(flat):
+    """material_arrays of "this description, same geometry": both tables of the flattened scene `flat` (what Scene.flatten
+    makes for upload_scene) and the material of every sphere and triangle."""
+    d = getattr(flat, "desc", flat)
+    mats = C.cast(d.materials, C.POINTER(A.CrMaterial * max(1, d.n_materials))).contents
+    texs = C.cast(d.textures, C.POINTER(A.CrTexture * max(1, d.n_textures))).contents
+    words = C.sizeof(A.CrPrimitive) // 4
+    if d.n_prims > 0:
+        rec = np.ctypeslib.as_array(C.cast(d.prims, C.POINTER(C.c_int32)), shape=(d.n_prims, words))
+        idx = np.flatnonzero((rec[:, 0] == A.CR_PRIM_SPHERE) | (rec[:, 0] == A.CR_PRIM_TRIANGLE)).astype(np.int32)
+        assign = (idx, rec[idx, 1].copy())
+    else:
+        assign = None
+    out = material_arrays(None, None, assign)
+    return (mats, d.n_materials, texs, d.n_textures) + out[4:]
+
+
+def image_arrays(rgb8, rect=None):
+    """cr_update_image's arguments after the image index: (x0, y0, width, height, bytes pointer).  rgb8: (height, width, 3)
+    uint8; rect = (x0, y0, width, height), or None: the array's own size at (0, 0)."""
+    px = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    if rect is None:
+        if px.ndim != 3 or px.shape[2] != 3:
+            raise ValueError("update_image: rgb8 must be (height, width, 3) when no rect is given")
+        rect = (0, 0, px.shape[1], px.shape[0])
+    x0, y0, w, h = (int(v) for v in rect)
+    if px.size != max(0, w) * max(0, h) * 3:
+        raise ValueError(f"update_image: {px.size} bytes for a {w} x {h} rectangle")
+    ptr = px.ctypes.data_as(C.POINTER(C.c_uint8))
+    ptr._keep = px
+    return x0, y0, w, h, ptr
+
+
 class Renderer:
     """One CrHandle (one HIP device).  Mirrors the call `Camera::render(&skybox, &world, fname)`
     (reference src/camera/mod.rs:270) split into upload_scene / render / write_ppm."""
@@ -98,6 +164,27 @@ class Renderer:
         idx, v, n = update_arrays(indices, values)
         self._check(self.lib.cr_update_primitives(self.h, idx, v.ctypes.data_as(C.POINTER(C.c_double)), n,
                                                   A.CR_UPDATE_REBUILD if rebuild else A.CR_UPDATE_REFIT))
+
+    def update_materials(self, materials=None, textures=None, assign=None):
+        """cr_update_materials: replace the material and / or texture table of the scene on this handle (None: kept;
+        else the whole new table) and give primitives another material (assign: {primitive index: material index} or
+        a pair of sequences).  The tree is not rebuilt; the handle then behaves as after an upload of the edited
+        description."""
+        self._check(self.lib.cr_update_materials(self.h, *material_arrays(materials, textures, assign)))
+
+    def update_shading(self, flat):
+        """This description, same geometry: both tables of the flattened scene `flat` and the material of every sphere
+        and triangle, through cr_update_materials."""
+        self._check(self.lib.cr_update_materials(self.h, *shading_arrays(flat)))
+
+    def update_image(self, index, rgb8, rect=None):
+        """cr_update_image: new texels for the rectangle rect = (x0, y0, width, height) of image `index` of the last
+        upload (None: the whole (height, width, 3) array at the image's origin)."""
+        self._check(self.lib.cr_update_image(self.h, index, *image_arrays(rgb8, rect)))
+
+    def set_sky(self, kind, image=-1):
+        """cr_set_sky: A.CR_SKY_DEFAULT, or A.CR_SKY_SPHERICAL with the index of an uploaded image."""
+        self._check(self.lib.cr_set_sky(self.h, kind, image))
 
     def _args(self, cam, seed, real_type, sample_begin=0, sample_count=None, output_sum=False, sum_order=None):
         """(CrCameraDesc, CrRenderParams) of a call; sum_order=None: this renderer's."""

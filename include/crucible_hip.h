@@ -856,6 +856,61 @@ enum { CR_UPDATE_REFIT = 0, CR_UPDATE_REBUILD = 1 };
 CR_API int32_t cr_update_primitives(CrHandle* h, const int32_t* prim_index, const double* v,
                                     int32_t n, int32_t flags);
 
+/*
+ * Edit what the uploaded scene's surfaces look like, in place and without another cr_upload_scene: the material and
+ * texture tables and the primitives' material indices (cr_update_materials), the texels of a rectangle of an image
+ * (cr_update_image), the sky (cr_set_sky).  The tree is a function of the geometry alone and is NOT rebuilt: topology,
+ * boxes, screening records and leaf order are what they were, and cr_build_info keeps reporting the build that made them.
+ *
+ * Equivalence: after a successful call the handle behaves as a handle that received cr_upload_scene of the EDITED
+ * description does -- the host copy with the new tables, the new CrPrimitive.material indices, the new texels, the new
+ * sky -- for every later call: every cr_render_* family and shape, cr_export_bvh, cr_export_render_bvh, cr_build_info,
+ * cr_update_primitives; in f32 and f64, under every sum_order, bvh_mode and refit_boxes value.  Output bytes, the integer
+ * CrStats counters, bvh_entries and scene_in_lds are equal bit for bit.
+ *
+ * cr_update_materials
+ *   materials / textures   NULL (with a count of 0): the table stays.  Else the WHOLE new table: it may grow or shrink.
+ *                      The device tables are repacked as an upload packs them -- live textures re-indexed densely, a
+ *                      solid top-level texture folded into its material -- so they are the bytes a fresh upload makes,
+ *                      and the LDS sizing of the next launch is what a fresh upload would choose.
+ *   prim_index / prim_material   n_assign pairs: CrPrimitive.material of prims[prim_index[k]] becomes prim_material[k].  A
+ *                      visible primitive's device record changes in every precision already built; a hidden primitive
+ *                      changes in the host copy only; a precision not built yet builds from the edited host copy at
+ *                      first use.  In a scene with CR_PRIM_LIST / CR_PRIM_BVH elements the objects of lists may be
+ *                      reassigned too: the trees are then rebuilt at next use from the edited host copy, as
+ *                      CR_UPDATE_REBUILD does (the side tables stay) -- the same result, at the cost of a build.
+ *   Validation is that of the resulting description, before anything changes, with cr_upload_scene's messages and codes:
+ *   the texture rules (kind, checker children with smaller indices, image index, solid colours in [0,1], nesting depth:
+ *   CR_ERR_UNSUPPORTED beyond CR_MAX_CHECKER_DEPTH), the material rules (kind, a Lambertian's texture index below the new
+ *   n_textures, metal fuzz and albedo, a finite param), and after the edit every sphere's and triangle's material below
+ *   the new n_materials ("primitive material index out of range": also a table that shrinks under a primitive that is
+ *   not reassigned).  A new table is checked against the other table as kept.
+ *   The call's own refusals, prefixed "cr_update_materials:": CR_ERR_INVALID_ARG for a null handle, a negative count, a
+ *   null table with a count that is not zero, n_assign > 0 with a null prim_index or prim_material, an index out of range,
+ *   named twice, or naming a CR_PRIM_LIST / CR_PRIM_BVH record; CR_ERR_NO_SCENE before an upload.  A call that names
+ *   nothing (both tables NULL, n_assign == 0) is CR_OK and does nothing.
+ *   Frame trees (CR_REFIT_REBUILD): a call that only replaces tables keeps them -- a later render with the same ray times
+ *   builds nothing and cr_frame_build_info is unchanged; a call with n_assign > 0 drops them, as cr_update_primitives does.
+ *
+ * cr_update_image   new texels for the rectangle (x0, y0, width, height) of image `image` of the last upload: rgb8 holds
+ *   width*height*3 bytes, row-major, RGB8.  The image's dimensions cannot change.  CR_ERR_INVALID_ARG for a null handle, a
+ *   null rgb8, a width or height below 1, an image outside [0, n_images), a rectangle that does not lie inside the image
+ *   as uploaded (the sums are formed in 64 bits); CR_ERR_NO_SCENE before an upload.  Keeps the frame trees.
+ *
+ * cr_set_sky   CrSceneDesc.sky_kind / sky_image of the uploaded scene, under cr_upload_scene's checks and messages
+ *   ("unknown sky kind"; "sky image index out of range" for CR_SKY_SPHERICAL).  Keeps the frame trees.
+ *
+ * Ordering, as for cr_update_primitives: each call is ordered on the handle's stream after earlier launches (an
+ * asynchronous render launched before it sees the scene as it was) and may synchronise; the caller's arrays are free on
+ * return.  A refused call leaves the handle as it was.
+ */
+CR_API int32_t cr_update_materials(CrHandle* h, const CrMaterial* materials, int32_t n_materials,
+                                   const CrTexture* textures, int32_t n_textures,
+                                   const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign);
+CR_API int32_t cr_update_image(CrHandle* h, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height,
+                               const uint8_t* rgb8);
+CR_API int32_t cr_set_sky(CrHandle* h, int32_t sky_kind, int32_t sky_image);
+
 /* Wait for the last render launched on this handle and return its kernel time in
  * milliseconds, measured with HIP events recorded on the handle's stream around the
  * launch (no counters are copied back). */
@@ -952,6 +1007,16 @@ CR_API int32_t cr_group_upload_scene(CrGroup* g, const CrSceneDesc* scene);
  * error wins.  In rank mode every rank calls it with the same arguments (no collective is involved). */
 CR_API int32_t cr_group_update_primitives(CrGroup* g, const int32_t* prim_index, const double* v,
                                           int32_t n, int32_t flags);
+
+/* cr_update_materials, cr_update_image and cr_set_sky on every local member, under cr_group_update_primitives' rule:
+ * every member is validated before any is changed, the first member's error wins, and in rank mode every rank calls with
+ * the same arguments (no collective is involved). */
+CR_API int32_t cr_group_update_materials(CrGroup* g, const CrMaterial* materials, int32_t n_materials,
+                                         const CrTexture* textures, int32_t n_textures,
+                                         const int32_t* prim_index, const int32_t* prim_material, int32_t n_assign);
+CR_API int32_t cr_group_update_image(CrGroup* g, int32_t image, int32_t x0, int32_t y0, int32_t width, int32_t height,
+                                     const uint8_t* rgb8);
+CR_API int32_t cr_group_set_sky(CrGroup* g, int32_t sky_kind, int32_t sky_image);
 
 /* Camera::render across the group.  params->sample_begin/sample_count/output_sum are ignored (output_sum must still be
  * a valid value): the group splits
