@@ -134,10 +134,8 @@ static int32_t call_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderPar
         HIP_TRY(h, hipMemcpyAsync(h->aov_counts.p, call.counts, count_bytes, hipMemcpyHostToDevice, h->stream));
         call.counts = (const int32_t*)h->aov_counts.p;
     }
-    // a render whose caller gave no stats runs with a local CrStats; guide layers and adaptive calls pass the null on
-    CrStats local;
-    const bool render = call.family == kCallRender;
-    int32_t rc = call_device(h, cam, p, call, h->out_buf.p, render && !stats ? &local : stats);
+    // a caller's null stats is passed on: such a render keeps no work counters where a kernel without them exists (render.hpp launch())
+    int32_t rc = call_device(h, cam, p, call, h->out_buf.p, stats);
     if (rc != CR_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h_out, h->out_buf.p, bytes, hipMemcpyDeviceToHost, h->stream));
     if (h_counts) HIP_TRY(h, hipMemcpyAsync(h_counts, h->ad_counts.p, count_bytes, hipMemcpyDeviceToHost, h->stream));

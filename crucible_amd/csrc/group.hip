@@ -210,7 +210,9 @@ static int32_t group_render_impl(CrGroup* g, const CrCameraDesc* cam, const CrRe
     const char* fail_member = getenv("CRUCIBLE_GROUP_FAIL_MEMBER");   // tests: this member's render reports a failure after it was launched
     for (int i = 0; i < local && local_rc == CR_OK; i++) {
         CrHandle* h = g->members[(size_t)i];
+        h->keep_counters = stats != nullptr;   // member_stats reads them once the stream is idle (a render without stats keeps none)
         int32_t rc = cr_render_device(h, cam, &ps[(size_t)i], summed ? g->partial[(size_t)i].p : d_out, nullptr);
+        h->keep_counters = false;
         if (rc == CR_OK && fail_member && atoi(fail_member) == g->first + i) rc = fail(h, CR_ERR_HIP, "render failure injected by CRUCIBLE_GROUP_FAIL_MEMBER");
         if (rc != CR_OK) note(rc, h->error);
     }

@@ -203,6 +203,7 @@ struct CrHandle {
                                        // book1 +1.5 %, movie frame +1.5 %, 1M spheres +2.9 %, profiles/experiments/r03_leaf_min.txt)
     int last_block = 0, last_grid = 0;
     bool check_abort = false;          // the last launch was a queue kernel whose abort word has not been read yet
+    bool keep_counters = false;        // a render without a CrStats still counts: its counters are read later (a group's member, group.hip)
 };
 
 namespace cr {

@@ -698,8 +698,15 @@ template <typename real> CR_D uint32_t as_index(real x, int32_t n) {   // `as us
     return (uint32_t)x;
 }
 
-template <typename real>
-CR_D V3<real> image_lookup(const ImageRef* images, const uint32_t* texels, int image, real u, real v, uint32_t& n_texel) {
+// The work counters of a kernel that keeps none (pathtrace_body's COUNT == false): no storage, and every ++ and +=
+// compiles away.  image_lookup, shade and walk_round take their counters' types as they come.
+struct NoCount {
+    CR_D void operator++(int) {}
+    template <typename T> CR_D void operator+=(T) {}
+};
+
+template <typename real, typename CT>
+CR_D V3<real> image_lookup(const ImageRef* images, const uint32_t* texels, int image, real u, real v, CT& n_texel) {
     ImageRef im = images[image];
     u = clamp01(u);
     v = real(1) - clamp01(v);
@@ -969,10 +976,10 @@ template <typename T> CR_D T load_rec(const T* p, bool in_lds) {
 // RELAX (CR_SUM_RELAXED): no stack -- *thr carries the product of the attenuations met so far (a_1 * a_2 * ... in path
 // order; the same multiplies as the reference's a_1 * (a_2 * (...)), associated the other way) and the colour handed
 // back is thr * sky.  Every factor is in [0, 1] or NaN, so Color's clamp (utils.rs:553-563) never changes a product.
-template <typename real, bool ANIM, bool SIDE_SPLIT = false, bool RELAX = false>
+template <typename real, bool ANIM, bool SIDE_SPLIT = false, bool RELAX = false, typename CT = uint32_t>
 CR_D bool shade(const KernelArgs<real>& A, const Prim<real>* prims, const Mat<real>* mats, const Tex<real>* texs, V3<real>& ro, V3<real>& rd,
                 real rtime, uint64_t& rng, int32_t& depth_left, int32_t& stack_n, real best_t, int32_t best, uint32_t stack_stride,
-                uint32_t stack_slot, uint32_t& c_tex, V3<real>& col, Diag* dg = nullptr, V3<real>* thr = nullptr, const real* dd = nullptr) {
+                uint32_t stack_slot, CT& c_tex, V3<real>& col, Diag* dg = nullptr, V3<real>* thr = nullptr, const real* dd = nullptr) {
     CR_DIAG_HIT(dg, DG_SHADE_WAVE, DG_SHADE_LANE);
     // unit(rd) of the incoming ray.  dd: the segment's |rd|^2 where the caller has it (WalkState::dd, walk_begin's len2(rd) of
     // this rd: the same expression on the same operands, and -ffp-contract=off keeps it the same bits)
@@ -1476,10 +1483,13 @@ template <typename real> CR_D V3<real> inv_of(V3<real> rd) {
 // SHARE: the caller began the walk with walk_begin<quot_form() == 1>; the guide-layer kernels and the cross-check pipelines do not.
 // LAZY_INV (f64 SCREEN kernels): the caller began it with walk_begin_screened; 1 / direction is divided where f64 needs it.
 // SPHERE_LOOP (sphere_loop()'s kernels): the leaf phase tests a scene of spheres alone in a loop of its own.
-template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false, bool SHARE = false, bool LAZY_INV = false, bool SPHERE_LOOP = false>
+// CN, CP: the node and primitive counters' types -- NoCount in the kernels that keep no work counters (pathtrace_kernel_quiet).
+template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false, bool SHARE = false, bool LAZY_INV = false, bool SPHERE_LOOP = false,
+          typename CN = unsigned long long, typename CP = uint32_t>
 CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, const Prim<real>* prims, V3<real> ro, V3<real> rd, real rtime,
-                     WalkState<real>& w, bool walking, uint32_t budget, unsigned long long& c_node, uint32_t& c_prim, Diag* dg = nullptr,
+                     WalkState<real>& w, bool walking, uint32_t budget, CN& c_node, CP& c_prim, Diag* dg = nullptr,
                      const void* lds_screen = nullptr) {
+    constexpr bool COUNT = !std::is_same<CN, NoCount>::value;
     // f64: decisions on the f32 copy where f32 can decide; f32 (EXACT below): the record IS the wrapper's box, in the link layout of ScreenEntry
     constexpr bool EXACT = std::is_same<real, float>::value;
     static_assert(!(SCREEN && EXACT && ORD), "the f32 kernels use ScreenEntry records for unordered trees only");
@@ -1580,6 +1590,9 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
                             off = miss ? se.skip : se.hit;
                             // the round's last step ends it for every lane: a scalar select of the limit (hidden from the optimiser,
                             // which would turn it back into a second exit mask)
+                            // (!COUNT: without the per-lane node count beside it the step count would become a per-lane
+                            // countdown, one vector instruction more than the scalar add it replaces: it is pinned to its register)
+                            if constexpr (!COUNT) asm volatile("" : "+s"(it));
                             uint32_t limit = (it + 1 == budget) ? 0u : end;
                             asm("" : "+s"(limit));
                             if (off >= limit) break;
@@ -1749,7 +1762,9 @@ template <typename real> CR_D const KernelArgs<real>& kernel_args() {
 // LIST: the work decode names its tiles through KernelArgs::tile_list (cr_render_adaptive_*).  Only pathtrace_kernel_listed
 // passes true: read in the kernels that movies and regions run on, the list cost them 0.3 - 0.8 % at unchanged registers
 // (profiles/experiments/adaptive_sampling.txt), so it has kernels of its own and every other kernel compiles to what it was.
-template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true, bool LIST = false>
+// COUNT: the body keeps the four work counters and adds them to KernelArgs::counters at its end.  Only pathtrace_kernel_quiet
+// passes false: its launches are the renders whose caller asked for no stats (render.hpp launch()).
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true, bool LIST = false, bool COUNT = true>
 CR_D void pathtrace_body(const KernelArgs<real>& A) {
     using EntryT = typename EntryOf<real, ORD>::type;
     constexpr bool BATCH = RELAX && (ANIM || CAMK);
@@ -1867,8 +1882,8 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
     real rtime = 0;
     uint64_t rng = 0;
     int32_t depth_left = 0, stack_n = 0;
-    uint32_t c_seg = 0, c_prim = 0, c_tex = 0;
-    unsigned long long c_node = 0;
+    std::conditional_t<COUNT, uint32_t, NoCount> c_seg{}, c_prim{}, c_tex{};
+    std::conditional_t<COUNT, unsigned long long, NoCount> c_node{};
     // walk state, kept across rounds: a lane whose walk is cut short resumes where it stopped
     WalkState<real> ws;
     ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.rda = quot_divide<real>(); ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
@@ -2092,30 +2107,31 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
 
     if constexpr (RELAX) { fx_flush(0, fx_tile0); fx_flush(1, fx_tile1); }
     // flush work counters: one atomic per counter per wave
-    auto wave_sum = [&](unsigned long long v) -> unsigned long long {
-        unsigned long long s = v;
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-        return s;
-    };
-    unsigned long long s0 = wave_sum(c_seg), s1 = wave_sum(c_node), s2 = wave_sum(c_prim), s3 = wave_sum(c_tex);
-    CR_DIAG_ONLY(
-        {
-            unsigned long long* c = (unsigned long long*)A.counters;
-            for (int i = 0; i < DG_N; i++) { unsigned long long w = wave_sum(dg_store.v[i]); if (lane == 0) atomicAdd(&c[16 + i], w); }
-            if (lane == 0) {
-                atomicAdd(&c[9], d_t_regen); atomicAdd(&c[10], d_t_trace); atomicAdd(&c[11], d_t_shade);
-                atomicAdd(&c[12], __builtin_readcyclecounter() - d_begin);
-            }
-        })
+    if constexpr (COUNT) {
+        auto wave_sum = [&](unsigned long long v) -> unsigned long long {
+            unsigned long long s = v;
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+            return s;
+        };
+        unsigned long long s0 = wave_sum(c_seg), s1 = wave_sum(c_node), s2 = wave_sum(c_prim), s3 = wave_sum(c_tex);
+        CR_DIAG_ONLY(
+            {
+                unsigned long long* c = (unsigned long long*)A.counters;
+                for (int i = 0; i < DG_N; i++) { unsigned long long w = wave_sum(dg_store.v[i]); if (lane == 0) atomicAdd(&c[16 + i], w); }
+                if (lane == 0) {
+                    atomicAdd(&c[9], d_t_regen); atomicAdd(&c[10], d_t_trace); atomicAdd(&c[11], d_t_shade);
+                    atomicAdd(&c[12], __builtin_readcyclecounter() - d_begin);
+                }
+            })
 #ifdef CR_HOLD_VCC
-    asm volatile("" :: "{vcc}"(vcc_hold));
+        asm volatile("" :: "{vcc}"(vcc_hold));
 #endif
-    if (lane == 0) {
-        atomicAdd((unsigned long long*)&A.counters[0], s0);
-        atomicAdd((unsigned long long*)&A.counters[1], s1);
-        atomicAdd((unsigned long long*)&A.counters[2], s2);
-        atomicAdd((unsigned long long*)&A.counters[3], s3);
-
+        if (lane == 0) {
+            atomicAdd((unsigned long long*)&A.counters[0], s0);
+            atomicAdd((unsigned long long*)&A.counters[1], s1);
+            atomicAdd((unsigned long long*)&A.counters[2], s2);
+            atomicAdd((unsigned long long*)&A.counters[3], s3);
+        }
     }
 }
 template <typename real, int RES, bool ANIM, bool ORD = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>
@@ -2123,6 +2139,17 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) pathtrace_kernel(const 
     // the LDS-resident f32 kernels have registers to spare and lose 1 % to the reloads: they keep the by-value parameter
     if constexpr (std::is_same<real, double>::value || RES != RES_LDS) pathtrace_body<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>(kernel_args<real>());
     else pathtrace_body<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>(A);
+}
+
+// The headline's kernel once more -- pathtrace_kernel<double, RES_LDS, false, false, false, true, true>: static f64, relaxed
+// sums, screening records of an unordered tree, the whole scene in LDS -- without the work counters: the same paths and the same
+// frame, for renders whose caller asked for no stats (render.hpp launch()).  No counter registers, and a vector instruction
+// of the screened box step fewer.  A name of its own, so that a profile tells the two apart.  RES_LDS alone:
+// the RES_TOP twin measured 0.3 % slower than the counted kernel on 1M spheres, so those scenes keep counting.
+template <int RES>
+__global__ void __launch_bounds__(MaxBlock<double>::value) pathtrace_kernel_quiet(const KernelArgs<double> A) {
+    static_assert(RES == RES_LDS, "the counter-free kernel exists for scenes staged whole in LDS");
+    pathtrace_body<double, RES, false, false, false, true, true, true, false, false>(kernel_args<double>());
 }
 
 // The relaxed kernels with keys once more, with the active-tile list in their work decode: the passes of cr_render_adaptive_*

@@ -45,6 +45,15 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     if constexpr (LATENCY) kern = pathtrace_kernel_latency<real, ANIM, ORD, CAMK, RELAX>;
     if constexpr (LIST) kern = pathtrace_kernel_listed<real, RES, ANIM, ORD, CAMK, SCREEN>;
     static_assert(!LIST || (RELAX && ANIM != CAMK && !LATENCY), "the listed kernels are relaxed kernels with keys");
+    // A render whose caller asked for no stats runs the kernel that keeps no work counters, where one exists: the static f64
+    // relaxed SCREEN kernel on an unordered tree with the scene in LDS (the headline's).  A CR_DIAG build counts every launch;
+    // adaptive calls and batches of frames run on kernels with keys, which all count; keep_counters: a group's member.
+    bool quiet = false;
+#ifndef CR_DIAG
+    if constexpr (std::is_same<real, double>::value && RES == RES_LDS && !ANIM && !ORD && !LATENCY && !CAMK && RELAX && SCREEN && !LIST) {
+        if (!stats && !h->keep_counters && !fb.ad && fb.n == 1) { kern = pathtrace_kernel_quiet<RES>; quiet = true; }
+    }
+#endif
     const int max_block = LATENCY ? LatencyBlock : MaxBlock<real>::value;
     // The work tile (sample-granular hand-out): 2^lw x 2^lh pixels times 64 >> (lw + lh) consecutive samples; by default
     // 4 x 4 x 4, wider tiles of fewer samples when fewer than 4 samples are rendered.
@@ -134,7 +143,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
         args.fx_acc = fixed ? (unsigned long long*)args.out : (unsigned long long*)h->fx_acc.p;
         if (!fb.ad) HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, (size_t)fb.n * npix * 3 * sizeof(unsigned long long), h->stream));
     }
-    HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
+    if (!quiet) HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
     // one launch of the kernel on `args` as they stand: the work counter starts at zero
     auto run = [&](uint32_t blocks) -> int32_t {
         HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
