@@ -22,7 +22,7 @@ template <typename real, int RES, bool ANIM>
 int32_t launch_queue(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats) {
     KernelArgs<real> args = args_in;
     auto kern = queue_kernel<real, RES, ANIM>;
-    const size_t lds_bytes = ((scene_lds_bytes + 15) & ~(size_t)15) + queue_state_bytes<real>();
+    const size_t lds_bytes = r16(scene_lds_bytes) + queue_state_bytes<real>();
     HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int per_cu = 0;
     HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)QK_SLOTS, lds_bytes));
@@ -163,7 +163,7 @@ int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>&
     W.hit_t = (real*)h->wf_hit_t.p; W.hit_prim = (int32_t*)h->wf_hit_prim.p; W.job_chunk = (uint32_t*)h->wf_chunk.p;
     W.ctrl = (uint32_t*)h->wf_ctrl.p; W.sample_rgb = (real*)h->wf_samples.p; W.acc = (real*)h->wf_acc.p;
     // the extend kernel stages entries | primitives when both fit, else the top levels of the tree
-    const size_t full = r16((size_t)ds.n_entries * sizeof(Entry<real>)) + r16((size_t)ds.n_prims * sizeof(Prim<real>));
+    const size_t full = whole_scene_layout(ds, sizeof(Entry<real>), false).end();
     const int32_t bc = (int32_t)cap;
     if (ds.n_entries > 0 && full <= h->lds_limit) {
         W.k.lds_entries = ds.n_entries;

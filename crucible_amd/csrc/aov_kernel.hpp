@@ -33,53 +33,23 @@ CR_D bool aov_word(double x, double scale, long long& v) {
 // their maximum as a scalar, and the group loop ends where that maximum ends: whole rounds disappear, not only lanes.
 template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS = false>
 CR_D void aov_body(const AovArgs<real>& G) {
-    using EntryT = typename EntryOf<real, ORD>::type;
     static_assert(BATCH || !COUNTS, "the COUNTS kernels are BATCH kernels");
     const KernelArgs<real>& A = G.k;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Entry<real>* lds_entries = nullptr;
-    const void* lds_screen = nullptr;
-    const Prim<real>* prims = A.prims;
-    const Mat<real>* mats = A.mats;
-    const Tex<real>* texs = A.texs;
-    if (RES != RES_GLOBAL) {   // the scene's LDS copy, laid out as pathtrace_body lays it out (the walk's fetches expect that)
-        auto copy = [&](const void* src, size_t off, size_t bytes) {
-            const uint32_t* s = (const uint32_t*)src;
-            uint32_t* d = (uint32_t*)(smem + off);
-            for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) d[i] = s[i];
-        };
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // (the waves' slots behind the scene)
+    const SceneStage<real> S = stage_scene<real, RES, ORD, SCREEN>(A);
+    const Entry<real>* lds_entries = S.lds_entries;
+    const void* lds_screen = S.lds_screen;
+    const Prim<real>* prims = S.prims;
+    const Mat<real>* mats = S.mats;
+    const Tex<real>* texs = S.texs;
+    if constexpr (SCREEN && RES == RES_LDS) {   // links of the staged screening records become LDS addresses (fetch_screen, fetch_screen_ordered)
         using ScreenT = typename ScreenOf<ORD>::type;
-        constexpr size_t window_rec = SCREEN ? sizeof(ScreenT) : sizeof(EntryT);
-        copy(SCREEN ? A.screen : (const void*)A.entries, 0, (size_t)A.lds_entries * window_rec);
-        lds_entries = (const Entry<real>*)smem;
-        if (SCREEN) lds_screen = (const void*)smem;
-        if (RES == RES_LDS) {   // entries | prims | mats | texs, each 16-B aligned
-            size_t o1 = (((size_t)A.n_entries * window_rec + 15) & ~(size_t)15);
-            size_t o2 = o1 + (((size_t)A.n_prims * sizeof(Prim<real>) + 15) & ~(size_t)15);
-            size_t o3 = o2 + (((size_t)A.n_mats * sizeof(Mat<real>) + 15) & ~(size_t)15);
-            copy(A.prims, o1, (size_t)A.n_prims * sizeof(Prim<real>));
-            copy(A.mats, o2, (size_t)A.n_mats * sizeof(Mat<real>));
-            copy(A.texs, o3, (size_t)A.n_texs * sizeof(Tex<real>));
-            prims = (const Prim<real>*)(smem + o1);
-            mats = (const Mat<real>*)(smem + o2);
-            texs = (const Tex<real>*)(smem + o3);
-            if constexpr (SCREEN) {   // links of the staged screening records become LDS addresses (fetch_screen)
-                __syncthreads();
-                const uint32_t base = screen_lds_base<RES>(smem);
-                ScreenT* rec = (ScreenT*)smem;
-                for (int32_t i = (int32_t)threadIdx.x; i < A.n_entries; i += (int32_t)blockDim.x) {
-                    if constexpr (ORD) { for (int k = 0; k < 8; k++) rec[i].skip[k] += base; }
-                    else rec[i].skip += base;
-                    if (!(rec[i].hit & kScreenLeaf)) rec[i].hit += base;
-                }
-            }
-        } else if (A.lds_side) {   // RES_TOP: entry window | mats | texs
-            size_t o2 = (((size_t)A.lds_entries * window_rec + 15) & ~(size_t)15);
-            size_t o3 = o2 + (((size_t)A.n_mats * sizeof(Mat<real>) + 15) & ~(size_t)15);
-            copy(A.mats, o2, (size_t)A.n_mats * sizeof(Mat<real>));
-            copy(A.texs, o3, (size_t)A.n_texs * sizeof(Tex<real>));
-            mats = (const Mat<real>*)(smem + o2);
-            texs = (const Tex<real>*)(smem + o3);
+        const uint32_t base = screen_lds_base<RES>(smem);
+        ScreenT* rec = (ScreenT*)smem;
+        for (int32_t i = (int32_t)threadIdx.x; i < A.n_entries; i += (int32_t)blockDim.x) {
+            if constexpr (ORD) { for (int k = 0; k < 8; k++) rec[i].skip[k] += base; }
+            else rec[i].skip += base;
+            if (!(rec[i].hit & kScreenLeaf)) rec[i].hit += base;
         }
         __syncthreads();
     }
@@ -252,19 +222,7 @@ CR_D void aov_body(const AovArgs<real>& G) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
 
-    // work counters: one atomic per counter per wave
-    auto wave_sum = [&](unsigned long long v) -> unsigned long long {
-        unsigned long long s = v;
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-        return s;
-    };
-    const unsigned long long s0 = wave_sum(c_seg), s1 = wave_sum(c_node), s2 = wave_sum(c_prim), s3 = wave_sum(c_tex);
-    if (lane == 0) {
-        atomicAdd((unsigned long long*)&A.counters[0], s0);
-        atomicAdd((unsigned long long*)&A.counters[1], s1);
-        atomicAdd((unsigned long long*)&A.counters[2], s2);
-        atomicAdd((unsigned long long*)&A.counters[3], s3);
-    }
+    flush_counters(WaveSum{}, A.counters, lane, c_seg, c_node, c_prim, c_tex);
 }
 
 // (the arguments are read through the kernarg segment where they are used, as pathtrace_kernel reads its own)

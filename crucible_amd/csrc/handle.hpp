@@ -330,18 +330,21 @@ ResidencyQuery residency_query(const CrHandle* h, const DevScene<real>& ds, cons
     q.ordered = ORD; q.can_screen = !(ORD && f32);
     q.screen = w.screen; q.screen_lds = w.screen_lds; q.plain_lds = w.plain_lds;
     q.lds_bytes = ds.lds_bytes; q.lds_all_screen = w.lds_all_screen;
-    q.side_bytes = r16((size_t)ds.n_mats * sizeof(Mat<real>)) + r16((size_t)ds.n_texs * sizeof(Tex<real>));
+    q.side_bytes = side_table_bytes((size_t)ds.n_mats * sizeof(Mat<real>), (size_t)ds.n_texs * sizeof(Tex<real>));
     q.lds_top_bytes = h->lds_top_bytes; q.lds_side_limit = h->lds_side_limit;
     q.f32 = f32; q.latency_entries = h->latency_entries; q.latency_top_bytes = h->latency_top_bytes;
     q.latency_slot_bytes = fx_lds_bytes(LatencyBlock, 4);
     return q;
 }
 
-// LDS a scene takes when it sits there whole: its wrappers, primitive records, materials and textures
-template <typename real> inline size_t scene_lds_bytes(const DevScene<real>& ds) {
-    return r16((size_t)ds.n_entries * ds.entry_bytes) + r16((size_t)ds.n_prims * sizeof(Prim<real>)) + r16((size_t)ds.n_mats * sizeof(Mat<real>)) +
-           r16((size_t)ds.n_texs * sizeof(Tex<real>));
+// A scene in LDS whole, as residency.hpp lays it out: records of record_bytes each (its wrappers, or screening records in
+// their place), primitive records and, with_side, materials and textures
+template <typename real> inline SceneLayout whole_scene_layout(const DevScene<real>& ds, size_t record_bytes, bool with_side = true) {
+    return scene_layout((size_t)ds.n_entries * record_bytes, (size_t)ds.n_prims * sizeof(Prim<real>), (size_t)ds.n_mats * sizeof(Mat<real>),
+                        (size_t)ds.n_texs * sizeof(Tex<real>), true, with_side);
 }
+// LDS a scene takes when it sits there whole with its wrappers
+template <typename real> inline size_t scene_lds_bytes(const DevScene<real>& ds) { return whole_scene_layout(ds, ds.entry_bytes).end(); }
 // A frame tree's side tables are the base tree's (not owned: a DevBuf without an allocation of its own releases nothing)
 template <typename real> inline void alias_side_tables(DevScene<real>& fs, const DevScene<real>& base) {
     for (auto pr : {std::make_pair(&fs.mats, &base.mats), std::make_pair(&fs.texs, &base.texs), std::make_pair(&fs.keys, &base.keys)}) {

@@ -705,6 +705,30 @@ struct NoCount {
     template <typename T> CR_D void operator+=(T) {}
 };
 
+// A kernel's end: its work counters, summed over the wave, into KernelArgs::counters -- one atomic per counter per wave:
+// flush_counters(WaveSum{}, A.counters, lane, c_seg, c_node, c_prim, c_tex).  A counter of type NoCount is one the kernel
+// does not keep: no sum and no atomic for it.
+// (The caller creates the wave sum, a function object: with a plain function, or the object made in here, the megakernels'
+// registers are initialised in another order -- the same instructions, not the same text; scripts/isa_diff.py.)
+struct WaveSum {
+    __device__ unsigned long long operator()(unsigned long long v) const {
+        unsigned long long s = v;
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+        return s;
+    }
+    __device__ NoCount operator()(NoCount) const { return {}; }
+};
+CR_D void add_counter(uint64_t* counter, unsigned long long s) { atomicAdd((unsigned long long*)counter, s); }
+CR_D void add_counter(uint64_t*, NoCount) {}
+template <typename C0, typename C1, typename C2, typename C3>
+CR_D void flush_counters(const WaveSum& wave_sum, uint64_t* counters, uint32_t lane, C0 c_seg, C1 c_node, C2 c_prim, C3 c_tex) {
+    const auto s0 = wave_sum(c_seg);
+    const auto s1 = wave_sum(c_node);
+    const auto s2 = wave_sum(c_prim);
+    const auto s3 = wave_sum(c_tex);
+    if (lane == 0) { add_counter(&counters[0], s0); add_counter(&counters[1], s1); add_counter(&counters[2], s2); add_counter(&counters[3], s3); }
+}
+
 template <typename real, typename CT>
 CR_D V3<real> image_lookup(const ImageRef* images, const uint32_t* texels, int image, real u, real v, CT& n_texel) {
     ImageRef im = images[image];
@@ -1278,6 +1302,13 @@ template <typename real> struct WalkState : WalkScreened<real> {
     int32_t pending;     // a leaf wrapper whose box was hit and whose primitives are still to be tested (-1: none)
 };
 
+// A state that walks nothing, every field set; `idx`: the kernel's own "no walk" (n_entries where walk_round may see the state
+// before a walk_begin).  The cross-check pipelines and the walk check programs begin with it; pathtrace_body and aov_body keep
+// lines of their own that leave unset what their kernels never read: setting that too changes the ordered kernels' code (6.8b).
+template <typename real> CR_D void walk_reset(WalkState<real>& ws, int32_t idx) {
+    ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.rda = quot_divide<real>(); ws.best_t = 0; ws.best = -1; ws.idx = idx; ws.exact_box = false; ws.oct = 0; ws.pending = -1;
+    if constexpr (std::is_same<real, double>::value) { ws.invf = mk<float>(0, 0, 0); ws.unscreened = false; }
+}
 // KernelArgs::exact_boxes, for the kernels that can meet such a tree: the f64 kernels compile to what they were
 CR_D bool tree_walks_exact(const KernelArgs<float>& A) { return A.exact_boxes != 0; }
 CR_D constexpr bool tree_walks_exact(const KernelArgs<double>&) { return false; }
@@ -1737,6 +1768,72 @@ CR_D uint32_t wave_rank(uint64_t ballot) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
 }
 
+// What stage_scene answers: the staged copies, else the launch's global tables (lds_entries, lds_screen: null); `end`: the first LDS byte behind the scene
+template <typename real> struct SceneStage {
+    const Entry<real>* lds_entries;
+    const void* lds_screen;
+    const Prim<real>* prims;
+    const Mat<real>* mats;
+    const Tex<real>* texs;
+    size_t end;
+};
+
+// Stages the scene in LDS as residency.hpp's scene_layout lays it out, whole workgroup, barrier at the end.  RES_LDS: all
+// records, primitives, materials, textures; RES_TOP: the window of A.lds_entries records and, where A.lds_side says so,
+// materials and textures; RES_GLOBAL: nothing.  SCREEN kernels stage the f32 screening records instead of the wrappers
+// (twice as many in the same bytes); with the whole tree there (RES_LDS) the caller then turns the records' links into LDS
+// addresses, after this routine's barrier and before one of its own -- the loop stands in pathtrace_body and aov_body,
+// because in here (or in any function) it changes nine reference-order and f32 megakernels.
+// SIDE = false: geometry only -- a kernel that does not shade (wf_extend_kernel).
+// It names the extern __shared__ array itself (as an argument the array is a generic pointer and the whole kernel's register
+// allocation moves), and keeps the shape the kernels' text was settled with (scripts/isa_diff.py).
+template <typename real, int RES, bool ORD, bool SCREEN, bool SIDE = true>
+CR_D SceneStage<real> stage_scene(const KernelArgs<real>& A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Entry<real>* lds_entries = nullptr;
+    const void* lds_screen = nullptr;
+    const Prim<real>* prims = A.prims;
+    const Mat<real>* mats = A.mats;
+    const Tex<real>* texs = A.texs;
+    size_t end = 0;
+    if (RES != RES_GLOBAL) {
+        auto copy = [&](const void* src, size_t off, size_t bytes) {
+            const uint32_t* s = (const uint32_t*)src;
+            uint32_t* d = (uint32_t*)(smem + off);
+            for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) d[i] = s[i];
+        };
+        using ScreenT = typename ScreenOf<ORD>::type;
+        constexpr size_t window_rec = SCREEN ? sizeof(ScreenT) : sizeof(typename EntryOf<real, ORD>::type);
+        copy(SCREEN ? A.screen : (const void*)A.entries, 0, (size_t)A.lds_entries * window_rec);
+        lds_entries = (const Entry<real>*)smem;
+        if (SCREEN) lds_screen = (const void*)smem;
+        if (RES == RES_LDS) {   // the whole scene
+            const SceneLayout L = scene_layout((size_t)A.n_entries * window_rec, (size_t)A.n_prims * sizeof(Prim<real>), (size_t)A.n_mats * sizeof(Mat<real>),
+                                               (size_t)A.n_texs * sizeof(Tex<real>), true, SIDE);
+            copy(A.prims, L.prims, (size_t)A.n_prims * sizeof(Prim<real>));
+            if (SIDE) {
+                copy(A.mats, L.mats, (size_t)A.n_mats * sizeof(Mat<real>));
+                copy(A.texs, L.texs, (size_t)A.n_texs * sizeof(Tex<real>));
+            }
+            prims = (const Prim<real>*)(smem + L.prims);
+            if (SIDE) {
+                mats = (const Mat<real>*)(smem + L.mats);
+                texs = (const Tex<real>*)(smem + L.texs);
+            }
+            end = L.end();
+        } else if (SIDE && A.lds_side) {   // RES_TOP: the window, and the side tables behind it
+            const SceneLayout L = scene_layout((size_t)A.lds_entries * window_rec, 0, (size_t)A.n_mats * sizeof(Mat<real>), (size_t)A.n_texs * sizeof(Tex<real>), false, true);
+            copy(A.mats, L.mats, (size_t)A.n_mats * sizeof(Mat<real>));
+            copy(A.texs, L.texs, (size_t)A.n_texs * sizeof(Tex<real>));
+            mats = (const Mat<real>*)(smem + L.mats);
+            texs = (const Tex<real>*)(smem + L.texs);
+            end = L.end();
+        } else end = scene_layout((size_t)A.lds_entries * window_rec, 0, 0, 0, false, false).end();   // RES_TOP: the window alone
+        __syncthreads();
+    }
+    return {lds_entries, lds_screen, prims, mats, texs, end};
+}
+
 // The persistent kernel body.  A work item is one (pixel, sample) handed out in chunks from one global counter (sample-granular
 // mode, the default); the reference-order variants keep per-sample colours for the ordered sum, the RELAX variants add into
 // fixed-point per-pixel sums.  (sg_on = 0, a fallback: one lane owns a pixel and sums its samples in draw order itself.)
@@ -1766,61 +1863,30 @@ template <typename real> CR_D const KernelArgs<real>& kernel_args() {
 // passes false: its launches are the renders whose caller asked for no stats (render.hpp launch()).
 template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true, bool LIST = false, bool COUNT = true>
 CR_D void pathtrace_body(const KernelArgs<real>& A) {
-    using EntryT = typename EntryOf<real, ORD>::type;
     constexpr bool BATCH = RELAX && (ANIM || CAMK);
     constexpr bool REGION = BATCH && REG;
     // REGION: the region's words (reg_x0 .. reg_h) are read through the kernarg segment where they are used, also in the
     // kernels that keep the by-value parameter: there they would be four more scalars alive for the whole launch
     const KernelArgs<real>& RG = kernel_args<real>();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // (RELAX: the waves' slots behind the scene)
 #ifdef CR_HOLD_VCC
     unsigned long long vcc_hold;
     asm volatile("s_mov_b64 %0, 0" : "={vcc}"(vcc_hold));
 #endif
-    const Entry<real>* lds_entries = nullptr;
-    const void* lds_screen = nullptr;
-    const Prim<real>* prims = A.prims;
-    const Mat<real>* mats = A.mats;
-    const Tex<real>* texs = A.texs;
-    if (RES != RES_GLOBAL) {
-        auto copy = [&](const void* src, size_t off, size_t bytes) {
-            const uint32_t* s = (const uint32_t*)src;
-            uint32_t* d = (uint32_t*)(smem + off);
-            for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) d[i] = s[i];
-        };
-        // SCREEN kernels stage the f32 screening records instead of the f64 wrappers (twice as many wrappers in the same bytes)
+    const SceneStage<real> S = stage_scene<real, RES, ORD, SCREEN>(A);
+    const Entry<real>* lds_entries = S.lds_entries;
+    const void* lds_screen = S.lds_screen;
+    const Prim<real>* prims = S.prims;
+    const Mat<real>* mats = S.mats;
+    const Tex<real>* texs = S.texs;
+    if constexpr (SCREEN && RES == RES_LDS) {   // links of the staged screening records become LDS addresses (fetch_screen, fetch_screen_ordered)
         using ScreenT = typename ScreenOf<ORD>::type;
-        constexpr size_t window_rec = SCREEN ? sizeof(ScreenT) : sizeof(EntryT);
-        copy(SCREEN ? A.screen : (const void*)A.entries, 0, (size_t)A.lds_entries * window_rec);
-        lds_entries = (const Entry<real>*)smem;
-        if (SCREEN) lds_screen = (const void*)smem;
-        if (RES == RES_LDS) {   // the whole scene: entries | prims | mats | texs, each 16-B aligned
-            size_t o1 = (((size_t)A.n_entries * window_rec + 15) & ~(size_t)15);
-            size_t o2 = o1 + (((size_t)A.n_prims * sizeof(Prim<real>) + 15) & ~(size_t)15);
-            size_t o3 = o2 + (((size_t)A.n_mats * sizeof(Mat<real>) + 15) & ~(size_t)15);
-            copy(A.prims, o1, (size_t)A.n_prims * sizeof(Prim<real>));
-            copy(A.mats, o2, (size_t)A.n_mats * sizeof(Mat<real>));
-            copy(A.texs, o3, (size_t)A.n_texs * sizeof(Tex<real>));
-            prims = (const Prim<real>*)(smem + o1);
-            mats = (const Mat<real>*)(smem + o2);
-            texs = (const Tex<real>*)(smem + o3);
-            if constexpr (SCREEN) {   // links of the staged screening records become LDS addresses (fetch_screen, fetch_screen_ordered)
-                __syncthreads();
-                const uint32_t base = screen_lds_base<RES>(smem);
-                ScreenT* rec = (ScreenT*)smem;
-                for (int32_t i = (int32_t)threadIdx.x; i < A.n_entries; i += (int32_t)blockDim.x) {
-                    if constexpr (ORD) { for (int k = 0; k < 8; k++) rec[i].skip[k] += base; }
-                    else rec[i].skip += base;
-                    if (!(rec[i].hit & kScreenLeaf)) rec[i].hit += base;
-                }
-            }
-        } else if (A.lds_side) {   // RES_TOP: entry window | mats | texs
-            size_t o2 = (((size_t)A.lds_entries * window_rec + 15) & ~(size_t)15);
-            size_t o3 = o2 + (((size_t)A.n_mats * sizeof(Mat<real>) + 15) & ~(size_t)15);
-            copy(A.mats, o2, (size_t)A.n_mats * sizeof(Mat<real>));
-            copy(A.texs, o3, (size_t)A.n_texs * sizeof(Tex<real>));
-            mats = (const Mat<real>*)(smem + o2);
-            texs = (const Tex<real>*)(smem + o3);
+        const uint32_t base = screen_lds_base<RES>(smem);
+        ScreenT* rec = (ScreenT*)smem;
+        for (int32_t i = (int32_t)threadIdx.x; i < A.n_entries; i += (int32_t)blockDim.x) {
+            if constexpr (ORD) { for (int k = 0; k < 8; k++) rec[i].skip[k] += base; }
+            else rec[i].skip += base;
+            if (!(rec[i].hit & kScreenLeaf)) rec[i].hit += base;
         }
         __syncthreads();
     }
@@ -2108,16 +2174,10 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
     if constexpr (RELAX) { fx_flush(0, fx_tile0); fx_flush(1, fx_tile1); }
     // flush work counters: one atomic per counter per wave
     if constexpr (COUNT) {
-        auto wave_sum = [&](unsigned long long v) -> unsigned long long {
-            unsigned long long s = v;
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-            return s;
-        };
-        unsigned long long s0 = wave_sum(c_seg), s1 = wave_sum(c_node), s2 = wave_sum(c_prim), s3 = wave_sum(c_tex);
         CR_DIAG_ONLY(
             {
                 unsigned long long* c = (unsigned long long*)A.counters;
-                for (int i = 0; i < DG_N; i++) { unsigned long long w = wave_sum(dg_store.v[i]); if (lane == 0) atomicAdd(&c[16 + i], w); }
+                for (int i = 0; i < DG_N; i++) { unsigned long long w = WaveSum{}(dg_store.v[i]); if (lane == 0) atomicAdd(&c[16 + i], w); }
                 if (lane == 0) {
                     atomicAdd(&c[9], d_t_regen); atomicAdd(&c[10], d_t_trace); atomicAdd(&c[11], d_t_shade);
                     atomicAdd(&c[12], __builtin_readcyclecounter() - d_begin);
@@ -2126,12 +2186,7 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
 #ifdef CR_HOLD_VCC
         asm volatile("" :: "{vcc}"(vcc_hold));
 #endif
-        if (lane == 0) {
-            atomicAdd((unsigned long long*)&A.counters[0], s0);
-            atomicAdd((unsigned long long*)&A.counters[1], s1);
-            atomicAdd((unsigned long long*)&A.counters[2], s2);
-            atomicAdd((unsigned long long*)&A.counters[3], s3);
-        }
+        flush_counters(WaveSum{}, A.counters, lane, c_seg, c_node, c_prim, c_tex);
     }
 }
 template <typename real, int RES, bool ANIM, bool ORD = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false>

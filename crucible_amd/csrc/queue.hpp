@@ -86,7 +86,8 @@ CR_D bool ring_read(const uint32_t* ring, uint32_t pos, uint32_t& slot, uint32_t
 template <typename real, int RES, bool ANIM>
 __global__ void __launch_bounds__(1024) queue_kernel(const KernelArgs<real> A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // ---- scene (as in pathtrace_kernel)
+    // ---- scene, by residency.hpp's scene_layout: wrappers, never screening records, and a window takes no side tables along.
+    // (In place, not through stage_scene: the call changes this kernel's count of spilled scalars)
     const Entry<real>* lds_entries = nullptr;
     const Prim<real>* prims = A.prims;
     const Mat<real>* mats = A.mats;
@@ -97,18 +98,18 @@ __global__ void __launch_bounds__(1024) queue_kernel(const KernelArgs<real> A) {
         uint32_t* d = (uint32_t*)(smem + o);
         for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) d[i] = s[i];
     };
-    auto r16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     if (RES != RES_GLOBAL) {
         copy(A.entries, 0, (size_t)A.lds_entries * sizeof(Entry<real>));
         lds_entries = (const Entry<real>*)smem;
-        off = r16((size_t)A.lds_entries * sizeof(Entry<real>));
+        off = scene_layout((size_t)A.lds_entries * sizeof(Entry<real>), 0, 0, 0, false, false).end();
         if (RES == RES_LDS) {
-            size_t o1 = off, o2 = o1 + r16((size_t)A.n_prims * sizeof(Prim<real>)), o3 = o2 + r16((size_t)A.n_mats * sizeof(Mat<real>));
-            copy(A.prims, o1, (size_t)A.n_prims * sizeof(Prim<real>));
-            copy(A.mats, o2, (size_t)A.n_mats * sizeof(Mat<real>));
-            copy(A.texs, o3, (size_t)A.n_texs * sizeof(Tex<real>));
-            prims = (const Prim<real>*)(smem + o1); mats = (const Mat<real>*)(smem + o2); texs = (const Tex<real>*)(smem + o3);
-            off = o3 + r16((size_t)A.n_texs * sizeof(Tex<real>));
+            const SceneLayout L = scene_layout((size_t)A.lds_entries * sizeof(Entry<real>), (size_t)A.n_prims * sizeof(Prim<real>), (size_t)A.n_mats * sizeof(Mat<real>),
+                                               (size_t)A.n_texs * sizeof(Tex<real>), true, true);
+            copy(A.prims, L.prims, (size_t)A.n_prims * sizeof(Prim<real>));
+            copy(A.mats, L.mats, (size_t)A.n_mats * sizeof(Mat<real>));
+            copy(A.texs, L.texs, (size_t)A.n_texs * sizeof(Tex<real>));
+            prims = (const Prim<real>*)(smem + L.prims); mats = (const Mat<real>*)(smem + L.mats); texs = (const Tex<real>*)(smem + L.texs);
+            off = L.end();
         }
     }
     // ---- path slots, rings, control
@@ -232,7 +233,7 @@ __global__ void __launch_bounds__(1024) queue_kernel(const KernelArgs<real> A) {
         V3<real> ro = mk<real>(0, 0, 0), rd = mk<real>(0, 0, 1);
         real rtime = 0;
         WalkState<real> ws;
-        ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
+        walk_reset(ws, 0);
         for (;;) {
             const uint64_t need = __ballot(!has_ray);
             if (need) {
@@ -282,18 +283,8 @@ __global__ void __launch_bounds__(1024) queue_kernel(const KernelArgs<real> A) {
     }
 
     // ---- flush work counters (and the abort flag) once per wave
-    auto wave_sum = [&](unsigned long long v) -> unsigned long long {
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-        return v;
-    };
-    const unsigned long long s0 = wave_sum(c_seg), s1 = wave_sum(c_node), s2 = wave_sum(c_prim), s3 = wave_sum(c_tex);
-    if (lane == 0) {
-        atomicAdd((unsigned long long*)&A.counters[0], s0);
-        atomicAdd((unsigned long long*)&A.counters[1], s1);
-        atomicAdd((unsigned long long*)&A.counters[2], s2);
-        atomicAdd((unsigned long long*)&A.counters[3], s3);
-        if (q_load(&ctrl[QC_ABORT])) atomicAdd((unsigned long long*)&A.counters[4], 1ull);
-    }
+    flush_counters(WaveSum{}, A.counters, lane, c_seg, c_node, c_prim, c_tex);
+    if (lane == 0 && q_load(&ctrl[QC_ABORT])) atomicAdd((unsigned long long*)&A.counters[4], 1ull);
 }
 
 #endif   // __HIPCC__

@@ -157,7 +157,7 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     // a SCREEN kernel stages screening records where the others stage wrappers
     const size_t screen_rec = ds.ordered ? sizeof(ScreenEntryO) : sizeof(ScreenEntry);
     w.screen = screen;
-    w.lds_all_screen = ds.lds_bytes - r16((size_t)ds.n_entries * ds.entry_bytes) + r16((size_t)ds.n_entries * screen_rec);
+    w.lds_all_screen = whole_scene_layout(ds, screen_rec).end();
     set_tiles(a, (uint32_t)(c.W + 7) / 8u, (uint32_t)(c.H + 7) / 8u);
     a.work_counter = (uint32_t*)h->work_counter.p;
     a.counters = (uint64_t*)h->counters.p;

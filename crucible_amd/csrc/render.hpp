@@ -64,7 +64,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     if (tile_lw < 0) default_tile(n_samples, tile_lw, tile_lh);
     // RELAX: the waves' accumulator slots follow the scene in LDS (2 x 384 B per wave for a 16-pixel tile); a tile too
     // large for what the scene leaves free falls back to 16 pixels (the surplus sample slots of its groups stay empty)
-    const size_t fx_off = RES != RES_GLOBAL ? ((scene_lds_bytes + 15) & ~(size_t)15) : 0;
+    const size_t fx_off = RES != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
     if (RELAX && fx_off + fx_lds_bytes(max_block, (uint32_t)(tile_lw + tile_lh)) > (size_t)160 * 1024) { tile_lw = 2; tile_lh = 2; }
     auto lds_for = [&](int block) { return RELAX ? fx_off + fx_lds_bytes(block, (uint32_t)(tile_lw + tile_lh)) : scene_lds_bytes; };
     args.fx_lds_off = (uint32_t)fx_off;

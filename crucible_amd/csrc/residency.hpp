@@ -1,4 +1,5 @@
-// residency.hpp -- how much of a scene a launch stages in LDS: one rule, choose_residency, for the render
+// residency.hpp -- how much of a scene a launch stages in LDS and where it lies there: one layout,
+// scene_layout, for every kernel that stages and every host computation of the bytes; one rule, choose_residency, for the render
 // kernels' ladder (render.hpp walk_ladder) and the guide kernels' (aov_kernel.hpp aov_ladder_ord), which only fill a query
 // and dispatch on the answer; and launch()'s two small rules, the work chunk and the default tile.  Free of the HIP runtime
 // and of the record types -- sizes arrive as numbers --, so that a plain C++ compiler can check it
@@ -21,6 +22,29 @@ enum : int { RES_GLOBAL = 0, RES_LDS = 1, RES_TOP = 2 };
 
 CR_HD size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 
+// The scene's LDS copy: records | primitives | materials | textures, each table at a multiple of 16 bytes.  The records
+// at offset 0 are wrappers or screening records (the whole tree, or a window of its top); with_prims: the primitive table
+// follows them (RES_LDS); with_side: materials and textures follow (RES_LDS, and RES_TOP where they ride along).  A table
+// that is not staged takes no room.  `bytes` ends the last table; what a launch puts behind the scene (the waves' slots,
+// the queue's state) begins at end().  stage_scene (pathtrace.hpp) copies by this, and the host sizes its launches by it.
+// The four sizes are the tables' bytes (records * bytes of one), formed by the caller: a kernel copies by the same products.
+struct SceneLayout {
+    size_t prims, mats, texs;   // offsets of the tables
+    size_t bytes;
+    CR_HD size_t end() const { return r16(bytes); }
+};
+CR_HD SceneLayout scene_layout(size_t record_bytes, size_t prim_bytes, size_t mat_bytes, size_t tex_bytes, bool with_prims, bool with_side) {
+    SceneLayout l;
+    l.bytes = record_bytes;
+    l.prims = l.mats = l.texs = r16(record_bytes);
+    if (with_prims) { l.bytes = l.prims + prim_bytes; l.mats = l.texs = l.prims + r16(prim_bytes); }
+    if (with_side) { l.texs = l.mats + r16(mat_bytes); l.bytes = l.texs + tex_bytes; }
+    return l;
+}
+
+// What the two side tables take behind a window: their own layout from offset 0
+CR_HD size_t side_table_bytes(size_t mat_bytes, size_t tex_bytes) { return scene_layout(0, 0, mat_bytes, tex_bytes, false, true).end(); }
+
 struct ResidencyQuery {
     int32_t n_entries;
     size_t entry_rec, screen_rec;        // bytes of one wrapper / one screening record of the tree's order
@@ -28,7 +52,7 @@ struct ResidencyQuery {
     bool can_screen;                     // false for an ordered f32 tree: it has no screening records, so no SCREEN kernels
     bool screen, screen_lds, plain_lds;  // WalkChoice: walk on screening records; the whole scene fits with them / with its wrappers
     size_t lds_bytes, lds_all_screen;    // LDS bytes of the whole scene with its wrappers / with screening records in their place
-    size_t side_bytes;                   // r16(materials) + r16(textures)
+    size_t side_bytes;                   // the side tables behind a window: side_table_bytes(materials, textures)
     size_t lds_top_bytes, lds_side_limit;   // the handle's window and its limit for the side tables
     // The 6-waves-per-SIMD entry point: f32 trees of more than latency_entries wrappers, whole frames outside adaptive runs,
     // on a window of latency_top_bytes.  Its three 512-thread groups per CU share 160 KB: window, side tables and
@@ -72,11 +96,13 @@ CR_HD Residency choose_residency(const ResidencyQuery& q) {
     r.lds_entries = top;
     r.latency = latency;
     r.screen = r.screen && !latency;
-    r.lds_bytes = (size_t)top * window_rec;
+    const SceneLayout window = scene_layout((size_t)top * window_rec, 0, 0, 0, false, false);
+    r.lds_bytes = window.bytes;
     if (!q.ordered) {   // materials and textures ride along when they are small (the tree can be large with two materials)
         const size_t third = (size_t)160 * 1024 / 3 - 16, used = r.lds_bytes + q.latency_slot_bytes;
         const size_t cap = latency ? (third > used ? third - used : 0) : q.lds_side_limit;
-        if (q.side_bytes <= (q.lds_side_limit < cap ? q.lds_side_limit : cap)) { r.lds_side = 1; r.lds_bytes = r16(r.lds_bytes) + q.side_bytes; }
+        // the side tables begin where the window's layout ends, and side_bytes is what a layout of the two alone takes
+        if (q.side_bytes <= (q.lds_side_limit < cap ? q.lds_side_limit : cap)) { r.lds_side = 1; r.lds_bytes = window.end() + q.side_bytes; }
     }
     return r;
 }

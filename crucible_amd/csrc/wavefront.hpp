@@ -153,29 +153,15 @@ __global__ void __launch_bounds__(256) wf_logic_kernel(const WfArgs<real> W) {
 template <typename real, int RES, bool ANIM>
 __global__ void __launch_bounds__(MaxBlock<real>::value) wf_extend_kernel(const WfArgs<real> W) {
     const KernelArgs<real>& A = W.k;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Entry<real>* lds_entries = nullptr;
-    const Prim<real>* prims = A.prims;
     uint32_t* my_set = &W.ctrl[WF_SET * W.ctrl_set];
     uint32_t q_count = 0;
     for (int i = 0; i < 32; i++) q_count += my_set[i];
     if (blockIdx.x == 0 && threadIdx.x == 0) *W.ring_slot = q_count;
     if (q_count == 0) return;
-    if (RES != RES_GLOBAL) {   // entries (all or the top levels) and, when they fit, the primitives: shading does not run here
-        auto copy = [&](const void* src, size_t off, size_t bytes) {
-            const uint32_t* s = (const uint32_t*)src;
-            uint32_t* d = (uint32_t*)(smem + off);
-            for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) d[i] = s[i];
-        };
-        copy(A.entries, 0, (size_t)A.lds_entries * sizeof(Entry<real>));
-        lds_entries = (const Entry<real>*)smem;
-        if (RES == RES_LDS) {
-            size_t o1 = (((size_t)A.n_entries * sizeof(Entry<real>) + 15) & ~(size_t)15);
-            copy(A.prims, o1, (size_t)A.n_prims * sizeof(Prim<real>));
-            prims = (const Prim<real>*)(smem + o1);
-        }
-        __syncthreads();
-    }
+    // entries (all or the top levels) and, when they fit, the primitives: shading does not run here
+    const SceneStage<real> St = stage_scene<real, RES, false, false, false>(A);
+    const Entry<real>* const lds_entries = St.lds_entries;
+    const Prim<real>* const prims = St.prims;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t N = W.n_slots;
     uint32_t* cursor = &my_set[32];
@@ -188,7 +174,7 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) wf_extend_kernel(const 
     V3<real> ro = mk<real>(0, 0, 0), rd = mk<real>(0, 0, 1);
     real rtime = 0;
     WalkState<real> ws;
-    ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
+    walk_reset(ws, 0);
     uint32_t c_prim = 0;
     unsigned long long c_node = 0;
 
@@ -228,12 +214,7 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) wf_extend_kernel(const 
             has_ray = false;
         }
     }
-    unsigned long long s1 = c_node, s2 = c_prim;
-    for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off); s2 += __shfl_down(s2, off); }
-    if (lane == 0) {
-        atomicAdd((unsigned long long*)&A.counters[1], s1);
-        atomicAdd((unsigned long long*)&A.counters[2], s2);
-    }
+    flush_counters(WaveSum{}, A.counters, lane, NoCount{}, c_node, c_prim, NoCount{});   // (segments and texels: wf_logic_kernel's)
 }
 
 // average_samples' running sum (ray_casting.rs:161-165): samples of the batch are added in sample order.

@@ -3,6 +3,8 @@
 //   R n_entries entry_rec screen_rec ordered can_screen screen screen_lds plain_lds lds_bytes lds_all_screen side_bytes
 //     lds_top_bytes lds_side_limit f32 whole_frame adaptive latency_entries latency_top_bytes latency_slot_bytes
 //       -> "res screen latency lds_entries lds_side lds_bytes clear_screen"
+//   L n_records record_rec n_prims prim_rec n_mats mat_rec n_texs tex_rec with_prims with_side
+//       -> "prims mats texs bytes end": scene_layout over the tables' bytes, formed as handle.hpp forms them (count * record)
 //   C sg_total grid block chunk_override   -> the chunk
 //   T n                                    -> "lw lh"
 #include "residency.hpp"
@@ -29,6 +31,13 @@ int main(int argc, char** argv) {
             q.latency_entries = (int32_t)v[16]; q.latency_top_bytes = (size_t)v[17]; q.latency_slot_bytes = (size_t)v[18];
             const cr::Residency r = cr::choose_residency(q);
             printf("%d %d %d %d %d %zu %d\n", r.res, r.screen ? 1 : 0, r.latency ? 1 : 0, r.lds_entries, r.lds_side, r.lds_bytes, r.clear_screen ? 1 : 0);
+        } else if (kind == 'L') {
+            long long v[10];
+            for (long long& x : v)
+                if (fscanf(f, "%lld", &x) != 1) return 2;
+            const cr::SceneLayout l = cr::scene_layout((size_t)v[0] * (size_t)v[1], (size_t)v[2] * (size_t)v[3], (size_t)v[4] * (size_t)v[5],
+                                                       (size_t)v[6] * (size_t)v[7], v[8] != 0, v[9] != 0);
+            printf("%zu %zu %zu %zu %zu\n", l.prims, l.mats, l.texs, l.bytes, l.end());
         } else if (kind == 'C') {
             uint64_t total, grid, block;
             int chunk_override;

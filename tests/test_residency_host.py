@@ -2,7 +2,8 @@
 walk_ladder and the guide pass's aov_ladder_ord) and launch()'s chunk and tile rules, checked without a device:
 tests/residency_check.cpp compiles the header with g++ (plain, and with -fsanitize=address,undefined) and prints the
 decision of each case.  The expected decisions below are written out by hand from the rule, not computed
-by a second copy of it: (res, screen, latency, lds_entries, lds_side, lds_bytes, clear_screen)."""
+by a second copy of it: (res, screen, latency, lds_entries, lds_side, lds_bytes, clear_screen).  So are the offsets of the layout
+that the rule, every launch's byte count and the kernels' stage_scene share (scene_layout): (prims, mats, texs, bytes, end)."""
 import os
 import subprocess
 
@@ -144,6 +145,62 @@ def test_global_row(exes, tmp_path):
         ("f32", R(F32, 10000, **none), (GLOBAL, 1, 0, 0, 0, 0, 0)),
         ("no SCREEN kernels, whatever w.screen says", R(F32_ORD, 10000, screen=1, **none), (GLOBAL, 0, 0, 0, 0, 0, 0)),
         ("the side tables do not matter", R(F64, 10000, side_bytes=64, **none), (GLOBAL, 1, 0, 0, 0, 0, 0)),
+    ])
+
+
+# bytes of a primitive, material and texture record (pathtrace.hpp Prim, Mat, Tex), per precision
+REC64 = dict(prim_rec=96, mat_rec=48, tex_rec=48)
+REC32 = dict(prim_rec=48, mat_rec=32, tex_rec=32)
+
+
+def L(n_records, record_rec, n_prims, n_mats, n_texs, with_prims, with_side, prim_rec, mat_rec, tex_rec):
+    return f"L {n_records} {record_rec} {n_prims} {prim_rec} {n_mats} {mat_rec} {n_texs} {tex_rec} {with_prims} {with_side}"
+
+
+def test_layout(exes, tmp_path):
+    """records | primitives | materials | textures, every table at a multiple of 16; `bytes` ends the last table staged."""
+    ODD = dict(prim_rec=20, mat_rec=24, tex_rec=20)   # no record of the library: sizes that 16 does not divide
+    check(exes, tmp_path, [
+        # the whole scene (RES_LDS), 2 primitives, 2 materials, 1 texture behind the four trees' records
+        ("f64 wrappers: 192 | 192 | 96 | 48", L(3, 64, 2, 2, 1, 1, 1, **REC64), (192, 384, 480, 528, 528)),
+        ("f64 screening records: 96 | 192 | 96 | 48", L(3, 32, 2, 2, 1, 1, 1, **REC64), (96, 288, 384, 432, 432)),
+        ("ordered f64 wrappers, one of each: 96 | 96 | 48 | 48", L(1, 96, 1, 1, 1, 1, 1, **REC64), (96, 192, 240, 288, 288)),
+        ("ordered f64 screening records, one of each: 64 | 96 | 48 | 48", L(1, 64, 1, 1, 1, 1, 1, **REC64), (64, 160, 208, 256, 256)),
+        ("f32: 96 | 96 | 64 | 32", L(3, 32, 2, 2, 1, 1, 1, **REC32), (96, 192, 256, 288, 288)),
+        ("ordered f32: 192 | 96 | 64 | 32", L(3, 64, 2, 2, 1, 1, 1, **REC32), (192, 288, 352, 384, 384)),
+        ("no records: the primitives at 0", L(0, 64, 2, 2, 1, 1, 1, **REC64), (0, 192, 288, 336, 336)),
+        ("no tables behind one record", L(1, 64, 0, 0, 0, 1, 1, **REC64), (64, 64, 64, 64, 64)),
+        # 3 x 40 = 120 -> 128; 3 x 20 = 60 -> 64; 24 -> 32; the last table ends at 224 + 20, unrounded, and end() rounds it
+        ("every size rounded up to 16, the end only in end()", L(3, 40, 3, 1, 1, 1, 1, **ODD), (128, 192, 224, 244, 256)),
+        # a window (RES_TOP): no primitives, whatever the scene has
+        ("window of 25 screening records with 5 materials, 1 texture", L(25, 32, 100, 5, 1, 0, 1, **REC64), (800, 800, 1040, 1088, 1088)),
+        ("window of 1000 bytes: rounded before the side tables follow", L(25, 40, 100, 1, 0, 0, 1, **REC32), (1008, 1008, 1040, 1040, 1040)),
+        ("window alone: 1000 bytes, what follows it begins at 1008", L(25, 40, 100, 5, 1, 0, 0, **REC64), (1008, 1008, 1008, 1000, 1008)),
+        ("window of no records, side tables at 0", L(0, 32, 100, 1, 1, 0, 1, **REC64), (0, 0, 48, 96, 96)),
+        # geometry only (the wavefront extend kernel): materials and textures take no room
+        ("geometry only", L(3, 64, 2, 5, 1, 1, 0, **REC64), (192, 384, 384, 384, 384)),
+        ("geometry only, 60 bytes of primitives", L(3, 64, 3, 5, 1, 1, 0, **ODD), (192, 256, 256, 252, 256)),
+    ])
+
+
+def test_layout_keeps_a_scene_s_bytes(exes, tmp_path):
+    """The two byte counts a handle derives from an uploaded scene, as they were computed before the layout existed -- the sum
+    of every table rounded up to 16 --, for the counts of test_motion_boxes_host.py's keyed scene: 11 primitives (a binary tree
+    over them has 21 wrappers), 5 materials, 1 texture.  DevScene::lds_bytes is end() over the wrappers, WalkChoice::
+    lds_all_screen end() over the screening records.  The counts are multiplied here by the record sizes above and handed to
+    scene_layout directly: handle.hpp's whole_scene_layout and scene_lds_bytes, which do that multiplication in the library,
+    need the HIP runtime and are not compiled here -- a wrong record size or flag there shows in the GPU tests alone
+    (test_gpu_variants.py, test_gpu_handle_memory.py)."""
+    check(exes, tmp_path, [
+        # f64: 21 x 64 = 1344, 11 x 96 = 1056, 5 x 48 = 240, 48: 2688; with 21 x 32 = 672 in the wrappers' place 2016
+        ("f64 lds_bytes", L(21, 64, 11, 5, 1, 1, 1, **REC64), (1344, 2400, 2640, 2688, 2688)),
+        ("f64 lds_all_screen", L(21, 32, 11, 5, 1, 1, 1, **REC64), (672, 1728, 1968, 2016, 2016)),
+        # f32: 21 x 32 = 672, 11 x 48 = 528, 5 x 32 = 160, 32: 1392, and the same with its 32-byte screening records
+        ("f32 lds_bytes and lds_all_screen", L(21, 32, 11, 5, 1, 1, 1, **REC32), (672, 1200, 1360, 1392, 1392)),
+        # ordered trees: 21 x 96 = 2016 -> 3360, 21 x 64 = 1344 -> 2688 (f64); 21 x 64 = 1344 -> 2064 (f32)
+        ("ordered f64 lds_bytes", L(21, 96, 11, 5, 1, 1, 1, **REC64), (2016, 3072, 3312, 3360, 3360)),
+        ("ordered f64 lds_all_screen", L(21, 64, 11, 5, 1, 1, 1, **REC64), (1344, 2400, 2640, 2688, 2688)),
+        ("ordered f32 lds_bytes", L(21, 64, 11, 5, 1, 1, 1, **REC32), (1344, 1872, 2032, 2064, 2064)),
     ])
 
 

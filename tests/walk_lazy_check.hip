@@ -80,8 +80,7 @@ __global__ void __launch_bounds__(64) walk_kernel(KernelArgs<double> A, const do
     V3<real> ro = mk<real>(0, 0, 0), rd = mk<real>(0, 0, 1);
     real rtime = 0;
     WalkState<real> ws;
-    ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.rda = 0; ws.best_t = 0; ws.best = -1; ws.idx = n_entries; ws.exact_box = false; ws.oct = 0; ws.pending = -1;
-    ws.invf = mk<float>(0, 0, 0); ws.unscreened = false;
+    walk_reset(ws, n_entries);
     for (;;) {
         if (cur < 0 && qi < K && queue[qi] >= 0) {   // the lane's next ray
             cur = queue[qi++];
