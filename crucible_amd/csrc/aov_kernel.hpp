@@ -253,21 +253,22 @@ auto aov_kernel_of() -> void (*)(const AovArgs<real>) {
 // batch with more runs as consecutive launches of whole frames, each on its own part of the accumulators.
 // COUNTS: sized from params->samples all the same -- the host does not see a device plane --, so a unit beyond its tile's
 // largest count costs one counter fetch and sixteen loads; each launch's frames read their own part of the plane.
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS = false>
-int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* res) {
-    void (*kern)(const AovArgs<real>) = aov_kernel_of<real, RES, ANIM, ORD, SCREEN, BATCH, COUNTS>();
+// One body per precision: what the launch depends on in its kernel -- the residency, BATCH and COUNTS -- arrives as
+// numbers beside the kernel's address (aov_variant names the kernels), so a unit compiles this once.
+template <typename real>
+int32_t aov_launch(CrHandle* h, void (*kern)(const AovArgs<real>), int res, bool batch, bool counts_plane, AovArgs<real>& a, size_t scene_lds_bytes, int* res_out) {
     const int max_block = MaxBlock<real>::value;
-    const size_t off = RES != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
+    const size_t off = res != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
     a.acc_lds_off = (uint32_t)off;
     HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(off + aov_lds_bytes(max_block))));
     int block = 256, per_cu = 1;
     { int32_t rc = pick_block(h, (const void*)kern, max_block, true, off, aov_lds_bytes(64), "guide kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
     const uint64_t tiles = (uint64_t)a.k.tiles_x * a.k.tiles_y;
-    const uint64_t n_frames = BATCH ? a.n_frames : 1;
+    const uint64_t n_frames = batch ? a.n_frames : 1;
     const uint64_t resident = (uint64_t)h->n_cus * per_cu * (block / 64);
     uint64_t ug = std::min<uint64_t>(a.groups, std::max<uint64_t>(1, n_frames * tiles * a.groups / (8 * resident)));
     // the 32-bit work counter (a frame has at most 2^22 tiles; a limit below one frame's tiles, which only a test sets, is raised to them)
-    const uint64_t max_units = BATCH ? std::max<uint64_t>(h->work_counter_max, tiles) : 0xF0000000ull;
+    const uint64_t max_units = batch ? std::max<uint64_t>(h->work_counter_max, tiles) : 0xF0000000ull;
     if (tiles * ((a.groups + ug - 1) / ug) > max_units) ug = (a.groups + max_units / tiles - 1) / (max_units / tiles);
     a.unit_groups = (uint32_t)ug;
     a.unit_chunks = (uint32_t)((a.groups + ug - 1) / ug);
@@ -281,12 +282,12 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
     const int32_t* const counts = a.counts;
     for (uint64_t f0 = 0; f0 < n_frames; f0 += per_launch) {
         const uint64_t fn = std::min<uint64_t>(per_launch, n_frames - f0);
-        if constexpr (BATCH) {
+        if (batch) {
             a.n_frames = (uint32_t)fn;
             a.frame_times = times + f0;
             a.acc = acc + f0 * npix * kAovWords;
             a.flags = flags + f0 * npix;
-            if constexpr (COUNTS) a.counts = counts + f0 * npix;
+            if (counts_plane) a.counts = counts + f0 * npix;
         }
         a.n_units = (uint32_t)(fn * frame_units);
         uint32_t grid = (uint32_t)(h->n_cus * per_cu);
@@ -298,7 +299,7 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
         HIP_TRY(h, hipGetLastError());
         h->last_block = block; h->last_grid = (int)grid;
     }
-    *res = RES;
+    *res_out = res;
     return CR_OK;
 }
 
@@ -306,13 +307,16 @@ int32_t aov_launch(CrHandle* h, AovArgs<real>& a, size_t scene_lds_bytes, int* r
 // a.n_frames != 0: a batch (cr_render_aov_frames_*), on the BATCH kernels whatever its length
 template <typename real, int RES, bool ORD, bool SCREEN, bool COUNTS = false>
 int32_t aov_variant(CrHandle* h, AovArgs<real>& a, size_t lds_bytes, const WalkChoice& w, int* res) {
-    if constexpr (COUNTS)   // (a.n_frames >= 1: a single frame is a batch of one here)
-        return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, true, true>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, true, true>(h, a, lds_bytes, res);
-    else {   // (inside the else: a COUNTS unit instantiates none of these)
-        if (a.n_frames)
-            return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, true>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, true>(h, a, lds_bytes, res);
-        return w.anim ? aov_launch<real, RES, true, ORD, SCREEN, false>(h, a, lds_bytes, res) : aov_launch<real, RES, false, ORD, SCREEN, false>(h, a, lds_bytes, res);
-    }
+    auto on = [&](auto batch) {
+        constexpr bool BATCH = decltype(batch)::value;
+        return aov_launch<real>(h, w.anim ? aov_kernel_of<real, RES, true, ORD, SCREEN, BATCH, COUNTS>() : aov_kernel_of<real, RES, false, ORD, SCREEN, BATCH, COUNTS>(),
+                                RES, BATCH, COUNTS, a, lds_bytes, res);
+    };
+    // (COUNTS: a.n_frames >= 1, a single frame is a batch of one there, and a COUNTS unit instantiates no other kernel.  The
+    // BATCH kernels are named first: a unit emits its kernels in the order it first names them, and the code the compiler
+    // makes of a kernel depends on that order -- scripts/isa_diff.py shows it)
+    if constexpr (COUNTS) return on(std::true_type{});
+    else return a.n_frames ? on(std::true_type{}) : on(std::false_type{});
 }
 
 // The guide kernels' residency ladder: the rule walk_ladder asks (residency.hpp), so a guide pass stages what the render

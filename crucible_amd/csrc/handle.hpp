@@ -9,9 +9,10 @@
 //   scene.hip          cr_upload_scene (its descriptor checks: scene_checks.hpp, a header free of the HIP runtime), refit.hpp's box kernels,
 //                      the screening records, cr_update_primitives, cr_update_materials, cr_update_image, cr_set_sky (update.hpp)
 //   render.hip         render_typed: a render's kernel arguments up to the choice of ladder; the stats epilogue
-//   render_*.hip       the megakernels of one precision and one sum order (render.hpp: launch, the residency ladder over residency.hpp's rule)
+//   render_*.hip       the megakernels of one precision and one sum order (render.hpp: the residency ladder over residency.hpp's rule, and
+//                      one launch<real, RELAX> per unit, which takes its kernel as a MegaKernel descriptor)
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
-//   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp)
+//   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp; one aov_launch<real> per unit)
 //   aov_counts_f32.hip, aov_counts_f64.hip   the first-hit kernels at a count plane, cr_render_aov_counts_* (aov_kernel.hpp's COUNTS axis; aov_counts.hpp: its integer rules)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
 //   adaptive.hip       the adaptive family behind its entry points: its argument checks, the pass loop, the judge and finalize kernels (adaptive.hpp)
@@ -316,6 +317,16 @@ struct WalkChoice {
     bool screen;                    // walk on the f32 screening records (a.screen is set)
     bool screen_lds, plain_lds;     // the whole scene fits in LDS with screening records / with its wrappers
     size_t lds_all_screen;          // LDS bytes of the whole scene with screening records in the wrappers' place
+};
+
+// What launch() (render.hpp) needs to know about the kernel it runs, as launch_variant settled it.  A kernel's other
+// template parameters (the tree order, the screening records, keyed primitives against camera keys) change its code, not its launch.
+template <typename real> struct MegaKernel {
+    void (*kern)(const KernelArgs<real>);
+    void (*quiet)(const KernelArgs<real>);   // the twin that keeps no work counters; nullptr where none exists
+    int res;                                 // RES_LDS / RES_TOP / RES_GLOBAL
+    bool keyed;                              // ANIM || CAMK: carries a batch's frame arithmetic and a region's offsets
+    bool latency, list;                      // the 6-waves-per-SIMD entry point; pathtrace_kernel_listed
 };
 
 // What a ladder asks residency.hpp's choose_residency about this tree on this handle.  The answer depends on the launch as

@@ -1,8 +1,9 @@
 // render.hpp -- the megakernel's host side for one precision and one sum order: launch() sets a pathtrace.hpp kernel up
-// and runs it, launch_variant() picks the kernel kind, walk_ladder() turns the scene's residency (residency.hpp's rule,
-// which the guide pass shares) into the kernel that stages it.  Included by the render_*.hip units only, each of which
-// instantiates walk_ladder (both tree orders) for its <real, RELAX>, so the kernels of the four combinations compile side
-// by side and no kernel is emitted twice.
+// and runs it, launch_variant() picks the kernel kind and describes it to launch() (MegaKernel, handle.hpp), walk_ladder()
+// turns the scene's residency (residency.hpp's rule, which the guide pass shares) into the kernel that stages it.  Included
+// by the render_*.hip units only, each of which instantiates walk_ladder (both tree orders) for its <real, RELAX>, so the
+// kernels of the four combinations compile side by side and no kernel is emitted twice.  launch() is a template over
+// <real, RELAX> alone: a unit compiles it once, whatever the number of its kernels.
 #pragma once
 #include "handle.hpp"
 
@@ -35,26 +36,20 @@ inline int32_t diag_dump(CrHandle* h, int block, uint32_t grid) {
 }
 #endif
 
-// LIST: the passes of cr_render_adaptive_* -- pathtrace_kernel_listed, handed to adaptive_passes (adaptive.hip)
-template <typename real, int RES, bool ANIM, bool ORD = false, bool LATENCY = false, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool LIST = false>
-int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats, const FrameBatch<real>& fb) {
-    constexpr bool LDS = RES != RES_GLOBAL || RELAX;
-    static_assert(!LATENCY || RES == RES_TOP, "the 6-waves-per-SIMD entry point exists for RES_TOP only");
+// One launch routine per unit.  What it depends on in the kernel it runs is MegaKernel's fields (handle.hpp), filled by
+// launch_variant below; the sum order alone stays a template parameter, because the two orders run different finalize
+// kernels and a unit may name only its own.  k.list: the passes of cr_render_adaptive_* -- pathtrace_kernel_listed, handed
+// to adaptive_passes (adaptive.hip).
+template <typename real, bool RELAX>
+int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats, const FrameBatch<real>& fb) {
+    const bool use_lds = k.res != RES_GLOBAL || RELAX;
     KernelArgs<real> args = args_in;
-    void (*kern)(const KernelArgs<real>) = pathtrace_kernel<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>;
-    if constexpr (LATENCY) kern = pathtrace_kernel_latency<real, ANIM, ORD, CAMK, RELAX>;
-    if constexpr (LIST) kern = pathtrace_kernel_listed<real, RES, ANIM, ORD, CAMK, SCREEN>;
-    static_assert(!LIST || (RELAX && ANIM != CAMK && !LATENCY), "the listed kernels are relaxed kernels with keys");
-    // A render whose caller asked for no stats runs the kernel that keeps no work counters, where one exists: the static f64
-    // relaxed SCREEN kernel on an unordered tree with the scene in LDS (the headline's).  A CR_DIAG build counts every launch;
-    // adaptive calls and batches of frames run on kernels with keys, which all count; keep_counters: a group's member.
-    bool quiet = false;
-#ifndef CR_DIAG
-    if constexpr (std::is_same<real, double>::value && RES == RES_LDS && !ANIM && !ORD && !LATENCY && !CAMK && RELAX && SCREEN && !LIST) {
-        if (!stats && !h->keep_counters && !fb.ad && fb.n == 1) { kern = pathtrace_kernel_quiet<RES>; quiet = true; }
-    }
-#endif
-    const int max_block = LATENCY ? LatencyBlock : MaxBlock<real>::value;
+    // A render whose caller asked for no stats runs the kernel that keeps no work counters, where one exists (k.quiet: the
+    // headline's kernel, never in a CR_DIAG build, which counts every launch); adaptive calls and batches of frames run on
+    // kernels with keys, which all count; keep_counters: a group's member.
+    const bool quiet = k.quiet && !stats && !h->keep_counters && !fb.ad && fb.n == 1;
+    void (*const kern)(const KernelArgs<real>) = quiet ? k.quiet : k.kern;
+    const int max_block = k.latency ? LatencyBlock : MaxBlock<real>::value;
     // The work tile (sample-granular hand-out): 2^lw x 2^lh pixels times 64 >> (lw + lh) consecutive samples; by default
     // 4 x 4 x 4, wider tiles of fewer samples when fewer than 4 samples are rendered.
     // (cr_render_adaptive_*: a launch renders one pass of pass_samples samples, and the tile's sides divide the block's)
@@ -64,13 +59,13 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     if (tile_lw < 0) default_tile(n_samples, tile_lw, tile_lh);
     // RELAX: the waves' accumulator slots follow the scene in LDS (2 x 384 B per wave for a 16-pixel tile); a tile too
     // large for what the scene leaves free falls back to 16 pixels (the surplus sample slots of its groups stay empty)
-    const size_t fx_off = RES != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
+    const size_t fx_off = k.res != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
     if (RELAX && fx_off + fx_lds_bytes(max_block, (uint32_t)(tile_lw + tile_lh)) > (size_t)160 * 1024) { tile_lw = 2; tile_lh = 2; }
     auto lds_for = [&](int block) { return RELAX ? fx_off + fx_lds_bytes(block, (uint32_t)(tile_lw + tile_lh)) : scene_lds_bytes; };
     args.fx_lds_off = (uint32_t)fx_off;
-    if (LDS) HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_for(max_block)));
+    if (use_lds) HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_for(max_block)));
     int block = 256, per_cu = 1;   // an override above max_block is ignored here (the latency entry point's 512 under CRUCIBLE_BLOCK=1024)
-    const size_t lds_base = RELAX ? fx_off : (LDS ? scene_lds_bytes : 0), lds_per_wave = RELAX ? fx_lds_bytes(64, (uint32_t)(tile_lw + tile_lh)) : 0;
+    const size_t lds_base = RELAX ? fx_off : (use_lds ? scene_lds_bytes : 0), lds_per_wave = RELAX ? fx_lds_bytes(64, (uint32_t)(tile_lw + tile_lh)) : 0;
     { int32_t rc = pick_block(h, (const void*)kern, max_block, true, lds_base, lds_per_wave, "kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
     const size_t lds_bytes = lds_for(block);
     // Sample-granular mode: batches of samples whose colours fit the buffer; each batch is one launch of the
@@ -81,10 +76,10 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     int32_t batch = 0;
     int32_t fpl = 1;   // frames per launch (a batch of frames: as many whole frames as the work counter holds)
     args.n_frames = 1; args.frame_times = nullptr;
-    if (fb.n > 1 && !(RELAX && (ANIM || CAMK))) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
-    if ((args.reg_x0 || args.reg_y0 || args.reg_w != (uint32_t)args.cam.W || args.reg_h != (uint32_t)args.cam.H) && (LATENCY || !(RELAX && (ANIM || CAMK))))
+    if (fb.n > 1 && !(RELAX && k.keyed)) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
+    if ((args.reg_x0 || args.reg_y0 || args.reg_w != (uint32_t)args.cam.W || args.reg_h != (uint32_t)args.cam.H) && (k.latency || !(RELAX && k.keyed)))
         return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders whole frames");
-    if (LIST != (fb.ad != nullptr)) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
+    if (k.list != (fb.ad != nullptr)) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
     if ((h->sample_granular || RELAX) && s_end > s_begin) {
         const size_t per_sample = npix * 3 * sizeof(real);
         batch = (int32_t)std::min<size_t>((size_t)(s_end - s_begin), RELAX ? (size_t)INT32_MAX : std::max<size_t>(1, h->sample_buf_limit / per_sample));
@@ -147,11 +142,21 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     // one launch of the kernel on `args` as they stand: the work counter starts at zero
     auto run = [&](uint32_t blocks) -> int32_t {
         HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), LDS ? lds_bytes : 0, h->stream, args);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), use_lds ? lds_bytes : 0, h->stream, args);
         HIP_TRY(h, hipGetLastError());
         return CR_OK;
     };
-    if constexpr (LIST) {
+    // one batch of samples [b0, b1) of n_tiles tiles (those of all the launch's frames): its groups, work items and chunk,
+    // then the launch.  fit: on no more blocks than the items fill (a pass may name few tiles); else on the whole grid
+    auto run_batch = [&](int32_t b0, int32_t b1, uint64_t n_tiles, bool fit) -> int32_t {
+        args.sample_begin = b0; args.sample_end = b1;
+        set_groups(args, groups_of(b1 - b0));
+        args.sg_total = (uint32_t)(n_tiles * args.sg_groups * 64u);
+        const uint32_t blocks = fit ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block)) : grid;
+        args.sg_chunk = work_chunk(args.sg_total, blocks, (uint64_t)block, h->sg_chunk_override);
+        return run(blocks);
+    };
+    if (k.list) {
         // cr_render_adaptive_*: the passes are adaptive_passes' (adaptive.hip), each one a launch of this kernel over the tiles
         // it names, into the accumulator it names; the counters add up over the passes
         if (!args.sg_on) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
@@ -164,20 +169,14 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
             args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
             // one launch, unless the work counter holds fewer samples of the tiles than the pass has (split_passes; batch >= 1)
             for (int64_t b0 = s0; b0 < s1; b0 += batch) {
-                const int32_t b1 = (int32_t)std::min<int64_t>(s1, b0 + batch);
-                args.sample_begin = (int32_t)b0; args.sample_end = b1;
-                set_groups(args, groups_of(b1 - (int32_t)b0));
-                args.sg_total = (uint32_t)((uint64_t)n_tiles * args.sg_groups * 64u);
-                const uint32_t pass_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block));
-                args.sg_chunk = work_chunk(args.sg_total, pass_grid, (uint64_t)block, h->sg_chunk_override);
-                const int32_t rc = run(pass_grid);
+                const int32_t rc = run_batch((int32_t)b0, (int32_t)std::min<int64_t>(s1, b0 + batch), n_tiles, true);
                 if (rc != CR_OK) return rc;
             }
             return CR_OK;
         };
         // (the pass loop judges the launch's pixels: a region's blocks and tiles share its origin)
         const AdaptiveFrame fr = {(int32_t)args.reg_w, (int32_t)args.reg_h, args.samples_total, fb.n, fpl, args.sg_lw, args.sg_lh, args.tiles_x, args.tiles_y, args.fx_scale,
-                                  (void*)args.out, std::is_same<real, double>::value, args.n_entries, RES};
+                                  (void*)args.out, std::is_same<real, double>::value, args.n_entries, k.res};
         return adaptive_passes(h, *fb.ad, fr, pass);
     }
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -197,11 +196,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
             }
             for (int64_t b0 = s_begin; b0 < s_end; b0 += batch) {   // (64 bits: b0 + batch may pass INT32_MAX)
                 const int32_t b1 = (int32_t)std::min<int64_t>(s_end, b0 + batch);
-                args.sample_begin = (int32_t)b0; args.sample_end = b1;
-                set_groups(args, groups_of(b1 - (int32_t)b0));
-                args.sg_total = (uint32_t)((uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn * args.sg_groups * 64u);
-                args.sg_chunk = work_chunk(args.sg_total, grid, (uint64_t)block, h->sg_chunk_override);
-                { int32_t rc = run(grid); if (rc != CR_OK) return rc; }
+                { int32_t rc = run_batch((int32_t)b0, b1, (uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn, false); if (rc != CR_OK) return rc; }
                 if constexpr (!RELAX) {   // (relaxed: the sums stay in fx_acc until the last batch)
                     const size_t fin_threads = ((size_t)args.tiles_x * args.tiles_y) << (args.sg_lw + args.sg_lh);
                     hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((fin_threads + 255) / 256)), dim3(256), 0, h->stream, args,
@@ -219,7 +214,7 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     h->last_block = block; h->last_grid = (int)grid;
     if (stats) {
-        int32_t rc = finish_stats(h, stats, (uint64_t)npix * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, RES);
+        int32_t rc = finish_stats(h, stats, (uint64_t)npix * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, k.res);
         if (rc != CR_OK) return rc;
 #ifdef CR_DIAG
         rc = diag_dump(h, block, grid);
@@ -231,17 +226,35 @@ int32_t launch(CrHandle* h, const KernelArgs<real>& args_in, size_t scene_lds_by
 
 // Picks the kernel kind: keyed primitives (ANIM), camera keys alone (CAMK) or neither.  The ANIM kernels follow a keyed
 // camera themselves, so ANIM with CAMK is never instantiated.
+// The one place that names the kernels: `on` describes the kernel of <ANIM, CAMK, LIST> to launch() and runs it.
 template <typename real, int RES, bool ORD, bool LATENCY, bool RELAX, bool SCREEN = false>
 int32_t launch_variant(CrHandle* h, const KernelArgs<real>& a, size_t lds_bytes, CrStats* stats, const WalkChoice& w, const FrameBatch<real>& fb) {
+    static_assert(!LATENCY || RES == RES_TOP, "the 6-waves-per-SIMD entry point exists for RES_TOP only");
+    using yes = std::true_type;
+    using no = std::false_type;
+    auto on = [&](auto anim, auto camk, auto list) {
+        constexpr bool ANIM = decltype(anim)::value, CAMK = decltype(camk)::value, LIST = decltype(list)::value;
+        static_assert(!LIST || (RELAX && ANIM != CAMK && !LATENCY), "the listed kernels are relaxed kernels with keys");
+        // (pathtrace_kernel is named whatever the kind, and first: a unit emits its kernels in the order it first names them,
+        // and the code the compiler makes of a kernel depends on that order -- scripts/isa_diff.py shows it)
+        MegaKernel<real> k = {pathtrace_kernel<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>, nullptr, RES, ANIM || CAMK, LATENCY, LIST};
+        if constexpr (LATENCY) k.kern = pathtrace_kernel_latency<real, ANIM, ORD, CAMK, RELAX>;
+        if constexpr (LIST) k.kern = pathtrace_kernel_listed<real, RES, ANIM, ORD, CAMK, SCREEN>;
+#ifndef CR_DIAG
+        // the twin that keeps no work counters: of the static f64 relaxed SCREEN kernel on an unordered tree with the scene in LDS
+        // (two conditions: what this function's parameters decide is settled before the lambda's own, so no f32 unit meets the f64 twin)
+        if constexpr (std::is_same<real, double>::value && RES == RES_LDS && !ORD && !LATENCY && RELAX && SCREEN)
+            if constexpr (!ANIM && !CAMK && !LIST) k.quiet = pathtrace_kernel_quiet<RES>;
+#endif
+        return launch<real, RELAX>(h, k, a, lds_bytes, stats, fb);
+    };
     if (fb.ad) {   // cr_render_adaptive_*: the listed kernels (a scene without keys on the camera-key one)
-        if constexpr (RELAX && !LATENCY) {
-            if (w.anim) return launch<real, RES, true, ORD, false, false, true, SCREEN, true>(h, a, lds_bytes, stats, fb);
-            return launch<real, RES, false, ORD, false, true, true, SCREEN, true>(h, a, lds_bytes, stats, fb);
-        } else return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
+        if constexpr (RELAX && !LATENCY) return w.anim ? on(yes{}, no{}, yes{}) : on(no{}, yes{}, yes{});
+        else return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
     }
-    if (w.anim) return launch<real, RES, true, ORD, LATENCY, false, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
-    if (w.cam_keys) return launch<real, RES, false, ORD, LATENCY, true, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
-    return launch<real, RES, false, ORD, LATENCY, false, RELAX, SCREEN>(h, a, lds_bytes, stats, fb);
+    if (w.anim) return on(yes{}, no{}, no{});
+    if (w.cam_keys) return on(no{}, yes{}, no{});
+    return on(no{}, no{}, no{});
 }
 
 // The residency ladder: residency.hpp's rule settles the residency, the window and whether the walk runs on screening

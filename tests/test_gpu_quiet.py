@@ -1,6 +1,6 @@
 """A render whose caller asks for no stats runs, where one exists, the kernel that keeps no work counters
 (pathtrace.hpp pathtrace_kernel_quiet: the static f64 relaxed SCREEN kernel on an unordered tree with the scene in LDS;
-render.hpp launch() picks it).  The paths are the same paths, so the frame must be the counted render's bit for bit: every
+render.hpp: launch_variant names it as that kernel's twin in the MegaKernel descriptor, launch() picks it).  The paths are the same paths, so the frame must be the counted render's bit for bit: every
 case below renders f64 with relaxed sums twice, without and with a CrStats, and compares with np.array_equal -- through
 the host entry point unless a case says otherwise.  The counted twin's scene_in_lds shows the residency the pair ran at."""
 import numpy as np
@@ -69,8 +69,8 @@ def test_spheres_and_triangles_with_two_primitive_leaves(renderer):
 @pytest.mark.parametrize("build", [book1, lambda: scenes.mixed_scene(96, 8)], ids=["book1", "mixed"])
 def test_tree_top_in_a_window(renderer, book1_frame, monkeypatch, build):
     """RES_TOP: a window of the tree's top in LDS, the rest and the primitives through L2.  The quiet twin of this kernel
-    measured slower than the counted one on 1M spheres and is not built: launch() must keep such a
-    render on the counted kernel, stats or none, and the frame is the same."""
+    measured slower than the counted one on 1M spheres and is not built: its descriptor names no twin, so
+    launch() must keep such a render on the counted kernel, stats or none, and the frame is the same."""
     for k, v in WINDOW.items():
         monkeypatch.setenv(k, v)
     sc = build()

@@ -4,7 +4,8 @@ the oracle in the same order: images and work counters.
 A kernel is pathtrace_kernel<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN> (or the 6-waves-per-SIMD entry point,
 LATENCY).  The handle's knobs pick RES / SCREEN / LATENCY (they are read in cr_create, so every cell makes a fresh
 Renderer), the scene picks ANIM / CAMK, CrRenderParams.sum_order picks RELAX and the tree mode picks ORD.  SELECTIONS
-below has one row per launch_variant selection of walk_ladder (10 per tree order); CELLS crosses them with the scene kinds and
+below has one row per launch_variant selection of walk_ladder (10 per tree order; launch_variant describes the kernel to the
+unit's one launch<real, RELAX> as a MegaKernel: address, RES, keys, LATENCY); CELLS crosses them with the scene kinds and
 the two orders.  The relaxed ANIM / CAMK cells also render a 3-frame batch (cr_render_frames_host), each frame against
 the relaxed oracle."""
 import collections
