@@ -146,6 +146,14 @@ SYMBOLS = {
                                                 C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_aov_frames_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.c_int32,
                                               C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_views_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.c_int32, C.POINTER(C.c_int32), C.POINTER(CrRenderParams),
+                                           C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_views_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.c_int32, C.POINTER(C.c_int32), C.POINTER(CrRenderParams),
+                                         C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_views_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.c_int32, C.POINTER(C.c_int32), C.POINTER(CrRenderParams),
+                                               C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
+    "cr_render_aov_views_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.c_int32, C.POINTER(C.c_int32), C.POINTER(CrRenderParams),
+                                             C.c_int32, C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_region_device": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.POINTER(CrRegion),
                                             C.c_void_p, C.POINTER(CrStats)]),
     "cr_render_region_host": (C.c_int32, [C.c_void_p, C.POINTER(CrCameraDesc), C.POINTER(CrRenderParams), C.POINTER(CrRegion),

@@ -74,6 +74,8 @@ __global__ void __launch_bounds__(256) aov_counts_finalize_kernel(const unsigned
 // call.counts (cr_render_aov_counts_*; device memory): the samples each pixel takes -- the COUNTS kernels, which are BATCH
 // kernels, so one frame runs as a batch of one; the finalize divides by the pixel's count, and stats->samples is the
 // kernel's own count of the primary rays it cast, since the host does not see the plane.
+// call.views (cr_render_aov_views_*): a batch whose frame k is seen through call.views[k] -- the VIEWS kernels, which are
+// BATCH kernels; prepare_args has packed the views' records and keys.
 template <typename real>
 int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, const RenderCall& call, void* d_out, CrStats* stats) {
     const int32_t* const frames = call.frames;
@@ -83,6 +85,9 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
     bool refit = false;
     int32_t rc = select_tree<real>(h, p, frames != nullptr, &walk, &refit);   // as a render decides it
     if (rc != CR_OK) return rc;
+    if (call.views && refit)
+        return fail(h, CR_ERR_UNSUPPORTED, "cr_render_aov_views cannot refit boxes: refit boxes are per frame, a launch shares one set "
+                                           "(render such views one at a time)");
     if (frames && refit)
         return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames cannot refit boxes: refit boxes are per frame, a batch shares one set "
                                            "(render such frames one at a time)");
@@ -124,7 +129,7 @@ int32_t aov_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* p, 
     HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     if (p->sample_count > 0) {
-        rc = call.counts ? aov_counts_ladder<real>(h, a, ds, w, &res) : aov_ladder<real>(h, a, ds, w, &res);
+        rc = call.views ? aov_views_ladder<real>(h, a, ds, w, &res) : (call.counts ? aov_counts_ladder<real>(h, a, ds, w, &res) : aov_ladder<real>(h, a, ds, w, &res));
         if (rc != CR_OK) return rc;
     }
     const size_t frame_reals = frame_pix * call.layer_channels();

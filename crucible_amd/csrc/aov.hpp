@@ -52,5 +52,8 @@ int32_t aov_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, cons
 // aov_counts_f32.hip, aov_counts_f64.hip: the same ladder over the COUNTS kernels (a.counts is set; a.n_frames >= 1)
 template <typename real>
 int32_t aov_counts_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res);
+// aov_views_f32.hip, aov_views_f64.hip: the same ladder over the VIEWS kernels (a.k.views is set; a.n_frames >= 1)
+template <typename real>
+int32_t aov_views_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res);
 
 }   // namespace cr

@@ -31,9 +31,12 @@ CR_D bool aov_word(double x, double scale, long long& v) {
 // COUNTS (with BATCH only): the kernels of cr_render_aov_counts_* -- pixel p takes the samples [0, n_p), n_p its clamped
 // value of the plane G.counts (aov_counts.hpp has the rules).  A unit reads its tile's sixteen counts, the wave forms
 // their maximum as a scalar, and the group loop ends where that maximum ends: whole rounds disappear, not only lanes.
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS = false>
+// VIEWS (with BATCH only): the kernels of cr_render_aov_views_* -- frame f of the batch is a view whose camera record is
+// A.views[f] (KernelArgs::views), wave-uniform like everything else of the frame.
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS = false, bool VIEWS = false>
 CR_D void aov_body(const AovArgs<real>& G) {
     static_assert(BATCH || !COUNTS, "the COUNTS kernels are BATCH kernels");
+    static_assert(BATCH || !VIEWS, "the VIEWS kernels are BATCH kernels");
     const KernelArgs<real>& A = G.k;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // (the waves' slots behind the scene)
     const SceneStage<real> S = stage_scene<real, RES, ORD, SCREEN>(A);
@@ -110,7 +113,8 @@ CR_D void aov_body(const AovArgs<real>& G) {
             ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.best_t = 0; ws.best = -1; ws.idx = n_entries; ws.exact_box = false; ws.oct = 0; ws.pending = -1;
             bool walking = false;
             if (active) {   // cast_ray's primary ray (the keyed camera is a per-launch, wave-uniform branch of camera_ray)
-                if constexpr (BATCH) camera_ray<real, true>(A, cam_i, cam_j, sample, rng, ro, rd, rtime, frame_time);
+                if constexpr (VIEWS) camera_ray_of<real, true>(A, A.views[frame], cam_i, cam_j, sample, rng, ro, rd, rtime, frame_time);
+                else if constexpr (BATCH) camera_ray<real, true>(A, cam_i, cam_j, sample, rng, ro, rd, rtime, frame_time);
                 else camera_ray<real, true>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
                 c_seg++;
                 walk_begin(ws, rd, tree_walks_exact(A));
@@ -238,9 +242,17 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) aov_counts_kernel(const
     aov_body<real, RES, ANIM, ORD, SCREEN, true, true>(*(const AovArgs<real>*)(const __attribute__((address_space(4))) AovArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
-template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS>
+// The kernels of several cameras in one launch (aov_views_f32.hip, aov_views_f64.hip): kernels of their own, for the same reason
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN>
+__global__ void __launch_bounds__(MaxBlock<real>::value) aov_views_kernel(const AovArgs<real> G) {
+    aov_body<real, RES, ANIM, ORD, SCREEN, true, false, true>(*(const AovArgs<real>*)(const __attribute__((address_space(4))) AovArgs<real>*)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
+template <typename real, int RES, bool ANIM, bool ORD, bool SCREEN, bool BATCH, bool COUNTS, bool VIEWS = false>
 auto aov_kernel_of() -> void (*)(const AovArgs<real>) {
-    if constexpr (COUNTS) return aov_counts_kernel<real, RES, ANIM, ORD, SCREEN>;
+    static_assert(!VIEWS || (BATCH && !COUNTS), "the VIEWS kernels are BATCH kernels without a count plane");
+    if constexpr (VIEWS) return aov_views_kernel<real, RES, ANIM, ORD, SCREEN>;
+    else if constexpr (COUNTS) return aov_counts_kernel<real, RES, ANIM, ORD, SCREEN>;
     else return aov_kernel<real, RES, ANIM, ORD, SCREEN, BATCH>;
 }
 
@@ -280,6 +292,7 @@ int32_t aov_launch(CrHandle* h, void (*kern)(const AovArgs<real>), int res, bool
     uint32_t* const flags = a.flags;
     const real* const times = a.frame_times;
     const int32_t* const counts = a.counts;
+    const CamConst<real>* const views = a.k.views;   // cr_render_aov_views_*: a frame is a view
     for (uint64_t f0 = 0; f0 < n_frames; f0 += per_launch) {
         const uint64_t fn = std::min<uint64_t>(per_launch, n_frames - f0);
         if (batch) {
@@ -288,6 +301,7 @@ int32_t aov_launch(CrHandle* h, void (*kern)(const AovArgs<real>), int res, bool
             a.acc = acc + f0 * npix * kAovWords;
             a.flags = flags + f0 * npix;
             if (counts_plane) a.counts = counts + f0 * npix;
+            if (views) a.k.views = views + f0;
         }
         a.n_units = (uint32_t)(fn * frame_units);
         uint32_t grid = (uint32_t)(h->n_cus * per_cu);
@@ -305,30 +319,30 @@ int32_t aov_launch(CrHandle* h, void (*kern)(const AovArgs<real>), int res, bool
 
 // keyed primitives and leaves that hold a list walk with the ANIM decode (render.hip); a keyed camera needs no kernel of its own here
 // a.n_frames != 0: a batch (cr_render_aov_frames_*), on the BATCH kernels whatever its length
-template <typename real, int RES, bool ORD, bool SCREEN, bool COUNTS = false>
+template <typename real, int RES, bool ORD, bool SCREEN, bool COUNTS = false, bool VIEWS = false>
 int32_t aov_variant(CrHandle* h, AovArgs<real>& a, size_t lds_bytes, const WalkChoice& w, int* res) {
     auto on = [&](auto batch) {
         constexpr bool BATCH = decltype(batch)::value;
-        return aov_launch<real>(h, w.anim ? aov_kernel_of<real, RES, true, ORD, SCREEN, BATCH, COUNTS>() : aov_kernel_of<real, RES, false, ORD, SCREEN, BATCH, COUNTS>(),
+        return aov_launch<real>(h, w.anim ? aov_kernel_of<real, RES, true, ORD, SCREEN, BATCH, COUNTS, VIEWS>() : aov_kernel_of<real, RES, false, ORD, SCREEN, BATCH, COUNTS, VIEWS>(),
                                 RES, BATCH, COUNTS, a, lds_bytes, res);
     };
     // (COUNTS: a.n_frames >= 1, a single frame is a batch of one there, and a COUNTS unit instantiates no other kernel.  The
     // BATCH kernels are named first: a unit emits its kernels in the order it first names them, and the code the compiler
     // makes of a kernel depends on that order -- scripts/isa_diff.py shows it)
-    if constexpr (COUNTS) return on(std::true_type{});
+    if constexpr (COUNTS || VIEWS) return on(std::true_type{});   // (VIEWS: a.n_frames >= 1 as well, and a VIEWS unit instantiates no other kernel)
     else return a.n_frames ? on(std::true_type{}) : on(std::false_type{});
 }
 
 // The guide kernels' residency ladder: the rule walk_ladder asks (residency.hpp), so a guide pass stages what the render
 // stages; the 6-waves-per-SIMD entry point has no counterpart here, so the query's latency inputs stay at never
-template <typename real, bool ORD, bool COUNTS = false>
+template <typename real, bool ORD, bool COUNTS = false, bool VIEWS = false>
 int32_t aov_ladder_ord(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
     const Residency r = choose_residency(residency_query<real, ORD>(h, ds, w));
     a.k.lds_entries = r.lds_entries;
     if (r.lds_side) a.k.lds_side = 1;
     if (r.clear_screen) a.k.screen = nullptr;
     return residency_dispatch<!(ORD && std::is_same<real, float>::value), false>(r, [&](auto rs, auto screen, auto) {
-        return aov_variant<real, decltype(rs)::value, ORD, decltype(screen)::value, COUNTS>(h, a, r.lds_bytes, w, res);
+        return aov_variant<real, decltype(rs)::value, ORD, decltype(screen)::value, COUNTS, VIEWS>(h, a, r.lds_bytes, w, res);
     });
 }
 
@@ -340,6 +354,11 @@ int32_t aov_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, cons
 template <typename real>
 int32_t aov_counts_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
     return ds.ordered ? aov_ladder_ord<real, true, true>(h, a, ds, w, res) : aov_ladder_ord<real, false, true>(h, a, ds, w, res);
+}
+
+template <typename real>
+int32_t aov_views_ladder(CrHandle* h, AovArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, int* res) {
+    return ds.ordered ? aov_ladder_ord<real, true, false, true>(h, a, ds, w, res) : aov_ladder_ord<real, false, false, true>(h, a, ds, w, res);
 }
 
 }   // namespace cr

@@ -60,8 +60,21 @@ int32_t validate_render(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
 // a call with two faults reports the first.  render: frames, n_frames, out, the region's sum order.  guide layers: frames,
 // n_frames, the layer mask, out, the fixed-point refusal; at a count plane after those the plane, then the shard.
 // adaptive: validate_adaptive's (out among them), then frames, n_frames.
+// views (cr_render_views_*, cr_render_aov_views_*): the views' own checks come first -- the table, then each view as a single
+// call of it is checked, then the frame sizes --, and behind the family's checks what a batch of views cannot do.
 static int32_t validate_call(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const RenderCall& call, const void* out,
                              const CrAdaptiveParams* ap) {
+    if (call.views_call) {
+        if (!h) return CR_ERR_INVALID_ARG;
+        if (!call.views) return fail(h, CR_ERR_INVALID_ARG, "cams is null");
+        if (call.n_frames < 1) return fail(h, CR_ERR_INVALID_ARG, "n_views must be at least 1");
+        for (int32_t k = 0; k < call.n_frames; k++) {
+            const int32_t rv = validate_render(h, &call.views[k], p);
+            if (rv != CR_OK) return fail(h, rv, "view " + std::to_string(k) + ": " + h->error);
+            if (call.views[k].image_width != call.views[0].image_width || call.views[k].image_height != call.views[0].image_height)
+                return fail(h, CR_ERR_INVALID_ARG, "view " + std::to_string(k) + ": the views of a call have one image size (view 0's)");
+        }
+    }
     int32_t rc = validate_render(h, cam, p, call.region, call.region_call);
     if (rc != CR_OK) return rc;
     if (call.family == kCallAdaptive && (rc = validate_adaptive(h, p, ap, out, call)) != CR_OK) return rc;
@@ -77,6 +90,13 @@ static int32_t validate_call(CrHandle* h, const CrCameraDesc* cam, const CrRende
     if (call.family == kCallGuideCounts && (p->sample_begin != 0 || p->sample_count != p->samples))
         return fail(h, CR_ERR_UNSUPPORTED, "guide layers at a count plane take a pixel's samples from sample 0 (sample_begin 0, sample_count == samples), "
                                            "as the adaptive calls do");
+    if (call.views_call) {
+        if (call.family == kCallRender && (resolve_sum_order(h, p) != CR_SUM_RELAXED || h->pipeline != 0))
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_views needs CR_SUM_RELAXED and the megakernel pipeline, as cr_render_frames does");
+        int64_t keys = 0;
+        for (int32_t k = 0; k < call.n_frames; k++) keys += (int64_t)call.views[k].from_key_count + call.views[k].at_key_count;
+        if (keys > (int64_t)CrHandle::kMaxCamKeys) return fail(h, CR_ERR_UNSUPPORTED, "more than 512 camera keyframes over all views");
+    }
     if (call.family == kCallRender && call.region_call && (resolve_sum_order(h, p) != CR_SUM_RELAXED || h->pipeline != 0))
         return fail(h, CR_ERR_UNSUPPORTED, "cr_render_region needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
                                            "sequential over samples; the region's offsets live in the relaxed kernels)");
@@ -154,6 +174,9 @@ static int32_t call_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderPar
     CrStats* const into = !call.adaptive ? stats : (run.stats ? &run.stats->render : nullptr);
     if (into) into->nan_pixels = bad;
     if (bad && !call.frames) return fail(h, CR_ERR_NAN, "a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
+    if (bad && call.views)
+        return fail(h, CR_ERR_NAN, "view " + std::to_string(first_bad) + " (frame " + std::to_string(call.frames[first_bad]) +
+                                       "): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
     if (bad)
         return fail(h, CR_ERR_NAN, "frame " + std::to_string(call.frames[first_bad]) + " (entry " + std::to_string(first_bad) +
                                        " of the batch): a pixel mean is NaN or outside [0,1] (the reference panics in Color::new)");
@@ -174,6 +197,8 @@ static int32_t run_call(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
                         const AdaptiveAsk& ask = {}) {
     const int32_t rc = validate_call(h, cam, p, call, out, ask.ap);
     if (rc != CR_OK) return rc;
+    std::vector<int32_t> same_frame;   // a views call without frame indices: params->frame for every view
+    if (call.views_call && !call.frames) { same_frame.assign((size_t)call.n_frames, p->frame); call.frames = same_frame.data(); }
     AdaptiveRun run = {};
     if (call.family == kCallAdaptive) {
         run = {ask.ap->min_samples, ask.ap->pass_samples, ask.ap->block_log2 ? ask.ap->block_log2 : 4, ask.ap->tolerance, ask.counts, ask.stats, call.region != nullptr};
@@ -185,6 +210,10 @@ static int32_t run_call(CrHandle* h, const CrCameraDesc* cam, const CrRenderPara
 // The descriptors the entry points start from: the shape, then the family
 static RenderCall one_frame() { return RenderCall(); }
 static RenderCall batch_of(const int32_t* frames, int32_t n_frames) { RenderCall c; c.frames = frames; c.n_frames = n_frames; c.batch = true; return c; }
+static RenderCall views_of(const CrCameraDesc* cams, int32_t n_views, const int32_t* frames) {   // a batch whose frame k has the camera cams[k]
+    RenderCall c; c.views = cams; c.views_call = true; c.frames = frames; c.n_frames = n_views; return c;
+}
+static const CrCameraDesc* first_view(const CrCameraDesc* cams, int32_t n_views) { return n_views >= 1 ? cams : nullptr; }   // the call's camera: view 0
 static RenderCall region_of(const CrRegion* region) { RenderCall c; c.region = region; c.region_call = true; return c; }
 static RenderCall guide(RenderCall c, int32_t layers) { c.family = kCallGuide; c.layers = layers; return c; }
 static RenderCall guide_at(RenderCall c, int32_t layers, const int32_t* counts) { c.family = kCallGuideCounts; c.layers = layers; c.counts = counts; return c; }
@@ -281,9 +310,9 @@ void cr_destroy(CrHandle* h) {
     delete h;
 }
 
-// The twenty-four render entry points: four families (render, guide layers, adaptive, guide layers at a count plane) in
-// three shapes (one frame, a batch of frames, a region of a frame) into device or host memory -- each a RenderCall and
-// where its results go.
+// The twenty-eight render entry points: four families (render, guide layers, adaptive, guide layers at a count plane) in
+// three shapes (one frame, a batch of frames, a region of a frame) into device or host memory, and the batches of views of
+// the first two families (cr_render_views_*, cr_render_aov_views_*) -- each a RenderCall and where its results go.
 
 int32_t cr_render_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, void* d_out, CrStats* stats) {
     return run_call(h, cam, p, one_frame(), kDevice, d_out, stats);
@@ -301,6 +330,16 @@ int32_t cr_render_frames_device(CrHandle* h, const CrCameraDesc* cam, const CrRe
 int32_t cr_render_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const int32_t* frames, int32_t n_frames,
                               void* h_out, CrStats* stats) {
     return run_call(h, cam, p, batch_of(frames, n_frames), kHost, h_out, stats);
+}
+
+int32_t cr_render_views_device(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames, const CrRenderParams* p,
+                               void* d_out, CrStats* stats) {
+    return run_call(h, first_view(cams, n_views), p, views_of(cams, n_views, frames), kDevice, d_out, stats);
+}
+
+int32_t cr_render_views_host(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames, const CrRenderParams* p,
+                             void* h_out, CrStats* stats) {
+    return run_call(h, first_view(cams, n_views), p, views_of(cams, n_views, frames), kHost, h_out, stats);
 }
 
 int32_t cr_render_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, const CrRegion* region, void* d_out, CrStats* stats) {
@@ -327,6 +366,16 @@ int32_t cr_render_aov_frames_device(CrHandle* h, const CrCameraDesc* cam, const 
 int32_t cr_render_aov_frames_host(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const int32_t* frames, int32_t n_frames,
                                   void* h_out, CrStats* stats) {
     return run_call(h, cam, p, guide(batch_of(frames, n_frames), layers), kHost, h_out, stats);
+}
+
+int32_t cr_render_aov_views_device(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames, const CrRenderParams* p,
+                                   int32_t layers, void* d_out, CrStats* stats) {
+    return run_call(h, first_view(cams, n_views), p, guide(views_of(cams, n_views, frames), layers), kDevice, d_out, stats);
+}
+
+int32_t cr_render_aov_views_host(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames, const CrRenderParams* p,
+                                 int32_t layers, void* h_out, CrStats* stats) {
+    return run_call(h, first_view(cams, n_views), p, guide(views_of(cams, n_views, frames), layers), kHost, h_out, stats);
 }
 
 int32_t cr_render_aov_region_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderParams* p, int32_t layers, const CrRegion* region,

@@ -13,6 +13,9 @@
 //                      one launch<real, RELAX> per unit, which takes its kernel as a MegaKernel descriptor)
 //   aov.hip            the guide pass cr_render_aov_* (aov.hpp): its host side and the finalize kernel
 //   aov_f32.hip, aov_f64.hip   the guide pass's first-hit kernels of one precision (aov_kernel.hpp; one aov_launch<real> per unit)
+//   render_views_f32.hip, render_views_f64.hip   the megakernels of several cameras in one launch, cr_render_views_* (render_views.hpp: their ladder
+//                      over pathtrace_kernel_views; launched by render.hpp's launch<real, true>)
+//   aov_views_f32.hip, aov_views_f64.hip   the first-hit kernels of several cameras in one launch, cr_render_aov_views_* (aov_kernel.hpp's VIEWS axis)
 //   aov_counts_f32.hip, aov_counts_f64.hip   the first-hit kernels at a count plane, cr_render_aov_counts_* (aov_kernel.hpp's COUNTS axis; aov_counts.hpp: its integer rules)
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
 //   adaptive.hip       the adaptive family behind its entry points: its argument checks, the pass loop, the judge and finalize kernels (adaptive.hpp)
@@ -156,7 +159,8 @@ struct CrHandle {
     DevBuf ad_acc, ad_lists, ad_block_n, ad_ctrl, ad_counts;
     hipEvent_t ad_ev0 = nullptr, ad_ev1 = nullptr;
     // cr_render_frames_*: a batch's per-frame ray times travel through one pinned host buffer, refilled only after the
-    // previous batch's copy has run (times_ev); the device table is reused in stream order
+    // previous batch's copy has run (times_ev); the device table is reused in stream order.  cr_render_views_*: the views'
+    // camera records (CamConst, one per view) follow the times in the same table, at the next multiple of 16 bytes
     void* times_host = nullptr;
     size_t times_cap = 0;
     DevBuf times_dev;
@@ -296,6 +300,9 @@ struct RenderCall {
     CallFamily family = kCallRender;          // the entry point's: the checks ask before `layers` and `adaptive` can tell
     int32_t layers = 0;                       // the guide pass's CR_AOV_* mask; 0: a render
     const AdaptiveRun* adaptive = nullptr;    // a render to a noise target (adaptive.hip); nullptr: all samples of every pixel
+    const CrCameraDesc* views = nullptr;      // cr_render_views_* / cr_render_aov_views_*: one camera per frame of the batch (n_frames of them, `frames` their
+                                              // frame indices); nullptr: every frame through the call's one camera
+    bool views_call = false;                  // the entry point is a views call: the checks ask, `views` may be null
     const int32_t* counts = nullptr;          // kCallGuideCounts: the samples each pixel takes, laid out as the adaptive sibling writes its counts;
                                               // device memory once call_device runs (call_host stages the caller's plane)
     bool guide() const { return family == kCallGuide || family == kCallGuideCounts; }
@@ -409,6 +416,9 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
 // render_f32_reference.hip, render_f32_relaxed.hip, render_f64_reference.hip, render_f64_relaxed.hip (render.hpp)
 template <typename real, bool ORD, bool RELAX>
 int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb);
+// render_views_f32.hip, render_views_f64.hip (render_views.hpp): the same ladder over the VIEWS kernels (a.views is set)
+template <typename real, bool ORD>
+int32_t views_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, const WalkChoice& w, CrStats* stats, const FrameBatch<real>& fb);
 template <typename real>   // the relaxed units: fixed-point sums -> means (or raw sums) of `count` samples
 int32_t fx_finalize(CrHandle* h, const unsigned long long* sums, real* out, size_t n, double inv_scale, double count, int32_t output_sum);
 // alt_pipelines.hip

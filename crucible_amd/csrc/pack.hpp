@@ -6,7 +6,9 @@
 #include "../../include/crucible_hip.h"
 #include "pathtrace.hpp"
 #include "scene_checks.hpp"
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
@@ -117,6 +119,30 @@ template <typename real> void pack_camera_frame(CamConst<real>& c) {
     CamFrame<real> f = camera_frame(c, from, at);
     if (!c.animated) c.from = f.from;
     c.p00 = f.p00; c.pdu = f.pdu; c.pdv = f.pdv; c.ddu = f.ddu; c.ddv = f.ddv;
+}
+
+// cr_render_views_*: the records of n cameras that share one key table -- view k's look_from keys, then its look_at keys,
+// behind those of the views before it, so its *_key_first count from the table's start.  Each record is otherwise what
+// pack_camera and pack_camera_frame make of the camera alone.  Returns the keys of all views together.
+template <typename real> int64_t pack_views(const CrCameraDesc* cams, int32_t n, CamConst<real>* table) {
+    int64_t first = 0;
+    for (int32_t k = 0; k < n; k++) {
+        CamConst<real>& c = table[k];
+        pack_camera(&cams[k], c);
+        // (a table longer than the key slot is refused by the caller: the offsets only need to stay defined up to there)
+        c.from_key_first = (int32_t)std::min<int64_t>(first, INT32_MAX);
+        c.at_key_first = (int32_t)std::min<int64_t>(first + cams[k].from_key_count, INT32_MAX);
+        first += (int64_t)cams[k].from_key_count + cams[k].at_key_count;
+        pack_camera_frame(c);
+    }
+    return first;
+}
+// ... and the table itself: dst receives the keys in that order
+template <typename real> void pack_view_keys(const CrCameraDesc* cams, int32_t n, Key<real>* dst) {
+    for (int32_t k = 0; k < n; k++) {
+        for (int i = 0; i < cams[k].from_key_count; i++) key_to_real(cams[k].from_keys[i], *dst++);
+        for (int i = 0; i < cams[k].at_key_count; i++) key_to_real(cams[k].at_keys[i], *dst++);
+    }
 }
 
 // The frame's ray times [current_time, current_time + shutter_length] in `real` (ray_casting.rs:77-79).

@@ -360,9 +360,17 @@ template <typename real> struct KernelArgs {
     // 1/direction: walk_begin's exact_box.  Read by the f32 kernels alone (tree_walks_exact); the word follows the record's
     // last one, so no other argument moved.
     int32_t exact_boxes;
+    // Several cameras in one launch (cr_render_views_*, the VIEWS kernels): view f of the launch -- frame f of
+    // the batch's work layout above -- takes its camera from views[f] instead of `cam`, a record packed as `cam` is, whose
+    // *_key_first count from the start of cam_keys (the views' keys lie there one view after the other).  `cam` holds view 0's
+    // record: every view has its W and H.  Read by the VIEWS kernels alone; the word follows the record's last one, so no
+    // other argument moved.
+    const CamConst<real>* views;
 };
-static_assert(sizeof(KernelArgs<float>) == 496 && sizeof(KernelArgs<double>) == 616 && offsetof(KernelArgs<float>, tile_list) == 480 &&
-              offsetof(KernelArgs<double>, tile_list) == 600, "the region's words fill padding, the tile list and exact_boxes follow the record");
+static_assert(sizeof(KernelArgs<float>) == 504 && sizeof(KernelArgs<double>) == 624 && offsetof(KernelArgs<float>, tile_list) == 480 &&
+              offsetof(KernelArgs<double>, tile_list) == 600 && offsetof(KernelArgs<float>, exact_boxes) == 488 && offsetof(KernelArgs<double>, exact_boxes) == 608 &&
+              offsetof(KernelArgs<float>, views) == 496 && offsetof(KernelArgs<double>, views) == 616,
+              "the region's words fill padding, the tile list, exact_boxes and the views' table follow the record");
 static_assert(offsetof(KernelArgs<float>, work_counter) == 304 && offsetof(KernelArgs<float>, out) == 368 && offsetof(KernelArgs<float>, fx_acc) == 408 &&
               offsetof(KernelArgs<float>, fd_tiles_y) == 464, "the region's words fill padding: no argument moved");
 template <typename real> inline void set_tiles(KernelArgs<real>& a, uint32_t tiles_x, uint32_t tiles_y) {
@@ -927,10 +935,11 @@ template <typename real> CR_D void random_in_unit_disk_dev(uint64_t& s, real& px
 // (the teapot orbit frame: +6.5 % in f64 over running it on the ANIM kernels; folding the camera code into the plain
 // static kernels instead cost book1 0.9 % f64 / 1.8 % f32, so it is a variant of its own).
 // `current_time`: the frame's first ray time (a frame of a batch has its own; pix_j is then the row within that frame).
+// camera_ray_of: the same through a camera record of the caller's choice -- the launch's own, or a view's (KernelArgs::views:
+// the record may then differ from lane to lane, and with it cam.animated, cam.defocus_on and the key counts).
 template <typename real, bool ANIM, bool CAMK = false>
-CR_D void camera_ray(const KernelArgs<real>& A, uint32_t pix_i, uint32_t pix_j, int32_t sample, uint64_t& rng, V3<real>& ro, V3<real>& rd,
-                     real& rtime, real current_time) {
-    const CamConst<real>& cam = A.cam;
+CR_D void camera_ray_of(const KernelArgs<real>& A, const CamConst<real>& cam, uint32_t pix_i, uint32_t pix_j, int32_t sample, uint64_t& rng, V3<real>& ro,
+                        V3<real>& rd, real& rtime, real current_time) {
     uint32_t pixel = pix_j * (uint32_t)cam.W + pix_i;
     rng = rng_key(A.seed_mixed, pixel, (uint32_t)sample);
     real ts = current_time + rng_range<real>(rng, real(0), A.shutter_length);
@@ -954,6 +963,11 @@ CR_D void camera_ray(const KernelArgs<real>& A, uint32_t pix_i, uint32_t pix_j, 
         orig = add(add(f.from, scale(px, f.ddu)), scale(py, f.ddv));
     }
     ro = orig; rd = sub(ps, orig); rtime = ts;
+}
+template <typename real, bool ANIM, bool CAMK = false>
+CR_D void camera_ray(const KernelArgs<real>& A, uint32_t pix_i, uint32_t pix_j, int32_t sample, uint64_t& rng, V3<real>& ro, V3<real>& rd,
+                     real& rtime, real current_time) {
+    camera_ray_of<real, ANIM, CAMK>(A, A.cam, pix_i, pix_j, sample, rng, ro, rd, rtime, current_time);
 }
 template <typename real, bool ANIM, bool CAMK = false>
 CR_D void camera_ray(const KernelArgs<real>& A, uint32_t pix_i, uint32_t pix_j, int32_t sample, uint64_t& rng, V3<real>& ro, V3<real>& rd,
@@ -1861,10 +1875,15 @@ template <typename real> CR_D const KernelArgs<real>& kernel_args() {
 // (profiles/experiments/adaptive_sampling.txt), so it has kernels of its own and every other kernel compiles to what it was.
 // COUNT: the body keeps the four work counters and adds them to KernelArgs::counters at its end.  Only pathtrace_kernel_quiet
 // passes false: its launches are the renders whose caller asked for no stats (render.hpp launch()).
-template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true, bool LIST = false, bool COUNT = true>
+// VIEWS: a frame of the batch is a view with a camera of its own (KernelArgs::views, cr_render_views_*).  Only
+// pathtrace_kernel_views passes true: the camera record becomes a per-lane read from global memory, so every other kernel
+// keeps its camera in the kernarg segment and compiles to what it was.
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK = false, bool RELAX = false, bool SCREEN = false, bool REG = true, bool LIST = false, bool COUNT = true,
+          bool VIEWS = false>
 CR_D void pathtrace_body(const KernelArgs<real>& A) {
     constexpr bool BATCH = RELAX && (ANIM || CAMK);
     constexpr bool REGION = BATCH && REG;
+    static_assert(!VIEWS || REGION, "the views' kernels are batch kernels");
     // REGION: the region's words (reg_x0 .. reg_h) are read through the kernarg segment where they are used, also in the
     // kernels that keep the by-value parameter: there they would be four more scalars alive for the whole launch
     const KernelArgs<real>& RG = kernel_args<real>();
@@ -2060,6 +2079,10 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
             CR_DIAG_HIT(dgp, DG_REGEN_WAVE, DG_REGEN_LANE);
             if constexpr (BATCH) {   // a frame of a batch: its own row and its own ray times; a region: the frame's own pixel, as one integer
                 const uint32_t f = batch_frame(A, REGION ? pix_j - RG.reg_y0 : pix_j);
+                if constexpr (VIEWS)   // the lane's view: its camera record, read where camera_ray uses it
+                    camera_ray_of<real, ANIM, CAMK>(A, RG.views[f], pix_i, pix_j - f * (A.tiles_y << A.sg_lh), sample, rng, ro, rd, rtime,
+                                                    A.n_frames > 1u ? A.frame_times[f] : A.current_time);
+                else
                 camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j - f * (A.tiles_y << A.sg_lh), sample, rng, ro, rd, rtime,
                                              A.n_frames > 1u ? A.frame_times[f] : A.current_time);
             } else camera_ray<real, ANIM, CAMK>(A, pix_i, pix_j, sample, rng, ro, rd, rtime);
@@ -2214,6 +2237,15 @@ __global__ void __launch_bounds__(MaxBlock<real>::value) pathtrace_kernel_listed
     static_assert(ANIM != CAMK, "keyed primitives or camera keys alone, as for pathtrace_kernel");
     if constexpr (std::is_same<real, double>::value || RES != RES_LDS) pathtrace_body<real, RES, ANIM, ORD, CAMK, true, SCREEN, true, true>(kernel_args<real>());
     else pathtrace_body<real, RES, ANIM, ORD, CAMK, true, SCREEN, true, true>(A);
+}
+
+// cr_render_views_* (DESIGN.md 6.18): the keyed RELAX kernel whose frames are views, each with its camera record in
+// KernelArgs::views.  Kernels of their own (render_views_f32.hip, render_views_f64.hip), for the reason the listed ones are.
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK, bool SCREEN = false>
+__global__ void __launch_bounds__(MaxBlock<real>::value) pathtrace_kernel_views(const KernelArgs<real> A) {
+    static_assert(ANIM != CAMK, "keyed primitives or camera keys alone, as for pathtrace_kernel");
+    if constexpr (std::is_same<real, double>::value || RES != RES_LDS) pathtrace_body<real, RES, ANIM, ORD, CAMK, true, SCREEN, true, false, true, true>(kernel_args<real>());
+    else pathtrace_body<real, RES, ANIM, ORD, CAMK, true, SCREEN, true, false, true, true>(A);
 }
 
 // The same kernel compiled for 6 waves per SIMD (<= 80 VGPRs, 512-thread groups), for trees far larger than the

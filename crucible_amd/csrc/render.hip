@@ -47,6 +47,7 @@ int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_lar
 }
 
 // cr_render_frames_*: the batch's ray times through the handle's pinned staging buffer into its device table
+// (cr_render_views_*: the views' camera records behind the times, one table)
 int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
     if (h->times_ev) HIP_TRY(h, hipEventSynchronize(h->times_ev));   // the previous batch's copy has read the staging buffer
     else HIP_TRY(h, hipEventCreateWithFlags(&h->times_ev, hipEventDisableTiming));
@@ -84,10 +85,15 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     a.sky_kind = h->sky_kind; a.sky_image = h->sky_image;
 
     // camera set-up (pack.hpp)
+    // (cr_render_views_*: cd is view 0, whose record a.cam holds for the frame's size; the views' records go into a table of
+    // their own and their keys one view after the other into the one slot -- pack.hpp pack_views)
     CamConst<real>& c = a.cam;
     pack_camera(cd, c);
-    int nk = cd->from_key_count + cd->at_key_count;
-    if ((size_t)nk > CrHandle::kMaxCamKeys) return fail(h, CR_ERR_UNSUPPORTED, "more than 512 camera keyframes");
+    int64_t nk = (int64_t)cd->from_key_count + cd->at_key_count;
+    std::vector<CamConst<real>> views;
+    if (call.views) { views.resize((size_t)call.n_frames); nk = pack_views(call.views, call.n_frames, views.data()); }
+    if (nk > (int64_t)CrHandle::kMaxCamKeys)
+        return fail(h, CR_ERR_UNSUPPORTED, call.views ? "more than 512 camera keyframes over all views" : "more than 512 camera keyframes");
     a.cam_keys = nullptr;
     if (nk > 0) {   // per-launch slot: never overwritten while an earlier render may still read it
         const int slot = h->cam_next;
@@ -108,8 +114,8 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
             h->cam_host[slot] = host; h->cam_ev[slot] = ev;
         } else HIP_TRY(h, hipEventSynchronize(h->cam_ev[slot]));   // the slot's previous user has finished with it
         Key<real>* ck = (Key<real>*)h->cam_host[slot];
-        for (int i = 0; i < cd->from_key_count; i++) key_to_real(cd->from_keys[i], ck[i]);
-        for (int i = 0; i < cd->at_key_count; i++) key_to_real(cd->at_keys[i], ck[cd->from_key_count + i]);
+        if (call.views) pack_view_keys(call.views, call.n_frames, ck);
+        else pack_view_keys(cd, 1, ck);
         HIP_TRY(h, hipMemcpyAsync(h->cam_dev[slot].p, ck, nk * sizeof(Key<real>), hipMemcpyHostToDevice, h->stream));
         a.cam_keys = (const Key<real>*)h->cam_dev[slot].p;
         h->cam_pending_slot = slot;
@@ -128,10 +134,18 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
         times.resize((size_t)call.n_frames);
         CrRenderParams q = *p;
         for (int32_t k = 0; k < call.n_frames; k++) { q.frame = frames[k]; frame_times(&q, times[(size_t)k], a.shutter_length); }
-        int32_t rc = stage_frame_times(h, times.data(), times.size() * sizeof(real));
+        // (cr_render_views_*: one table, the views' camera records behind the times at the next multiple of 16 bytes)
+        const size_t time_bytes = times.size() * sizeof(real), views_at = (time_bytes + 15) & ~(size_t)15;
+        std::vector<char> table(call.views ? views_at + views.size() * sizeof(CamConst<real>) : 0);
+        if (call.views) {
+            memcpy(table.data(), times.data(), time_bytes);
+            memcpy(table.data() + views_at, views.data(), views.size() * sizeof(CamConst<real>));
+        }
+        int32_t rc = call.views ? stage_frame_times(h, table.data(), table.size()) : stage_frame_times(h, times.data(), time_bytes);
         if (rc != CR_OK) return rc;
         a.current_time = times[0];
         fb.n = call.n_frames; fb.times = times.data(); fb.d_times = (const real*)h->times_dev.p;
+        if (call.views) a.views = (const CamConst<real>*)((const char*)h->times_dev.p + views_at);
     }
     if (refit) {   // refit.hpp: wrapper boxes for this frame's ray times [current_time, current_time + shutter_length]
         const size_t bytes = (size_t)ds.n_entries * ds.entry_bytes;
@@ -193,6 +207,9 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     if (fixed && (sum_order != CR_SUM_RELAXED || h->pipeline != 0))
         return fail(h, CR_ERR_UNSUPPORTED, "CR_OUTPUT_FIXED_SUM needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is sequential over samples)");
     if (call.frames) {
+        if (call.views && refit)
+            return fail(h, CR_ERR_UNSUPPORTED, "cr_render_views cannot refit boxes: refit boxes are per frame, a launch shares one set "
+                                               "(render such views one at a time)");
         if (sum_order != CR_SUM_RELAXED || h->pipeline != 0)
             return fail(h, CR_ERR_UNSUPPORTED, "cr_render_frames needs CR_SUM_RELAXED and the megakernel pipeline (a reference-order sum is "
                                                "sequential over samples and would need a per-sample buffer per frame)");
@@ -223,6 +240,8 @@ int32_t render_typed(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
     const size_t fx_need = relax ? fx_lds_bytes(MaxBlock<real>::value, 4) : 0;   // the relaxed sums' slots share the LDS
     w.screen_lds = w.screen && h->screen_lds && w.lds_all_screen + fx_need <= h->lds_limit;
     w.plain_lds = ds.lds_bytes + fx_need <= h->lds_limit;
+    // cr_render_views_*: the kernels that read a camera record per view (render_views.hpp; relaxed sums, the megakernel)
+    if (call.views) return ds.ordered ? views_ladder<real, true>(h, a, ds, w, stats, fb) : views_ladder<real, false>(h, a, ds, w, stats, fb);
     if (ds.ordered) {   // near-child-first walk: megakernel only
         if (h->pipeline != 0) return fail(h, CR_ERR_UNSUPPORTED, "CR_BVH_SAH_ORDERED is implemented by the megakernel pipeline only");
         return relax ? walk_ladder<real, true, true>(h, a, ds, w, stats, fb) : walk_ladder<real, true, false>(h, a, ds, w, stats, fb);

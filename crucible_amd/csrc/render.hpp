@@ -186,6 +186,7 @@ int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& a
     } else {
         args.sample_buf = (real*)h->sample_buf.p;
         unsigned long long* const fx_frame0 = args.fx_acc;
+        const CamConst<real>* const views0 = args.views;   // cr_render_views_*: a frame is a view, its camera record travels with it
         for (int32_t f0 = 0; f0 < fb.n; f0 += fpl) {   // one pass for a single render
             const int32_t fn = std::min(fpl, fb.n - f0);
             if constexpr (RELAX) {   // frames [f0, f0 + fn) of a batch
@@ -193,6 +194,7 @@ int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& a
                 args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
                 args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
                 args.fx_acc = fx_frame0 + (size_t)f0 * npix * 3;
+                if (views0) args.views = views0 + f0;
             }
             for (int64_t b0 = s_begin; b0 < s_end; b0 += batch) {   // (64 bits: b0 + batch may pass INT32_MAX)
                 const int32_t b1 = (int32_t)std::min<int64_t>(s_end, b0 + batch);

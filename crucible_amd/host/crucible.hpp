@@ -629,8 +629,8 @@ public:
     int sum_order = CR_SUM_DEFAULT;    // CrRenderParams.sum_order
     static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-    CrCameraDesc camera_desc(std::vector<CrKeyframe>& fk, std::vector<CrKeyframe>& ak) const {
-        const Camera& c = scene_cam;
+    CrCameraDesc camera_desc(std::vector<CrKeyframe>& fk, std::vector<CrKeyframe>& ak) const { return camera_desc(scene_cam, fk, ak); }
+    static CrCameraDesc camera_desc(const Camera& c, std::vector<CrKeyframe>& fk, std::vector<CrKeyframe>& ak) {
         fk = c.look_from_tl.keyframes(); ak = c.look_at_tl.keyframes();
         return CrCameraDesc{c.image_width, c.image_height, c.vfov_degrees, c.defocus_angle_degrees, c.focus_dist,
                             {c.look_from_tl.start_pos.x, c.look_from_tl.start_pos.y, c.look_from_tl.start_pos.z},
@@ -667,6 +667,28 @@ public:
         CrRenderParams p = render_params(0);   // the frame indices come from frs
         buf.resize((size_t)scene_cam.image_width * scene_cam.image_height * 3 * frs.size());
         return cr_render_frames_host(h, &cd, &p, frs.data(), (int32_t)frs.size(), buf.data(), stats);
+    }
+    // The cameras `cams` of this scene in one call (cr_render_views_host): view k at k * W*H*3 reals of `real_type` in `buf`,
+    // at frame frs[k] (frs empty: scene_cam.frame for every view).  Image size, samples, depth, frame rate and shutter are
+    // scene_cam's; a view whose size differs is refused by the library.
+    struct ViewTable {   // the descriptors of a views call and the key arrays they point into
+        std::vector<std::vector<CrKeyframe>> fk, ak;
+        std::vector<CrCameraDesc> desc;
+        explicit ViewTable(const std::vector<Camera>& cams) : fk(cams.size()), ak(cams.size()) {
+            for (size_t k = 0; k < cams.size(); k++) desc.push_back(camera_desc(cams[k], fk[k], ak[k]));
+        }
+    };
+    int32_t render_views(CrHandle* h, std::vector<double>& buf, const std::vector<Camera>& cams, const std::vector<int32_t>& frs, CrStats* stats) const {
+        const ViewTable t(cams);
+        CrRenderParams p = render_params((size_t)scene_cam.frame);
+        buf.resize(std::max<size_t>(1, (size_t)scene_cam.image_width * scene_cam.image_height * 3 * cams.size()));
+        return cr_render_views_host(h, t.desc.data(), (int32_t)cams.size(), frs.empty() ? nullptr : frs.data(), &p, buf.data(), stats);
+    }
+    // Their guide layers in one call (cr_render_aov_views_host): view k at k * aov_reals() reals in `planes`
+    int32_t render_aov_views(CrHandle* h, void* planes, const std::vector<Camera>& cams, const std::vector<int32_t>& frs, CrStats* stats = nullptr) const {
+        const ViewTable t(cams);
+        CrRenderParams p = render_params((size_t)scene_cam.frame);
+        return cr_render_aov_views_host(h, t.desc.data(), (int32_t)cams.size(), frs.empty() ? nullptr : frs.data(), &p, aov_layers, planes, stats);
     }
     // The frames `frs` to the noise target in one call (cr_render_adaptive_frames_host): frame k at k * W*H*3 reals in `buf`,
     // its counts at k * W*H in `counts`; the call's stats stay in adaptive_stats.

@@ -278,6 +278,60 @@ class Renderer:
         st = self._call("cr_render_aov_frames_device", args, aov_mask(layers), fr_ptr, fr.size, C.c_void_p(d_ptr), want_stats=want_stats)
         return st.as_dict() if want_stats else None
 
+    def _views_call(self, name, cams, frames, params_of, *rest, want_stats):
+        """The views entry point `name` with (handle, the cameras' descriptors, their number, frames or a null pointer, the
+        params of cams[0], *rest, stats or a null pointer), checked.  Returns the stats struct."""
+        descs, keep = view_table(cams)
+        fr, fr_ptr = frame_list(frames)
+        p = params_of(cams[0]) if cams else None
+        st = A.CrStats()
+        self._check(getattr(self.lib, name)(self.h, descs, len(cams) if cams is not None else 0, fr_ptr, C.byref(p) if p is not None else None, *rest,
+                                            C.byref(st) if want_stats else None))
+        del keep
+        return st
+
+    def render_views(self, cams, frames=None, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                     output_sum=False, want_stats=True, sum_order=None):
+        """cr_render_views_host: the cameras `cams` (one image size; samples, depth, frame rate and shutter are cams[0]'s) in
+        one launch, as a (V, H, W, 3) host array shaped like render_frames'.  frames: one frame index per view, None: cams[0].frame
+        for every view.  View k equals render() of cams[k] at frame frames[k] bit for bit.  Needs CR_SUM_RELAXED.  Returns
+        (views array, stats dict of the whole call)."""
+        n = len(cams) if cams else 0
+        H, W = (cams[0].image_height, cams[0].image_width) if n else (1, 1)
+        out, _ = frame_arrays((max(1, n), H, W), out_dtype(output_sum, real_type))
+        params = lambda c: c.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
+        st = self._views_call("cr_render_views_host", cams, frames, params, host_ptr(out), want_stats=want_stats)
+        return out, st.as_dict()
+
+    def render_views_device(self, cams, d_ptr, frames=None, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None,
+                            output_sum=False, want_stats=False, sum_order=None):
+        """cr_render_views_device: view after view into device memory at `d_ptr` (V*W*H*3 reals, or uint64 words with
+        output_sum=A.CR_OUTPUT_FIXED_SUM).  Asynchronous unless want_stats."""
+        params = lambda c: c.params(seed, real_type, sample_begin, sample_count, output_sum, self.sum_order if sum_order is None else sum_order)
+        st = self._views_call("cr_render_views_device", cams, frames, params, C.c_void_p(d_ptr), want_stats=want_stats)
+        return st.as_dict() if want_stats else None
+
+    def render_aov_views(self, cams, frames=None, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32, sample_begin=0,
+                         sample_count=None, output_sum=False, want_stats=True):
+        """cr_render_aov_views_host: the guide layers `layers` of the cameras `cams` in one launch.  Returns (list of per-view
+        dicts shaped like render_aov's, stats dict of the whole call); view k equals render_aov() of cams[k] at frame
+        frames[k] bit for bit."""
+        layers = aov_mask(layers)
+        n = len(cams) if cams else 0
+        H, W = (cams[0].image_height, cams[0].image_width) if n else (1, 1)
+        buf, planes = guide_buffer(layers, real_type, W, H, n)
+        params = lambda c: c.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        st = self._views_call("cr_render_aov_views_host", cams, frames, params, layers, host_ptr(buf), want_stats=want_stats)
+        return [guide_planes(buf, planes, W, H, k) for k in range(n)], st.as_dict()
+
+    def render_aov_views_device(self, cams, d_ptr, frames=None, layers=A.CR_AOV_ALL, *, seed, real_type=A.CR_REAL_F32,
+                                sample_begin=0, sample_count=None, output_sum=False, want_stats=False):
+        """cr_render_aov_views_device: view after view into device memory at `d_ptr`, each view's requested planes one after
+        the other in ascending bit order.  Asynchronous unless want_stats."""
+        params = lambda c: c.params(seed, real_type, sample_begin, sample_count, output_sum, A.CR_SUM_DEFAULT)
+        st = self._views_call("cr_render_aov_views_device", cams, frames, params, aov_mask(layers), C.c_void_p(d_ptr), want_stats=want_stats)
+        return st.as_dict() if want_stats else None
+
     def render_region(self, cam, region, *, seed, real_type=A.CR_REAL_F32, sample_begin=0, sample_count=None, output_sum=False,
                       want_stats=True, sum_order=None):
         """cr_render_region_host: the pixels `region` = (x0, y0, w, h) of the frame `cam` describes, as an (h, w, 3) host
@@ -661,6 +715,18 @@ def frame_list(frames):
         return np.zeros(0, dtype=np.int32), None
     fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
     return fr, fr.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def view_table(cams):
+    """(contiguous CrCameraDesc array of the cameras `cams`, what keeps its key arrays alive); None or an empty list stays a
+    null pointer (the library refuses it)."""
+    if not cams:
+        return None, None
+    descs = [c.desc() for c in cams]
+    table = (A.CrCameraDesc * len(descs))()
+    for k, d in enumerate(descs):
+        C.memmove(C.byref(table, k * C.sizeof(A.CrCameraDesc)), C.byref(d), C.sizeof(A.CrCameraDesc))
+    return table, descs
 
 
 def region_arg(region):

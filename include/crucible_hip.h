@@ -515,6 +515,55 @@ CR_API int32_t cr_render_aov_frames_host(CrHandle* h, const CrCameraDesc* cam, c
                                          const int32_t* frames, int32_t n_frames, void* h_out, CrStats* stats);
 
 /*
+ * Several cameras of one scene in one launch: the views cams[0..n_views-1] under one set of params -- a stereo pair,
+ * the faces of a cube map, a turntable, a movie whose camera zooms, pulls focus, rolls or follows a path sampled on the
+ * host.  Where a batch of frames (cr_render_frames_*) may differ only in its ray times, the views of a call may differ
+ * in everything a CrCameraDesc holds but the image size: vfov_degrees, defocus_angle_degrees, focus_dist, look_from,
+ * look_at, vup and the look_from / look_at keys, whose numbers may differ from view to view too.  frames[k] is the frame
+ * index params->frame would carry for view k; frames == NULL: params->frame for every view.  The output holds n_views
+ * consecutive views, view k at k * image_width*image_height*3 elements, laid out as cr_render_frames_device lays out
+ * frames (reals for output_sum 0 and 1, uint64_t words for CR_OUTPUT_FIXED_SUM).
+ *
+ * View k is bit for bit what cr_render_device writes for cams[k] and params with frame = frames[k], in f32 and f64, for
+ * every output_sum, every sample_begin / sample_count, every bvh_mode and every residency of the scene; a repeated view
+ * gives the same bytes twice, and a call of one view the single call's bytes and counters.  `stats` covers the whole
+ * call: the counters and `samples` summed over the views, one kernel_ms.
+ *
+ * CR_ERR_INVALID_ARG: a null `cams`, n_views < 1, a view whose image_width / image_height differ from view 0's, and
+ * whatever cr_render_device rejects for any one view (the message names the first such view).  CR_ERR_UNSUPPORTED, as
+ * for cr_render_frames_*: a sum order other than CR_SUM_RELAXED (after CR_SUM_DEFAULT / CRUCIBLE_SUM_ORDER are
+ * resolved), a pipeline other than the megakernel, a call that would refit or rebuild boxes, and more than 512 camera
+ * keyframes over all views together (the views' keys share the one table a single camera's keys have).  Everything is
+ * checked before anything changes: a refused call leaves the handle as it was.
+ * The handle keeps fixed-point sums for all views (24 bytes per pixel per view) and one camera record per view.  A
+ * call that would overflow the 32-bit work counter runs as several launches of whole views; a view that alone needs
+ * sample batches runs view by view.  Asynchronous unless `stats` is non-NULL, like cr_render_device.
+ */
+CR_API int32_t cr_render_views_device(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames,
+                                      const CrRenderParams* params, void* d_out, CrStats* stats);
+
+/* Same, into a HOST buffer of n_views views (synchronous).  The Color::new check of cr_render_host applies view by
+ * view; CR_ERR_NAN's message names the first view that fails it (stats->nan_pixels counts all views). */
+CR_API int32_t cr_render_views_host(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames,
+                                    const CrRenderParams* params, void* h_out, CrStats* stats);
+
+/*
+ * The guide layers of several cameras in one launch: what cr_render_views_* is to cr_render_device, for
+ * cr_render_aov_device.  The output holds n_views consecutive views, view k at k * R reals, each laid out as
+ * cr_render_aov_frames_device lays out a frame.  View k is bit for bit what cr_render_aov_device writes for cams[k],
+ * params and `layers` with frame = frames[k] (frames == NULL: params->frame).  Like cr_render_aov_frames_* it takes every
+ * sum order and pipeline; CR_OUTPUT_FIXED_SUM, a call that would refit or rebuild boxes and more than 512 camera
+ * keyframes over all views are CR_ERR_UNSUPPORTED, the arguments' refusals those of cr_render_views_* (and layers == 0
+ * or an unknown bit: CR_ERR_INVALID_ARG).  `stats` covers the whole call.  Asynchronous unless `stats` is non-NULL.
+ */
+CR_API int32_t cr_render_aov_views_device(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames,
+                                          const CrRenderParams* params, int32_t layers, void* d_out, CrStats* stats);
+
+/* Same, into a HOST buffer of n_views views (synchronous). */
+CR_API int32_t cr_render_aov_views_host(CrHandle* h, const CrCameraDesc* cams, int32_t n_views, const int32_t* frames,
+                                        const CrRenderParams* params, int32_t layers, void* h_out, CrStats* stats);
+
+/*
  * A region of a frame: the pixels [x0, x0 + width) x [y0, y0 + height) of the frame that `cam` describes.
  * cam->image_width / image_height stay the WHOLE frame's: they define the viewport, the pixel deltas and the RNG's
  * pixel index (y0 + j) * image_width + (x0 + i).  The output holds the region only: width*height*3 reals, row-major
