@@ -14,13 +14,14 @@
 #pragma once
 #include "handle.hpp"
 #include "aov_counts.hpp"
+#include "launch_plan.hpp"   // aov_lds_bytes, the guide pass's unit plan
 
 namespace cr {
 
 constexpr uint32_t kAovWords = 8, kAovDepth = 7, kAovCoverage = 6;
 constexpr uint32_t kAovTileLog2 = 4;                                            // 4 x 4 pixels
 constexpr uint32_t kAovSlotWords = kAovWords << kAovTileLog2;                   // one wave's LDS slot
-constexpr size_t aov_lds_bytes(int block) { return (size_t)(block / 64) * kAovSlotWords * sizeof(unsigned long long); }
+static_assert(kAovSlotBytes == kAovSlotWords * sizeof(unsigned long long), "aov_lds_bytes (launch_plan.hpp) counts this slot");
 
 template <typename real> struct AovArgs {
     KernelArgs<real> k;             // what the walk, the camera and the texture code read (prepare_args, render.hip)

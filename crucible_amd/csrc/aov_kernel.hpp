@@ -3,7 +3,8 @@
 // smaller body -- a primary ray per work item, its closest hit, four values, no path state.  Included by aov_f32.hip
 // and aov_f64.hip, each of which instantiates aov_ladder for its precision, and by aov_counts_f32.hip and aov_counts_f64.hip,
 // which instantiate aov_counts_ladder (the kernels at a count plane), so no kernel is emitted twice.  Which
-// kernel runs -- the scene's residency, screening records or wrappers -- is residency.hpp's rule, the render's own.
+// kernel runs -- the scene's residency, screening records or wrappers -- is residency.hpp's rule, the render's own; how
+// a pass is cut into units and launches is launch_plan.hpp's, and aov_launch keeps the HIP calls.
 #pragma once
 #include "aov.hpp"
 
@@ -259,10 +260,10 @@ auto aov_kernel_of() -> void (*)(const AovArgs<real>) {
 #endif   // __HIPCC__
 
 // One launch: persistent workgroups (one LDS copy of the scene each), the waves' slots behind the scene, units handed
-// out by the work counter -- about eight per resident wave, so that the tail is short and a unit still flushes rarely.
-// A batch (a.n_frames frames, the BATCH kernels) is sized as one piece of work: the eight units per wave count the units
-// of all its frames, which share one ramp-up and one tail.  Its units are capped by the handle's work_counter_max; a
-// batch with more runs as consecutive launches of whole frames, each on its own part of the accumulators.
+// out by the work counter.  How large a unit is, how many a launch holds and on how many blocks it runs is
+// launch_plan.hpp's arithmetic (plan_guide_units, plan_grid): a batch (a.n_frames frames, the BATCH
+// kernels) is sized as one piece of work, whose frames share one ramp-up and one tail, and a batch with more units than
+// the work counter holds runs as consecutive launches of whole frames, each on its own part of the accumulators.
 // COUNTS: sized from params->samples all the same -- the host does not see a device plane --, so a unit beyond its tile's
 // largest count costs one counter fetch and sixteen loads; each launch's frames read their own part of the plane.
 // One body per precision: what the launch depends on in its kernel -- the residency, BATCH and COUNTS -- arrives as
@@ -275,26 +276,18 @@ int32_t aov_launch(CrHandle* h, void (*kern)(const AovArgs<real>), int res, bool
     HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(off + aov_lds_bytes(max_block))));
     int block = 256, per_cu = 1;
     { int32_t rc = pick_block(h, (const void*)kern, max_block, true, off, aov_lds_bytes(64), "guide kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
-    const uint64_t tiles = (uint64_t)a.k.tiles_x * a.k.tiles_y;
-    const uint64_t n_frames = batch ? a.n_frames : 1;
-    const uint64_t resident = (uint64_t)h->n_cus * per_cu * (block / 64);
-    uint64_t ug = std::min<uint64_t>(a.groups, std::max<uint64_t>(1, n_frames * tiles * a.groups / (8 * resident)));
-    // the 32-bit work counter (a frame has at most 2^22 tiles; a limit below one frame's tiles, which only a test sets, is raised to them)
-    const uint64_t max_units = batch ? std::max<uint64_t>(h->work_counter_max, tiles) : 0xF0000000ull;
-    if (tiles * ((a.groups + ug - 1) / ug) > max_units) ug = (a.groups + max_units / tiles - 1) / (max_units / tiles);
-    a.unit_groups = (uint32_t)ug;
-    a.unit_chunks = (uint32_t)((a.groups + ug - 1) / ug);
-    a.frame_tiles = (uint32_t)tiles;
-    const uint64_t frame_units = tiles * a.unit_chunks;
-    const uint64_t per_launch = std::min<uint64_t>(n_frames, max_units / frame_units);   // frames
+    const GuidePlan g = plan_guide_units(a.k.tiles_x, a.k.tiles_y, a.groups, batch, a.n_frames, h->n_cus, per_cu, block, h->work_counter_max);
+    a.unit_groups = g.unit_groups;
+    a.unit_chunks = g.unit_chunks;
+    a.frame_tiles = g.frame_tiles;
     const size_t npix = (size_t)a.k.reg_w * (size_t)a.k.reg_h;
     unsigned long long* const acc = a.acc;
     uint32_t* const flags = a.flags;
     const real* const times = a.frame_times;
     const int32_t* const counts = a.counts;
     const CamConst<real>* const views = a.k.views;   // cr_render_aov_views_*: a frame is a view
-    for (uint64_t f0 = 0; f0 < n_frames; f0 += per_launch) {
-        const uint64_t fn = std::min<uint64_t>(per_launch, n_frames - f0);
+    for (uint64_t f0 = 0; f0 < g.n_frames; f0 += g.frames_per_launch) {
+        const uint64_t fn = g.slice_frames(f0);
         if (batch) {
             a.n_frames = (uint32_t)fn;
             a.frame_times = times + f0;
@@ -303,11 +296,8 @@ int32_t aov_launch(CrHandle* h, void (*kern)(const AovArgs<real>), int res, bool
             if (counts_plane) a.counts = counts + f0 * npix;
             if (views) a.k.views = views + f0;
         }
-        a.n_units = (uint32_t)(fn * frame_units);
-        uint32_t grid = (uint32_t)(h->n_cus * per_cu);
-        const uint64_t need_blocks = ((uint64_t)a.n_units + (block / 64) - 1) / (block / 64);
-        if ((uint64_t)grid > need_blocks) grid = (uint32_t)need_blocks;
-        if (grid < 1) grid = 1;
+        a.n_units = g.units(fn);
+        const uint32_t grid = plan_grid(h->n_cus, per_cu, a.n_units, block, 64).blocks;   // a unit is a wave's
         HIP_TRY(h, hipMemsetAsync(h->work_counter.p, 0, 4, h->stream));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(block), off + aov_lds_bytes(block), h->stream, a);
         HIP_TRY(h, hipGetLastError());

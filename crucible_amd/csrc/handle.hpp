@@ -23,6 +23,7 @@
 #pragma once
 #include "../../include/crucible_hip.h"
 #include "pathtrace.hpp"
+#include "launch_plan.hpp"   // fx_scale_for, and what launch() and aov_launch() ask about their launches
 
 #include <algorithm>
 #include <cmath>
@@ -239,13 +240,6 @@ inline void drop_frame_trees(CrHandle* h) {
 }
 
 inline size_t real_size(int32_t real_type) { return real_type == CR_REAL_F64 ? sizeof(double) : sizeof(float); }
-
-// CR_SUM_RELAXED's fixed-point scale 2^S for n samples per pixel: n * 2^S < 2^63, S = 52 up to 2047 samples
-inline double fx_scale_for(int64_t n) {
-    int lg = 0;
-    while ((n >> (lg + 1)) > 0) lg++;
-    return std::ldexp(1.0, std::min(52, 62 - lg));
-}
 
 // what CrRenderParams.sum_order means on this handle: CR_SUM_DEFAULT is the handle's default in the megakernel and the
 // reference order in the alternative pipelines

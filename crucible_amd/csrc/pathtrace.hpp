@@ -23,6 +23,7 @@
 #define CR_D __device__ __forceinline__
 #include "fastdiv.hpp"
 #include "residency.hpp"   // RES_GLOBAL / RES_LDS / RES_TOP, where the scene is read from, and the rule that picks one
+#include "launch_plan.hpp"   // fx_lds_bytes: the LDS of the relaxed sums' slots, and the rest of what sizes a launch
 
 namespace cr {
 
@@ -390,7 +391,6 @@ template <typename real> CR_HD uint32_t batch_frame(const KernelArgs<real>& A, u
     return A.n_frames > 1u ? fastdiv(pix_j >> A.sg_lh, A.fd_tiles_y) : 0u;
 }
 constexpr unsigned long long kFxNaN = 0x8000000000000000ull;
-constexpr size_t fx_lds_bytes(int block, uint32_t tile_log2) { return (size_t)(block / 64) * 2 * ((size_t)3 << tile_log2) * sizeof(unsigned long long); }
 
 // ------------------------------------------------------------------ timeline (timeline/mod.rs:233-263)
 // combine_and_compute = S * T * (0,0,0,1): T's last column is the initial position plus every active translate

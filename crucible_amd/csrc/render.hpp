@@ -3,7 +3,9 @@
 // turns the scene's residency (residency.hpp's rule, which the guide pass shares) into the kernel that stages it.  Included
 // by the render_*.hip units only, each of which instantiates walk_ladder (both tree orders) for its <real, RELAX>, so the
 // kernels of the four combinations compile side by side and no kernel is emitted twice.  launch() is a template over
-// <real, RELAX> alone: a unit compiles it once, whatever the number of its kernels.
+// <real, RELAX> alone: a unit compiles it once, whatever the number of its kernels.  How a render is cut
+// into launches -- tile, LDS, sample batches, frames per launch, grid, chunk -- is launch_plan.hpp's arithmetic (DESIGN.md
+// 6.19), which a plain compiler checks; launch() keeps the HIP calls and the refusals' texts, in their order.
 #pragma once
 #include "handle.hpp"
 
@@ -36,13 +38,22 @@ inline int32_t diag_dump(CrHandle* h, int block, uint32_t grid) {
 }
 #endif
 
+// the frames [f0, f0 + fn) of a batch as one launch's: their count and where their ray times start (a single render: its own)
+template <typename real>
+void set_frame_slice(KernelArgs<real>& args, const KernelArgs<real>& args_in, const FrameBatch<real>& fb, int32_t f0, int32_t fn) {
+    args.n_frames = (uint32_t)fn;
+    args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
+    args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
+}
+
 // One launch routine per unit.  What it depends on in the kernel it runs is MegaKernel's fields (handle.hpp), filled by
 // launch_variant below; the sum order alone stays a template parameter, because the two orders run different finalize
 // kernels and a unit may name only its own.  k.list: the passes of cr_render_adaptive_* -- pathtrace_kernel_listed, handed
 // to adaptive_passes (adaptive.hip).
+// The sequence: plan the tile; attribute and pick_block; what the kernel kind renders; plan the samples and frames; the buffers
+// and memsets; per frame slice and batch, the arguments from the plan and the launch; finalize; stats.
 template <typename real, bool RELAX>
 int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& args_in, size_t scene_lds_bytes, CrStats* stats, const FrameBatch<real>& fb) {
-    const bool use_lds = k.res != RES_GLOBAL || RELAX;
     KernelArgs<real> args = args_in;
     // A render whose caller asked for no stats runs the kernel that keeps no work counters, where one exists (k.quiet: the
     // headline's kernel, never in a CR_DIAG build, which counts every launch); adaptive calls and batches of frames run on
@@ -50,93 +61,61 @@ int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& a
     const bool quiet = k.quiet && !stats && !h->keep_counters && !fb.ad && fb.n == 1;
     void (*const kern)(const KernelArgs<real>) = quiet ? k.quiet : k.kern;
     const int max_block = k.latency ? LatencyBlock : MaxBlock<real>::value;
-    // The work tile (sample-granular hand-out): 2^lw x 2^lh pixels times 64 >> (lw + lh) consecutive samples; by default
-    // 4 x 4 x 4, wider tiles of fewer samples when fewer than 4 samples are rendered.
-    // (cr_render_adaptive_*: a launch renders one pass of pass_samples samples, and the tile's sides divide the block's)
-    const int32_t n_samples = fb.ad ? fb.ad->pass_samples : args.sample_end - args.sample_begin;
-    int tile_lw = h->sg_lw, tile_lh = h->sg_lh;
-    if (fb.ad && (tile_lw > fb.ad->block_log2 || tile_lh > fb.ad->block_log2)) tile_lw = tile_lh = -1;
-    if (tile_lw < 0) default_tile(n_samples, tile_lw, tile_lh);
-    // RELAX: the waves' accumulator slots follow the scene in LDS (2 x 384 B per wave for a 16-pixel tile); a tile too
-    // large for what the scene leaves free falls back to 16 pixels (the surplus sample slots of its groups stay empty)
-    const size_t fx_off = k.res != RES_GLOBAL ? r16(scene_lds_bytes) : 0;
-    if (RELAX && fx_off + fx_lds_bytes(max_block, (uint32_t)(tile_lw + tile_lh)) > (size_t)160 * 1024) { tile_lw = 2; tile_lh = 2; }
-    auto lds_for = [&](int block) { return RELAX ? fx_off + fx_lds_bytes(block, (uint32_t)(tile_lw + tile_lh)) : scene_lds_bytes; };
-    args.fx_lds_off = (uint32_t)fx_off;
-    if (use_lds) HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_for(max_block)));
+    // the samples of one launch (cr_render_adaptive_*: one pass of pass_samples samples) and of the launch's pixels: the region's
+    // (prepare_args: the whole frame unless cr_render_region_* named one; RELAX kernels with keys only)
+    const int32_t s_begin = args.sample_begin, s_end = fb.ad ? s_begin + fb.ad->pass_samples : args.sample_end;
+    const bool fixed = args.output_sum == CR_OUTPUT_FIXED_SUM;
+    const TilePlan tile = plan_tile(h->sg_lw, h->sg_lh, s_end - s_begin, fb.ad ? fb.ad->block_log2 : -1, RELAX, k.res, scene_lds_bytes, max_block);
+    const bool use_lds = tile.use_lds;
+    args.fx_lds_off = (uint32_t)tile.fx_off;
+    if (use_lds) HIP_TRY(h, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile.lds_bytes(max_block)));
     int block = 256, per_cu = 1;   // an override above max_block is ignored here (the latency entry point's 512 under CRUCIBLE_BLOCK=1024)
-    const size_t lds_base = RELAX ? fx_off : (use_lds ? scene_lds_bytes : 0), lds_per_wave = RELAX ? fx_lds_bytes(64, (uint32_t)(tile_lw + tile_lh)) : 0;
-    { int32_t rc = pick_block(h, (const void*)kern, max_block, true, lds_base, lds_per_wave, "kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
-    const size_t lds_bytes = lds_for(block);
-    // Sample-granular mode: batches of samples whose colours fit the buffer; each batch is one launch of the
-    // path tracer followed by the ordered sum (sg_finalize_kernel).
-    // the launch's pixels: the region's (prepare_args: the whole frame unless cr_render_region_* named one; RELAX kernels with keys only)
-    const size_t npix = (size_t)args.reg_w * (size_t)args.reg_h;
-    const int32_t s_begin = args.sample_begin, s_end = fb.ad ? s_begin + n_samples : args.sample_end;
-    int32_t batch = 0;
-    int32_t fpl = 1;   // frames per launch (a batch of frames: as many whole frames as the work counter holds)
+    { int32_t rc = pick_block(h, (const void*)kern, max_block, true, tile.lds_base, tile.lds_per_wave, "kernel does not fit on a CU", block, per_cu); if (rc != CR_OK) return rc; }
+    const size_t lds_bytes = tile.lds_bytes(block);
     args.n_frames = 1; args.frame_times = nullptr;
-    if (fb.n > 1 && !(RELAX && k.keyed)) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
-    if ((args.reg_x0 || args.reg_y0 || args.reg_w != (uint32_t)args.cam.W || args.reg_h != (uint32_t)args.cam.H) && (k.latency || !(RELAX && k.keyed)))
-        return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders whole frames");
-    if (k.list != (fb.ad != nullptr)) return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
-    if ((h->sample_granular || RELAX) && s_end > s_begin) {
-        const size_t per_sample = npix * 3 * sizeof(real);
-        batch = (int32_t)std::min<size_t>((size_t)(s_end - s_begin), RELAX ? (size_t)INT32_MAX : std::max<size_t>(1, h->sample_buf_limit / per_sample));
-        int lw = tile_lw, lh = tile_lh;
-        if (!RELAX && h->sg_lw < 0) default_tile(batch, lw, lh);   // by the batch, which the buffer may have cut
-        const uint32_t ns = 64u >> (lw + lh);
-        args.sg_lw = (uint32_t)lw; args.sg_lh = (uint32_t)lh;
-        set_tiles(args, (args.reg_w + (1u << lw) - 1) >> lw, (args.reg_h + (1u << lh) - 1) >> lh);
-        const uint64_t tiles = (uint64_t)args.tiles_x * args.tiles_y;
-        // the 32-bit work counter must hold tiles * groups * 64 plus one chunk per wave
-        const uint64_t max_groups = h->work_counter_max / (tiles * 64);
-        if (max_groups < 1) batch = 0;
-        else batch = (int32_t)std::min<uint64_t>((uint64_t)batch, max_groups * ns);
-        // the buffer holds one colour per work item of a batch: whole tiles and whole sample groups (edge padding included)
-        if constexpr (RELAX) {
-            if (batch <= 0) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
-            // a frame that needs sample batches on its own renders frame by frame
-            if (batch == s_end - s_begin) fpl = (int32_t)std::min<uint64_t>((uint64_t)fb.n, max_groups / (((uint64_t)batch + ns - 1) / ns));
-            // (cr_render_adaptive_region_*: such a pass runs as consecutive launches of `batch` samples, as a region render's samples do)
-            if (fb.ad && !fb.ad->split_passes && batch < s_end - s_begin)
-                return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter at this pass_samples");
-            if (args.output_sum != CR_OUTPUT_FIXED_SUM && !fb.ad) {   // (adaptive_passes keeps its own two accumulators)
-                const hipError_t e = h->fx_acc.ensure((size_t)fb.n * npix * 3 * sizeof(unsigned long long));
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(h, CR_ERR_HIP, "fixed-point sums of " + std::to_string(fb.n) + " frame(s): " + hipGetErrorString(e));
-                }
-            }
-        } else {
-            auto batch_bytes = [&](int32_t b) { return (size_t)tiles * (((size_t)b + ns - 1) / ns) * 64u * 3u * sizeof(real); };
-            while (batch > (int32_t)ns && batch_bytes(batch) > std::max(h->sample_buf_limit, batch_bytes((int32_t)ns))) batch -= (int32_t)ns;
-            if (batch > 0 && h->sample_buf.ensure(batch_bytes(batch)) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
-            if (batch > 0 && batch < s_end - s_begin && h->sg_acc.ensure(per_sample) != hipSuccess) { (void)hipGetLastError(); batch = 0; }
-            if (batch == 0) set_tiles(args, args_in.tiles_x, args_in.tiles_y);   // fall back: a lane owns a pixel
-        }
+    switch (check_call_shape(RELAX, k.keyed, k.latency, k.list, fb.n, whole_frame(args.reg_x0, args.reg_y0, args.reg_w, args.reg_h, args.cam.W, args.cam.H), fb.ad != nullptr)) {
+    case kShapeOneFrame: return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders one frame per launch");
+    case kShapeWholeFrames: return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant renders whole frames");
+    case kShapeNoList: return fail(h, CR_ERR_UNSUPPORTED, "this kernel variant does not carry the active-tile list");
+    case kShapeOk: break;
     }
-    args.sg_on = batch > 0 ? 1u : 0u;
-    const uint32_t ns = args.sg_on ? (64u >> (args.sg_lw + args.sg_lh)) : 1u;
-    auto groups_of = [&](int32_t n) { return (uint32_t)(((int64_t)n + ns - 1) / ns); };
-    uint64_t total_work = args.sg_on ? (uint64_t)args.tiles_x * args.tiles_y * fpl * groups_of(std::min(batch, s_end - s_begin)) * 64u
-                                     : (uint64_t)args.tiles_x * args.tiles_y * 64u;
-    uint32_t grid = (uint32_t)(h->n_cus * per_cu);
-    uint64_t need_blocks = (total_work + block - 1) / block;
-    if ((uint64_t)grid > need_blocks) grid = (uint32_t)need_blocks;
-    if (grid < 1) grid = 1;
-    args.n_threads = grid * (uint32_t)block;
+    // Sample-granular mode: batches of samples; each batch is one launch of the path tracer, in the reference order followed
+    // by the ordered sum (sg_finalize_kernel) over the colours it left in the buffer
+    const SampleQuery sq = {RELAX, h->sample_granular != 0, s_begin, s_end, args.reg_w, args.reg_h, sizeof(real), h->sample_buf_limit, h->work_counter_max, tile.lw, tile.lh,
+                            h->sg_lw >= 0, fb.n, fb.ad != nullptr, fb.ad && fb.ad->split_passes, fixed, args_in.tiles_x, args_in.tiles_y};
+    SamplePlan sp = plan_samples(sq);
+    if constexpr (RELAX) {   // (the reference order's plan refuses nothing: it falls back)
+        if (sp.refusal == kPlanCounter) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter");
+        if (sp.refusal == kPlanCounterPass) return fail(h, CR_ERR_UNSUPPORTED, "image too large for the 32-bit work counter at this pass_samples");
+        if (sp.fx_acc_bytes) {
+            const hipError_t e = h->fx_acc.ensure(sp.fx_acc_bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(h, CR_ERR_HIP, "fixed-point sums of " + std::to_string(fb.n) + " frame(s): " + hipGetErrorString(e));
+            }
+        }
+    } else {   // a buffer that cannot be had: a lane owns a pixel
+        if (sp.sample_buf_bytes && h->sample_buf.ensure(sp.sample_buf_bytes) != hipSuccess) { (void)hipGetLastError(); lane_owns_pixel(sp); }
+        if (sp.sg_acc_bytes && h->sg_acc.ensure(sp.sg_acc_bytes) != hipSuccess) { (void)hipGetLastError(); lane_owns_pixel(sp); }
+    }
+    if (sp.tiled) { args.sg_lw = (uint32_t)sp.lw; args.sg_lh = (uint32_t)sp.lh; }
+    set_tiles(args, sp.tiles_x, sp.tiles_y);
+    args.sg_on = sp.batch > 0 ? 1u : 0u;
+    const int32_t batch = sp.batch, fpl = sp.fpl;   // (the plan as numbers: the closures below keep these, not the plan)
+    const uint32_t ns = sp.ns;
+    const uint64_t frame_tiles = sp.tiles();
+    const size_t frame_words = sp.frame_words;
+    const GridPlan gp = plan_grid(h->n_cus, per_cu, sp.grid_work(s_end - s_begin), block, 1);
+    const uint32_t grid = gp.blocks;
+    args.n_threads = gp.n_threads;
     if constexpr (!RELAX) {
-        size_t stack_bytes = (size_t)3 * (size_t)(args.max_depth > 0 ? args.max_depth : 1) * args.n_threads * sizeof(real);
-        HIP_TRY(h, h->att_stack.ensure(stack_bytes));
+        HIP_TRY(h, h->att_stack.ensure(att_stack_bytes(args.max_depth, args.n_threads, sizeof(real))));
         args.att_stack = (real*)h->att_stack.p;
     } else {
-        // the scale of the n samples a pixel receives in this render; CR_OUTPUT_FIXED_SUM: of the whole frame, so the words
-        // of any shards of it add up to the frame's, and they go straight into the caller's buffer
-        const bool fixed = args.output_sum == CR_OUTPUT_FIXED_SUM;
-        args.fx_scale = fx_scale_for(fixed || fb.ad ? args.samples_total : s_end - s_begin);
+        // the scale of the n samples a pixel receives in this render; CR_OUTPUT_FIXED_SUM: the sums go straight into the caller's buffer
+        args.fx_scale = fx_scale_for(fx_scale_samples(fixed, fb.ad != nullptr, args.samples_total, s_begin, s_end));
         args.fx_acc = fixed ? (unsigned long long*)args.out : (unsigned long long*)h->fx_acc.p;
-        if (!fb.ad) HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, (size_t)fb.n * npix * 3 * sizeof(unsigned long long), h->stream));
+        if (!fb.ad) HIP_TRY(h, hipMemsetAsync(args.fx_acc, 0, sp.fx_words * sizeof(unsigned long long), h->stream));
     }
     if (!quiet) HIP_TRY(h, hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint64_t), h->stream));
     // one launch of the kernel on `args` as they stand: the work counter starts at zero
@@ -146,15 +125,14 @@ int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& a
         HIP_TRY(h, hipGetLastError());
         return CR_OK;
     };
-    // one batch of samples [b0, b1) of n_tiles tiles (those of all the launch's frames): its groups, work items and chunk,
-    // then the launch.  fit: on no more blocks than the items fill (a pass may name few tiles); else on the whole grid
-    auto run_batch = [&](int32_t b0, int32_t b1, uint64_t n_tiles, bool fit) -> int32_t {
+    // one batch of samples [b0, b1) of fn frames of `tiles` tiles, as plan_batch sizes it
+    auto run_batch = [&](int32_t b0, int32_t b1, uint64_t tiles, int32_t fn, bool fit) -> int32_t {
+        const BatchLaunch bl = plan_batch(ns, b1 - b0, tiles, fn, fit, grid, block, h->sg_chunk_override);
         args.sample_begin = b0; args.sample_end = b1;
-        set_groups(args, groups_of(b1 - b0));
-        args.sg_total = (uint32_t)(n_tiles * args.sg_groups * 64u);
-        const uint32_t blocks = fit ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, ((uint64_t)args.sg_total + block - 1) / block)) : grid;
-        args.sg_chunk = work_chunk(args.sg_total, blocks, (uint64_t)block, h->sg_chunk_override);
-        return run(blocks);
+        set_groups(args, bl.groups);
+        args.sg_total = bl.sg_total;
+        args.sg_chunk = bl.chunk;
+        return run(bl.blocks);
     };
     if (k.list) {
         // cr_render_adaptive_*: the passes are adaptive_passes' (adaptive.hip), each one a launch of this kernel over the tiles
@@ -164,12 +142,10 @@ int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& a
         // (cr_render_adaptive_frames_*: a pass loop's frames [f0, f0 + fn) of the batch, at most fpl, as the loop below sets them)
         const AdaptivePass pass = [&](int32_t f0, int32_t fn, const int32_t* tile_list, uint32_t n_tiles, int32_t s0, int32_t s1, unsigned long long* acc) -> int32_t {
             args.tile_list = tile_list; args.fx_acc = acc;
-            args.n_frames = (uint32_t)fn;
-            args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
-            args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
+            set_frame_slice(args, args_in, fb, f0, fn);
             // one launch, unless the work counter holds fewer samples of the tiles than the pass has (split_passes; batch >= 1)
             for (int64_t b0 = s0; b0 < s1; b0 += batch) {
-                const int32_t rc = run_batch((int32_t)b0, (int32_t)std::min<int64_t>(s1, b0 + batch), n_tiles, true);
+                const int32_t rc = run_batch((int32_t)b0, batch_end(b0, batch, s1), n_tiles, 1, true);   // (the list's tiles are the batch's, of all its frames)
                 if (rc != CR_OK) return rc;
             }
             return CR_OK;
@@ -190,25 +166,22 @@ int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& a
         for (int32_t f0 = 0; f0 < fb.n; f0 += fpl) {   // one pass for a single render
             const int32_t fn = std::min(fpl, fb.n - f0);
             if constexpr (RELAX) {   // frames [f0, f0 + fn) of a batch
-                args.n_frames = (uint32_t)fn;
-                args.current_time = fb.times ? fb.times[f0] : args_in.current_time;
-                args.frame_times = fb.d_times ? fb.d_times + f0 : nullptr;
-                args.fx_acc = fx_frame0 + (size_t)f0 * npix * 3;
+                set_frame_slice(args, args_in, fb, f0, fn);
+                args.fx_acc = fx_frame0 + (size_t)f0 * frame_words;
                 if (views0) args.views = views0 + f0;
             }
             for (int64_t b0 = s_begin; b0 < s_end; b0 += batch) {   // (64 bits: b0 + batch may pass INT32_MAX)
-                const int32_t b1 = (int32_t)std::min<int64_t>(s_end, b0 + batch);
-                { int32_t rc = run_batch((int32_t)b0, b1, (uint64_t)args.tiles_x * args.tiles_y * (uint64_t)fn, false); if (rc != CR_OK) return rc; }
+                const int32_t b1 = batch_end(b0, batch, s_end);
+                { int32_t rc = run_batch((int32_t)b0, b1, frame_tiles, fn, false); if (rc != CR_OK) return rc; }
                 if constexpr (!RELAX) {   // (relaxed: the sums stay in fx_acc until the last batch)
-                    const size_t fin_threads = ((size_t)args.tiles_x * args.tiles_y) << (args.sg_lw + args.sg_lh);
-                    hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((fin_threads + 255) / 256)), dim3(256), 0, h->stream, args,
+                    hipLaunchKernelGGL((sg_finalize_kernel<real>), dim3((unsigned)((sp.tile_pixels() + 255) / 256)), dim3(256), 0, h->stream, args,
                                        (real*)h->sg_acc.p, b1 - (int32_t)b0, b0 == s_begin ? 1 : 0, b1 == s_end ? 1 : 0);
                     HIP_TRY(h, hipGetLastError());
                 }
             }
         }
-        if constexpr (RELAX) if (args.output_sum != CR_OUTPUT_FIXED_SUM) {   // a batch's frames follow each other in fx_acc and in the output
-            int32_t rc = fx_finalize<real>(h, (const unsigned long long*)h->fx_acc.p, args.out, (size_t)fb.n * npix * 3, 1.0 / args.fx_scale, (double)args.samples_total, args.output_sum);
+        if constexpr (RELAX) if (!fixed) {   // a batch's frames follow each other in fx_acc and in the output
+            int32_t rc = fx_finalize<real>(h, (const unsigned long long*)h->fx_acc.p, args.out, sp.fx_words, 1.0 / args.fx_scale, (double)args.samples_total, args.output_sum);
             if (rc != CR_OK) return rc;
         }
         args.sample_begin = s_begin; args.sample_end = s_end;
@@ -216,7 +189,7 @@ int32_t launch(CrHandle* h, const MegaKernel<real>& k, const KernelArgs<real>& a
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     h->last_block = block; h->last_grid = (int)grid;
     if (stats) {
-        int32_t rc = finish_stats(h, stats, (uint64_t)npix * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, k.res);
+        int32_t rc = finish_stats(h, stats, (uint64_t)sp.npix * (uint64_t)(args.sample_end - args.sample_begin) * (uint64_t)fb.n, args.n_entries, k.res);
         if (rc != CR_OK) return rc;
 #ifdef CR_DIAG
         rc = diag_dump(h, block, grid);
@@ -267,7 +240,7 @@ int32_t walk_ladder(CrHandle* h, KernelArgs<real>& a, const DevScene<real>& ds, 
     constexpr bool f32 = std::is_same<real, float>::value;   // the double kernel needs far more than 80 VGPRs: it halves there
     ResidencyQuery q = residency_query<real, ORD>(h, ds, w);
     // (the 6-waves-per-SIMD kernels render whole frames: a region of such a tree runs on the regular kernel, the same bytes)
-    q.whole_frame = !a.reg_x0 && !a.reg_y0 && a.reg_w == (uint32_t)a.cam.W && a.reg_h == (uint32_t)a.cam.H;
+    q.whole_frame = whole_frame(a.reg_x0, a.reg_y0, a.reg_w, a.reg_h, a.cam.W, a.cam.H);
     q.adaptive = fb.ad != nullptr;
     const Residency r = choose_residency(q);
     a.lds_entries = r.lds_entries;

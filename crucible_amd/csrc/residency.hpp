@@ -1,9 +1,9 @@
 // residency.hpp -- how much of a scene a launch stages in LDS and where it lies there: one layout,
 // scene_layout, for every kernel that stages and every host computation of the bytes; one rule, choose_residency, for the render
 // kernels' ladder (render.hpp walk_ladder) and the guide kernels' (aov_kernel.hpp aov_ladder_ord), which only fill a query
-// and dispatch on the answer; and launch()'s two small rules, the work chunk and the default tile.  Free of the HIP runtime
-// and of the record types -- sizes arrive as numbers --, so that a plain C++ compiler can check it
-// (tests/residency_check.cpp), as it checks fastdiv.hpp, tree.hpp and adaptive.hpp.
+// and dispatch on the answer.  Free of the HIP runtime and of the record types -- sizes arrive as numbers --, so that a
+// plain C++ compiler can check it (tests/residency_check.cpp), as it checks fastdiv.hpp, tree.hpp and adaptive.hpp.  How a
+// launch is sized once the residency is settled is launch_plan.hpp's, which builds on this header.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -125,21 +125,7 @@ auto residency_dispatch(const Residency& r, F&& f) {
     return by_screen(std::integral_constant<int, RES_GLOBAL>{});
 }
 
-// launch(): work items per atomic on the work counter.  1024 keeps the counter quiet on long launches; a short launch (a
-// small frame, or one GPU's shard of the samples) would end with whole chunks of imbalance, so a wave's chunk is at most
-// 1/128 of its share, and at least one wave's round.  chunk_override: CRUCIBLE_SG_CHUNK.
-CR_HD uint32_t work_chunk(uint64_t sg_total, uint64_t grid, uint64_t block, int chunk_override) {
-    const uint64_t waves = grid * block / 64, per_wave = sg_total / (waves > 1 ? waves : 1);
-    const uint64_t share = per_wave / 128;
-    const uint64_t c = chunk_override > 0 ? (uint64_t)chunk_override : (share < 64 ? 64 : (share > 1024 ? 1024 : share));
-    return (uint32_t)((c + 63) / 64 * 64);
-}
-
-// launch(): the default work tile of 2^lw x 2^lh pixels times 64 >> (lw + lh) samples, by the samples n a launch renders:
-// 4 x 4 x 4, wider tiles of fewer samples when there are fewer than 4
-CR_HD void default_tile(int64_t n, int& lw, int& lh) {
-    lw = n >= 4 ? 2 : 3;
-    lh = n >= 2 ? 2 : 3;
-}
-
 }   // namespace cr
+
+// (launch()'s chunk and tile rules, which lived here, are part of the launch plan now; whoever includes this header finds them)
+#include "launch_plan.hpp"

@@ -1,15 +1,12 @@
 // residency_check.cpp -- crucible_amd/csrc/residency.hpp on the CPU (tests/test_residency_host.py): the residency rule and
-// launch()'s chunk and tile rules over a case file, one case per line:
+// the scene's layout over a case file, one case per line (launch()'s chunk and tile rules: tests/launch_plan_check.cpp):
 //   R n_entries entry_rec screen_rec ordered can_screen screen screen_lds plain_lds lds_bytes lds_all_screen side_bytes
 //     lds_top_bytes lds_side_limit f32 whole_frame adaptive latency_entries latency_top_bytes latency_slot_bytes
 //       -> "res screen latency lds_entries lds_side lds_bytes clear_screen"
 //   L n_records record_rec n_prims prim_rec n_mats mat_rec n_texs tex_rec with_prims with_side
 //       -> "prims mats texs bytes end": scene_layout over the tables' bytes, formed as handle.hpp forms them (count * record)
-//   C sg_total grid block chunk_override   -> the chunk
-//   T n                                    -> "lw lh"
 #include "residency.hpp"
 
-#include <cinttypes>
 #include <cstdio>
 
 int main(int argc, char** argv) {
@@ -38,17 +35,6 @@ int main(int argc, char** argv) {
             const cr::SceneLayout l = cr::scene_layout((size_t)v[0] * (size_t)v[1], (size_t)v[2] * (size_t)v[3], (size_t)v[4] * (size_t)v[5],
                                                        (size_t)v[6] * (size_t)v[7], v[8] != 0, v[9] != 0);
             printf("%zu %zu %zu %zu %zu\n", l.prims, l.mats, l.texs, l.bytes, l.end());
-        } else if (kind == 'C') {
-            uint64_t total, grid, block;
-            int chunk_override;
-            if (fscanf(f, "%" SCNu64 " %" SCNu64 " %" SCNu64 " %d", &total, &grid, &block, &chunk_override) != 4) return 2;
-            printf("%u\n", cr::work_chunk(total, grid, block, chunk_override));
-        } else if (kind == 'T') {
-            long long n;
-            if (fscanf(f, "%lld", &n) != 1) return 2;
-            int lw = -1, lh = -1;
-            cr::default_tile(n, lw, lh);
-            printf("%d %d\n", lw, lh);
         } else return 2;
     }
     fclose(f);

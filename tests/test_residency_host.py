@@ -1,5 +1,6 @@
 """crucible_amd/csrc/residency.hpp, the rule that settles how much of a scene a launch stages in LDS (shared by the render's
-walk_ladder and the guide pass's aov_ladder_ord) and launch()'s chunk and tile rules, checked without a device:
+walk_ladder and the guide pass's aov_ladder_ord), checked without a device (launch()'s chunk and tile rules, once here, are
+part of the launch plan: tests/test_launch_plan_host.py):
 tests/residency_check.cpp compiles the header with g++ (plain, and with -fsanitize=address,undefined) and prints the
 decision of each case.  The expected decisions below are written out by hand from the rule, not computed
 by a second copy of it: (res, screen, latency, lds_entries, lds_side, lds_bytes, clear_screen).  So are the offsets of the layout
@@ -201,23 +202,4 @@ def test_layout_keeps_a_scene_s_bytes(exes, tmp_path):
         ("ordered f64 lds_bytes", L(21, 96, 11, 5, 1, 1, 1, **REC64), (2016, 3072, 3312, 3360, 3360)),
         ("ordered f64 lds_all_screen", L(21, 64, 11, 5, 1, 1, 1, **REC64), (1344, 2400, 2640, 2688, 2688)),
         ("ordered f32 lds_bytes", L(21, 64, 11, 5, 1, 1, 1, **REC32), (1344, 1872, 2032, 2064, 2064)),
-    ])
-
-
-def test_chunk_and_tile(exes, tmp_path):
-    check(exes, tmp_path, [
-        ("the override wins, rounded to whole rounds", "C 1000000 256 256 100", (128,)),
-        ("the override wins over the clamp", "C 1000000 256 256 4096", (4096,)),
-        ("lower clamp: 6400 items over 40 waves, 160 / 128 = 1", "C 6400 10 256 0", (64,)),
-        ("upper clamp: 2^30 items over 4096 waves, 262144 / 128 = 2048", "C 1073741824 256 1024 0", (1024,)),
-        ("just inside: 131072 items over one wave, 1024", "C 131072 1 64 0", (1024,)),
-        ("rounding: 51200 items over 4 waves, 12800 / 128 = 100", "C 51200 1 256 0", (128,)),
-        ("a multiple of 64 stays: 24576 / 128 = 192", "C 24576 1 64 0", (192,)),
-        ("grid * block < 64 counts as one wave: 25600 / 128 = 200", "C 25600 1 32 0", (256,)),
-        ("no work", "C 0 1 256 0", (64,)),
-        ("1 sample: 8 x 8", "T 1", (3, 3)),
-        ("2 samples: 8 x 4", "T 2", (3, 2)),
-        ("3 samples: 8 x 4", "T 3", (3, 2)),
-        ("4 samples: 4 x 4", "T 4", (2, 2)),
-        ("many samples: 4 x 4", "T 2147483647", (2, 2)),
     ])
