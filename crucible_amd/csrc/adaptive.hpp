@@ -2,11 +2,9 @@
 // the host share: a block's geometry, one term of its difference sum D_b and its threshold T_b.  Free of the HIP runtime,
 // so that a plain C++ compiler can check it (tests/adaptive_check.cpp), as it checks fastdiv.hpp and tree.hpp.
 #pragma once
-#include <stdint.h>
+#include "hd.hpp"
 
-#if !defined(CR_HD)          // a plain C++ compiler; the library defines it in pathtrace.hpp
-#define CR_HD inline
-#endif
+#include <stdint.h>
 
 namespace cr {
 

@@ -4,11 +4,9 @@
 // it.  Free of the HIP runtime, so that a plain C++ compiler can check them (tests/aov_counts_check.cpp), as it checks
 // residency.hpp and adaptive.hpp.
 #pragma once
-#include <stdint.h>
+#include "hd.hpp"
 
-#if !defined(CR_HD)          // a plain C++ compiler; the library defines it in pathtrace.hpp
-#define CR_HD inline
-#endif
+#include <stdint.h>
 
 namespace cr {
 

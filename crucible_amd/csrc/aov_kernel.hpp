@@ -7,6 +7,7 @@
 // a pass is cut into units and launches is launch_plan.hpp's, and aov_launch keeps the HIP calls.
 #pragma once
 #include "aov.hpp"
+#include "pathtrace.hpp"
 
 #include <type_traits>
 

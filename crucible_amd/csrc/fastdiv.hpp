@@ -10,11 +10,9 @@
 // Exact for every n in [0, 2^32) and every d in [1, 2^32): d = 1 gives m = 1, t = 0 and both shifts 0 (n itself), a
 // power of two gives m = 1, t = 0 and a plain shift by l.
 #pragma once
-#include <stdint.h>
+#include "hd.hpp"
 
-#if !defined(CR_HD)          // a plain C++ compiler; the library defines it in pathtrace.hpp
-#define CR_HD inline
-#endif
+#include <stdint.h>
 
 namespace cr {
 

@@ -20,10 +20,17 @@
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
 //   adaptive.hip       the adaptive family behind its entry points: its argument checks, the pass loop, the judge and finalize kernels (adaptive.hpp)
 //   api.hip            cr_create / cr_destroy, all cr_render_* entry points over one RenderCall, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
+// The path tracer's code lies in layered headers.  This header reads the bottom layer alone -- records.hpp: the
+// records, KernelArgs, MaxBlock and LatencyBlock, over hd.hpp's CR_HD / CR_D -- and launch_plan.hpp, so api, group, scene, build,
+// sah_device, adaptive, aov and render parse no kernel code of it.  The units that emit its kernels (render_*, render_views_*,
+// aov_*, aov_views_*, aov_counts_*, alt_pipelines) read pathtrace.hpp -- intersect.hpp, shade.hpp, walk.hpp, megakernel.hpp --
+// through render.hpp, aov_kernel.hpp, wavefront.hpp and queue.hpp.
 #pragma once
 #include "../../include/crucible_hip.h"
-#include "pathtrace.hpp"
+#include "records.hpp"       // the records and KernelArgs; no kernel code of the path tracer: the units that launch it include pathtrace.hpp
 #include "launch_plan.hpp"   // fx_scale_for, and what launch() and aov_launch() ask about their launches
+
+#include <hip/hip_runtime.h>   // hipError_t, hipStream_t, hipMalloc: this header is read by hipcc alone
 
 #include <algorithm>
 #include <cmath>

@@ -5,6 +5,7 @@
 // the HIP runtime and of the record types -- sizes arrive as numbers --, so that a plain C++ compiler can check it
 // (tests/launch_plan_check.cpp), as it checks residency.hpp, whose layout and RES_* this header builds on.
 #pragma once
+#include "hd.hpp"
 #include "residency.hpp"
 
 #include <cmath>

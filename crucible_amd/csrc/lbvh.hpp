@@ -15,7 +15,7 @@
 // topology: faster to build (a few milliseconds for 10^6 primitives against 0.3-0.4 s on the host), walked like any
 // other tree, checked the same way (cr_export_bvh + the test suite's CPU checker).  Not the reference's tree.
 #pragma once
-#include "pathtrace.hpp"
+#include "records.hpp"
 
 namespace cr {
 

@@ -1,10 +1,10 @@
-// Host-side packing of the C-ABI descriptors (include/crucible_hip.h) into the device records of pathtrace.hpp: primitives,
+// Host-side packing of the C-ABI descriptors (include/crucible_hip.h) into the device records of records.hpp: primitives,
 // materials, textures, keyframes, images and the camera constants.  build.hip, scene.hip and render.hip upload what these functions make, and
 // tests/shade_check.hip packs its inputs with the same functions, so the device checks see the library's own records
 // (Schlick's r0, 1/scatter_prob, 1/radius, the texel words) rather than a copy of the packing.
 #pragma once
 #include "../../include/crucible_hip.h"
-#include "pathtrace.hpp"
+#include "records.hpp"
 #include "scene_checks.hpp"
 #include <algorithm>
 #include <cmath>

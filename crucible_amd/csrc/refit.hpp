@@ -35,7 +35,7 @@
 // with the same kernels: build.hip, build_frame_scene.
 #pragma once
 #include "pack.hpp"
-#include "pathtrace.hpp"
+#include "records.hpp"
 
 namespace cr {
 

@@ -8,6 +8,7 @@
 // 6.19), which a plain compiler checks; launch() keeps the HIP calls and the refusals' texts, in their order.
 #pragma once
 #include "handle.hpp"
+#include "pathtrace.hpp"
 
 #include <type_traits>
 

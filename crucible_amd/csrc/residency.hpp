@@ -5,14 +5,12 @@
 // plain C++ compiler can check it (tests/residency_check.cpp), as it checks fastdiv.hpp, tree.hpp and adaptive.hpp.  How a
 // launch is sized once the residency is settled is launch_plan.hpp's, which builds on this header.
 #pragma once
+#include "hd.hpp"
+
 #include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
-
-#if !defined(CR_HD)          // a plain C++ compiler; the library defines it in pathtrace.hpp
-#define CR_HD inline
-#endif
 
 namespace cr {
 
@@ -26,7 +24,7 @@ CR_HD size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
 // at offset 0 are wrappers or screening records (the whole tree, or a window of its top); with_prims: the primitive table
 // follows them (RES_LDS); with_side: materials and textures follow (RES_LDS, and RES_TOP where they ride along).  A table
 // that is not staged takes no room.  `bytes` ends the last table; what a launch puts behind the scene (the waves' slots,
-// the queue's state) begins at end().  stage_scene (pathtrace.hpp) copies by this, and the host sizes its launches by it.
+// the queue's state) begins at end().  stage_scene (megakernel.hpp) copies by this, and the host sizes its launches by it.
 // The four sizes are the tables' bytes (records * bytes of one), formed by the caller: a kernel copies by the same products.
 struct SceneLayout {
     size_t prims, mats, texs;   // offsets of the tables
@@ -126,6 +124,3 @@ auto residency_dispatch(const Residency& r, F&& f) {
 }
 
 }   // namespace cr
-
-// (launch()'s chunk and tile rules, which lived here, are part of the launch plan now; whoever includes this header finds them)
-#include "launch_plan.hpp"

@@ -17,11 +17,9 @@
 // integer keys (sah_key): they commute, a NaN is skipped rather than ordered, and of two zeros a minimum keeps -0 and a
 // maximum +0 whatever the schedule -- which decides nothing: every use is a difference or a comparison.
 #pragma once
-#include <cstdint>
+#include "hd.hpp"   // CR_HD: inline under a plain C++ compiler (tests/sah_device_check.cpp)
 
-#if !defined(CR_HD)          // a plain C++ compiler (tests/sah_device_check.cpp); the library defines it in pathtrace.hpp
-#define CR_HD inline
-#endif
+#include <cstdint>
 
 namespace cr {
 

@@ -1,12 +1,12 @@
-// screen.hpp -- the kernels that derive a tree's f32 screening records (pathtrace.hpp: ScreenEntry, ScreenEntryO, walk_round)
+// screen.hpp -- the kernels that derive a tree's f32 screening records (records.hpp: ScreenEntry, ScreenEntryO; walk.hpp: walk_round)
 // from its wrappers.  Included by scene.hip alone: one of the kernels is no template, so every unit that read its
 // definition would emit it.
 #pragma once
-#include "pathtrace.hpp"
+#include "records.hpp"
 
 namespace cr {
 
-// One record per wrapper: its box plane by plane through screen_plane (pathtrace.hpp), its links copied.  Run after every
+// One record per wrapper: its box plane by plane through screen_plane (records.hpp), its links copied.  Run after every
 // upload and after every refit of the f64 boxes.
 template <typename real>
 __global__ void __launch_bounds__(256) screen_from_entries_kernel(const Entry<real>* e, ScreenEntry* s, int32_t n, int32_t* overflow) {

@@ -15,7 +15,7 @@
 #pragma once
 #include "lbvh.hpp"
 #include "pack.hpp"
-#include "pathtrace.hpp"
+#include "records.hpp"
 #include "sah_device.hpp"
 
 #include <algorithm>

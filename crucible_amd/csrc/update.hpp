@@ -10,7 +10,7 @@
 // cr_update_materials, cr_update_image add the two scatters below: a primitive's material index through the
 // same table, and an image rectangle's RGB8 bytes into pack_images' texel words.  Both leave the tree alone.
 #pragma once
-#include "pathtrace.hpp"
+#include "records.hpp"
 
 namespace cr {
 

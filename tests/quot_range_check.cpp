@@ -1,10 +1,10 @@
-// Host check for tests/test_quotient_host.py: quot_in_range of crucible_amd/csrc/pathtrace.hpp -- the range test of Sphere::hit's
+// Host check for tests/test_quotient_host.py: quot_in_range of crucible_amd/csrc/records.hpp -- the range test of Sphere::hit's
 // short quotient, read from the word that holds sign and exponent -- against frexp: 2^-400 <= |x| < 2^400.  Every power of two of
 // the format with its two neighbours and a few fractions, both signs; zeros, every kind of subnormal, infinities and NaNs; and
 // seeded random bit patterns.  Also: the reciprocal that means "divide" reads as out of range to the guard, and every reciprocal
 // of an in-range divisor reads as valid.
 // usage: quot_range_check SEED  ->  "cases N mismatches M"
-#include "pathtrace.hpp"
+#include "records.hpp"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

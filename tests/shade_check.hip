@@ -20,6 +20,7 @@
 //   DIR/refit.in      n x 5 f64: prim, ta64, tb64, ta32, tb32 -> DIR/refit{64,32}.out: n x 6 f64 (lo xyz, hi xyz)
 // Every result is written as f64 (an f32 result converts exactly).  --host: only the timeline and refit parts, run on the
 // CPU through the same __host__ __device__ functions (no GPU needed).  Exit code 0 when every part ran; 2 on an I/O or HIP error.
+#include "pathtrace.hpp"
 #include "pack.hpp"
 #include "refit.hpp"
 #include <cstdio>

@@ -1,5 +1,5 @@
 """Sphere::hit's quotient with a shared reciprocal, the parts that need no device.
-- tests/quot_range_check.cpp compiles crucible_amd/csrc/pathtrace.hpp with g++ and holds quot_in_range -- the guard's range test --
+- tests/quot_range_check.cpp compiles crucible_amd/csrc/records.hpp with g++ alone (no HIP include path) and holds quot_in_range -- the guard's range test --
   to frexp over every exponent of the format (so at and around both bounds), zeros, subnormals, infinities, NaNs and seeded random
   bit patterns; built twice, plain and with -fsanitize=address,undefined, both must print the same line and nothing on stderr.
 - tests/quotient_check.hip and tests/sphere_hoist_check.hip compile for gfx950.
@@ -24,8 +24,8 @@ def exes(tmp_path_factory):
     built = []
     for tag, extra in (("plain", ()), ("san", ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))):
         exe = str(out / f"quot_range_check_{tag}")
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include",
-                               "-I", os.path.join(ROOT, "crucible_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "quot_range_check.cpp")])
+        subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-I", os.path.join(ROOT, "crucible_amd", "csrc"), "-o", exe,
+                               os.path.join(ROOT, "tests", "quot_range_check.cpp")])
         built.append(exe)
     return built
 

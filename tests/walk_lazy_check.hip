@@ -11,6 +11,7 @@
 //   -> lds.out, top.out (and lds_sl.out on an unordered tree: SPHERE_LOOP): S x P x n RayOut, then S x P x B WaveOut
 // Exit code 0 when it ran; 2 on an I/O, input or HIP error.
 #define CR_DIAG 1
+#include "pathtrace.hpp"
 #include "tree.hpp"
 #include "screen.hpp"
 #include "handle.hpp"

@@ -21,6 +21,7 @@
 //                        An f32 CR_BVH_SAH_ORDERED scene has no SCREEN kernel.
 // Exit code 0 when it ran; 2 on an I/O, input or HIP error.
 #define CR_DIAG 1
+#include "pathtrace.hpp"
 #include "tree.hpp"
 #include "screen.hpp"
 #include "handle.hpp"
