@@ -197,8 +197,8 @@ int32_t adaptive_passes(CrHandle* h, const AdaptiveRun& run, const AdaptiveFrame
     if ((rc = need(h->ad_lists, 2 * n_tiles * sizeof(int32_t), "adaptive tile lists")) != CR_OK) return rc;
     if ((rc = need(h->ad_block_n, n_blocks * sizeof(int32_t), "adaptive block counts")) != CR_OK) return rc;
     if ((rc = need(h->ad_ctrl, 16, "adaptive cursor")) != CR_OK) return rc;
-    if (!h->ad_ev0) HIP_TRY(h, hipEventCreate(&h->ad_ev0));
-    if (!h->ad_ev1) HIP_TRY(h, hipEventCreate(&h->ad_ev1));
+    HIP_TRY(h, h->ad_ev0.create());
+    HIP_TRY(h, h->ad_ev1.create());
     AdaptiveTotals tot;
     for (int32_t f0 = 0; f0 < fr.n_frames; f0 += cap)
         if ((rc = adaptive_pass_loop(h, run, fr, pass, f0, std::min(cap, fr.n_frames - f0), tot)) != CR_OK) return rc;

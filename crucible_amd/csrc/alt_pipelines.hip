@@ -102,7 +102,7 @@ int32_t wf_run(CrHandle* h, WfArgs<real>& W, size_t lds_bytes, int32_t s_begin, 
             if (it >= LAG) {   // lagged check: the GPU is already LAG iterations ahead, so it never waits for the host
                 int k = it - LAG;
                 HIP_TRY(h, hipEventSynchronize(h->wf_ev[k % RING]));
-                if (h->wf_ring_host[k % RING] == 0) break;   // logic found nothing to trace and no job left: batch done
+                if (((const uint32_t*)h->wf_ring_host.p)[k % RING] == 0) break;   // logic found nothing to trace and no job left: batch done
             }
         }
         hipLaunchKernelGGL((wf_finalize_kernel<real>), dim3(fin_grid), dim3(256), 0, h->stream, W);
@@ -152,11 +152,10 @@ int32_t render_wavefront(CrHandle* h, const KernelArgs<real>& a, DevScene<real>&
     HIP_TRY(h, h->wf_samples.ensure((size_t)cap * npix * 3 * sizeof(real)));
     HIP_TRY(h, h->wf_acc.ensure(npix * 3 * sizeof(real)));
     HIP_TRY(h, h->att_stack.ensure((size_t)3 * (size_t)std::max(1, a.max_depth) * N * sizeof(real)));
-    if (!h->wf_ring_host) {
-        HIP_TRY(h, hipHostMalloc((void**)&h->wf_ring_host, 64, hipHostMallocMapped));
-        HIP_TRY(h, hipHostGetDevicePointer((void**)&h->wf_ring_dev, h->wf_ring_host, 0));
-        for (int i = 0; i < 8; i++) HIP_TRY(h, hipEventCreateWithFlags(&h->wf_ev[i], hipEventDisableTiming));
-    }
+    // the ring, its device address and its events: each made once, so a call that failed halfway is completed by the next
+    HIP_TRY(h, h->wf_ring_host.ensure(64, hipHostMallocMapped));
+    if (!h->wf_ring_dev) HIP_TRY(h, hipHostGetDevicePointer((void**)&h->wf_ring_dev, h->wf_ring_host.p, 0));
+    for (int i = 0; i < 8; i++) HIP_TRY(h, h->wf_ev[i].create(hipEventDisableTiming));
     W.k.att_stack = (real*)h->att_stack.p;
     W.k.n_threads = W.n_slots;
     W.job = (uint32_t*)h->wf_job.p; W.rng = (uint64_t*)h->wf_rng.p; W.ray = (real*)h->wf_ray.p; W.depth = (int32_t*)h->wf_depth.p;

@@ -111,7 +111,7 @@ static int32_t call_device(CrHandle* h, const CrCameraDesc* cam, const CrRenderP
     int32_t rc = call.layers ? (f64 ? aov_typed<double>(h, cam, p, call, d_out, stats) : aov_typed<float>(h, cam, p, call, d_out, stats))
                              : (f64 ? render_typed<double>(h, cam, p, call, d_out, stats) : render_typed<float>(h, cam, p, call, d_out, stats));
     if (h->cam_pending_slot >= 0) {   // the camera-key slot is free again once everything queued so far has run
-        hipError_t e = hipEventRecord(h->cam_ev[h->cam_pending_slot], h->stream);
+        hipError_t e = hipEventRecord(h->cam[h->cam_pending_slot].ev, h->stream);
         h->cam_pending_slot = -1;
         if (e != hipSuccess && rc == CR_OK) { h->error = std::string("hipEventRecord: ") + hipGetErrorString(e); rc = CR_ERR_HIP; }
     }
@@ -245,9 +245,9 @@ int32_t cr_create(int32_t device_id, CrHandle** out) {
     hipDeviceProp_t prop;
     if ((e = hipGetDeviceProperties(&prop, device_id)) != hipSuccess) return bail("hipGetDeviceProperties", e);
     h->n_cus = prop.multiProcessorCount;
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipEventCreate(&h->ev0)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreate(&h->ev1)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = h->stream.create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = h->ev0.create()) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = h->ev1.create()) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = h->work_counter.ensure(16)) != hipSuccess) return bail("hipMalloc", e);
     if ((e = h->counters.ensure(64 * sizeof(uint64_t))) != hipSuccess) return bail("hipMalloc", e);
     if (const char* s = getenv("CRUCIBLE_LDS_LIMIT")) h->lds_limit = (size_t)atol(s);
@@ -283,32 +283,7 @@ int32_t cr_create(int32_t device_id, CrHandle** out) {
     return CR_OK;
 }
 
-void cr_destroy(CrHandle* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->s32.release(); h->s64.release(); h->f32.release(); h->f64.release(); h->update_stage.release(); h->sah_work.release();
-    h->images.release(); h->texels.release(); h->work_counter.release(); h->counters.release();
-    h->att_stack.release(); h->out_buf.release(); h->sample_buf.release(); h->sg_acc.release(); h->fx_acc.release(); h->aov_acc.release(); h->aov_flags.release(); h->aov_counts.release();
-    h->wf_job.release(); h->wf_rng.release(); h->wf_ray.release(); h->wf_depth.release(); h->wf_hit_t.release(); h->wf_hit_prim.release();
-    h->wf_chunk.release(); h->wf_ctrl.release(); h->wf_samples.release(); h->wf_acc.release();
-    for (int i = 0; i < CrHandle::kCamSlots; i++) {
-        if (h->cam_host[i]) (void)hipHostFree(h->cam_host[i]);
-        h->cam_dev[i].release();
-        if (h->cam_ev[i]) (void)hipEventDestroy(h->cam_ev[i]);
-    }
-    h->ad_acc.release(); h->ad_lists.release(); h->ad_block_n.release(); h->ad_ctrl.release(); h->ad_counts.release();
-    if (h->ad_ev0) (void)hipEventDestroy(h->ad_ev0);
-    if (h->ad_ev1) (void)hipEventDestroy(h->ad_ev1);
-    if (h->times_host) (void)hipHostFree(h->times_host);
-    h->times_dev.release();
-    if (h->times_ev) (void)hipEventDestroy(h->times_ev);
-    if (h->wf_ring_host) { (void)hipHostFree(h->wf_ring_host); for (int i = 0; i < 8; i++) if (h->wf_ev[i]) (void)hipEventDestroy(h->wf_ev[i]); }
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void cr_destroy(CrHandle* h) { if (h) delete h; }   // ~CrHandle drains the stream; the members give their resources back
 
 // The twenty-eight render entry points: four families (render, guide layers, adaptive, guide layers at a count plane) in
 // three shapes (one frame, a batch of frames, a region of a frame) into device or host memory, and the batches of views of

@@ -24,8 +24,7 @@ int32_t build_lbvh(CrHandle* h, const std::vector<Prim<real>>& src, const std::v
     if (n == 0) return CR_OK;
     const LbvhBounds bnd = lbvh_bounds(bmin, bmax, n);
     DevBuf d_src, d_keys, d_keys2, d_idx, d_idx2, d_tmp, d_children;
-    auto cleanup = [&] { d_src.release(); d_keys.release(); d_keys2.release(); d_idx.release(); d_idx2.release(); d_tmp.release(); d_children.release(); };
-#define LBVH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(h, CR_ERR_HIP, hipGetErrorString(e_)); } } while (0)
+#define LBVH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(h, CR_ERR_HIP, hipGetErrorString(e_)); } while (0)
     LBVH_TRY(d_src.ensure((size_t)n * sizeof(Prim<real>)));
     LBVH_TRY(hipMemcpyAsync(d_src.p, src.data(), (size_t)n * sizeof(Prim<real>), hipMemcpyHostToDevice, h->stream));
     LBVH_TRY(d_keys.ensure((size_t)n * 8)); LBVH_TRY(d_keys2.ensure((size_t)n * 8));
@@ -50,7 +49,6 @@ int32_t build_lbvh(CrHandle* h, const std::vector<Prim<real>>& src, const std::v
     if (n >= 2) LBVH_TRY(hipMemcpyAsync(children.data(), d_children.p, (size_t)(n - 1) * 8, hipMemcpyDeviceToHost, h->stream));
     LBVH_TRY(hipStreamSynchronize(h->stream));
 #undef LBVH_TRY
-    cleanup();
     if (!lbvh_number(children, n, entries, level_begin)) return fail(h, CR_ERR_HIP, "LBVH: malformed topology from the device");
     return CR_OK;
 }

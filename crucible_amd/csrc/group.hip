@@ -44,7 +44,7 @@ int32_t cr_group_create(const int32_t* device_ids, int32_t n_devices, CrGroup** 
         if (r != ncclSuccess) { g_group_create_error = std::string("ncclCommInitAll: ") + api.GetErrorString(r); g->comms.clear(); group_free(g); return CR_ERR_HIP; }
     }
     (void)hipSetDevice(g->members[0]->device);
-    if (hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess) { g_group_create_error = "hipEventCreate failed"; group_free(g); return CR_ERR_HIP; }
+    if (g->ev0.create() != hipSuccess || g->ev1.create() != hipSuccess) { g_group_create_error = "hipEventCreate failed"; group_free(g); return CR_ERR_HIP; }
     *out = g;
     return CR_OK;
 }
@@ -87,7 +87,7 @@ int32_t cr_group_create_rank(int32_t device_id, int32_t rank, int32_t world_size
         if (r != ncclSuccess) { g_group_create_error = std::string("ncclCommInitRank: ") + api.GetErrorString(r); g->comms.clear(); group_free(g); return CR_ERR_HIP; }
     }
     (void)hipSetDevice(device_id);
-    if (hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess) { g_group_create_error = "hipEventCreate failed"; group_free(g); return CR_ERR_HIP; }
+    if (g->ev0.create() != hipSuccess || g->ev1.create() != hipSuccess) { g_group_create_error = "hipEventCreate failed"; group_free(g); return CR_ERR_HIP; }
     *out = g;
     return CR_OK;
 }

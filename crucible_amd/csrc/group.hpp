@@ -115,7 +115,7 @@ struct CrGroup {
     bool poisoned = false;             // a collective call failed: peers may still be inside it, the communicators are gone
     int first = 0;                     // group-wide index of members[0]
     int world = 1;                     // members in the whole group
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // on the root member's stream: reduce + divide
+    DevEvent ev0, ev1;                 // on the root member's stream: reduce + divide
     std::string error;
 };
 
@@ -156,7 +156,7 @@ void group_free(CrGroup* g) {
         if (i < g->partial.size()) g->partial[i].release();
         if (i < g->flags.size()) g->flags[i].release();
         if (i < g->status.size()) g->status[i].release();
-        if (i == 0) { if (g->ev0) (void)hipEventDestroy(g->ev0); if (g->ev1) (void)hipEventDestroy(g->ev1); }
+        if (i == 0) { g->ev0.release(); g->ev1.release(); }
         cr_destroy(g->members[i]);
     }
     delete g;

@@ -20,6 +20,8 @@
 //   alt_pipelines.hip  the wavefront and LDS-queue cross-check pipelines (wavefront.hpp, queue.hpp)
 //   adaptive.hip       the adaptive family behind its entry points: its argument checks, the pass loop, the judge and finalize kernels (adaptive.hpp)
 //   api.hip            cr_create / cr_destroy, all cr_render_* entry points over one RenderCall, errors;  files.hip: PPM / PNG writers;  group.hip: cr_group_*
+// What the host side holds on the device is owned by the types of devres.hpp (device memory, events, pinned memory, the stream):
+// deleting a handle gives everything back, and no unit frees or destroys by hand.
 // The path tracer's code lies in layered headers.  This header reads the bottom layer alone -- records.hpp: the
 // records, KernelArgs, MaxBlock and LatencyBlock, over hd.hpp's CR_HD / CR_D -- and launch_plan.hpp, so api, group, scene, build,
 // sah_device, adaptive, aov and render parse no kernel code of it.  The units that emit its kernels (render_*, render_views_*,
@@ -29,8 +31,7 @@
 #include "../../include/crucible_hip.h"
 #include "records.hpp"       // the records and KernelArgs; no kernel code of the path tracer: the units that launch it include pathtrace.hpp
 #include "launch_plan.hpp"   // fx_scale_for, and what launch() and aov_launch() ask about their launches
-
-#include <hip/hip_runtime.h>   // hipError_t, hipStream_t, hipMalloc: this header is read by hipcc alone
+#include "devres.hpp"        // DevBuf, DevEvent, PinnedBuf, DevStream, CamSlot: what owns the device resources (and <hip/hip_runtime.h>)
 
 #include <algorithm>
 #include <cmath>
@@ -44,21 +45,6 @@
 
 namespace cr {
 
-struct DevBuf {
-    void* p = nullptr;      // what users address: raw + pad
-    void* raw = nullptr;    // the allocation (hipMalloc aligns it to 256 bytes)
-    size_t bytes = 0, pad = 0;
-    // pad: bytes skipped at the front, so that p is deliberately MISaligned by that much (see entry_pad)
-    hipError_t ensure(size_t n, size_t front_pad = 0) {
-        if (n <= bytes && front_pad == pad) return hipSuccess;
-        if (raw) (void)hipFree(raw);
-        p = raw = nullptr; bytes = 0; pad = 0;
-        hipError_t e = hipMalloc(&raw, n + front_pad);
-        if (e == hipSuccess) { bytes = n; pad = front_pad; p = (char*)raw + front_pad; }
-        return e;
-    }
-    void release() { if (raw) (void)hipFree(raw); p = raw = nullptr; bytes = 0; pad = 0; }
-};
 // Sibling wrappers are adjacent in the level-order array and start at ODD indices (1,2), (3,4), ...  Skipping one
 // entry at the front of the allocation puts every pair on one 2*sizeof(Entry) boundary: the two children of a
 // wrapper then share a cache line (f64: exactly one 128-byte line), so the walk's left-then-right visits touch it once.
@@ -104,25 +90,28 @@ template <typename real> struct DevScene {
     bool frame_valid = false;
     real frame_ta = real(0), frame_tb = real(0);
     DevBuf frame_map;                        // a frame build's index tables on the device (input positions, then gather sources)
-    void release() { frame_map.release(); frame_valid = false; last_walk = kWalkNone; desc_pos.release(); desc_pos_valid = false; side_tables = false; entries.release(); entries_refit.release(); screen.release(); screen_refit.release(); screen_overflow.release(); screen_usable = true; nan_planes = false; leaf_runs.release(); prims.release(); mats.release(); texs.release(); keys.release(); built = false; }
 };
 
 }   // namespace cr
 
 using cr::DevBuf;
+using cr::DevEvent;
+using cr::PinnedBuf;
+using cr::DevStream;
+using cr::CamSlot;
 using cr::DevScene;
 
 // The device-side SAH build's working set (sah_device.hip).  Grow-only and kept on the handle, so that a rebuild of the
-// same scene allocates nothing; an upload without CR_BVH_BUILD_DEVICE and cr_destroy release it.
+// same scene allocates nothing; an upload without CR_BVH_BUILD_DEVICE releases it.
 struct SahDeviceWork {
     DevBuf box, order[2], seg[2], pbins, flags, scan, tmp, slots[2], nodes, small, ctr;
-    void release() { for (DevBuf* b : {&box, &order[0], &order[1], &seg[0], &seg[1], &pbins, &flags, &scan, &tmp, &slots[0], &slots[1], &nodes, &small, &ctr}) b->release(); }
+    void release() { *this = SahDeviceWork(); }
 };
 
 struct CrHandle {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevStream stream;                 // declared before every other resource: destroyed after all of them
+    DevEvent ev0, ev1;
     int n_cus = 0;
     std::string error;
     // host copy of the scene description
@@ -153,9 +142,7 @@ struct CrHandle {
     // renders (a movie's frames) never see each other's keys.
     static constexpr int kCamSlots = 4;
     static constexpr size_t kMaxCamKeys = 512;
-    void* cam_host[kCamSlots] = {};
-    DevBuf cam_dev[kCamSlots];
-    hipEvent_t cam_ev[kCamSlots] = {};
+    CamSlot cam[kCamSlots];
     int cam_next = 0, cam_pending_slot = -1;
     DevBuf sample_buf, sg_acc;   // sample-granular megakernel: per-sample colours of a batch, running sums between batches
     DevBuf aov_acc, aov_flags;   // cr_render_aov_*: per pixel 8 x u64 (albedo, normal, coverage sums; depth) and the channels' NaN bits
@@ -165,22 +152,21 @@ struct CrHandle {
     // tile lists, each block's final sample count, the judge's cursor, the count plane of the host form; the judge's events.
     // cr_render_adaptive_frames_*: of all frames of a pass loop -- E of every frame, then O of every frame
     DevBuf ad_acc, ad_lists, ad_block_n, ad_ctrl, ad_counts;
-    hipEvent_t ad_ev0 = nullptr, ad_ev1 = nullptr;
+    DevEvent ad_ev0, ad_ev1;
     // cr_render_frames_*: a batch's per-frame ray times travel through one pinned host buffer, refilled only after the
     // previous batch's copy has run (times_ev); the device table is reused in stream order.  cr_render_views_*: the views'
     // camera records (CamConst, one per view) follow the times in the same table, at the next multiple of 16 bytes
-    void* times_host = nullptr;
-    size_t times_cap = 0;
+    PinnedBuf times_host;
     DevBuf times_dev;
-    hipEvent_t times_ev = nullptr;
+    DevEvent times_ev;
     int screen_boxes = 1;        // f64, unordered trees: box tests decided on f32 screening records where f32 can (CRUCIBLE_SCREEN=0: never)
     int screen_lds = 1;          // ... also for scenes that sit in LDS whole (CRUCIBLE_SCREEN_LDS=0: only trees read from global memory)
     int default_sum_order = CR_SUM_RELAXED;   // what CR_SUM_DEFAULT means on this handle (CRUCIBLE_SUM_ORDER=reference|relaxed)
     // wavefront pipeline state (wavefront.hpp)
     DevBuf wf_job, wf_rng, wf_ray, wf_depth, wf_hit_t, wf_hit_prim, wf_chunk, wf_ctrl, wf_samples, wf_acc;
-    uint32_t* wf_ring_host = nullptr;   // host-mapped ring the extend kernel reports its queue length into
-    uint32_t* wf_ring_dev = nullptr;
-    hipEvent_t wf_ev[8] = {};
+    PinnedBuf wf_ring_host;             // host-mapped ring the extend kernel reports its queue length into (16 words)
+    uint32_t* wf_ring_dev = nullptr;    // its device address: borrowed, owns nothing
+    DevEvent wf_ev[8];
     int pipeline = 0;                   // 0 = megakernel (default), 1 = wavefront kernels, 2 = LDS-queue megakernel (CRUCIBLE_PIPELINE=mega|wavefront|queue)
     int queue_walk_waves = 9, queue_min_batch = 48, queue_patience = 64;
     uint32_t wf_slots = 1u << 21;
@@ -217,6 +203,8 @@ struct CrHandle {
     int last_block = 0, last_grid = 0;
     bool check_abort = false;          // the last launch was a queue kernel whose abort word has not been read yet
     bool keep_counters = false;        // a render without a CrStats still counts: its counters are read later (a group's member, group.hip)
+    // The handle's work drains on its device before the members give their resources back (in reverse order of declaration)
+    ~CrHandle() { (void)hipSetDevice(device); if (stream) (void)hipStreamSynchronize(stream); }
 };
 
 namespace cr {
@@ -364,11 +352,9 @@ template <typename real> inline SceneLayout whole_scene_layout(const DevScene<re
 }
 // LDS a scene takes when it sits there whole with its wrappers
 template <typename real> inline size_t scene_lds_bytes(const DevScene<real>& ds) { return whole_scene_layout(ds, ds.entry_bytes).end(); }
-// A frame tree's side tables are the base tree's (not owned: a DevBuf without an allocation of its own releases nothing)
+// A frame tree's side tables are the base tree's (DevBuf::borrow: not owned)
 template <typename real> inline void alias_side_tables(DevScene<real>& fs, const DevScene<real>& base) {
-    for (auto pr : {std::make_pair(&fs.mats, &base.mats), std::make_pair(&fs.texs, &base.texs), std::make_pair(&fs.keys, &base.keys)}) {
-        pr.first->p = pr.second->p; pr.first->raw = nullptr; pr.first->bytes = pr.second->bytes; pr.first->pad = pr.second->pad;
-    }
+    fs.mats.borrow(base.mats); fs.texs.borrow(base.texs); fs.keys.borrow(base.keys);
     fs.n_mats = base.n_mats; fs.n_texs = base.n_texs; fs.n_scene_keys = base.n_scene_keys;
 }
 

@@ -50,18 +50,15 @@ int32_t pick_block(CrHandle* h, const void* kern, int max_block, bool ignore_lar
 // (cr_render_views_*: the views' camera records behind the times, one table)
 int32_t stage_frame_times(CrHandle* h, const void* times, size_t bytes) {
     if (h->times_ev) HIP_TRY(h, hipEventSynchronize(h->times_ev));   // the previous batch's copy has read the staging buffer
-    else HIP_TRY(h, hipEventCreateWithFlags(&h->times_ev, hipEventDisableTiming));
-    if (bytes > h->times_cap) {
-        if (h->times_host) (void)hipHostFree(h->times_host);
-        h->times_host = nullptr; h->times_cap = 0;
-        const hipError_t e = hipHostMalloc(&h->times_host, bytes, hipHostMallocDefault);
-        if (e != hipSuccess) { h->times_host = nullptr; (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("frame times: ") + hipGetErrorString(e)); }
-        h->times_cap = bytes;
+    else HIP_TRY(h, h->times_ev.create(hipEventDisableTiming));
+    {
+        const hipError_t e = h->times_host.ensure(bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("frame times: ") + hipGetErrorString(e)); }
     }
     const hipError_t e = h->times_dev.ensure(bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("frame times: ") + hipGetErrorString(e)); }
-    memcpy(h->times_host, times, bytes);
-    HIP_TRY(h, hipMemcpyAsync(h->times_dev.p, h->times_host, bytes, hipMemcpyHostToDevice, h->stream));
+    memcpy(h->times_host.p, times, bytes);
+    HIP_TRY(h, hipMemcpyAsync(h->times_dev.p, h->times_host.p, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipEventRecord(h->times_ev, h->stream));
     return CR_OK;
 }
@@ -99,25 +96,16 @@ int32_t prepare_args(CrHandle* h, const CrCameraDesc* cd, const CrRenderParams* 
         const int slot = h->cam_next;
         h->cam_next = (slot + 1) % CrHandle::kCamSlots;
         const size_t slot_bytes = CrHandle::kMaxCamKeys * sizeof(Key<double>);
-        if (!h->cam_host[slot]) {   // the slot's three resources together, or none of them (a later render tries again)
-            void* host = nullptr;
-            hipEvent_t ev = nullptr;
-            hipError_t e = hipHostMalloc(&host, slot_bytes, hipHostMallocDefault);
-            if (e == hipSuccess) e = h->cam_dev[slot].ensure(slot_bytes);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e != hipSuccess) {
-                if (host) (void)hipHostFree(host);
-                h->cam_dev[slot].release();
-                (void)hipGetLastError();
-                return fail(h, CR_ERR_HIP, std::string("camera keyframe slot: ") + hipGetErrorString(e));
-            }
-            h->cam_host[slot] = host; h->cam_ev[slot] = ev;
-        } else HIP_TRY(h, hipEventSynchronize(h->cam_ev[slot]));   // the slot's previous user has finished with it
-        Key<real>* ck = (Key<real>*)h->cam_host[slot];
+        CamSlot& cs = h->cam[slot];
+        if (!cs) {   // the slot's three resources together, or none of them (a later render tries again)
+            const hipError_t e = cs.acquire(slot_bytes);
+            if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, CR_ERR_HIP, std::string("camera keyframe slot: ") + hipGetErrorString(e)); }
+        } else HIP_TRY(h, hipEventSynchronize(cs.ev));   // the slot's previous user has finished with it
+        Key<real>* ck = (Key<real>*)cs.host.p;
         if (call.views) pack_view_keys(call.views, call.n_frames, ck);
         else pack_view_keys(cd, 1, ck);
-        HIP_TRY(h, hipMemcpyAsync(h->cam_dev[slot].p, ck, nk * sizeof(Key<real>), hipMemcpyHostToDevice, h->stream));
-        a.cam_keys = (const Key<real>*)h->cam_dev[slot].p;
+        HIP_TRY(h, hipMemcpyAsync(cs.dev.p, ck, nk * sizeof(Key<real>), hipMemcpyHostToDevice, h->stream));
+        a.cam_keys = (const Key<real>*)cs.dev.p;
         h->cam_pending_slot = slot;
     }
     pack_camera_frame(c);   // static camera: the per-sample vectors

@@ -1,18 +1,27 @@
-"""Every resource a handle declares is given back by name.
+"""Every resource a handle holds is owned by a type, and the types give it back: checked by running them.
 
-DevBuf has no destructor: cr_destroy, DevScene::release, SahDeviceWork::release and group_free are lists a person keeps.
-This reads the declarations in crucible_amd/csrc/handle.hpp and group.hpp -- every DevBuf, every hipEvent_t and every pinned
-host pointer of CrHandle, DevScene, SahDeviceWork and CrGroup -- and asserts that each name is released in the body that
-owns it.  A member added without its release fails here, on the CPU; tests/test_gpu_handle_memory.py can only see a leak of
-an allocation granule or more per handle."""
+The device buffers, events, pinned blocks and the stream of CrHandle, DevScene, SahDeviceWork and CrGroup are DevBuf, DevEvent,
+PinnedBuf, DevStream and CamSlot members (crucible_amd/csrc/devres.hpp), whose destructors release them.  This compiles
+tests/handle_lifetime_check.cpp with g++ and the address and undefined-behaviour sanitizers against tests/hip_stub, a stand-in
+for the HIP runtime that counts what is live and logs every call, and runs it: each type's ensure / create / release / move /
+borrow, CamSlot::acquire with each of its three allocations failing, and a whole CrHandle whose every owning member -- found
+here by its declared type in handle.hpp, not by a list -- is filled and which is then deleted.  What no program can show, that
+no resource sits in a member no type owns, the declarations and a search of the sources show."""
 import os
 import re
+import subprocess
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "crucible_amd", "csrc")
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "crucible_amd", "csrc")
+TESTS = os.path.join(ROOT, "tests")
 
 # raw pointer members that own nothing, and why
-BORROWED = {"wf_ring_dev": "the device address of wf_ring_host (hipHostGetDevicePointer)",
-            "p": "DevBuf's own", "raw": "DevBuf's own"}
+BORROWED = {"wf_ring_dev": "the device address of wf_ring_host's block (hipHostGetDevicePointer): freed with it"}
+
+OWNING = r"DevBuf|DevEvent|PinnedBuf|DevStream|CamSlot"
+TOUCH = {"DevBuf": "ensure_buf", "DevEvent": "create_event", "PinnedBuf": "ensure_pinned", "DevStream": "create_stream", "CamSlot": "acquire_slot"}
 
 
 def read(name):
@@ -40,12 +49,6 @@ def struct_body(text, name):
     m = re.search(r"\bstruct\s+" + name + r"\s*\{", text)
     assert m, name
     return braces(text, m.start())
-
-
-def function_body(text, signature):
-    m = re.search(signature, text)
-    assert m, signature
-    return braces(text, m.end() - 1)
 
 
 def without_functions(body):
@@ -88,92 +91,102 @@ def pointer_members(body):
     return names
 
 
-def released(body, name, how):
-    """`name` handed to `how` in `body`: name.release(), &name (a list of buffers that is released in a loop),
-    hipEventDestroy(.. name ..), hipHostFree(.. name ..)."""
-    n = re.escape(name)
-    if how == "release":
-        return bool(re.search(r"(?:->|\b)" + n + r"(?:\[\w+\])?\s*\.\s*release\s*\(", body) or re.search(r"&\s*" + n + r"\b", body))
-    return bool(re.search(how + r"\s*\(\s*(?:\(void\*\)\s*)?(?:\w+->)?" + n + r"\b", body))
-
-
 HANDLE = strip_comments(read("handle.hpp"))
-API = strip_comments(read("api.hip"))
-GROUP = strip_comments(read("group.hpp")) + strip_comments(read("group.hip"))
+GROUP = strip_comments(read("group.hpp"))
+STRUCTS = {"CrHandle": struct_body(HANDLE, "CrHandle"), "DevScene": struct_body(HANDLE, "DevScene"),
+           "SahDeviceWork": struct_body(HANDLE, "SahDeviceWork"), "CrGroup": struct_body(GROUP, "CrGroup")}
 
 
-def owners():
-    """(struct, its body, the body that releases its members)"""
-    return [("CrHandle", struct_body(HANDLE, "CrHandle"), function_body(API, r"void\s+cr_destroy\s*\([^)]*\)\s*\{")),
-            ("DevScene", struct_body(HANDLE, "DevScene"), function_body(struct_body(HANDLE, "DevScene"), r"void\s+release\s*\(\s*\)\s*\{")),
-            ("SahDeviceWork", struct_body(HANDLE, "SahDeviceWork"), function_body(struct_body(HANDLE, "SahDeviceWork"), r"void\s+release\s*\(\s*\)\s*\{")),
-            ("CrGroup", struct_body(GROUP, "CrGroup"), function_body(GROUP, r"void\s+group_free\s*\([^)]*\)\s*\{"))]
+def touches(body, prefix):
+    """One C++ statement per owning member of `body`, by its declared type."""
+    return [f"    each({prefix}{name}, {TOUCH[kind]});" for kind in TOUCH for name in members(body, kind)]
 
 
-def missing():
-    out = []
-    for struct, body, free in owners():
-        for name in members(body, r"DevBuf|std::vector<DevBuf>|DevScene<\w+>|SahDeviceWork"):
-            if not released(free, name, "release"):
-                out.append(f"{struct}::{name}: no release()")
-        for name in members(body, r"hipEvent_t"):
-            if not released(free, name, "hipEventDestroy"):
-                out.append(f"{struct}::{name}: no hipEventDestroy")
-        for name in pointer_members(body):
-            if name in BORROWED:
-                continue
-            if not released(free, name, "hipHostFree"):
-                out.append(f"{struct}::{name}: no hipHostFree (or say in BORROWED why it owns nothing)")
-        if struct == "CrHandle":
-            if not re.search(r"hipStreamDestroy\s*\(\s*h->stream", free):
-                out.append("CrHandle::stream: no hipStreamDestroy")
-        if struct == "CrGroup":
-            if not re.search(r"CommDestroy\s*\(\s*g->comms", free) or not re.search(r"cr_destroy\s*\(\s*g->members", free):
-                out.append("CrGroup: comms or members not destroyed")
-    return out
+def touch_source():
+    """touch_handle: every owning member of CrHandle, those of its four scenes and of its SAH working set included."""
+    lines = ["static void touch_handle(CrHandle& h) {"] + touches(STRUCTS["CrHandle"], "h.")
+    scenes = members(STRUCTS["CrHandle"], r"DevScene<\w+>")
+    for scene in scenes:
+        lines += touches(STRUCTS["DevScene"], f"h.{scene}.")
+    for work in members(STRUCTS["CrHandle"], "SahDeviceWork"):
+        lines += touches(STRUCTS["SahDeviceWork"], f"h.{work}.")
+    lines += ["}", "static void touch_sah_work(SahDeviceWork& w) {"] + touches(STRUCTS["SahDeviceWork"], "w.") + ["}"]
+    return "\n".join(lines) + "\n", scenes
+
+
+@pytest.fixture(scope="module")
+def check_run(tmp_path_factory):
+    """handle_lifetime_check.cpp over the generated handle_touch.inc: compiled once, run once as a child process."""
+    tmp = tmp_path_factory.mktemp("handle_lifetime")
+    source, _ = touch_source()
+    (tmp / "handle_touch.inc").write_text(source)
+    exe = str(tmp / "handle_lifetime_check")
+    res = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(TESTS, "hip_stub"),
+                          "-I", CSRC, "-I", str(tmp), os.path.join(TESTS, "handle_lifetime_check.cpp"), "-o", exe],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr
+    return subprocess.run([exe], capture_output=True, text=True, timeout=120)
 
 
 def test_the_parser_sees_the_members():
-    by = {s: b for s, b, _ in owners()}
-    h = members(by["CrHandle"], r"DevBuf")
+    h = members(STRUCTS["CrHandle"], r"DevBuf")
     for name in ("fx_acc", "aov_acc", "aov_flags", "aov_counts", "ad_acc", "ad_lists", "ad_block_n", "ad_ctrl", "ad_counts", "out_buf", "sample_buf", "sg_acc",
-                 "att_stack", "times_dev", "update_stage", "cam_dev", "images", "texels", "work_counter", "counters", "wf_job", "wf_acc"):
+                 "att_stack", "times_dev", "update_stage", "images", "texels", "work_counter", "counters", "wf_job", "wf_acc"):
         assert name in h, name
-    assert len(h) >= 30
-    assert set(members(by["CrHandle"], r"hipEvent_t")) == {"ev0", "ev1", "cam_ev", "ad_ev0", "ad_ev1", "times_ev", "wf_ev"}
-    assert set(pointer_members(by["CrHandle"])) == {"cam_host", "times_host", "wf_ring_host", "wf_ring_dev"}
-    assert set(members(by["CrHandle"], r"DevScene<\w+>")) == {"s32", "s64", "f32", "f64"} and members(by["CrHandle"], r"SahDeviceWork") == ["sah_work"]
-    d = members(by["DevScene"], r"DevBuf")
+    assert len(h) >= 29
+    assert set(members(STRUCTS["CrHandle"], r"DevEvent")) == {"ev0", "ev1", "ad_ev0", "ad_ev1", "times_ev", "wf_ev"}
+    assert set(members(STRUCTS["CrHandle"], r"PinnedBuf")) == {"times_host", "wf_ring_host"}
+    assert members(STRUCTS["CrHandle"], r"DevStream") == ["stream"] and members(STRUCTS["CrHandle"], r"CamSlot") == ["cam"]
+    assert set(pointer_members(STRUCTS["CrHandle"])) == {"wf_ring_dev"}
+    assert set(members(STRUCTS["CrHandle"], r"DevScene<\w+>")) == {"s32", "s64", "f32", "f64"} and members(STRUCTS["CrHandle"], r"SahDeviceWork") == ["sah_work"]
+    d = members(STRUCTS["DevScene"], r"DevBuf")
     for name in ("entries", "prims", "mats", "texs", "keys", "leaf_runs", "entries_refit", "screen", "screen_refit", "screen_overflow", "desc_pos", "frame_map"):
         assert name in d, name
-    assert set(members(by["SahDeviceWork"], r"DevBuf")) == {"box", "order", "seg", "pbins", "flags", "scan", "tmp", "slots", "nodes", "small", "ctr"}
-    assert set(members(by["CrGroup"], r"std::vector<DevBuf>")) == {"partial", "flags", "status"} and set(members(by["CrGroup"], r"hipEvent_t")) == {"ev0", "ev1"}
+    assert set(members(STRUCTS["SahDeviceWork"], r"DevBuf")) == {"box", "order", "seg", "pbins", "flags", "scan", "tmp", "slots", "nodes", "small", "ctr"}
+    assert set(members(STRUCTS["CrGroup"], r"std::vector<DevBuf>")) == {"partial", "flags", "status"} and set(members(STRUCTS["CrGroup"], r"DevEvent")) == {"ev0", "ev1"}
+    # and the generated program touches each of them: a line per member, the scenes' members once per scene
+    source, scenes = touch_source()
+    assert len(scenes) == 4
+    for line in ("each(h.stream, create_stream);", "each(h.cam, acquire_slot);", "each(h.wf_ev, create_event);", "each(h.times_host, ensure_pinned);",
+                 "each(h.aov_flags, ensure_buf);", "each(h.f64.frame_map, ensure_buf);", "each(h.s32.mats, ensure_buf);", "each(h.sah_work.slots, ensure_buf);"):
+        assert source.count(line) == 1, line
+    assert source.count("each(h.") == len(h) + 6 + 2 + 1 + 1 + 4 * len(d) + 11
 
 
-def test_every_member_is_released():
-    assert missing() == []
+def test_the_stream_is_declared_before_every_other_resource():
+    """Members are destroyed in reverse order of declaration: the stream goes last, as the program's log shows."""
+    body = without_functions(STRUCTS["CrHandle"])
+    first = min(m.start() for m in re.finditer(r"\b(?:" + OWNING + r"|DevScene<\w+>|SahDeviceWork)\s+\w", body))
+    assert re.match(r"DevStream\s+stream\b", body[first:])
 
 
-def test_a_dropped_release_is_noticed():
-    """What the check is worth: take one entry out of each list and it fails, naming the member."""
-    global API, HANDLE, GROUP
-    keep = API, HANDLE, GROUP
-    try:
-        for text, which, entry, name in ((API, "API", "h->ad_lists.release();", "CrHandle::ad_lists"),
-                                         (API, "API", "h->cam_dev[i].release();", "CrHandle::cam_dev"),
-                                         (API, "API", "if (h->times_ev) (void)hipEventDestroy(h->times_ev);", "CrHandle::times_ev"),
-                                         (API, "API", "if (h->times_host) (void)hipHostFree(h->times_host);", "CrHandle::times_host"),
-                                         (API, "API", "h->f64.release();", "CrHandle::f64"),
-                                         (HANDLE, "HANDLE", "screen_overflow.release();", "DevScene::screen_overflow"),
-                                         (HANDLE, "HANDLE", "&slots[1], ", None), (HANDLE, "HANDLE", "&scan, ", "SahDeviceWork::scan"),
-                                         (GROUP, "GROUP", "if (i < g->flags.size()) g->flags[i].release();", "CrGroup::flags")):
-            assert text.count(entry) == 1, entry
-            globals()[which] = text.replace(entry, "")
-            found = missing()
-            API, HANDLE, GROUP = keep
-            if name is None:        # slots[0] is still in the list: an array is one name
-                assert found == [], found
-            else:
-                assert len(found) == 1 and found[0].startswith(name + ":"), (entry, found)
-    finally:
-        API, HANDLE, GROUP = keep
+def test_the_check_program_is_clean(check_run):
+    """Under -fsanitize=address,undefined: no finding, no leak, every CHECK held."""
+    assert check_run.returncode == 0, check_run.stdout + check_run.stderr
+    assert "runtime error" not in check_run.stderr and "Sanitizer" not in check_run.stderr, check_run.stderr
+
+
+@pytest.mark.parametrize("section", ["DevBuf", "DevEvent PinnedBuf DevStream", "CamSlot", "CrHandle"])
+def test_the_check_program_ran(check_run, section):
+    """DevBuf etc.: each owning type; CamSlot: acquire with its 1st, 2nd, 3rd allocation failing; CrHandle: the whole handle."""
+    assert ("ok " + section) in check_run.stdout.splitlines(), check_run.stdout + check_run.stderr
+
+
+@pytest.mark.parametrize("struct", sorted(STRUCTS))
+def test_no_member_is_a_raw_resource(struct):
+    body = STRUCTS[struct]
+    assert members(body, r"hipEvent_t|hipStream_t") == []
+    assert [name for name in pointer_members(body) if name not in BORROWED] == []
+
+
+def test_only_devres_frees_and_allocates():
+    found = {}
+    for name in sorted(os.listdir(CSRC)):
+        if not name.endswith((".hpp", ".hip", ".h", ".cpp")):
+            continue
+        text = re.sub(r'"(?:[^"\\\n]|\\.)*"', '""', strip_comments(read(name)))   # calls, not the error texts that name one
+        for call in (r"\bhipFree\b", r"\bhipHostFree\b", r"\bhipEventDestroy\b", r"\bhipStreamDestroy\b", r"\bhipMalloc\(", r"\bhipHostMalloc\(", r"\bhipEventCreate"):
+            if re.search(call, text):
+                found.setdefault(name, []).append(call)
+    assert sorted(found) == ["devres.hpp"], found
+    assert len(found["devres.hpp"]) == 7

@@ -33,7 +33,7 @@ def test_the_bottom_layer_compiles_without_hip(tmp_path, header):
 
 
 @needs_hipcc
-@pytest.mark.parametrize("header", LAYERS + ["pathtrace.hpp", "handle.hpp"])
+@pytest.mark.parametrize("header", LAYERS + ["pathtrace.hpp", "devres.hpp", "handle.hpp"])
 def test_each_header_is_self_contained_for_gfx950(tmp_path, header):
     res = subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", CSRC, one_line_source(tmp_path, header, ".hip")],
                          capture_output=True, text=True, timeout=600)
