@@ -215,8 +215,18 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
     std::conditional_t<COUNT, uint32_t, NoCount> c_seg{}, c_prim{}, c_tex{};
     std::conditional_t<COUNT, unsigned long long, NoCount> c_node{};
     // walk state, kept across rounds: a lane whose walk is cut short resumes where it stopped
-    WalkState<real> ws;
+    // HEAD: the headline's kernels, the ones the switches of the work around the box step apply to (walk.hpp);
+    // OFFS: their position is WalkOffset's LDS address, from walk_start (the first record) to walk_end (walk finished)
+    constexpr bool HEAD = walk_offset<real, RES, ANIM, ORD, CAMK, RELAX, SCREEN>();
+    constexpr bool OFFS = HEAD && CR_WALK_OFFSET != 0;
+    std::conditional_t<OFFS, WalkOffset, WalkState<real>> ws;
+    uint32_t walk_start = 0u, walk_end = 0u;
+    if constexpr (OFFS) {
+        walk_start = screen_lds_base<RES>(lds_screen); walk_end = walk_start + ((uint32_t)A.n_entries << 5);
+        ws.dd = 0; ws.rda = quot_divide<real>(); ws.best_t = 0; ws.best = -1; ws.off = walk_start; ws.pending = -1;
+    } else {
     ws.inv = mk<real>(0, 0, 0); ws.dd = 0; ws.rda = quot_divide<real>(); ws.best_t = 0; ws.best = -1; ws.idx = 0; ws.exact_box = false; ws.pending = -1;
+    }
     constexpr bool LAZY = lazy_inv<real, RES, ANIM, ORD, CAMK, SCREEN>();   // walk_begin_screened / walk_round's LAZY_INV
     if constexpr (LAZY) { ws.invf = mk<float>(0, 0, 0); ws.unscreened = false; }
     const int32_t n_entries = A.n_entries;
@@ -344,7 +354,8 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
             if (depth_left == 0) finished = true;   // ray_color: depth == 0 -> black
             else {
                 c_seg++;
-                if constexpr (LAZY) walk_begin_screened<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, ro, rd);
+                if constexpr (OFFS) walk_begin_screened<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, ro, rd, walk_start);
+                else if constexpr (LAZY) walk_begin_screened<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, ro, rd);
                 else walk_begin<quot_form<real, RES, ANIM, SCREEN>() == 1>(ws, rd, exact_tree != 0u);
                 state = n_entries > 0 ? ST_WALK : ST_SHADE;
             }
@@ -353,6 +364,25 @@ CR_D void pathtrace_body(const KernelArgs<real>& A) {
         // lanes are done: the stragglers keep their WalkState and resume on the next round of the outer loop, so
         // each lane still performs BVHWrapper::hit's exact sequence; only the interleaving with other lanes'
         // shading changes.
+        // The headline's kernels under either switch (walk.hpp): CR_WALK_PRIO -- the rounds run at wave priority 1, everything
+        // else at 0; s_setprio ignores EXEC, so both stand under the scalar branch on the ballot, which the whole wave takes or
+        // skips.  CR_WALK_OFFSET -- "walk finished" is one unsigned compare of the address with walk_end.  With both switches
+        // off, and in every other kernel, the loop below is compiled: one loop with `if constexpr` around the three spots
+        // did not compile those kernels to the code they had, so the loop stands twice.
+        if constexpr (HEAD && (CR_WALK_OFFSET != 0 || CR_WALK_PRIO != 0)) {
+            if (__ballot(state == ST_WALK)) {
+                if constexpr (CR_WALK_PRIO != 0) __builtin_amdgcn_s_setprio(1);
+                for (;;) {
+                    walk_round<real, RES, ANIM, ORD, SCREEN, true, LAZY, sphere_loop<real, RES, ANIM, ORD, CAMK, SCREEN>()>(A, lds_entries, prims, ro, rd, rtime, ws, state == ST_WALK, A.walk_round_steps, c_node, c_prim, dgp, lds_screen);
+                    bool done;
+                    if constexpr (OFFS) done = ws.off >= walk_end; else done = ws.idx >= n_entries;
+                    if (state == ST_WALK && done && ws.pending < 0) state = ST_SHADE;
+                    const uint64_t walking = __ballot(state == ST_WALK);
+                    if (!walking || 64u - (uint32_t)__popcll(walking) >= A.walk_exit_lanes) break;
+                }
+                if constexpr (CR_WALK_PRIO != 0) __builtin_amdgcn_s_setprio(0);
+            }
+        } else
         if (__ballot(state == ST_WALK)) {
             for (;;) {
                 walk_round<real, RES, ANIM, ORD, SCREEN, true, LAZY, sphere_loop<real, RES, ANIM, ORD, CAMK, SCREEN>()>(A, lds_entries, prims, ro, rd, rtime, ws, state == ST_WALK, A.walk_round_steps, c_node, c_prim, dgp, lds_screen);

@@ -1,7 +1,9 @@
 // walk.hpp -- device only: the stackless BVH walk.  Reads of a wrapper from LDS or global memory, the
-// screened box steps of the f64 kernels, WalkState, walk_begin / walk_begin_screened, the experiment switches of the sphere
-// test (CR_QUOT_FORM, CR_SPHERE_LOOP, CR_SHADE_DD, CR_LAZY_INV) and walk_round, which every pipeline and the guide pass
-// call.  Its text has been settled against the register allocator: it moves, it is not edited.
+// screened box steps of the f64 kernels, WalkState and the headline kernels' WalkOffset, walk_begin / walk_begin_screened, the
+// experiment switches of the sphere test (CR_QUOT_FORM, CR_SPHERE_LOOP, CR_SHADE_DD, CR_LAZY_INV) and of the work around the
+// box step (CR_WALK_OFFSET, CR_WALK_PRIO), and walk_round, which every pipeline and the guide pass call.
+// Its text has been settled against the register allocator: an edit is held to compiling every kernel it does
+// not mean to change to the code it had (scripts/kernel_resources.py and the ISA tests; DESIGN.md 3.13 for the last one).
 #pragma once
 #include "intersect.hpp"
 
@@ -145,6 +147,19 @@ template <typename real> struct WalkState : WalkScreened<real> {
     int32_t pending;     // a leaf wrapper whose box was hit and whose primitives are still to be tested (-1: none)
 };
 
+// The state of the kernels of walk_offset() (the headline's two: static f64, relaxed sums, screening records of an unordered tree,
+// the whole scene in LDS): the position is `off`, the LDS address of the next screening record as fetch_screen<RES_LDS> reads
+// it, carried across rounds and outer iterations; screen_lds_base + (n_entries << 5) = walk finished.  An index is made of it
+// only where one is read: the band branch's f64 fetch and the compare/select loop.  No `inv`, `exact_box` or `oct`: a
+// LAZY_INV walk of an unordered tree reads none of them.
+struct WalkOffset : WalkScreened<double> {
+    double dd, rda, best_t;   // as WalkState's
+    int32_t best;
+    uint32_t off;             // next record to visit, an LDS address
+    int32_t pending;
+    static constexpr int32_t oct = 0;   // (named by walk_round's ordered reads, which these kernels do not compile)
+};
+
 // A state that walks nothing, every field set; `idx`: the kernel's own "no walk" (n_entries where walk_round may see the state
 // before a walk_begin).  The cross-check pipelines and the walk check programs begin with it; pathtrace_body and aov_body keep
 // lines of their own that leave unset what their kernels never read: setting that too changes the ordered kernels' code (6.8b).
@@ -170,6 +185,8 @@ template <bool SHARED = false, typename real> CR_D void walk_begin(WalkState<rea
 // ray's classification, once per segment (screen_inv, above screen_q, has the argument).  `inv` and `exact_box` are left as they
 // are: walk_round<..., LAZY_INV = true> reads neither, and divides 1.0 / rd itself where Aabb::hit's f64 form runs.
 template <bool SHARED = false, typename real> CR_D void walk_begin_screened(WalkState<real>& w, V3<real> ro, V3<real> rd);
+// `start`: the address of the tree's first record (screen_lds_base of the staged copy)
+template <bool SHARED = false> CR_D void walk_begin_screened(WalkOffset& w, V3<double> ro, V3<double> rd, uint32_t start);
 
 // One round of the while-while walk for the lanes with `walking` set: step through wrappers in the reference's
 // order (left child on a box hit, skip link on a miss) until the lane reaches a leaf wrapper, runs out of wrappers
@@ -267,6 +284,14 @@ template <bool SHARED, typename real> CR_D void walk_begin_screened(WalkState<re
     w.idx = 0; w.best_t = r_inf(real(0)); w.best = -1; w.pending = -1;
     w.oct = (rd.x < real(0) ? 1 : 0) | (rd.y < real(0) ? 2 : 0) | (rd.z < real(0) ? 4 : 0);
 }
+template <bool SHARED> CR_D void walk_begin_screened(WalkOffset& w, V3<double> ro, V3<double> rd, uint32_t start) {
+    w.invf = mk<float>(screen_inv(rd.x), screen_inv(rd.y), screen_inv(rd.z));
+    const float mo = r_max(r_max(__builtin_fabsf((float)ro.x), __builtin_fabsf((float)ro.y)), __builtin_fabsf((float)ro.z));
+    w.unscreened = !screen_in_range_lazy(mo, w.invf.x, w.invf.y, w.invf.z);
+    w.dd = len2(rd);
+    w.rda = SHARED ? shared_rcp(w.dd) : quot_divide<double>();
+    w.off = start; w.best_t = r_inf(0.0); w.best = -1; w.pending = -1;
+}
 // f64 kernels: hi32 - lo32 on the screening box b, and its TH in `th`.  The decision is d < -th (miss) or d > th (hit);
 // anything else (NaN included) is left to Aabb::hit in f64.
 // hi = r_min(r_min(fx, fy), r_min(fz, tmaxf)) and m = r_max(|lo|, |hi|), written out: the compiler re-quiets the
@@ -329,6 +354,16 @@ template <typename real, int RES, bool ANIM, bool SCREEN> constexpr int quot_for
 #ifndef CR_SHADE_DD
 #define CR_SHADE_DD 1
 #endif
+// The A/B switches of the work around the box step (profiles/experiments/round_overhead_ab.txt), both in
+// the kernels of walk_offset() -- the headline's counted and quiet kernel:
+// -DCR_WALK_OFFSET=0: the position across rounds is WalkState's index, not WalkOffset's LDS address.
+// -DCR_WALK_PRIO=0:   no s_setprio around the rounds loop (1: the walking wave at priority 1, a shading wave at 0).
+#ifndef CR_WALK_OFFSET
+#define CR_WALK_OFFSET 1
+#endif
+#ifndef CR_WALK_PRIO
+#define CR_WALK_PRIO 1
+#endif
 // Which kernels begin a segment with walk_begin_screened and walk with LAZY_INV: decided like quot_form(), from the compiler's
 // allocation and the A/B (DESIGN.md section 3.11 has the table) -- the static f64 render kernels that walk on screening records
 // of an unordered tree.  The keyed and batch kernels (ANIM, CAMK) would gain SGPR spills, the ordered-tree kernels measured
@@ -346,6 +381,11 @@ template <typename real, int RES, bool ANIM, bool ORD, bool CAMK, bool SCREEN> c
     return CR_SPHERE_LOOP && std::is_same<real, double>::value && SCREEN && RES == RES_LDS && !ANIM && !ORD && !CAMK;
 }
 
+// The headline's kernels: the ones the switches above apply to
+template <typename real, int RES, bool ANIM, bool ORD, bool CAMK, bool RELAX, bool SCREEN> constexpr bool walk_offset() {
+    return lazy_inv<real, RES, ANIM, ORD, CAMK, SCREEN>() && RES == RES_LDS && RELAX;
+}
+
 // 1 / direction as walk_begin divides it, for Aabb::hit's f64 form where a LAZY_INV walk runs it
 // (the direction passes through an empty asm: the divisions are loop-invariant and free of side effects, and the optimiser
 // hoisted them out of the band branch and the rounds loop to where walk_begin had them, once per outer iteration)
@@ -359,11 +399,16 @@ template <typename real> CR_D V3<real> inv_of(V3<real> rd) {
 // SPHERE_LOOP (sphere_loop()'s kernels): the leaf phase tests a scene of spheres alone in a loop of its own.
 // CN, CP: the node and primitive counters' types -- NoCount in the kernels that keep no work counters (pathtrace_kernel_quiet).
 template <typename real, int RES, bool ANIM, bool ORD = false, bool SCREEN = false, bool SHARE = false, bool LAZY_INV = false, bool SPHERE_LOOP = false,
-          typename CN = unsigned long long, typename CP = uint32_t>
+          typename CN = unsigned long long, typename CP = uint32_t, typename WS = WalkState<real>>
 CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, const Prim<real>* prims, V3<real> ro, V3<real> rd, real rtime,
-                     WalkState<real>& w, bool walking, uint32_t budget, CN& c_node, CP& c_prim, Diag* dg = nullptr,
+                     WS& w, bool walking, uint32_t budget, CN& c_node, CP& c_prim, Diag* dg = nullptr,
                      const void* lds_screen = nullptr) {
     constexpr bool COUNT = !std::is_same<CN, NoCount>::value;
+    // WS = WalkOffset: the position is the LDS address w.off (obase: the first record's, oend: walk finished)
+    constexpr bool OFFS = std::is_same<WS, WalkOffset>::value;
+    static_assert(!OFFS || (LAZY_INV && RES == RES_LDS && !ORD), "WalkOffset is the state of walk_offset()'s kernels");
+    uint32_t obase = 0u, oend = 0u;
+    if constexpr (OFFS) { obase = screen_lds_base<RES>(lds_screen); oend = obase + ((uint32_t)A.n_entries << 5); }
     // f64: decisions on the f32 copy where f32 can decide; f32 (EXACT below): the record IS the wrapper's box, in the link layout of ScreenEntry
     constexpr bool EXACT = std::is_same<real, float>::value;
     static_assert(!(SCREEN && EXACT && ORD), "the f32 kernels use ScreenEntry records for unordered trees only");
@@ -455,7 +500,8 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
                     // end of the array or with a leaf in hand, and one compare sees both
                     const uint32_t base = screen_lds_base<RES>(lds_screen);
                     const uint32_t end = base + ((uint32_t)n_entries << 5);
-                    uint32_t off = base + ((uint32_t)w.idx << 5), after_leaf = 0;
+                    uint32_t off, after_leaf = 0;
+                    if constexpr (OFFS) off = w.off; else off = base + ((uint32_t)w.idx << 5);
                     if (off < end) {
                         for (uint32_t it = 0;; it++) {
                             const ScreenEntry se = fetch_screen<RES>((const ScreenEntry*)lds_screen, (const ScreenEntry*)A.screen, (uint32_t)A.lds_entries << 5, off);
@@ -472,7 +518,7 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
                             if (off >= limit) break;
                         }
                         if (off & kScreenLeaf) { leaf = (int32_t)(off & ~kScreenLeaf); off = after_leaf; }
-                        w.idx = (int32_t)((off - base) >> 5);
+                        if constexpr (OFFS) w.off = off; else w.idx = (int32_t)((off - base) >> 5);
                     }
                 }
                 c_node += nodes;
@@ -497,6 +543,24 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             c_node += nodes;
         }
         V3<real> inv_lazy = mk<real>(0, 0, 0);   // LAZY_INV: the divisions only where the loop runs
+        if constexpr (OFFS) {
+            // The same loop for a position kept as an address: the index is made where the loop runs, and turned back behind it.
+            // A copy, not the loop below on a reference to either index: that form changed the code of the kernels that keep
+            // WalkState (the counted headline kernel with both switches off no longer compiled to the parent's assembly) and
+            // moved the headline kernels' own allocation.
+            if (exact_steps != 0u && w.off < oend) {
+                inv_lazy = inv_of(rd);
+                int32_t idx = (int32_t)((w.off - obase) >> 5);
+                for (; exact_steps != 0u && idx < n_entries; exact_steps--) {
+                    const Entry<real> e = fetch_entry<real, RES64>(lds_entries, A.entries, lds_n64, idx);
+                    c_node++;
+                    const bool hit = box_hit(e.b, ro, inv_lazy, tmin, w.best_t);
+                    idx = (hit && e.leaf < 0) ? -e.leaf : e.skip;
+                    if (hit && e.leaf >= 0) { leaf = e.leaf; break; }
+                }
+                w.off = obase + ((uint32_t)idx << 5);
+            }
+        } else {
         if constexpr (LAZY_INV) { if (exact_steps != 0u && w.idx < n_entries) inv_lazy = inv_of(rd); }
         for (; exact_steps != 0u && w.idx < n_entries; exact_steps--) {
             const Entry<real> e = ORD ? fetch_entry_ordered<real, RES64>(lds_entries, A.entries, lds_n64, w.idx, w.oct)
@@ -508,6 +572,7 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
             w.idx = (hit && e.leaf < 0) ? (ORD ? ordered_near(e.leaf, w.oct) : -e.leaf) : e.skip;
             if (hit && e.leaf >= 0) { leaf = e.leaf; break; }
         }
+        }
     }
     // The parked lanes intersect their leaves together; with walk_leaf_min set, a thin group waits (parked) while other lanes
     // of the wave can still step, so that the expensive primitive test runs with more lanes.  Per lane the sequence of
@@ -515,7 +580,10 @@ CR_D void walk_round(const KernelArgs<real>& A, const Entry<real>* lds_entries, 
     w.pending = leaf;
     if (A.walk_leaf_min > 0u) {
         const uint32_t parked = (uint32_t)__popcll(__ballot(leaf >= 0));
-        const bool can_step = __ballot(walking && leaf < 0 && w.idx < n_entries) != 0ull;
+        bool stepping;
+        if constexpr (OFFS) stepping = walking && leaf < 0 && w.off < oend;
+        else stepping = walking && leaf < 0 && w.idx < n_entries;
+        const bool can_step = __ballot(stepping) != 0ull;
         if (parked < A.walk_leaf_min && can_step) return;
     }
     w.pending = -1;
